@@ -10,6 +10,12 @@ noise draws included) over one batch of BASELINE.json configs[1]: LJS-v3-shaped 
 weights, identical architecture/format), batch 16 of random 80x864 mels, fp16 I/O, sigma 0.6.  Inputs are
 resident in HBM before the timed region.  Multi-GPU = independent utterance shards per rank (no collective on
 the data path); per-GPU work is fixed => weak scaling.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line.  ``--full`` adds everything else: the MFMA
+roofline (hipEvents around the launches, recorded inside the timed region) and, after that region, the other BASELINE
+configs under `secondary` and the CPU baseline.  ``--dump-outputs DIR`` writes what the timed path returned in its last step as
+DIR/<name>.npy (float32; a fixed, seeded sample where an output would exceed the size budget); the inputs depend only
+on the arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -26,6 +32,25 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_FP16_DENSE_TFLOPS = 2500.0   # MI355X dense fp16/bf16 MFMA peak (MI355X_MICROARCH.md: ~2.5 PF dense)
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+  """Write each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy in float32 (float64 stays float64).  The
+  budget is shared equally; a tensor larger than its share is written as a fixed, seeded sample of its flattened
+  elements (the same positions in every run with the same arguments)."""
+  import numpy as np
+  os.makedirs(out_dir, exist_ok=True)
+  share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+  for name, t in arrays.items():
+    t = t.detach()
+    dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+    cap = (share - 4096) // (8 if dt == torch.float64 else 4)
+    if t.numel() > cap:
+      g = torch.Generator().manual_seed(20240601)
+      idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+      t = t.reshape(-1).index_select(0, idx.to(t.device))
+    np.save(os.path.join(out_dir, name + ".npy"), t.to(dt).cpu().numpy())
 
 
 def wn_layer_macs_per_group_step(hp) -> float:
@@ -211,10 +236,12 @@ def train_roofline(hp, B, S, steps, ms, cnt, overlapped_ms_per_step=None):
           "overlapped_ms_per_step": overlapped_ms_per_step}
 
 
-def run_train(channels, B, S, steps, warmup, rank, world, dev, dist):
+def run_train(channels, B, S, steps, warmup, rank, world, dev, dist, roofline=True, dump_dir=None):
   """BASELINE configs[3]: the training step of src/waveglow/train.py:190-199 (forward, WaveGlowLoss, backward, Adam),
   data-parallel: per-GPU batch fixed (weak scaling), gradients averaged by one all-reduce per flow inside backward().
-  Returns the result dict (every rank; the times are the max over ranks)."""
+  Returns the result dict (every rank; the times are the max over ranks).  `roofline`: the kernel-timing passes after
+  the timed region (`roofline` of the result); `dump_dir`: the last timed step's loss, gradients and updated
+  parameters (flattened in named_parameters order) go there, before any further step."""
   from waveglow_amd import synthetic
   from waveglow_amd.distributed import GradientAllReducer
   from waveglow_amd.hparams import HParams
@@ -257,38 +284,42 @@ def run_train(channels, B, S, steps, warmup, rank, world, dev, dist):
     dist.barrier()
   elapsed = time.perf_counter() - t0
   assert torch.isfinite(loss.detach()).all()
-  # Kernel timing is taken AFTER the timed region (profiling records ~200 hipEvents per step on the weight-gradient
-  # stream): first as the step runs (streams overlapped), then with every launch on one stream (the kernel on its own).
-  ms = (C.c_double * 8)()
-  cnt = (C.c_int64 * 8)()
-  prof_steps = min(3, steps)
-  eng.lib.wg_profile_enable(eng.handle, 1 << 6)  # hipEvents around the wgrad launches only (one pair per launch), on their stream
-  for _ in range(prof_steps):
-    step()
-  torch.cuda.synchronize(dev)
-  eng.lib.wg_profile_read(eng.handle, ms, cnt, 8)
-  overlapped = round(ms[6] / prof_steps, 3)
-  os.environ["WG_TRAIN_SERIAL"] = "1"
-  try:
-    eng.lib.wg_profile_enable(eng.handle, 0)
-    step()
-    torch.cuda.synchronize(dev)
-    eng.lib.wg_profile_enable(eng.handle, (1 << 4) | (1 << 5) | (1 << 6))
+  if dump_dir is not None:
+    params = [p for _, p in model.named_parameters()]
+    dump_outputs(dump_dir, {"loss": loss.detach().float().reshape(1),
+                            "grads": torch.cat([p.grad.detach().reshape(-1).float() for p in params if p.grad is not None]),
+                            "params": torch.cat([p.detach().reshape(-1).float() for p in params])})
+  if roofline:
+    # Kernel timing is taken AFTER the timed region (profiling records ~200 hipEvents per step on the weight-gradient
+    # stream): first as the step runs (streams overlapped), then with every launch on one stream (the kernel on its own).
+    ms = (C.c_double * 8)()
+    cnt = (C.c_int64 * 8)()
+    prof_steps = min(3, steps)
+    eng.lib.wg_profile_enable(eng.handle, 1 << 6)  # hipEvents around the wgrad launches only (one pair per launch), on their stream
     for _ in range(prof_steps):
       step()
     torch.cuda.synchronize(dev)
     eng.lib.wg_profile_read(eng.handle, ms, cnt, 8)
-    eng.lib.wg_profile_enable(eng.handle, 0)
-  finally:
-    del os.environ["WG_TRAIN_SERIAL"]
+    overlapped = round(ms[6] / prof_steps, 3)
+    os.environ["WG_TRAIN_SERIAL"] = "1"
+    try:
+      eng.lib.wg_profile_enable(eng.handle, 0)
+      step()
+      torch.cuda.synchronize(dev)
+      eng.lib.wg_profile_enable(eng.handle, (1 << 4) | (1 << 5) | (1 << 6))
+      for _ in range(prof_steps):
+        step()
+      torch.cuda.synchronize(dev)
+      eng.lib.wg_profile_read(eng.handle, ms, cnt, 8)
+      eng.lib.wg_profile_enable(eng.handle, 0)
+    finally:
+      del os.environ["WG_TRAIN_SERIAL"]
   if dist is not None:
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
   samples = B * S * world
   flops = 3 * 2.0 * (81235408 / 8 if channels == 256 else 261355984 / 8) * samples   # fwd + 2x bwd, SURVEY 8d
-  roof = train_roofline(hp, B, S, prof_steps, ms, cnt, overlapped)
-  roof["kernel_ms_per_step"].update({"wn_layer_forward": round(ms[4] / prof_steps, 3), "dgrad": round(ms[5] / prof_steps, 3)})
   out = {
     "metric": "training samples/sec (WaveGlow-256 train step: forward + loss + backward + all-reduce + Adam)",
     "value": round(samples * steps / elapsed, 1), "unit": "samples/s", "n_gpus": world, "steps": steps,
@@ -299,8 +330,11 @@ def run_train(channels, B, S, steps, warmup, rank, world, dev, dist):
     "config": {"workload": f"configs[3]: {channels}ch train step, batch={B}/GPU x {S} samples, {F_} mel frames",
                "parallelism": f"dp{world}, per-flow gradient all-reduce (RCCL) overlapped with backward"},
     "loss": float(loss.detach()),
-    "algorithmic_TFLOP_per_s": round(flops * steps / elapsed / 1e12, 1),
-    "roofline": roof}
+    "algorithmic_TFLOP_per_s": round(flops * steps / elapsed / 1e12, 1)}
+  if roofline:
+    roof = train_roofline(hp, B, S, prof_steps, ms, cnt, overlapped)
+    roof["kernel_ms_per_step"].update({"wn_layer_forward": round(ms[4] / prof_steps, 3), "dgrad": round(ms[5] / prof_steps, 3)})
+    out["roofline"] = roof
   del model, opt, eng
   torch.cuda.empty_cache()
   return out
@@ -319,9 +353,10 @@ def build_infer_model(channels, dev):
 
 def run_infer(hp, model, B, T, dtype_name, steps, warmup, rank, dev, dist, profile=True):
   """`steps` timed WaveGlow.infer calls (noise draws included) on one batch resident in HBM; returns
-  (elapsed seconds: max over ranks, per-class kernel ms, launch counts).  `profile`: hipEvents around every launch
-  inside the timed region (the headline: two event records per 0.5 ms launch are noise there); False: the events are
-  taken in a pass of their own after the timed one (single-utterance latency: 110 launches of ~25 us per call)."""
+  (elapsed seconds: max over ranks, per-class kernel ms, launch counts, audio of the last timed call).  `profile`: True:
+  hipEvents around every launch inside the timed region (the headline under --full: two event records per 0.5 ms launch
+  are noise there); False: the events are taken in a pass of their own after the timed one (single-utterance latency:
+  110 launches of ~25 us per call); None: no events at all (kernel ms and counts are None)."""
   from waveglow_amd import synthetic
   dtype = torch.float16 if dtype_name == "fp16" else torch.float32
   mel = synthetic.make_mel(B, T, seed=1234 + rank).to(dev, dtype)
@@ -345,19 +380,22 @@ def run_infer(hp, model, B, T, dtype_name, steps, warmup, rank, dev, dist, profi
     if dist is not None:
       dist.barrier()
     elapsed = time.perf_counter() - t0
-    if not profile:
+    if profile is False:
       eng.lib.wg_profile_enable(eng.handle, 1)
       for _ in range(steps):
-        audio = model.infer(mel, sigma=sigma)
+        model.infer(mel, sigma=sigma)
       torch.cuda.synchronize(dev)
   assert torch.isfinite(audio).all()
-  eng.lib.wg_profile_read(eng.handle, ms, cnt, 4)
-  eng.lib.wg_profile_enable(eng.handle, 0)
+  if profile is not None:
+    eng.lib.wg_profile_read(eng.handle, ms, cnt, 4)
+    eng.lib.wg_profile_enable(eng.handle, 0)
   if dist is not None:
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
-  return elapsed, list(ms), list(cnt)
+  if profile is None:
+    return elapsed, None, None, audio
+  return elapsed, list(ms), list(cnt), audio
 
 
 def infer_roofline(hp, B, T, steps, ms, cnt, traffic=None):
@@ -381,7 +419,7 @@ def infer_roofline(hp, B, T, steps, ms, cnt, traffic=None):
 
 def secondary_infer(label, hp, model, B, T, dtype_name, steps, warmup, rank, world, dev, dist):
   """One more BASELINE config, after the headline's timed region: the same measurement, condensed."""
-  elapsed, ms, cnt = run_infer(hp, model, B, T, dtype_name, steps, warmup, rank, dev, dist, profile=False)
+  elapsed, ms, cnt, _audio = run_infer(hp, model, B, T, dtype_name, steps, warmup, rank, dev, dist, profile=False)
   roof = infer_roofline(hp, B, T, steps, ms, cnt)
   samples = B * T * 256 * world
   flops_per_sample = 2.0 * (81235408 if hp.n_channels == 256 else 261355984) / 8 if hp.n_channels in (256, 512) else None
@@ -404,15 +442,23 @@ def main():
   ap.add_argument("--frames", type=int, default=864)
   ap.add_argument("--channels", type=int, default=256)
   ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp32"])
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="also measure what the headline does not need, after its timed region: the MFMA roofline "
+                       "(`roofline`), the other BASELINE configs (`secondary`) and the CPU baseline (`cpu_baseline`)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the timed path returned in its last step as DIR/<name>.npy (float32, < 64 MB in all): "
+                       "infer: `audio`; train: `loss`, `grads`, `params` (fixed, seeded samples of the flattened tensors)")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
   ap.add_argument("--no-secondary", action="store_true",
-                  help="skip the other BASELINE configs (configs[0], [2], [3], [4]) that the default run measures after the "
-                       "headline's timed region and reports under `secondary`")
+                  help="with --full: skip the other BASELINE configs (configs[0], [2], [3], [4]) measured after the "
+                       "headline's timed region and reported under `secondary`")
   ap.add_argument("--workload", default="infer", choices=["infer", "train"],
                   help="infer: BASELINE configs[1] (the headline metric, default); train: configs[3], one optimiser step "
                        "(forward + loss + backward + gradient all-reduce + Adam) on batch 32 x 16000 samples per GPU")
   ap.add_argument("--segment", type=int, default=16000)
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be >= 1 and --warmup >= 0")
 
   rank = int(os.environ.get("RANK", "0"))
   local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -432,16 +478,21 @@ def main():
       dist.barrier()
       dist.destroy_process_group()
 
+  dump_dir = args.dump_outputs if rank == 0 else None
   if args.workload == "train":
     out = run_train(args.channels, args.batch if args.batch != 16 else 32, args.segment, args.steps, args.warmup,
-                    rank, world, dev, dist)
+                    rank, world, dev, dist, roofline=args.full, dump_dir=dump_dir)
     if rank == 0:
       print(json.dumps(out), flush=True)
     return finish()
 
   hp, sd, model = build_infer_model(args.channels, dev)
   B, T = args.batch, args.frames
-  elapsed, ms, cnt = run_infer(hp, model, B, T, args.dtype, args.steps, args.warmup, rank, dev, dist)
+  elapsed, ms, cnt, audio = run_infer(hp, model, B, T, args.dtype, args.steps, args.warmup, rank, dev, dist,
+                                      profile=True if args.full else None)
+  if dump_dir is not None:
+    dump_outputs(dump_dir, {"audio": audio})
+  del audio
 
   samples_per_step = B * T * 256 * world
   value = samples_per_step * args.steps / elapsed
@@ -463,12 +514,13 @@ def main():
                "per_gpu_samples_per_step": B * T * 256, "parallelism": f"utterance-sharded x{world}, no collective"},
     "real_time_factor": round(value / 22050.0, 1),
     "samples_per_s_per_gpu": round(value / world, 1),
-    "roofline": infer_roofline(hp, B, T, args.steps, ms, cnt, pmc_traffic_bytes(args)),
   }
+  if args.full:
+    out["roofline"] = infer_roofline(hp, B, T, args.steps, ms, cnt, pmc_traffic_bytes(args))
 
   # ---- the other BASELINE configs, each after the headline's timed region, in the SAME JSON line (`secondary`).
   # Every rank runs them (utterance shards: no collective; the training step all-reduces its gradients over RCCL).
-  if not args.no_secondary and workload_label(args) == "configs[1]":
+  if args.full and not args.no_secondary and workload_label(args) == "configs[1]":
     sec = {}
     t_sec = time.perf_counter()
     try:
@@ -495,7 +547,7 @@ def main():
     out["secondary"] = sec
 
   if rank == 0:
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       out["cpu_baseline"] = cpu_baseline(hp, sd)
     print(json.dumps(out), flush=True)
   finish()

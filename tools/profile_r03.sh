@@ -18,8 +18,8 @@ echo "== PMC: training (serial)"
 WG_TRAIN_SERIAL=1 bash $ROOT/tools/profile_pmc_train.sh r03t > $OUT/pmc_train.log 2>&1
 echo "== un-profiled bench lines"
 cd $ROOT
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
-timeout -k 10 300 python3 bench.py --workload train --steps 10 --warmup 3 > $OUT/bench_train.json 2> $OUT/bench_train.err
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 300 python3 bench.py --full --workload train --steps 10 --warmup 3 > $OUT/bench_train.json 2> $OUT/bench_train.err
 timeout -k 10 200 python3 tools/bench_latency.py > $OUT/latency.json 2> $OUT/latency.err
 find $OUT -name "*kernel_stats.csv" | head
 tail -c 600 $OUT/bench_train.json

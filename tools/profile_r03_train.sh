@@ -7,5 +7,5 @@ WG_TRAIN_SERIAL=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-fo
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train_streams -- python3 $ROOT/tools/bench_train.py --adam --steps 2 --warmup 1 > $OUT/train_streams.log 2>&1 || echo "train streams trace failed"
 WG_TRAIN_SERIAL=1 bash $ROOT/tools/profile_pmc_train.sh r03u > $OUT/pmc_train.log 2>&1
 cd $ROOT
-timeout -k 10 300 python3 bench.py --workload train --steps 10 --warmup 3 > $OUT/bench_train.json 2> $OUT/bench_train.err
+timeout -k 10 300 python3 bench.py --full --workload train --steps 10 --warmup 3 > $OUT/bench_train.json 2> $OUT/bench_train.err
 tail -c 700 $OUT/bench_train.json

@@ -3,7 +3,7 @@
 for b in ${1:-1 2 4 8 16 32}; do
   for f in ${FORCE:-auto}; do
     if [ "$f" = auto ]; then unset WG_FORCE_BN; else export WG_FORCE_BN=$f; fi
-    timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary --steps 5 --warmup 2 --batch $b 2>/dev/null | python -c "
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary --steps 5 --warmup 2 --batch $b 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
   if l.startswith('{'):
