@@ -206,6 +206,11 @@ typedef struct wg_train_weights {
   const float* const* bstart;    /* [C] */
   const float* const* out_init;  /* [8]   W_end.(sum_i b_skip_i) + b_end, zero padded */
   const float* const* w1x1;      /* [c_k][c_k] fp32 row-major (model.py:64) */
+  /* Optional (null: not packed, not read): the upsample transposed for the mel input gradient (wg_train_backward_ex with
+   * g_mel), fp16 [32 p][4 j][M8/64 t][NB][4 s][64 lanes][8] with NB = ceil(n_mel/32): lane (r, h), element e of sub-step
+   * s = W_up[i = 32 blk + r][o][8p + g + 256j] for the spectrogram channel (o, g) = 8o + g at d spect plane position
+   * 64t + 32h + 8s + e (zero for i >= n_mel).  wg_train_pack / wg_train_prepare fill it when it is non-null. */
+  const void* wupt;
 } wg_train_weights;
 
 /* Gradients: fp32 device buffers in NATURAL channel order, w.r.t. the matrices of wg_train_plain (dw1, dw2, dwes, dwup)
@@ -304,6 +309,21 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* w, const wg_tr
                             const float* const* g_log_s, float scale, const void* audio, int32_t B, int32_t n_frames,
                             int32_t audio_len, void* workspace, size_t workspace_bytes, int32_t flow_hi,
                             int32_t flow_lo, void* stream);
+
+/* The backward pass with input gradients and an optional weight-gradient part.  WaveGlow.forward is plain autograd in the
+ * reference (src/waveglow/model.py:178-221): after loss.backward() the inputs hold mel.grad and audio.grad as well.
+ *   grads   null: no parameter gradient is computed at all (a frozen model used as a likelihood loss): no weight-gradient
+ *           launch, slab reduction, start / 1x1 partial or upsample-gradient job runs, and the d spect GEMM only for g_mel.
+ *           Otherwise exactly wg_train_backward_flows.
+ *   g_mel   null, or fp32 [B][n_mel][n_frames]: d loss / d mel through the upsample and squeeze (model.py:186-193); frames
+ *           whose spectrogram columns were trimmed to audio_len (model.py:188-189) get 0.  Needs w->wupt.
+ *   g_audio null, or fp32 [B][audio_len]: d loss / d audio through the unfold and flow 0's 1x1 conv (model.py:195, :64).
+ * Both are written entirely (no accumulation) and are final on `stream` after the call with flow_lo == 0; the flow range
+ * works as for wg_train_backward_flows (flow_hi = n_flows-1, flow_lo = 0: the whole pass).  Enqueue-only. */
+int wg_train_backward_ex(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_z,
+                         const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
+                         int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
+                         int32_t flow_hi, int32_t flow_lo, void* stream);
 
 /* Diagnostic builds only (-DWG_STAMPS): device buffer of n_tiles*8 uint64 that the WN-layer kernel fills with
  * s_memtime stamps at its phase boundaries (last launch wins).  A no-op pointer in the shipped library. */

@@ -960,6 +960,20 @@ __global__ void __launch_bounds__(256) pack_kernel(const PackArgs a) {
       const int r0 = (q0 & ~31) + nat0_of(q0 & 31);
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = (_Float16)S.w1(fl, r0 + (j & 3) + 2 * (j & 4), 3 * C + 32 * b + r);
+    } else if (a.kind == PACK_WUPT) {
+      // [p][j][t][b][s][h][r][8] = Wup[p][pos_to_chan(64 t + 32 h + 8 s + e)][128 j + 32 b + r]: the upsample transposed for
+      // the input gradient (dmel_kernel); rows = mel channels (natural, zero past M), K = the d spect plane positions
+      const int r = q & 31, h = (q >> 5) & 1, s_ = (q >> 6) & 3, NB = wupt_blocks(M8), mc = M8 / 64;
+      size_t e = q >> 8;
+      const int b = (int)(e % NB);
+      e /= NB;
+      const int t = (int)(e % mc);
+      e /= mc;
+      const int j = (int)(e & 3), p = (int)(e >> 2);
+      const int i = 32 * b + r;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        o[k] = i < M8 / 8 ? (_Float16)S.wup(p, pos_to_chan(64 * t + 32 * h + 8 * s_ + k), 128 * j + i) : (_Float16)0.0f;
     } else {
       // PACK_WUP [p][t][b][s][h][r][8] = Wup[p][32 b + r][64 t + 32 h + 8 s + j]   (rows natural: pos(chan_to_pos(r)) = r)
       const int r = q & 31, h = (q >> 5) & 1, s_ = (q >> 6) & 3;
@@ -1171,6 +1185,22 @@ __global__ void __launch_bounds__(FB_ROWS) flow_bwd_post_kernel(const FlowBwdArg
     } else {
 #pragma unroll
       for (int e = 0; e < kMaxGroup; ++e) xin[e] = a.audio[(size_t)b * L * 8 + (size_t)t * 8 + e];
+      if (a.g_audio) {
+        // d audio[b][8t + e] = sum_r W[r][e] d(W audio)[r] / scale   (the unfold of model.py:195 is this row's 8 samples)
+        const float inv = 1.0f / a.scale;
+        float ga[kMaxGroup];
+#pragma unroll
+        for (int e = 0; e < kMaxGroup; ++e) {
+          float v = 0.0f;
+#pragma unroll
+          for (int rr = 0; rr < kMaxGroup; ++rr)
+            if (rr < c && e < c) v = fmaf(a.w1x1[rr * c + e], gy[rr], v);
+          ga[e] = v * inv;
+        }
+        float4* dst = (float4*)(a.g_audio + (size_t)b * L * 8 + (size_t)t * 8);
+        dst[0] = make_float4(ga[0], ga[1], ga[2], ga[3]);
+        dst[1] = make_float4(ga[4], ga[5], ga[6], ga[7]);
+      }
     }
     if (a.Zprev) {
       // d(previous flow's output) = (d z[peeled channels] | W^T d(W z))
@@ -1203,7 +1233,7 @@ __global__ void __launch_bounds__(FB_ROWS) flow_bwd_post_kernel(const FlowBwdArg
     s_x[threadIdx.x][j] = xin[j];
   }
   __syncthreads();
-  if (threadIdx.x < 64) {
+  if (a.dw_partial && threadIdx.x < 64) {
     const int rr = threadIdx.x >> 3, cc = threadIdx.x & 7;
     float s = 0.0f;
     for (int i = 0; i < FB_ROWS; ++i) s = fmaf(s_g[i][rr], s_x[i][cc], s);
@@ -1299,6 +1329,129 @@ int start_wgrad_workgroups(const RowGeom& g) { return kPhases * (g.Rp / 128); }
 
 hipError_t launch_start_wgrad(const StartWgradArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(start_wgrad_kernel, dim3(a.g.Rp / 128, kPhases), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// =============================================================================================
+// d mel: the input gradient of the upsample + squeeze (model.py:186-193).  The forward runs one [M8 x 512] matrix per
+// phase over mel frames q, q-1, q-2, q-3 (plane_gemm_kernel with the runs MELP at -32 j); its transpose contracts over
+// phase, tap and spectrogram channel:
+//   d mel[b][i][f] = sum_{p < 32} sum_{j < 4} sum_{m < M8} Wup_p[m][128 j + i] . GSP_p[m][row of frame f + j of b] / scale
+// A GEMM of M = n_mel (padded to 32) rows, one column per frame row of a phase block (Rp) and K = 32 x 4 x M8.
+// Workgroup = 32 frame rows x every mel channel; its 8 waves split K by (phase, tap) pair -- wave w takes pairs w, w+8,
+// ... -- and their accumulators are summed through LDS in a fixed order (bitwise reproducible, no atomics).  A lane's
+// B fragment is 16 contiguous bytes of its row of the d spect plane (positions 32h + 8s .. +7 of a 64-channel chunk;
+// the four sub-steps of a chunk read the lane's 64 contiguous bytes), the A fragments come pre-packed in that K order
+// (PACK_WUPT: one contiguous KiB per wave and sub-step).  Operands double-buffered in registers one K-step ahead.
+// Spectrogram frames past an utterance's last valid frame read as zero (masked, whatever the guard width), so the frames
+// whose columns were all trimmed to the audio length (model.py:188-189) come out 0; frames past the tile rows (mel
+// longer than the audio) are written as 0 by a grid-stride tail.
+// =============================================================================================
+constexpr int DM_WAVES = 8;
+
+template <int NB>
+__global__ void __launch_bounds__(64 * DM_WAVES) dmel_kernel(const DmelArgs a) {
+  __shared__ float red[DM_WAVES / 2][NB * 16][64];
+  const RowGeom& g = a.g;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c = lane & 31, h = lane >> 5;
+  const int rr = blockIdx.x * 32 + c;
+  const int b = rr / g.Fp, f = rr - b * g.Fp - g.Gf;
+  const bool col_ok = b < g.B && f >= 0;
+  const int mc = a.M8 / 64;
+  const size_t R64 = (size_t)g.R * 64;
+  const size_t a_pair = (size_t)mc * NB * 2048;          // wupt elements per (phase, tap) pair
+  const int n_steps = (4 * kPhases / DM_WAVES) * mc;     // K-steps of 64 of this wave
+
+  f32x16 acc[NB];
+#pragma unroll
+  for (int ib = 0; ib < NB; ++ib)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[ib][e] = 0.0f;
+
+  half8 fa[2][NB][4], fb[2][4];
+  auto fetch = [&](int st, half8 (*da)[4], half8* db) {
+    const int q = st / mc, t = st - q * mc;
+    const int pj = w + DM_WAVES * q, p = pj >> 2, j = pj & 3;
+    const bool ok = col_ok && f + j < g.F;
+    const _Float16* bsrc = a.GSP + (size_t)t * R64 + ((size_t)kRowPad + (size_t)p * g.Rp + rr + j) * 64 + 32 * h;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      half8 v;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (_Float16)0.0f;
+      if (ok) v = *(const half8*)(bsrc + 8 * s);
+      db[s] = v;
+    }
+    const _Float16* asrc = a.wupt + (size_t)pj * a_pair + (size_t)t * NB * 2048 + lane * 8;
+#pragma unroll
+    for (int ib = 0; ib < NB; ++ib)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) da[ib][s] = *(const half8*)(asrc + (size_t)ib * 2048 + 512 * s);
+  };
+  auto mma = [&](half8 (*da)[4], const half8* db) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int ib = 0; ib < NB; ++ib) acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_f16(da[ib][s], db[s], acc[ib], 0, 0, 0);
+  };
+  // n_steps is even (16 pairs per wave); past the end the fetch repeats the last step (branch-free loop body)
+  fetch(0, fa[0], fb[0]);
+  for (int st = 0; st < n_steps; st += 2) {
+    fetch(st + 1, fa[1], fb[1]);
+    mma(fa[0], fb[0]);
+    fetch(st + 2 < n_steps ? st + 2 : n_steps - 1, fa[0], fb[0]);
+    mma(fa[1], fb[1]);
+  }
+
+  // fixed-order tree over the waves: 4-7 into 0-3, 2-3 into 0-1, 1 into 0
+#pragma unroll
+  for (int half = DM_WAVES / 2; half >= 1; half >>= 1) {
+    if (w >= half && w < 2 * half) {
+#pragma unroll
+      for (int ib = 0; ib < NB; ++ib)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) red[w - half][ib * 16 + e][lane] = acc[ib][e];
+    }
+    __syncthreads();
+    if (w < half) {
+#pragma unroll
+      for (int ib = 0; ib < NB; ++ib)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[ib][e] += red[w][ib * 16 + e][lane];
+    }
+    __syncthreads();
+  }
+  const int fmax = g.F < g.T ? g.F : g.T;
+  if (w == 0 && col_ok && f < fmax) {
+    // accumulator element e of lane (c, h) = row (e & 3) + 8 (e >> 2) + 4 h of the 32-block, column c
+#pragma unroll
+    for (int ib = 0; ib < NB; ++ib)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = 32 * ib + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (i < a.M) a.g_mel[((size_t)b * a.M + i) * g.T + f] = acc[ib][e] * a.inv_scale;
+      }
+  }
+  const int nz = g.T - fmax;
+  if (nz > 0) {
+    const size_t n = (size_t)g.B * a.M * nz;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) {
+      const size_t bi = q / nz;
+      a.g_mel[bi * g.T + fmax + (q - bi * nz)] = 0.0f;
+    }
+  }
+}
+
+hipError_t launch_dmel(const DmelArgs& a, hipStream_t s) {
+  const int nb = wupt_blocks(a.M8);
+  if (a.M < 1 || a.M > 128 || a.M8 != 8 * a.M || a.M8 % 64 || a.g.Rp % 32 || !a.GSP || !a.wupt || !a.g_mel)
+    return hipErrorInvalidValue;
+  const dim3 grid(a.g.Rp / 32), block(64 * DM_WAVES);
+  if (nb == 1) hipLaunchKernelGGL(dmel_kernel<1>, grid, block, 0, s, a);
+  else if (nb == 2) hipLaunchKernelGGL(dmel_kernel<2>, grid, block, 0, s, a);
+  else if (nb == 3) hipLaunchKernelGGL(dmel_kernel<3>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(dmel_kernel<4>, grid, block, 0, s, a);
   return hipGetLastError();
 }
 

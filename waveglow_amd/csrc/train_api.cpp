@@ -302,6 +302,7 @@ int wg_train_pack(wg_handle* h, const wg_train_plain* in, const wg_train_weights
   TR_TRY(run(PACK_WBT, out->wbt, nullptr, (size_t)FL * C * 6 * C));
   TR_TRY(run(PACK_WCT, out->wct, nullptr, (size_t)M8 * FL * 2 * C));
   TR_TRY(run(PACK_WUP, out->wup, nullptr, (size_t)32 * M8 * 512));
+  if (out->wupt) TR_TRY(run(PACK_WUPT, out->wupt, nullptr, (size_t)32 * 4 * M8 * wupt_blocks(M8) * 32));
   return WG_OK;
 }
 
@@ -452,20 +453,34 @@ int wg_train_backward(wg_handle* h, const wg_train_weights* wt, const wg_train_g
                       int32_t audio_len, void* workspace, size_t workspace_bytes, void* stream) {
   const wg_config* c = wg_internal_config(h);
   if (!c) return wg_set_error(WG_ERR_INVALID, "null handle");
-  return wg_train_backward_flows(h, wt, gr, g_z, g_log_s, scale, audio, B, n_frames, audio_len, workspace, workspace_bytes,
-                                 c->n_flows - 1, 0, stream);
+  if (!gr) return wg_set_error(WG_ERR_INVALID, "null argument");
+  return wg_train_backward_ex(h, wt, gr, g_z, g_log_s, scale, audio, nullptr, nullptr, B, n_frames, audio_len, workspace,
+                              workspace_bytes, c->n_flows - 1, 0, stream);
 }
 
 int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_z,
                             const float* const* g_log_s, float scale, const void* audio, int32_t B, int32_t n_frames,
                             int32_t audio_len, void* workspace, size_t workspace_bytes, int32_t flow_hi, int32_t flow_lo,
                             void* stream) {
-  if (!wt || !gr || !audio || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
+  if (!gr) return wg_set_error(WG_ERR_INVALID, "null argument");
+  return wg_train_backward_ex(h, wt, gr, g_z, g_log_s, scale, audio, nullptr, nullptr, B, n_frames, audio_len, workspace,
+                              workspace_bytes, flow_hi, flow_lo, stream);
+}
+
+int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_z,
+                         const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
+                         int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
+                         int32_t flow_hi, int32_t flow_lo, void* stream) {
+  if (!wt || !audio || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
   if (!(scale > 0.f)) return wg_set_error(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
   int rc = setup(h, B, n_frames, audio_len, workspace, workspace_bytes, x);
   if (rc) return rc;
-  if ((rc = check_weights(wt, x.c->n_flows)) || (rc = check_grads(gr, x.c->n_flows))) return rc;
+  if ((rc = check_weights(wt, x.c->n_flows)) || (gr && (rc = check_grads(gr, x.c->n_flows)))) return rc;
+  if (g_mel && !wt->wupt) return wg_set_error(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
+  // gr == null: no parameter gradients -- the data-gradient chain alone (no weight-gradient launch, slab reduction, start /
+  // 1x1 partial, d upsample job; the d spect GEMM only for g_mel)
+  const bool pg = gr != nullptr;
   const wg_config& c = *x.c;
   const RowGeom& g = x.g;
   TrainWs& w = x.w;
@@ -492,8 +507,8 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
   hipStream_t sB = s, sW = s, sR = s;
   if (!x.serial) {
     if (bh == 2 && !(sB = wg_internal_aux_stream(h, 0))) return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
-    if (!(sW = wg_internal_aux_stream(h, 1))) return wg_set_error(WG_ERR_HIP, "cannot create the weight-gradient stream");
-    if (!(sR = wg_internal_aux_stream(h, 2))) return wg_set_error(WG_ERR_HIP, "cannot create the slab-reduction stream");
+    if (pg && !(sW = wg_internal_aux_stream(h, 1))) return wg_set_error(WG_ERR_HIP, "cannot create the weight-gradient stream");
+    if (pg && !(sR = wg_internal_aux_stream(h, 2))) return wg_set_error(WG_ERR_HIP, "cannot create the slab-reduction stream");
   }
   const int* const n_slabs = x.n_slabs;
   bool fuse = true;                       // WG_TRAIN_NO_FUSE=1 (tests, A/B): d acts + gate derivative as launches of their own
@@ -509,7 +524,7 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
     if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
   }
   // where entry fl of a per-layer gradient tensor lives: dense, or in interleaved per-layer records (wg_train_grads)
-  if ((gr->layer_stride == 0) != (gr->flow_stride == 0) || gr->layer_stride < 0 || gr->flow_stride < 0)
+  if (pg && ((gr->layer_stride == 0) != (gr->flow_stride == 0) || gr->layer_stride < 0 || gr->flow_stride < 0))
     return wg_set_error(WG_ERR_INVALID, "wg_train_grads: layer_stride and flow_stride must both be 0 or both positive");
   auto gofs = [&](int fl, size_t dense) -> size_t {
     return gr->layer_stride ? (size_t)(fl / nl) * (size_t)gr->flow_stride + (size_t)(fl % nl) * (size_t)gr->layer_stride
@@ -532,7 +547,7 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
   //   GO[k & 1]        written by flow k's pre kernel on s, read by the chains and by all of flow k's jobs on sW: the pre
   //                    kernel of flow k-2 waits for the last of them (w_flow[k & 1]);
   //   GP, X, T, S, A   one set per layer of the whole model: no reuse inside a call.
-  TR_ORDER(order_after(h, s, sW));
+  if (pg) TR_ORDER(order_after(h, s, sW));
   // A layer's slabs are reduced by a launch of its own on a third stream (sR, lowest priority too): it is HBM-bound and
   // small in registers and LDS, so its workgroups run beside the NEXT layer's weight-gradient workgroups (MFMA / L2-bound,
   // one per CU).  Two slab sets: launch n + 2 on sW waits for the reduction of launch n (r_done), the reduction of launch
@@ -615,9 +630,9 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
         }
       }
       // the weight-gradient stream continues once both chains have written their half of d pre (and of d x_{i+1} before it)
-      TR_ORDER(order_after(h, s, sW));
-      TR_ORDER(order_after(h, sB, sW));
-      {
+      if (pg) {
+        TR_ORDER(order_after(h, s, sW));
+        TR_ORDER(order_after(h, sB, sW));
         // d W1 = d pre x [x taps | spect]^T, d b1;
         // d W2 = d x_{i+1} x acts^T, d b2  and  d (W_end W_skip_i) = d out x acts^T  share the X operand (acts): one
         // job with the d out plane as the `extra` 16 rows (the last layer has no d x: the d out plane stands in as the
@@ -710,9 +725,9 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
         gx = gxi;
       }
     }
-    TR_ORDER(mark(sW, w_flow[k & 1], 10 + (k & 1)));
+    if (pg) TR_ORDER(mark(sW, w_flow[k & 1], 10 + (k & 1)));
     TR_ORDER(order_after(h, sB, s));
-    {
+    if (pg) {
       StartWgradArgs a;
       a.g = g;
       a.C = C;
@@ -736,15 +751,23 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
       fb.z_peel_ch0 = z_final_ch0;
     } else {
       fb.audio = (const float*)audio;
+      fb.g_audio = g_audio;
     }
-    fb.dw_partial = w.part3;
-    TR_TRY(launch_flow_bwd_post(fb, s));
-    const SlabSeg sg = make_seg(w.part3, flow_bwd_workgroups(g), 64, 64, inv, gr->dw1x1[k], 0, 0);
-    TR_TRY(launch_slab_reduce_multi(&sg, 1, s));
+    // flow 0 without parameter gradients: the kernel's only outputs would be d W_0 (and d audio)
+    if (pg || k > 0 || g_audio) {
+      fb.dw_partial = pg ? w.part3 : nullptr;
+      TR_TRY(launch_flow_bwd_post(fb, s));
+    }
+    if (pg) {
+      const SlabSeg sg = make_seg(w.part3, flow_bwd_workgroups(g), 64, 64, inv, gr->dw1x1[k], 0, 0);
+      TR_TRY(launch_slab_reduce_multi(&sg, 1, s));
+    }
   }
-  if (flow_lo > 0) {                      // the upsample gradient needs the d pre planes of every flow
-    TR_ORDER(order_after(h, sW, s));      // every gradient of the call is final on the caller's stream
-    TR_ORDER(order_after(h, sR, s));
+  if (flow_lo > 0 || !(pg || g_mel)) {    // the upsample / mel gradients need the d pre planes of every flow
+    if (pg) {
+      TR_ORDER(order_after(h, sW, s));    // every gradient of the call is final on the caller's stream
+      TR_ORDER(order_after(h, sR, s));
+    }
     return WG_OK;
   }
   {
@@ -761,7 +784,19 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
     a.o0 = w.GSP;
     TR_TRY(launch_plane_gemm(a, s));
   }
-  {
+  if (g_mel) {
+    // d mel = the upsample's transpose applied to d spect (train.hip: dmel_kernel)
+    DmelArgs a;
+    a.g = g;
+    a.GSP = w.GSP;
+    a.wupt = (const _Float16*)wt->wupt;
+    a.M = c.n_mel_channels;
+    a.M8 = M8;
+    a.inv_scale = inv;
+    a.g_mel = g_mel;
+    TR_TRY(launch_dmel(a, s));
+  }
+  if (pg) {
     WgradJob a;   // d upsample: per phase, d spect x mel frames q..q-3 (no sum over phases: one slab = one phase = one result)
     memset(&a, 0, sizeof a);
     a.G = w.GSP;
@@ -779,9 +814,9 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
     sg[0].blocked = 1; sg[0].m_chunks = mc; sg[0].k_chunks = 8; sg[0].n_groups = kPhases; sg[0].out_group_stride = (size_t)M8 * 512;
     sg[1] = make_seg(w.part3, kPhases, M8, M8, inv, gr->dbup, M8, 2);
     TR_TRY(launch_slab_reduce_multi(sg, 2, s));
+    TR_ORDER(order_after(h, sW, s));      // every gradient of the call is final on the caller's stream
+    TR_ORDER(order_after(h, sR, s));
   }
-  TR_ORDER(order_after(h, sW, s));        // every gradient of the call is final on the caller's stream
-  TR_ORDER(order_after(h, sR, s));
   return WG_OK;
 }
 
@@ -981,6 +1016,7 @@ int wg_train_prepare(wg_handle* h, const void* const* params, int32_t weight_nor
   TR_TRY(run(PACK_WBT, out->wbt, nullptr, (size_t)FL * C * 6 * C));
   TR_TRY(run(PACK_WCT, out->wct, nullptr, (size_t)M8 * FL * 2 * C));
   TR_TRY(run(PACK_WUP, out->wup, nullptr, (size_t)32 * M8 * 512));
+  if (out->wupt) TR_TRY(run(PACK_WUPT, out->wupt, nullptr, (size_t)32 * 4 * M8 * wupt_blocks(M8) * 32));
   return WG_OK;
 }
 

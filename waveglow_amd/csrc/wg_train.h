@@ -115,7 +115,8 @@ struct FlowBwdArgs {
   int n_peel;               // channels peeled before this flow (model.py:201-203)
   int z_peel_ch0;           // their channel offset in z
   const float* audio;       // k == 0: the input audio [B][8L] fp32
-  float* dw_partial;        // [n_workgroups][64]: per-workgroup partial of d W[r][cc]
+  float* dw_partial;        // [n_workgroups][64]: per-workgroup partial of d W[r][cc], or null (no parameter gradients)
+  float* g_audio;           // k == 0, optional: d audio [B][8L] fp32 = W^T d(W audio) / scale  (model.py:195, :64)
 };
 
 struct StartWgradArgs {
@@ -169,7 +170,9 @@ hipError_t launch_prepare(const PrepArgs& a, hipStream_t s);
 hipError_t launch_param_grads(const PrepArgs& a, hipStream_t s);
 
 // weight packing (train.hip: pack_kernel), one launch per output tensor
-enum PackKind : int { PACK_A1 = 0, PACK_A2, PACK_ES, PACK_WAT, PACK_WBT, PACK_WCT, PACK_WUP };
+enum PackKind : int { PACK_A1 = 0, PACK_A2, PACK_ES, PACK_WAT, PACK_WBT, PACK_WCT, PACK_WUP, PACK_WUPT };
+// 32-row blocks of the transposed upsample pack (PACK_WUPT, dmel_kernel): mel channels padded to 32
+__host__ __device__ inline int wupt_blocks(int M8) { return (M8 / 8 + 31) / 32; }
 struct PackArgs {
   int kind;
   int C, M8, FL, NW;
@@ -212,5 +215,19 @@ hipError_t launch_flow_bwd_post(const FlowBwdArgs& a, hipStream_t s);
 int flow_bwd_workgroups(const RowGeom& g);
 hipError_t launch_start_wgrad(const StartWgradArgs& a, hipStream_t s);
 int start_wgrad_workgroups(const RowGeom& g);
+
+// Input gradient of the upsample + squeeze (model.py:186-193): the forward's per-phase [M8 x 512] GEMM over mel frames
+// q, q-1, q-2, q-3 transposed, summed over phases and taps (train.hip: dmel_kernel):
+//   d mel[b][i][f] = sum_{p, j, m} Wup_p[m][128 j + i] . d spect_p[m][frame f + j of utterance b] / scale
+struct DmelArgs {
+  RowGeom g;
+  const _Float16* GSP;      // d spect planes [M8/64][R][64] (loss-scaled)
+  const _Float16* wupt;     // PACK_WUPT: [32 p][4 j][M8/64 t][wupt_blocks][4 s][64 lanes][8]: lane (r, h), element e
+                            //   = Wup_p[pos_to_chan(64 t + 32 h + 8 s + e)][128 j + 32 blk + r]  (0 past the mel channels)
+  int M, M8;                // mel channels, 8 M
+  float inv_scale;
+  float* g_mel;             // [B][M][T] fp32: every entry written (frames without a valid spectrogram column: 0)
+};
+hipError_t launch_dmel(const DmelArgs& a, hipStream_t s);
 
 }  // namespace wg

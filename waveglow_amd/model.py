@@ -365,10 +365,13 @@ class WaveGlow(nn.Module):
 
   def forward(self, forward_input):
     """model.py:178-221: (mel [B,M,F], audio [B,S]) -> (z [B,8,L], [log_s_k], [log_det_W_k]).
-    With grad mode on and trainable parameters this is the training direction (waveglow_amd/train.py: saved
-    activations, ``loss.backward()`` runs the library's backward pass); otherwise the lighter inference-only pass."""
+    With grad mode on and trainable parameters, or a ``mel`` / ``audio`` that requires grad (a frozen model used as a
+    likelihood loss), this is the training direction (waveglow_amd/train.py: saved activations, ``loss.backward()`` runs
+    the library's backward pass and fills ``mel.grad`` / ``audio.grad`` too); otherwise the lighter inference-only pass.
+    A shape the training direction does not take raises ``WgError`` there -- never a silent no-grad pass."""
     spect, audio = forward_input
-    if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+    if torch.is_grad_enabled() and (spect.requires_grad or audio.requires_grad
+                                    or any(p.requires_grad for p in self.parameters())):
       from .train import train_forward
       # grad_scale: loss scale of the fp16 gradient planes (0 = automatic, 2^round(log2 N) for the reference's mean loss)
       return train_forward(self, spect, audio, float(getattr(self, "grad_scale", 0.0)))

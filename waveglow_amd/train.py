@@ -250,7 +250,7 @@ class _Weights:
   orders).  ``pack_weights`` / ``wn_forward_fragments`` / ``plain_fragments`` / ``to_fragments`` above are the same
   computation written as torch ops: the tests hold the library to them."""
 
-  def __init__(self, model, tensors, wn: bool, flow_c: List[int], eng, stream):
+  def __init__(self, model, tensors, wn: bool, flow_c: List[int], eng, stream, want_wupt: bool = False):
     hp = model._hp
     Cc, nf, nl = hp.n_channels, model.n_flows, hp.n_layers
     M8 = hp.n_mel_channels * 8
@@ -265,6 +265,8 @@ class _Weights:
     self.wat, self.wbt = h16(FL * Cc * (Cc + 64)), h16(FL * Cc * 6 * Cc)
     self.wct, self.wup = h16(M8 * FL * 2 * Cc), h16(32 * M8 * 512)
     self.b1, self.b2, self.bup = f32(FL, 2 * Cc), f32(FL, Cc), f32(M8)
+    # the transposed upsample of the mel input gradient: packed only for a step that needs d mel
+    self.wupt = h16(32 * 4 * M8 * ((hp.n_mel_channels + 31) // 32) * 32) if want_wupt else None
     # per-flow operands as rows of one buffer each
     small = f32(nf, Cc * 4 + Cc + 8 + 64)
     self._small = small
@@ -277,7 +279,8 @@ class _Weights:
     self.struct = _lib.WgTrainWeights(_ptr(self.a1), _ptr(self.a1c), _ptr(self.b1), _ptr(self.a2), _ptr(self.b2), _ptr(self.es),
                                       _ptr(self.wat), _ptr(self.wbt), _ptr(self.wct), _ptr(self.wup), _ptr(self.bup),
                                       C.cast(self._arrs[0], C.c_void_p), C.cast(self._arrs[1], C.c_void_p),
-                                      C.cast(self._arrs[2], C.c_void_p), C.cast(self._arrs[3], C.c_void_p))
+                                      C.cast(self._arrs[2], C.c_void_p), C.cast(self._arrs[3], C.c_void_p),
+                                      _ptr(self.wupt) if want_wupt else None)
     self.wn = int(wn)
     self.params = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
     self.aux = torch.empty(eng.lib.wg_train_prepare_bytes(eng.handle), dtype=torch.uint8, device=dev)
@@ -414,8 +417,11 @@ def flow_backward_schedule(n_flows: int, run_flow, bufs, group=None) -> None:
 
 
 class _TrainFn(torch.autograd.Function):
-  """Inputs: the module's parameters in the library's canonical order (``canonical_params``); outputs (z, log_s...).
-  backward() returns one gradient per parameter, each a view of ONE flat buffer the library fills."""
+  """Inputs: mel, audio and the module's parameters in the library's canonical order (``canonical_params``); outputs
+  (z, log_s...).  backward() returns what ``ctx.needs_input_grad`` asks for: d mel / d audio (written by the library
+  into tensors of their own), and one gradient per parameter, each a view of ONE flat buffer the library fills --
+  or, when no parameter needs one (a frozen model used as a loss), no parameter gradient at all: the library then runs
+  the data-gradient chain alone (include/waveglow_amd.h: wg_train_backward_ex)."""
 
   @staticmethod
   def forward(ctx, model, mel, audio, scale, wn, *params):
@@ -428,7 +434,7 @@ class _TrainFn(torch.autograd.Function):
     if int(lib.wg_wn_waves(model._hp.n_channels)) <= 0:
       raise _lib.WgError(f"n_channels={model._hp.n_channels} unsupported (64, 128, 256, 512)")
     stream = torch.cuda.current_stream(mel.device).cuda_stream
-    wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream)
+    wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=ctx.needs_input_grad[1])
     z = torch.empty((B, model.n_group, L), dtype=torch.float32, device=mel.device)
     log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=mel.device) for c in flow_c]
     nbytes = lib.wg_train_workspace_bytes(eng.handle, B, F_, S)
@@ -456,48 +462,63 @@ class _TrainFn(torch.autograd.Function):
     dev = ctx.audio.device
     nf = model.n_flows
     hp = model._hp
-    bufs = GradBuffers(hp.n_channels, hp.n_layers, nf, hp.n_mel_channels * 8, dev)
-    gstruct, _keep = bufs.struct()
+    want_mel, want_audio = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+    want_params = any(ctx.needs_input_grad[5:])
+    poison = os.environ.get("WG_TRAIN_POISON_GRADS") == "1"
+    # input gradients: every entry is written by the library (NaN first under WG_TRAIN_POISON_GRADS=1, tests)
+    new = (lambda *sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)) if poison else \
+        (lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev))
+    g_mel = new(B, hp.n_mel_channels, F_) if want_mel else None
+    g_audio = new(B, S) if want_audio else None
+    bufs = GradBuffers(hp.n_channels, hp.n_layers, nf, hp.n_mel_channels * 8, dev) if want_params else None
+    gstruct, _keep = bufs.struct() if want_params else (None, None)
+    gs_ptr = C.byref(gstruct) if want_params else None
+    gm_ptr = _ptr(g_mel) if want_mel else None
+    ga_ptr = _ptr(g_audio) if want_audio else None
     gz = g_z.float().contiguous() if g_z is not None else None
     gls = [g.float().contiguous() if g is not None else None for g in g_log_s]
     gl_arr = (C.c_void_p * nf)(*[(g.data_ptr() if g is not None else None) for g in gls])
     stream = torch.cuda.current_stream(dev).cuda_stream
     gz_ptr = _ptr(gz) if gz is not None else None
-    group = _ddp_group(model)
+    # input gradients stay local (as under torch DDP); only parameter gradients are averaged over the ranks
+    group = _ddp_group(model) if want_params else None
     if group is None:
-      _lib.check(lib.wg_train_backward(eng.handle, C.byref(wts.struct), C.byref(gstruct), gz_ptr, gl_arr,
-                                       C.c_float(ctx.scale), _ptr(ctx.audio), B, F_, S, _ptr(ctx.ws), ctx.ws.numel(),
-                                       C.c_void_p(stream)))
+      _lib.check(lib.wg_train_backward_ex(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
+                                          _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(),
+                                          nf - 1, 0, C.c_void_p(stream)))
     else:
       # Data parallel: the backward pass is cut at flow boundaries and every flow's gradients -- ONE contiguous region
       # of the flat buffer -- are all-reduced right behind it (flow_backward_schedule).  What follows (weight-norm
       # backward, the fold's chain rule: wg_train_param_grads) is linear in these gradients, so averaging here equals
       # averaging the parameter gradients (the logdet term of the 1x1 weights is identical on every rank).
       def run_flow(k):
-        _lib.check(lib.wg_train_backward_flows(eng.handle, C.byref(wts.struct), C.byref(gstruct), gz_ptr, gl_arr,
-                                               C.c_float(ctx.scale), _ptr(ctx.audio), B, F_, S, _ptr(ctx.ws),
-                                               ctx.ws.numel(), k, k, C.c_void_p(stream)))
+        _lib.check(lib.wg_train_backward_ex(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
+                                            _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(), k, k,
+                                            C.c_void_p(stream)))
       flow_backward_schedule(nf, run_flow, bufs, group)
     ctx.guard.release()
     # Overflow of the fp16 gradient planes (the automatic scale 2^round(log2 N) assumes the reference's MEAN loss; a
     # loss with another normalisation needs model.grad_scale) or inf / nan inputs: every gradient tensor is checked,
     # on the device.  model.grad_finite is read by waveglow_amd.training.train() before the optimiser step;
     # WG_TRAIN_CHECK_FINITE=1 raises here (one host sync per step).
-    # (one reduction: inf / nan anywhere makes the sum non-finite, and 8.6e7 finite fp32 values cannot overflow it)
-    model.grad_finite = torch.isfinite(bufs.flat.sum())
+    # (one reduction per tensor: inf / nan anywhere makes a sum non-finite, and 8.6e7 finite fp32 values cannot overflow it)
+    sums = [t.sum() for t in (bufs.flat if want_params else None, g_mel, g_audio) if t is not None]
+    model.grad_finite = torch.isfinite(torch.stack(sums)).all() if len(sums) > 1 else torch.isfinite(sums[0])
     if os.environ.get("WG_TRAIN_CHECK_FINITE") == "1" and not bool(model.grad_finite):
       ctx.wts = None
       raise _lib.WgError(nonfinite_message(ctx.scale))
+    ctx.wts = None
+    if not want_params:
+      return (None, g_mel, g_audio, None, None, *([None] * len(ctx.shapes)))
     # one gradient per parameter, views of one flat buffer in the canonical order
     sizes = [math.prod(sh) for sh in ctx.shapes]
     flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-    if os.environ.get("WG_TRAIN_POISON_GRADS") == "1":
+    if poison:
       flat.fill_(float("nan"))
     _lib.check(lib.wg_train_param_grads(eng.handle, wts.params, wts.wn, C.byref(gstruct), _ptr(wts.aux), wts.aux.numel(),
                                         _ptr(flat), C.c_void_p(stream)))
-    ctx.wts = None
     grads = [v.view(sh) for v, sh in zip(flat.split(sizes), ctx.shapes)]
-    return (None, None, None, None, None, *grads)
+    return (None, g_mel, g_audio, None, None, *grads)
 
 
 def nonfinite_message(scale: float) -> str:
@@ -507,7 +528,9 @@ def nonfinite_message(scale: float) -> str:
 
 
 def train_forward(model, mel: torch.Tensor, audio: torch.Tensor, grad_scale: float = 0.0):
-  """(z, [log_s_k], [log_det_W_k]) with an autograd graph back to the module's parameters (model.py:178-221)."""
+  """(z, [log_s_k], [log_det_W_k]) with an autograd graph back to the module's parameters and to ``mel`` / ``audio``
+  (model.py:178-221).  The crop to a multiple of n_group and ``.contiguous()`` are torch ops in front of the autograd
+  node: dropped trailing samples get a zero gradient and the input gradients the inputs' own shapes."""
   if mel.device.type != "cuda":
     raise _lib.WgError("waveglow_amd runs on MI355X only: there is no CPU fallback")
   if mel.dtype != torch.float32 or audio.dtype != torch.float32:
