@@ -325,6 +325,28 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* w, const wg_train
                          int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
                          int32_t flow_hi, int32_t flow_lo, void* stream);
 
+/* Differentiable synthesis: WaveGlow.infer with injected noise (src/waveglow/model.py:223-273) with saved state, and its
+ * backward w.r.t. mel and the noise (the weights are constants).  Both run on the training workspace of the same
+ * geometry, wg_train_workspace_bytes(h, B, n_frames, 256 * n_frames) (infer's trim to 256 T samples is forward's crop to
+ * audio_len), and on the wg_train_weights of wg_train_prepare (with wupt for g_mel).  The inverse 1x1 matrices are those
+ * wg_infer uses: the handle must be finalised with the same weights (WG_ERR_STATE otherwise).
+ *
+ * Forward: mel [B][n_mel][n_frames] fp32, z_init [B][c_last][L] fp32, z_early[i] [B][n_early_size][L] fp32 in descending
+ * flow order (as wg_infer), audio [B][256 n_frames] fp32 out; L = 32 n_frames.  `fresh` as for wg_train_forward.  The
+ * workspace must stay untouched until wg_train_infer_backward has run.  Enqueue-only. */
+int wg_train_infer_forward(wg_handle* h, const wg_train_weights* w, const void* mel, const void* z_init,
+                           const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
+                           int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of the last wg_train_infer_forward on this workspace.  g_audio [B][256 n_frames] fp32 is the gradient of the
+ * returned audio; `scale` multiplies it on entry (fp16 gradient planes) and is divided out of every result.  Outputs,
+ * each optional (null: not computed) and written entirely (no accumulation): g_mel [B][n_mel][n_frames],
+ * g_z_init [B][c_last][L], g_z_early[i] [B][n_early_size][L] (g_z_early itself or any entry may be null).  Runs on
+ * `stream` alone.  Enqueue-only. */
+int wg_train_infer_backward(wg_handle* h, const wg_train_weights* w, const float* g_audio, float scale, float sigma,
+                            float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
+                            int32_t n_frames, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Diagnostic builds only (-DWG_STAMPS): device buffer of n_tiles*8 uint64 that the WN-layer kernel fills with
  * s_memtime stamps at its phase boundaries (last launch wins).  A no-op pointer in the shipped library. */
 int wg_debug_set_stamp_buffer(wg_handle* h, void* device_buffer);

@@ -243,6 +243,11 @@ const int* wg_internal_flow_channels(const wg_handle* h) { return h ? h->c_k.dat
 int wg_internal_device(const wg_handle* h) { return h ? h->device : -1; }
 int wg_internal_n_cu(const wg_handle* h) { return h ? h->n_cu : 256; }   // of the HANDLE's device (wg_create)
 wg::RowGeom wg_internal_geom(const wg_handle* h, int B, int L, int T) { return make_geom(h->cfg, B, L, T); }
+// W_k^-1 of the finalised handle on the device (fp32 of the fp64 inverse, the matrix wg_infer uses), null before wg_finalize
+const float* wg_internal_winv(const wg_handle* h, int k) {
+  if (!h || !h->finalized || k < 0 || k >= (int)h->flows.size()) return nullptr;
+  return (const float*)(h->d_blob + h->flows[k].winv);
+}
 // one profiling event of class cls on stream s (a no-op unless wg_profile_enable is on); events come in begin/end pairs
 void wg_internal_prof_event(wg_handle* h, void* s, int cls) {
   if (!h || !h->prof || !((h->prof_mask >> cls) & 1u)) return;

@@ -1081,32 +1081,22 @@ __global__ void __launch_bounds__(FB_ROWS) flow_bwd_pre_kernel(const FlowBwdArgs
   *(half8*)(a.GO + prow * 64) = o16;
 }
 
-// Flow backward, part 2 (after the WN backward): start conv, 1x1 conv, peel.
-//   d a0 += Wstart^T d x_0 ;  d(W z)= (d a0 | d a1) ;  d z_in = W^T d(W z) ;  d W += d(W z) z_in^T  (model.py:64, :117)
-__global__ void __launch_bounds__(FB_ROWS) flow_bwd_post_kernel(const FlowBwdArgs a) {
-  __shared__ float s_g[FB_ROWS][9];
-  __shared__ float s_x[FB_ROWS][9];
-  const int L = a.g.L;
-  const size_t nrows = (size_t)a.g.B * L;
-  const size_t row = (size_t)blockIdx.x * FB_ROWS + threadIdx.x;
-  const int h = a.h, c = a.c;
-  float gy[kMaxGroup], xin[kMaxGroup];
-#pragma unroll
-  for (int j = 0; j < kMaxGroup; ++j) { gy[j] = 0.0f; xin[j] = 0.0f; }
-  // ---- d a0 += Wstart^T d x_0.  A thread owns one row, but a row's 512 bytes of d x_0 sit in four planes whose rows for
-  // consecutive t are far apart (phase-major): read per owner, every load instruction touched 64 different 128-byte lines
-  // for 16 bytes each (58 us per launch).  Now 8 lanes fetch one row's 128-byte line of a plane together, multiply their
-  // 8 channels by their rows of Wstart and the partial sums meet in LDS.
-  __shared__ unsigned s_prow[FB_ROWS];
-  __shared__ float s_wn[FB_ROWS][4];
-  int b = 0, t = 0;
+// d a0 += Wstart^T d x_0 (model.py:117) for the FB_ROWS rows of this workgroup: s_wn[thread][j], j < h.  A thread owns one
+// row, but a row's 512 bytes of d x_0 sit in four planes whose rows for consecutive t are far apart (phase-major): read per
+// owner, every load instruction touched 64 different 128-byte lines for 16 bytes each (58 us per launch).  Now 8 lanes
+// fetch one row's 128-byte line of a plane together, multiply their 8 channels by their rows of Wstart and the partial
+// sums meet in LDS.  Ends with a barrier; (b, t) of the thread's own row are returned.
+__device__ __forceinline__ void start_dgrad_rows(const _Float16* __restrict__ GX, const float* __restrict__ wstart, int C, int h,
+                                                 const RowGeom& g, size_t row, unsigned* s_prow, float (*s_wn)[4], int& b, int& t) {
+  const int L = g.L;
+  const size_t nrows = (size_t)g.B * L;
   {
     unsigned pr = 0xffffffffu;
     if (row < nrows) {
       const unsigned r32 = (unsigned)row;
       b = (int)(r32 / (unsigned)L);
       t = (int)(r32 - (unsigned)b * (unsigned)L);
-      pr = (unsigned)kRowPad + (unsigned)(t & 31) * (unsigned)a.g.Rp + (unsigned)b * (unsigned)a.g.Fp + (unsigned)a.g.Gf + (unsigned)(t >> 5);
+      pr = (unsigned)kRowPad + (unsigned)(t & 31) * (unsigned)g.Rp + (unsigned)b * (unsigned)g.Fp + (unsigned)g.Gf + (unsigned)(t >> 5);
     }
     s_prow[threadIdx.x] = pr;
   }
@@ -1118,17 +1108,17 @@ __global__ void __launch_bounds__(FB_ROWS) flow_bwd_post_kernel(const FlowBwdArg
     for (int ps = 0; ps < FB_ROWS / 32; ++ps)
 #pragma unroll
       for (int j = 0; j < 4; ++j) wacc[ps][j] = 0.0f;
-    for (int cc = 0; cc < a.C / 64; ++cc) {
+    for (int cc = 0; cc < C / 64; ++cc) {
       float w[8][4];                                             // Wstart rows of this lane's 8 channels of the chunk
 #pragma unroll
       for (int e = 0; e < 8; ++e)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[e][j] = (j < h) ? a.wstart[(cc * 64 + sub * 8 + e) * h + j] : 0.0f;
+        for (int j = 0; j < 4; ++j) w[e][j] = (j < h) ? wstart[(cc * 64 + sub * 8 + e) * h + j] : 0.0f;
 #pragma unroll
       for (int ps = 0; ps < FB_ROWS / 32; ++ps) {
         const unsigned pr = s_prow[ps * 32 + r8];
         if (pr == 0xffffffffu) continue;
-        const half8 x = *(const half8*)(a.GX + ((size_t)cc * a.g.R + pr) * 64 + sub * 8);
+        const half8 x = *(const half8*)(GX + ((size_t)cc * g.R + pr) * 64 + sub * 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float xv = (float)x[e];
@@ -1149,6 +1139,24 @@ __global__ void __launch_bounds__(FB_ROWS) flow_bwd_post_kernel(const FlowBwdArg
       }
   }
   __syncthreads();
+}
+
+// Flow backward, part 2 (after the WN backward): start conv, 1x1 conv, peel.
+//   d a0 += Wstart^T d x_0 ;  d(W z)= (d a0 | d a1) ;  d z_in = W^T d(W z) ;  d W += d(W z) z_in^T  (model.py:64, :117)
+__global__ void __launch_bounds__(FB_ROWS) flow_bwd_post_kernel(const FlowBwdArgs a) {
+  __shared__ float s_g[FB_ROWS][9];
+  __shared__ float s_x[FB_ROWS][9];
+  const int L = a.g.L;
+  const size_t nrows = (size_t)a.g.B * L;
+  const size_t row = (size_t)blockIdx.x * FB_ROWS + threadIdx.x;
+  const int h = a.h, c = a.c;
+  float gy[kMaxGroup], xin[kMaxGroup];
+#pragma unroll
+  for (int j = 0; j < kMaxGroup; ++j) { gy[j] = 0.0f; xin[j] = 0.0f; }
+  __shared__ unsigned s_prow[FB_ROWS];
+  __shared__ float s_wn[FB_ROWS][4];
+  int b = 0, t = 0;
+  start_dgrad_rows(a.GX, a.wstart, a.C, h, a.g, row, s_prow, s_wn, b, t);
   if (row < nrows) {
     {
       const float4* gp = (const float4*)(a.GZ + row * 8);
@@ -1249,6 +1257,136 @@ hipError_t launch_flow_bwd_pre(const FlowBwdArgs& a, hipStream_t s) {
 }
 hipError_t launch_flow_bwd_post(const FlowBwdArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(flow_bwd_post_kernel, dim3(flow_bwd_workgroups(a.g)), dim3(FB_ROWS), 0, s, a);
+  return hipGetLastError();
+}
+
+// =============================================================================================
+// Synthesis backward (wg_train_infer_backward): inverse flow step k (model.py:253-259) differentiated, before the WN
+// backward.  With u1 = (y1 - b) e^-s and g = d w (the step's output, early channels already peeled):
+//   g_v = W^-T g ;  d y0 = g_v0 (direct part) ;  d y1 = g_v1 e^-s ;  d b = -g_v1 e^-s ;  d s = -g_v1 u1
+// (d b | d s) is the gradient of the WN output: the fp16 K-segment plane of the dgrad chain, as flow_bwd_pre_kernel.
+// =============================================================================================
+__global__ void __launch_bounds__(FB_ROWS) inv_bwd_pre_kernel(const InvBwdArgs a) {
+  const int L = a.g.L;
+  const size_t nrows = (size_t)a.g.B * L;
+  const size_t row = (size_t)blockIdx.x * FB_ROWS + threadIdx.x;
+  if (row >= nrows) return;
+  const unsigned r32 = (unsigned)row;
+  const int b = (int)(r32 / (unsigned)L), t = (int)(r32 - (unsigned)b * (unsigned)L);
+  const int h = a.h, c = a.c;
+  float g[kMaxGroup], y[kMaxGroup], o[kMaxGroup];
+  {
+    const float4* yp = (const float4*)(a.Y + row * 8);
+    const float4* op = (const float4*)(a.OUT + row * 8);
+    const float4 y0 = yp[0], y1 = yp[1], o0 = op[0], o1 = op[1];
+    y[0] = y0.x; y[1] = y0.y; y[2] = y0.z; y[3] = y0.w; y[4] = y1.x; y[5] = y1.y; y[6] = y1.z; y[7] = y1.w;
+    o[0] = o0.x; o[1] = o0.y; o[2] = o0.z; o[3] = o0.w; o[4] = o1.x; o[5] = o1.y; o[6] = o1.z; o[7] = o1.w;
+  }
+  if (a.g_audio) {
+    // step 0 writes audio[b][8t + j] = w[j] (model.py:273): the row's 8 samples
+    const float4* gp = (const float4*)(a.g_audio + (size_t)b * L * 8 + (size_t)t * 8);
+    const float4 g0 = gp[0], g1 = gp[1];
+    g[0] = g0.x; g[1] = g0.y; g[2] = g0.z; g[3] = g0.w; g[4] = g1.x; g[5] = g1.y; g[6] = g1.z; g[7] = g1.w;
+#pragma unroll
+    for (int j = 0; j < kMaxGroup; ++j) g[j] *= a.scale;
+  } else {
+    const float4* gp = (const float4*)(a.GZ + row * 8);
+    const float4 g0 = gp[0], g1 = gp[1];
+    g[0] = g0.x; g[1] = g0.y; g[2] = g0.z; g[3] = g0.w; g[4] = g1.x; g[5] = g1.y; g[6] = g1.z; g[7] = g1.w;
+  }
+  float gv[kMaxGroup];
+#pragma unroll
+  for (int r = 0; r < kMaxGroup; ++r) {                  // (W^-1)^T g   (model.py:259)
+    float s = 0.0f;
+#pragma unroll
+    for (int q = 0; q < kMaxGroup; ++q)
+      if (r < c && q < c) s = fmaf(a.winv[q * c + r], g[q], s);
+    gv[r] = s;
+  }
+  float gy[kMaxGroup], gout[kMaxGroup];
+#pragma unroll
+  for (int j = 0; j < kMaxGroup; ++j) { gy[j] = 0.0f; gout[j] = 0.0f; }
+#pragma unroll
+  for (int j = 0; j < kMaxGroup; ++j) {
+    if (j < h) gy[j] = gv[j];                            // d y0 (direct part)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (j >= h && j - h == q && q < h) {
+        const float e = expf(-o[j]);                     // o[h+q] = s_q, o[q] = b_q     (model.py:253-255)
+        const float u1 = (y[j] - o[q]) * e;
+        const float gb = gv[j] * e;
+        gy[j] = gb;                                      // d y1
+        gout[q] = -gb;                                   // d b
+        gout[j] = -gv[j] * u1;                           // d s
+      }
+  }
+  float4* gp = (float4*)(a.GZ + row * 8);
+  gp[0] = make_float4(gy[0], gy[1], gy[2], gy[3]);
+  gp[1] = make_float4(gy[4], gy[5], gy[6], gy[7]);
+  half8 o16;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o16[j] = (_Float16)gout[j];
+  const size_t prow = (size_t)kRowPad + (size_t)(t & 31) * a.g.Rp + (size_t)b * a.g.Fp + a.g.Gf + (t >> 5);
+  *(half8*)(a.GO + prow * 64) = o16;
+}
+
+// ... after the WN backward: d y0 += Wstart^T d x_0, then the early channels that step k+1 prepended are peeled
+// (model.py:260-271): d z_early = sigma d y[:n_peel], the rest is d w of step k+1.  The first inverse step's input is
+// sigma z_init (model.py:243-244): d z_init = sigma d y.
+__global__ void __launch_bounds__(FB_ROWS) inv_bwd_post_kernel(const InvBwdArgs a) {
+  __shared__ unsigned s_prow[FB_ROWS];
+  __shared__ float s_wn[FB_ROWS][4];
+  const int L = a.g.L;
+  const size_t nrows = (size_t)a.g.B * L;
+  const size_t row = (size_t)blockIdx.x * FB_ROWS + threadIdx.x;
+  const int h = a.h, c = a.c;
+  int b = 0, t = 0;
+  start_dgrad_rows(a.GX, a.wstart, a.C, h, a.g, row, s_prow, s_wn, b, t);
+  if (row >= nrows) return;
+  float gy[kMaxGroup];
+  {
+    const float4* gp = (const float4*)(a.GZ + row * 8);
+    const float4 g0 = gp[0], g1 = gp[1];
+    gy[0] = g0.x; gy[1] = g0.y; gy[2] = g0.z; gy[3] = g0.w; gy[4] = g1.x; gy[5] = g1.y; gy[6] = g1.z; gy[7] = g1.w;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (j < h) gy[j] += s_wn[threadIdx.x][j];
+  const float f = a.sigma / a.scale;
+  if (a.last) {
+    if (a.g_z_init) {
+#pragma unroll
+      for (int e = 0; e < kMaxGroup; ++e)
+        if (e < c) a.g_z_init[((size_t)b * c + e) * L + t] = f * gy[e];
+    }
+    return;
+  }
+  const int np = a.n_peel;
+  if (a.g_peel) {
+#pragma unroll
+    for (int e = 0; e < kMaxGroup; ++e)
+      if (e < np) a.g_peel[((size_t)b * np + e) * L + t] = f * gy[e];
+  }
+  float gw[kMaxGroup];
+#pragma unroll
+  for (int e = 0; e < kMaxGroup; ++e) {
+    float v = 0.0f;
+#pragma unroll
+    for (int q = 0; q < kMaxGroup; ++q)
+      if (q - np == e && q < c) v = gy[q];
+    gw[e] = v;
+  }
+  float4* gp = (float4*)(a.GZ + row * 8);
+  gp[0] = make_float4(gw[0], gw[1], gw[2], gw[3]);
+  gp[1] = make_float4(gw[4], gw[5], gw[6], gw[7]);
+}
+
+hipError_t launch_inv_bwd_pre(const InvBwdArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(inv_bwd_pre_kernel, dim3(flow_bwd_workgroups(a.g)), dim3(FB_ROWS), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_inv_bwd_post(const InvBwdArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(inv_bwd_post_kernel, dim3(flow_bwd_workgroups(a.g)), dim3(FB_ROWS), 0, s, a);
   return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@ hipEvent_t wg_internal_sync_event(wg_handle* h);                          // api
 hipEvent_t wg_internal_mark_event(wg_handle* h, int slot);                // api.cpp
 hipError_t wg_internal_upload(wg_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);   // api.cpp
 int wg_internal_n_cu(const wg_handle* h);                                 // api.cpp
+const float* wg_internal_winv(const wg_handle* h, int k);                 // api.cpp
 
 namespace {
 
@@ -268,6 +269,94 @@ PRun run_of(const _Float16* base, int n_chunks, int dt) {
   return r;
 }
 
+
+// tile width of the fused layer kernel in the training forward: as the inference path chooses it (api.cpp: run_wn)
+int fwd_block_n(const Ctx& x) {
+  const int C = x.C;
+  int BNw = wn_block_n(C);
+  if (BNw == 128 && (int64_t)kPhases * (x.g.Rp / 128) < (int64_t)x.n_cu) BNw = 64;
+  if (const char* e = getenv("WG_FORCE_BN")) {
+    const int f = atoi(e);
+    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
+  }
+  return BNw;
+}
+
+// mel planes, then upsample (ConvTranspose1d 1024/256, model.py:145-150, :186-189) + squeeze (:191-193): one matrix per
+// phase -> the SP planes every layer's conditioning K-segment reads
+int spect_planes(const Ctx& x, const wg_train_weights* wt, const void* mel, hipStream_t s) {
+  const RowGeom& g = x.g;
+  const TrainWs& w = x.w;
+  TR_TRY(launch_mel_plane(mel, 0, x.c->n_mel_channels, g, w.MELP, s));
+  PGemmArgs a;
+  memset(&a, 0, sizeof a);
+  a.n_runs = 4;
+  for (int j = 0; j < 4; ++j) a.run[j] = run_of(w.MELP, 2, -32 * j);
+  a.A = (const _Float16*)wt->wup;
+  a.a_phase_stride = (long long)x.M8 * 512;
+  a.ktot = 512;
+  a.n_blk = x.M8 / 32;
+  a.M = x.M8;
+  a.bias = wt->bup;
+  a.g = g;
+  a.o0 = w.SP;
+  TR_TRY(launch_plane_gemm(a, s));
+  return WG_OK;
+}
+
+// The WN of flow k with saved activations (X / T / S / A planes of its layers), its output accumulated into OUT[k]
+// (initialised by the flow step before it).  The flow step's writes on `s` come first; sB (the second chain, = s for one)
+// is joined back into `s` at the end.
+int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int k, int BNw, hipStream_t s, hipStream_t sB) {
+  const wg_config& c = *x.c;
+  const RowGeom& g = x.g;
+  const TrainWs& w = x.w;
+  const int C = x.C, nl = x.nl, M8 = x.M8;
+  const int cc = C / 64, mc = M8 / 64;
+  // per-layer sizes (fp16 elements) of the forward fragment tensors (include/waveglow_amd.h: wg_train_weights)
+  const int NW = wn_waves(C), MBw = C / (32 * NW), MTw = 2 * MBw;
+  const size_t a1_n = (size_t)2 * (3 * cc) * NW * MTw * 2 * 64 * 8, a1c_n = (size_t)2 * mc * NW * MTw * 2 * 64 * 8;
+  const size_t a2_n = (size_t)NW * MBw * (C / 16) * 64 * 8, es_n = (size_t)(C / 32) * 64 * 8;
+  TR_ORDER(order_after(h, s, sB));
+  for (int i = 0; i < nl; ++i) {
+    const int fl = k * nl + i, d = 1 << i;
+    const _Float16* Xi = w.X + (size_t)fl * w.plane_c;
+    _Float16* Ai = w.A + (size_t)fl * w.plane_c;
+    // ONE fused launch per layer (kernels.hip: wn_layer_kernel<..., TR = true>): in_layers[i] + cond_layer slice as one
+    // K-extended GEMM, gate in registers (tanh / sigmoid / acts saved as planes for the backward pass), res rows +
+    // residual add -> x_{i+1}, skip rows folded through WN.end -> OUT   (model.py:123-137)
+    WnLayerArgs a;
+    memset(&a, 0, sizeof a);
+    a.x_in = Xi;
+    a.x_tap = Xi;
+    a.x_chunks_per_tap = cc;
+    a.x_out = (i < nl - 1) ? w.X + (size_t)(fl + 1) * w.plane_c : nullptr;
+    a.wA1 = (const _Float16*)wt->a1 + (size_t)fl * a1_n;
+    a.wA1c = (const _Float16*)wt->a1c + (size_t)fl * a1c_n;
+    a.bias1 = wt->b1 + (size_t)fl * 2 * C;
+    a.wA2 = (const _Float16*)wt->a2 + (size_t)fl * a2_n;
+    a.bias2 = wt->b2 + (size_t)fl * C;
+    a.wEs = (const _Float16*)wt->es + (size_t)fl * es_n;
+    a.out = w.OUT + (size_t)k * w.rows8;
+    a.g = g;
+    a.dil = d;
+    a.n_cond_steps = mc;
+    a.M = c.n_mel_channels;
+    a.has_res = i < nl - 1;
+    a.n_cu = x.n_cu;
+    a.sp = w.SP;
+    a.save_t = w.T + (size_t)fl * w.plane_c;
+    a.save_s = w.S + (size_t)fl * w.plane_c;
+    a.save_a = Ai;
+    for (int half = 0; half < x.halves; ++half) {
+      hipStream_t sh = half ? sB : s;
+      TR_PROF(sh, 4, TR_TRY(launch_part(a, g, BNw, half, x.halves, [&](const WnLayerArgs& q, int bn) { return launch_wn_layer_train(q, C, bn, sh); })));
+    }
+  }
+  TR_ORDER(order_after(h, sB, s));
+  return WG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -324,46 +413,17 @@ int wg_train_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, 
   const RowGeom& g = x.g;
   TrainWs& w = x.w;
   hipStream_t s = (hipStream_t)stream;
-  const int C = x.C, nl = x.nl, M8 = x.M8, K1 = x.K1;
-  const int cc = C / 64, mc = M8 / 64;
-  // per-layer sizes (fp16 elements) of the forward fragment tensors (include/waveglow_amd.h: wg_train_weights)
-  const int NW = wn_waves(C), MBw = C / (32 * NW), MTw = 2 * MBw;
-  const size_t a1_n = (size_t)2 * (3 * cc) * NW * MTw * 2 * 64 * 8, a1c_n = (size_t)2 * mc * NW * MTw * 2 * 64 * 8;
-  const size_t a2_n = (size_t)NW * MBw * (C / 16) * 64 * 8, es_n = (size_t)(C / 32) * 64 * 8;
-  const int n_cu = x.n_cu;
+  const int C = x.C, nl = x.nl;
   // second chain (the caller's stream is the first): see setup
   hipStream_t sB = s;
   if (x.halves == 2 && !x.serial) {
     sB = wg_internal_aux_stream(h, 0);
     if (!sB) return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
   }
-  // tile width of the fused layer kernel: as the inference path chooses it (api.cpp: run_wn)
-  int BNw = wn_block_n(C);
-  if (BNw == 128 && (int64_t)kPhases * (g.Rp / 128) < (int64_t)n_cu) BNw = 64;
-  if (const char* e = getenv("WG_FORCE_BN")) {
-    const int f = atoi(e);
-    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
-  }
-  (void)K1;
+  const int BNw = fwd_block_n(x);
 
   if (fresh) TR_TRY(hipMemsetAsync(workspace, 0, w.zero_bytes, s));
-  TR_TRY(launch_mel_plane(mel, 0, c.n_mel_channels, g, w.MELP, s));
-  {
-    // upsample (ConvTranspose1d 1024/256, model.py:145-150, :186-189) + squeeze (:191-193): one matrix per phase
-    PGemmArgs a;
-    memset(&a, 0, sizeof a);
-    a.n_runs = 4;
-    for (int j = 0; j < 4; ++j) a.run[j] = run_of(w.MELP, 2, -32 * j);
-    a.A = (const _Float16*)wt->wup;
-    a.a_phase_stride = (long long)M8 * 512;
-    a.ktot = 512;
-    a.n_blk = M8 / 32;
-    a.M = M8;
-    a.bias = wt->bup;
-    a.g = g;
-    a.o0 = w.SP;
-    TR_TRY(launch_plane_gemm(a, s));
-  }
+  if ((rc = spect_planes(x, wt, mel, s))) return rc;
   int z_ch = 0;
   for (int k = 0; k <= c.n_flows; ++k) {
     FlowArgs f;
@@ -405,45 +465,7 @@ int wg_train_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, 
     //  drift apart and the forward pass took 0.2-1.0 ms longer than with this join per flow)
     TR_TRY(launch_flow(f, s));
     if (f.last) break;
-    TR_ORDER(order_after(h, s, sB));
-    for (int i = 0; i < nl; ++i) {
-      const int fl = k * nl + i, d = 1 << i;
-      const _Float16* Xi = w.X + (size_t)fl * w.plane_c;
-      _Float16* Ai = w.A + (size_t)fl * w.plane_c;
-      {
-        // ONE fused launch per layer (kernels.hip: wn_layer_kernel<..., TR = true>): in_layers[i] + cond_layer slice as one
-        // K-extended GEMM, gate in registers (tanh / sigmoid / acts saved as planes for the backward pass), res rows +
-        // residual add -> x_{i+1}, skip rows folded through WN.end -> OUT   (model.py:123-137)
-        WnLayerArgs a;
-        memset(&a, 0, sizeof a);
-        a.x_in = Xi;
-        a.x_tap = Xi;
-        a.x_chunks_per_tap = cc;
-        a.x_out = (i < nl - 1) ? w.X + (size_t)(fl + 1) * w.plane_c : nullptr;
-        a.wA1 = (const _Float16*)wt->a1 + (size_t)fl * a1_n;
-        a.wA1c = (const _Float16*)wt->a1c + (size_t)fl * a1c_n;
-        a.bias1 = wt->b1 + (size_t)fl * 2 * C;
-        a.wA2 = (const _Float16*)wt->a2 + (size_t)fl * a2_n;
-        a.bias2 = wt->b2 + (size_t)fl * C;
-        a.wEs = (const _Float16*)wt->es + (size_t)fl * es_n;
-        a.out = w.OUT + (size_t)k * w.rows8;
-        a.g = g;
-        a.dil = d;
-        a.n_cond_steps = mc;
-        a.M = c.n_mel_channels;
-        a.has_res = i < nl - 1;
-        a.n_cu = n_cu;
-        a.sp = w.SP;
-        a.save_t = w.T + (size_t)fl * w.plane_c;
-        a.save_s = w.S + (size_t)fl * w.plane_c;
-        a.save_a = Ai;
-        for (int half = 0; half < x.halves; ++half) {
-          hipStream_t sh = half ? sB : s;
-          TR_PROF(sh, 4, TR_TRY(launch_part(a, g, BNw, half, x.halves, [&](const WnLayerArgs& q, int bn) { return launch_wn_layer_train(q, C, bn, sh); })));
-        }
-      }
-    }
-    TR_ORDER(order_after(h, sB, s));
+    if ((rc = wn_flow_forward(h, x, wt, k, BNw, s, sB))) return rc;
   }
   return WG_OK;
 }
@@ -816,6 +838,281 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
     TR_TRY(launch_slab_reduce_multi(sg, 2, s));
     TR_ORDER(order_after(h, sW, s));      // every gradient of the call is final on the caller's stream
     TR_ORDER(order_after(h, sR, s));
+  }
+  return WG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Differentiable synthesis (include/waveglow_amd.h: wg_train_infer_*): WaveGlow.infer (model.py:223-273) on the training
+// kernels, with the state that enters every inverse step saved, and its backward w.r.t. mel and the noise.
+//   workspace: Zpost[k] = the state y entering inverse step k (step n_flows-1: sigma z_init), OUT[k] = (b | s) of WN_k,
+//   X / T / S / A planes of flow k's layers as in the training forward; the backward keeps GP of every layer for d spect.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+int n_early_flows(const wg_config& c) {
+  int n = 0;
+  for (int k = 0; k < c.n_flows; ++k) n += is_early(c, k);
+  return n;
+}
+
+// common checks and geometry of both calls: audio_len = 256 n_frames (infer's trim, model.py:228)
+int infer_setup(wg_handle* h, const wg_train_weights* wt, int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace,
+                size_t workspace_bytes, Ctx& x, const float** winv) {
+  const wg_config* c = wg_internal_config(h);
+  if (!c) return wg_set_error(WG_ERR_INVALID, "null handle");
+  if (n_frames < 1) return wg_set_error(WG_ERR_INVALID, "bad n_frames");
+  if (c->n_flows > 64) return wg_set_error(WG_ERR_INVALID, "too many flows");
+  int rc = setup(h, B, n_frames, n_frames * c->upsample_stride, workspace, workspace_bytes, x);
+  if (rc) return rc;
+  if ((rc = check_weights(wt, c->n_flows))) return rc;
+  if (n_z_early != n_early_flows(*c)) return wg_set_error(WG_ERR_INVALID, "wrong number of early-noise tensors");
+  for (int k = 0; k < c->n_flows; ++k)
+    if (!(winv[k] = wg_internal_winv(h, k)))
+      return wg_set_error(WG_ERR_STATE, "wg_finalize has not been called: the synthesis direction uses the handle's W^-1");
+  return WG_OK;
+}
+
+// the step's next flow j: its state, WN output and x_0 planes get buffers of their own
+void infer_next(const Ctx& x, const wg_train_weights* wt, int j, FlowArgs& f) {
+  f.c_next = x.ck[j];
+  f.h_next = f.c_next / 2;
+  f.wstart = wt->wstart[j];
+  f.bstart = wt->bstart[j];
+  f.out_init = wt->out_init[j];
+  f.Z_w = x.w.Zpost + (size_t)j * x.w.rows8;
+  f.out_w = x.w.OUT + (size_t)j * x.w.rows8;
+  f.x = x.w.X + (size_t)(j * x.nl) * x.w.plane_c;
+  f.skip_x = 0;
+  f.a0p = nullptr;
+}
+
+}  // namespace
+
+int wg_train_infer_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* z_init,
+                           const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
+                           int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!wt || !mel || !z_init || !audio || !workspace || (n_z_early > 0 && !z_early))
+    return wg_set_error(WG_ERR_INVALID, "null argument");
+  Ctx x;
+  const float* winv[64];
+  int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, x, winv);
+  if (rc) return rc;
+  for (int i = 0; i < n_z_early; ++i)
+    if (!z_early[i]) return wg_set_error(WG_ERR_INVALID, "null early-noise tensor");
+  const wg_config& c = *x.c;
+  hipStream_t s = (hipStream_t)stream;
+  hipStream_t sB = s;
+  if (x.halves == 2 && !x.serial) {
+    sB = wg_internal_aux_stream(h, 0);
+    if (!sB) return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
+  }
+  const int BNw = fwd_block_n(x);
+  if (fresh) TR_TRY(hipMemsetAsync(workspace, 0, x.w.zero_bytes, s));
+  if ((rc = spect_planes(x, wt, mel, s))) return rc;
+  auto base = [&]() {
+    FlowArgs f;
+    memset(&f, 0, sizeof f);
+    f.direction = 0;
+    f.sigma = sigma;
+    f.g = x.g;
+    f.C = x.C;
+    f.io_f16 = 0;
+    return f;
+  };
+  {
+    FlowArgs f = base();            // audio = sigma * z_init   (model.py:243-244)
+    f.first = 1;
+    f.z_extra = z_init;
+    infer_next(x, wt, c.n_flows - 1, f);
+    TR_TRY(launch_flow(f, s));
+  }
+  int ze = 0;
+  for (int k = c.n_flows - 1; k >= 0; --k) {
+    if ((rc = wn_flow_forward(h, x, wt, k, BNw, s, sB))) return rc;
+    // inverse coupling, W_k^-1, early noise in front   (model.py:253-271); the input state stays in Zpost[k]
+    FlowArgs f = base();
+    f.Z = x.w.Zpost + (size_t)k * x.w.rows8;
+    f.out = x.w.OUT + (size_t)k * x.w.rows8;
+    f.c_in = x.ck[k];
+    f.h_in = f.c_in / 2;
+    f.winv = winv[k];
+    if (is_early(c, k)) {
+      f.z_extra = z_early[ze++];
+      f.n_extra = c.n_early_size;
+    }
+    const int c_next = f.c_in + f.n_extra;
+    f.last = (k == 0);
+    if (f.last) {
+      if (c_next != c.n_group) return wg_set_error(WG_ERR_STATE, "flow bookkeeping error");
+      f.c_next = c_next;
+      f.audio_out = audio;
+    } else {
+      if (x.ck[k - 1] != c_next) return wg_set_error(WG_ERR_STATE, "flow bookkeeping error");
+      infer_next(x, wt, k - 1, f);
+    }
+    TR_TRY(launch_flow(f, s));
+  }
+  return WG_OK;
+}
+
+int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const float* g_audio, float scale, float sigma,
+                            float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
+                            int32_t n_frames, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!wt || !g_audio || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
+  if (!(scale > 0.f)) return wg_set_error(WG_ERR_INVALID, "scale must be positive");
+  Ctx x;
+  const float* winv[64];
+  int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, x, winv);
+  if (rc) return rc;
+  if (g_mel && !wt->wupt) return wg_set_error(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
+  const wg_config& c = *x.c;
+  const RowGeom& g = x.g;
+  TrainWs& w = x.w;
+  hipStream_t s = (hipStream_t)stream;
+  const int C = x.C, nl = x.nl, M8 = x.M8, FL = x.FL;
+  const int cc = C / 64;
+  const _Float16* wat = (const _Float16*)wt->wat;
+  const _Float16* wbt = (const _Float16*)wt->wbt;
+  // fragment tensors of the two dgrad GEMMs, as in wg_train_backward_ex
+  const int NW = wn_waves(C), MBw = C / (32 * NW);
+  const size_t kstep_n = (size_t)2 * NW * MBw * 2 * 64 * 8;
+  const size_t wat_n = (size_t)(cc + 1) * kstep_n, wbt_n = (size_t)(6 * cc) * kstep_n;
+  bool fuse = true;                       // WG_TRAIN_NO_FUSE=1: as in wg_train_backward_ex
+  if (const char* e = getenv("WG_TRAIN_NO_FUSE")) fuse = !(*e == '1');
+  int BNw = wn_block_n(C);
+  if (BNw == 128 && (int64_t)kPhases * (g.Rp / 128) < (int64_t)x.n_cu) BNw = 64;
+  if (const char* e = getenv("WG_FORCE_BN")) {
+    const int f = atoi(e);
+    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
+  }
+  if (const char* e = getenv("WG_TRAIN_BWD_BN")) {
+    const int f = atoi(e);
+    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
+  }
+  // index in z_early (descending flow order) of early flow k
+  auto early_index = [&](int k) {
+    int n = 0;
+    for (int q = c.n_flows - 1; q > k; --q) n += is_early(c, q);
+    return n;
+  };
+  // Ascending flow order: the gradient enters at the audio, the output of inverse step 0.  Everything runs on `s`, so the
+  // GO plane, GXL and GZ are reused in stream order (GO[k & 1] only keeps the training direction's plane names).
+  for (int k = 0; k < c.n_flows; ++k) {
+    const int ck = x.ck[k];
+    InvBwdArgs ib;
+    memset(&ib, 0, sizeof ib);
+    ib.g = g;
+    ib.C = C;
+    ib.c = ck;
+    ib.h = ck / 2;
+    ib.scale = scale;
+    ib.sigma = sigma;
+    ib.Y = w.Zpost + (size_t)k * w.rows8;
+    ib.OUT = w.OUT + (size_t)k * w.rows8;
+    ib.winv = winv[k];
+    ib.g_audio = k == 0 ? g_audio : nullptr;
+    ib.GZ = w.GZ;
+    _Float16* const GOk = w.GO[k & 1];
+    ib.GO = GOk;
+    TR_TRY(launch_inv_bwd_pre(ib, s));
+    // the WN data-gradient chain of flow k: wg_train_backward_ex's launches without parameter gradients, one chain
+    _Float16* gx = nullptr;                     // d x_{i+1} (null: the last layer has no res output)
+    for (int i = nl - 1; i >= 0; --i) {
+      const int fl = k * nl + i, d = 1 << i;
+      _Float16* GPi = w.GP + (size_t)fl * 2 * w.plane_c;
+      if (!fuse || i == nl - 1) {
+        // d acts = W_res^T d x_{i+1} + (W_end W_skip_i)^T d out ; gate derivative -> d pre   (wn_layer_kernel MODE 3)
+        WnLayerArgs a;
+        memset(&a, 0, sizeof a);
+        const _Float16* Am = wat + (size_t)fl * wat_n;
+        if (gx) {
+          a.x_tap = gx;
+          a.x_chunks_per_tap = cc;
+          a.sp = GOk;
+          a.n_cond_steps = 1;
+          a.wA1 = Am;
+          a.wA1c = Am + (size_t)cc * kstep_n;
+        } else {
+          a.x_tap = GOk;
+          a.x_chunks_per_tap = 1;
+          a.n_cond_steps = 0;
+          a.wA1 = Am + (size_t)cc * kstep_n;
+          a.wA1c = a.wA1;
+        }
+        a.dil = 0;
+        a.g = g;
+        a.M = c.n_mel_channels;
+        a.n_cu = x.n_cu;
+        a.in0 = w.T + (size_t)fl * w.plane_c;
+        a.in1 = w.S + (size_t)fl * w.plane_c;
+        a.out0 = GPi;
+        TR_PROF(s, 5, TR_TRY(launch_part(a, g, BNw, 0, 1, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, 3, bn, s); })));
+      }
+      {
+        // d x_i = d x_{i+1} + sum_tap W_in[tap]^T d pre (MODE 2), fused with layer i-1's d acts + gate derivative (MODE 4)
+        WnLayerArgs a;
+        memset(&a, 0, sizeof a);
+        a.x_tap = GPi;
+        a.x_chunks_per_tap = 2 * cc;
+        a.n_cond_steps = 0;
+        a.wA1 = wbt + (size_t)fl * wbt_n;
+        a.wA1c = a.wA1;
+        a.dil = -d;
+        a.g = g;
+        a.M = c.n_mel_channels;
+        a.n_cu = x.n_cu;
+        a.in0 = gx;
+        _Float16* const gxi = w.GXL + (size_t)i * w.plane_c;
+        a.out0 = gxi;
+        const int kind = (fuse && i > 0) ? 4 : 2;
+        if (kind == 4) {
+          a.wat_prev = wat + (size_t)(fl - 1) * wat_n;
+          a.gout = GOk;
+          a.t_prev = w.T + (size_t)(fl - 1) * w.plane_c;
+          a.s_prev = w.S + (size_t)(fl - 1) * w.plane_c;
+          a.dpre_prev = w.GP + (size_t)(fl - 1) * 2 * w.plane_c;
+        }
+        TR_PROF(s, 5, TR_TRY(launch_part(a, g, BNw, 0, 1, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, kind, bn, s); })));
+        gx = gxi;
+      }
+    }
+    ib.GX = gx;
+    ib.wstart = wt->wstart[k];
+    ib.last = (k == c.n_flows - 1);
+    if (ib.last) {
+      ib.g_z_init = g_z_init;
+    } else if (is_early(c, k + 1)) {
+      ib.n_peel = c.n_early_size;
+      ib.g_peel = g_z_early ? g_z_early[early_index(k + 1)] : nullptr;
+    }
+    TR_TRY(launch_inv_bwd_post(ib, s));
+  }
+  if (!g_mel) return WG_OK;
+  {
+    // d spect = sum over every layer of cond_layer^T d pre: ONE GEMM with K = FL*2C over the kept d pre planes
+    PGemmArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_runs = 1;
+    a.run[0] = run_of(w.GP, FL * 2 * cc, 0);
+    a.A = (const _Float16*)wt->wct;
+    a.ktot = FL * 2 * C;
+    a.n_blk = M8 / 32;
+    a.M = M8;
+    a.g = g;
+    a.o0 = w.GSP;
+    TR_TRY(launch_plane_gemm(a, s));
+  }
+  {
+    DmelArgs a;                           // d mel = the upsample's transpose applied to d spect (train.hip: dmel_kernel)
+    a.g = g;
+    a.GSP = w.GSP;
+    a.wupt = (const _Float16*)wt->wupt;
+    a.M = c.n_mel_channels;
+    a.M8 = M8;
+    a.inv_scale = 1.0f / scale;
+    a.g_mel = g_mel;
+    TR_TRY(launch_dmel(a, s));
   }
   return WG_OK;
 }

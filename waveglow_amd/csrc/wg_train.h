@@ -119,6 +119,31 @@ struct FlowBwdArgs {
   float* g_audio;           // k == 0, optional: d audio [B][8L] fp32 = W^T d(W audio) / scale  (model.py:195, :64)
 };
 
+// Row kernels of the synthesis backward (include/waveglow_amd.h: wg_train_infer_backward): inverse flow step k of
+// WaveGlow.infer (model.py:246-271) differentiated.  Step k maps its input state y = (y0 | y1) (c_k channels) to
+// w = W_k^-1 (y0 | (y1 - b) e^-s) with (b | s) = WN_k(y0), and prepends sigma * z_early when flow k is an early one.
+// Every gradient plane and GZ carry the loss scale; it is divided out of the outputs only.
+struct InvBwdArgs {
+  RowGeom g;
+  int C, c, h;              // WN channels, c_k, h_k
+  float scale;              // loss scale (pre: applied to g_audio)
+  float sigma;
+  const float* Y;           // [B*L][8] state entering inverse step k (saved by wg_train_infer_forward)
+  const float* OUT;         // [B*L][8] (b | s) of WN_k
+  const float* winv;        // [c][c] W_k^-1 row-major
+  const float* g_audio;     // pre, k == 0: [B][8L] d audio (unscaled); otherwise null and d w comes from GZ
+  float* GZ;                // [B*L][8] fp32: pre in = d w (scaled), out = (d y0 direct | d y1);
+                            //                post in = that, out = d w of step k+1 (early channels peeled)
+  _Float16* GO;             // pre: fp16 plane (1 chunk): ch [0,h) = d b, [h,2h) = d s, rest 0
+  // post
+  const _Float16* GX;       // d x_0 planes [C/64][R][64]
+  const float* wstart;      // [C][h] pos rows
+  int n_peel;               // channels step k+1 prepended (its z_early), 0 if none
+  float* g_peel;            // [B][n_peel][L] d z_early of step k+1 (written, not accumulated), or null
+  float* g_z_init;          // k == n_flows-1 (the first inverse step): [B][c][L] d z_init, or null
+  int last;                 // k == n_flows-1: the state is sigma * z_init
+};
+
 struct StartWgradArgs {
   RowGeom g;
   int C, h;
@@ -213,6 +238,8 @@ hipError_t launch_mel_plane(const void* mel, int io_f16, int M, const RowGeom& g
 hipError_t launch_flow_bwd_pre(const FlowBwdArgs& a, hipStream_t s);
 hipError_t launch_flow_bwd_post(const FlowBwdArgs& a, hipStream_t s);
 int flow_bwd_workgroups(const RowGeom& g);
+hipError_t launch_inv_bwd_pre(const InvBwdArgs& a, hipStream_t s);
+hipError_t launch_inv_bwd_post(const InvBwdArgs& a, hipStream_t s);
 hipError_t launch_start_wgrad(const StartWgradArgs& a, hipStream_t s);
 int start_wgrad_workgroups(const RowGeom& g);
 

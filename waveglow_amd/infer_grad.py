@@ -1,0 +1,144 @@
+"""Differentiable synthesis: ``WaveGlow.infer_differentiable`` under autograd on the HIP library.
+
+Reference: src/waveglow/model.py:223-273 (``infer``; the reference ends it with ``.data``, so its output never carries a
+graph).  Here the output of the frozen vocoder carries one back to ``mel`` and to the noise, so that a waveform-domain loss
+(a multi-resolution STFT loss, a discriminator) can train an acoustic model, or optimise a mel or a noise tensor, through
+it.  The weights are constants: a parameter that requires grad is refused, never silently dropped.
+
+* ``wg_train_infer_forward``: the same 12 WN stacks as the training direction (``wg_train_forward``), in inverse flow
+  order, with the training kernels' saved activations and the state that enters every inverse step; the inverse 1x1
+  matrices are the fp64-computed ones ``infer`` uses (the engine is finalised with the current weights);
+* ``wg_train_infer_backward``: ascending flow order, two row kernels per flow around the training direction's WN
+  data-gradient chain, then the d spect GEMM and the transposed upsample for ``d mel``.
+
+The binding mirrors ``_TrainFn`` (waveglow_amd/train.py): ``_Weights`` from ``wg_train_prepare``, one training workspace
+per outstanding graph, the fp16 loss scale and ``model.grad_finite``.  There is no fallback: CPU tensors raise.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import os
+from typing import List
+
+import torch
+
+from . import _lib
+from .train import _ptr, _SlotGuard, _Weights, canonical_params, nonfinite_message
+
+
+class _InferFn(torch.autograd.Function):
+  """Inputs: model, sigma, loss scale (0 = automatic), weight-norm flag, number of early-noise tensors, mel, z_init,
+  z_early..., then the module's parameters in the library's canonical order (constants: never differentiated, but the
+  library reads them through ``wg_train_prepare``).  Output: audio [B, 256 T] fp32.  backward() returns only what
+  ``ctx.needs_input_grad`` asks for among mel, z_init and the z_early entries."""
+
+  N_META = 5      # model, sigma, scale, wn, n_early
+
+  @staticmethod
+  def forward(ctx, model, sigma, scale, wn, n_early, mel, z_init, *rest):
+    z_early, params = rest[:n_early], rest[n_early:]
+    eng = model._get_engine(mel.device)          # finalised with the current weights: the W^-1 of infer
+    lib = eng.lib
+    B, M, T = mel.shape
+    flow_c = model.flow_channels()
+    stream = torch.cuda.current_stream(mel.device).cuda_stream
+    want_mel = ctx.needs_input_grad[5]
+    wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=want_mel)
+    S = 256 * T
+    nbytes = lib.wg_train_workspace_bytes(eng.handle, B, T, S)
+    if nbytes == 0:
+      raise _lib.WgError(lib.wg_last_error().decode())
+    slot, fresh = eng.train_workspace(nbytes, (B, T, S, nbytes))      # held until this graph's backward has run
+    ws = slot["ws"]
+    audio = torch.empty((B, S), dtype=torch.float32, device=mel.device)
+    ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
+    _lib.check(lib.wg_train_infer_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
+                                          float(sigma), _ptr(audio), B, T, 1 if fresh else 0, _ptr(ws), ws.numel(),
+                                          C.c_void_p(stream)))
+    ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.guard = model, wts, ws, (B, M, T), _SlotGuard(slot)
+    ctx.sigma, ctx.n_early, ctx.n_params = float(sigma), n_early, len(params)
+    ctx.sig = eng.signature
+    ctx.z_shapes = [tuple(z_init.shape)] + [tuple(z.shape) for z in z_early]
+    # the automatic scale assumes a loss normalised by the number of samples (|d loss / d audio| ~ 1 / N)
+    ctx.scale = float(scale) if scale else float(2.0 ** round(math.log2(audio.numel())))
+    return audio
+
+  @staticmethod
+  def backward(ctx, g_audio):
+    model = ctx.model
+    if ctx.wts is None:
+      raise _lib.WgError("the saved state of this infer_differentiable call is gone: backward() already ran for it "
+                         "(retain_graph is not supported)")
+    eng = model._engine
+    if eng is None or eng.signature != ctx.sig or model._weights_signature() != ctx.sig:
+      ctx.wts = None
+      ctx.guard.release()
+      raise _lib.WgError("the vocoder's weights changed between infer_differentiable and backward(): the saved state "
+                         "belongs to the old weights")
+    lib = eng.lib
+    B, M, T = ctx.dims
+    dev = ctx.ws.device
+    ne = ctx.n_early
+    need = ctx.needs_input_grad
+    want_mel, want_zi = need[5], need[6]
+    want_ze = list(need[7:7 + ne])
+    poison = os.environ.get("WG_TRAIN_POISON_GRADS") == "1"
+    new = (lambda sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)) if poison else \
+        (lambda sh: torch.empty(sh, dtype=torch.float32, device=dev))
+    g_mel = new((B, M, T)) if want_mel else None
+    g_zi = new(ctx.z_shapes[0]) if want_zi else None
+    g_ze = [new(ctx.z_shapes[1 + i]) if w else None for i, w in enumerate(want_ze)]
+    ga = g_audio.float().contiguous() if g_audio is not None else torch.zeros((B, 256 * T), dtype=torch.float32, device=dev)
+    ze = (C.c_void_p * max(1, ne))(*[(g.data_ptr() if g is not None else None) for g in g_ze])
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    try:
+      _lib.check(lib.wg_train_infer_backward(eng.handle, C.byref(ctx.wts.struct), _ptr(ga), C.c_float(ctx.scale),
+                                             C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
+                                             _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws), ctx.ws.numel(),
+                                             C.c_void_p(stream)))
+    finally:
+      ctx.guard.release()
+      ctx.wts = None
+    # overflow of the fp16 gradient planes (see infer_differentiable: grad_scale), or inf / nan inputs
+    outs = [t for t in [g_mel, g_zi] + g_ze if t is not None]
+    sums = [t.sum() for t in outs]
+    model.grad_finite = torch.isfinite(torch.stack(sums)).all() if len(sums) > 1 else torch.isfinite(sums[0])
+    if os.environ.get("WG_TRAIN_CHECK_FINITE") == "1" and not bool(model.grad_finite):
+      raise _lib.WgError(nonfinite_message(ctx.scale))
+    return (None,) * _InferFn.N_META + (g_mel, g_zi, *g_ze) + (None,) * ctx.n_params
+
+
+def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_early: List[torch.Tensor], sigma: float,
+                         grad_scale: float = 0.0) -> torch.Tensor:
+  """``model.infer_with_noise(spect, z_init, z_early, sigma)`` (fp32) with an autograd graph back to ``spect``, ``z_init``
+  and every ``z_early[i]`` that requires grad.  Without grad mode, or when none of them requires grad, exactly
+  ``infer_with_noise`` (nothing is saved)."""
+  ins = [spect, z_init] + list(z_early)
+  for t in ins:
+    if t.device.type != "cuda":
+      raise _lib.WgError("waveglow_amd runs on MI355X only: there is no CPU fallback")
+    if t.dtype != torch.float32:
+      raise _lib.WgError("infer_differentiable takes float32 mel and noise (the training direction's kernels)")
+  eng = model._get_engine(spect.device, need_weights=False)
+  if eng.width != eng.n_channels or eng.mel_width != eng.n_mel or int(eng.lib.wg_wn_waves(eng.n_channels)) <= 0:
+    raise _lib.WgError(f"n_channels={eng.n_channels}, n_mel_channels={eng.n_mel}: infer_differentiable runs on the training "
+                       f"direction's kernels, which take the widths {eng.KERNEL_WIDTHS} and mel counts that are multiples "
+                       "of 16 only (infer / infer_with_noise zero-pad the others)")
+  B, M, T = spect.shape
+  L = T * 256 // model.n_group
+  if tuple(z_init.shape) != (B, model.n_remaining_channels, L):
+    raise _lib.WgError(f"z_init: expected shape {(B, model.n_remaining_channels, L)}, got {tuple(z_init.shape)}")
+  n_early = sum(1 for k in range(model.n_flows) if k % model.n_early_every == 0 and k > 0)
+  if len(z_early) != n_early or any(tuple(z.shape) != (B, model.n_early_size, L) for z in z_early):
+    raise _lib.WgError(f"z_early: expected {n_early} tensors of shape {(B, model.n_early_size, L)}")
+  if not torch.is_grad_enabled():
+    return model.infer_with_noise(spect, z_init, z_early, sigma)
+  if any(p.requires_grad for p in model.parameters()):
+    raise _lib.WgError("infer_differentiable treats the vocoder's weights as constants and gives no weight gradients: "
+                       "freeze the model first (model.requires_grad_(False))")
+  if not any(t.requires_grad for t in ins):
+    return model.infer_with_noise(spect, z_init, z_early, sigma)
+  _names, tensors, wn = canonical_params(model, eng)
+  ins = [t.contiguous() for t in ins]
+  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, n_early, *ins, *tensors)
