@@ -166,6 +166,21 @@ size_t wg_stft_mel_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_sample
 int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out, int32_t B,
                 int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mel front-end with an audio gradient, TacotronSTFT.mel_spectrogram_differentiable (taco_stft.py:84-104 without the
+ * detach at :99; conv-STFT of stft.py:135-163).  Same arguments and n_samples rule as wg_stft_mel (n_mel <= 128).
+ * wg_stft_mel_forward_saved: mel_out bit-identical to wg_stft_mel; keeps (re, im), |X| and the pre-log sums in the
+ *   workspace for the backward.
+ * wg_stft_mel_backward: g_mel [B][n_mel][n_samples/256 + 1] fp32 device -> audio_grad_out [B][n_samples] = d loss /
+ *   d audio, through log(clamp(., 1e-5)) (gradient where the sum >= 1e-5), the mel projection, |X| (0 where |X| = 0),
+ *   the conv-STFT and the reflect padding.  Reads the workspace of a forward_saved call with the same mel_basis, n_mel,
+ *   B and n_samples; leaves that call's saved state intact, so it may run more than once.
+ * One workspace of wg_stft_mel_grad_workspace_bytes serves both.  Enqueue-only. */
+size_t wg_stft_mel_grad_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples);
+int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out,
+                              int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
+int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
+                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Training direction: WaveGlow.forward under autograd and loss.backward() ---------------------------------------
  * (src/waveglow/model.py:178-221, train.py:190-199).  Weights change every optimiser step, so they are NOT taken from
  * the handle: the caller passes device buffers.  Every fp16 matrix below is given as [rows][K] in "(pos,pos)" order

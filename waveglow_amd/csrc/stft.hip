@@ -3,6 +3,9 @@
 // (stft.py:165-198) as a 4-tap polyphase GEMM with the pseudo-inverse basis, window-sum-square normalisation and
 // cropping in its epilogue.  fp32 in / fp32 accumulate (v_mfma_f32_32x32x2_f32 is bit-for-bit an fp32 fma chain).
 // Fixed geometry: filter 1024, hop 256 (TSTFTHParams defaults, taco_stft.py:36-43).
+// Mel gradients (TacotronSTFT.mel_spectrogram_differentiable): mel_kernel also keeps the pre-log sums, mel_bwd_kernel
+// turns d mel into d (re, im) in the inverse's [B][1056][Fs] layout, istft_kernel<true> is the transposed conv-STFT
+// with the forward basis, and reflect_fold_kernel adds the reflect-padded edges back onto the audio gradient.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -29,13 +32,24 @@ struct MelArgs {
   const float* basis;      // [n_mel][513]  Slaney mel filterbank (taco_stft.py:66-73)
   float* mel;              // [B][n_mel][F]  log(clamp(basis . mag, 1e-5))   (taco_stft.py:10-16, :99-104)
   int n_mel, F;
+  float* pre;              // optional [B][n_mel][F]: the pre-log sums basis . mag (saved for the backward)
 };
 struct IstftArgs {
   const float* rec;        // [B][1056][Fs]
-  const float* invA;       // packed A fragments [8 mtile][4 j][528 kstep][64 lanes]
+  const float* invA;       // packed A fragments [8 mtile][4 j][528 kstep][64 lanes] (the forward basis for the grad)
   const float* win_sq;     // [1024]
   float* out;              // [B][N]
   int N, F, Fs;
+  float* edge;             // grad only: [B][1024] padded positions 0..511 and N+512..N+1023
+};
+struct MelBwdArgs {
+  const float* g;          // [B][n_mel][F]  d mel
+  const float* pre;        // [B][n_mel][F]  pre-log sums A
+  const float* mag;        // [B][513][F]
+  const float* rec;        // [B][1056][Fs]  raw (re, im) of the forward
+  const float* basis;      // [n_mel][513]
+  float* gX;               // [B][1056][Fs]  d (re, im); pad rows / columns zero
+  int n_mel, F, Fs;
 };
 
 // LDS index of padded-audio position pos inside a 32-frame segment: one extra word per 256 so that the 32 lanes
@@ -106,6 +120,10 @@ __global__ void __launch_bounds__(512) stft_kernel(const StftArgs a) {
   }
 }
 
+// kGrad = false: inverse STFT (stft.py:165-198).  kGrad = true: the same 4-tap polyphase GEMM with the forward basis
+// is the transposed conv-STFT, g ypad[256 q + r] = sum_j sum_c fwd[c][r + 256 j] gX[c][q - j]; its epilogue stores the
+// interior (audio positions 0..N-1) straight to out and the reflect-padded edges to a.edge.
+template <bool kGrad>
 __global__ void __launch_bounds__(512) istft_kernel(const IstftArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // M tile: output phase r in [32w, 32w+32)
@@ -131,6 +149,13 @@ __global__ void __launch_bounds__(512) istft_kernel(const IstftArgs a) {
       const int r = wave * 32 + 8 * g + 4 * kk + e;
       const int n = q * kHop + r;                         // position in the un-cropped inverse transform
       const int o = n - kFL / 2;
+      if (kGrad) {
+        const float v = acc[4 * g + e];
+        if (o >= 0 && o < a.N) a.out[(size_t)b * a.N + o] = v;
+        else if (o < 0) a.edge[(size_t)b * kFL + n] = v;                      // n in [0, 512)
+        else if (o < a.N + kFL / 2) a.edge[(size_t)b * kFL + kFL / 2 + (o - a.N)] = v;
+        continue;
+      }
       if (o < 0 || o >= a.N) continue;
       float ws = 0.0f;                                    // window_sumsquare at n (stft.py:45-95)
 #pragma unroll
@@ -166,8 +191,78 @@ __global__ void __launch_bounds__(256) mel_kernel(const MelArgs a) {
 #pragma unroll
   for (int i = 0; i < 32; ++i) {
     const int m = grp * per + i;
-    if (i < per && m < a.n_mel) a.mel[((size_t)b * a.n_mel + m) * a.F + f] = logf(fmaxf(acc[i], 1e-5f));
+    if (i < per && m < a.n_mel) {
+      a.mel[((size_t)b * a.n_mel + m) * a.F + f] = logf(fmaxf(acc[i], 1e-5f));
+      if (a.pre) a.pre[((size_t)b * a.n_mel + m) * a.F + f] = acc[i];
+    }
   }
+}
+
+// d mel -> d (re, im) for 64 frames x a quarter of the bins (blockIdx.z):
+//   gA = g / A where A >= 1e-5 (torch's clamp passes its bound), else 0;  gmag[k] = sum_m basis[m][k] gA[m];
+//   (g re, g im) = gmag (re, im) / mag, 0 where mag == 0.
+// grid (ceil(F/64), B, 4), 256 threads = 64 frames x 4 waves; a wave's bin is uniform, so basis reads are broadcasts.
+constexpr int kBwdSplit = 4;
+__global__ void __launch_bounds__(256) mel_bwd_kernel(const MelBwdArgs a) {
+  __shared__ float sg[128][64];
+  const int fl = threadIdx.x & 63, b = blockIdx.y;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int f = blockIdx.x * 64 + fl;
+  for (int m = wave; m < a.n_mel; m += 4) {
+    float v = 0.0f;
+    if (f < a.F) {
+      const size_t i = ((size_t)b * a.n_mel + m) * a.F + f;
+      const float A = a.pre[i];
+      v = A >= 1e-5f ? a.g[i] / A : 0.0f;
+    }
+    sg[m][fl] = v;
+  }
+  __syncthreads();
+  if (f >= a.F) return;
+  const float* mp = a.mag + (size_t)b * kCut * a.F + f;
+  const float* rp = a.rec + (size_t)b * kRows * a.Fs + 3 + f;
+  float* gp = a.gX + (size_t)b * kRows * a.Fs + 3 + f;
+  for (int k = blockIdx.z * 4 + wave; k < kCut; k += 4 * kBwdSplit) {
+    const float* bp = a.basis + k;
+    float gm = 0.0f;
+    for (int m = 0; m < a.n_mel; ++m) gm = fmaf(bp[(size_t)m * kCut], sg[m][fl], gm);
+    const float mag = mp[(size_t)k * a.F];
+    const float s = mag > 0.0f ? gm / mag : 0.0f;
+    gp[(size_t)(2 * k) * a.Fs] = s * rp[(size_t)(2 * k) * a.Fs];
+    gp[(size_t)(2 * k + 1) * a.Fs] = s * rp[(size_t)(2 * k + 1) * a.Fs];
+  }
+}
+
+// g y[s] += g ypad[512 - s] (1 <= s <= 512) + g ypad[2(N-1) - s + 512] (N-513 <= s <= N-2): the reflect padding of
+// stft.py:141-147 folded back.  One thread per audio position, so overlapping edges of a short utterance do not race.
+// grid (B), 256 threads; runs after istft_kernel<true> in stream order.
+__global__ void __launch_bounds__(256) reflect_fold_kernel(const float* edge, float* gy, int N) {
+  const int b = blockIdx.x;
+  const float* e = edge + (size_t)b * kFL;
+  float* y = gy + (size_t)b * N;
+  constexpr int kHalf = kFL / 2;
+  for (int t = threadIdx.x; t < 2 * (kHalf + 1); t += 256) {
+    const int s = t <= kHalf ? t : N - 2 * (kHalf + 1) + t;      // [0, 512] then [N-513, N-1]
+    if (t > kHalf && s <= kHalf) continue;                        // already this block's lower range
+    float v = y[s];
+    if (s >= 1 && s <= kHalf) v += e[kHalf - s];
+    if (s >= N - kHalf - 1 && s <= N - 2) v += e[kHalf + (N - 2 - s)];
+    y[s] = v;
+  }
+}
+
+hipError_t launch_mel_bwd(const MelBwdArgs& a, int B, hipStream_t s) {
+  if (a.n_mel < 1 || a.n_mel > 128) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mel_bwd_kernel, dim3((a.F + 63) / 64, B, kBwdSplit), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_stft_grad(const IstftArgs& a, int B, hipStream_t s) {
+  hipLaunchKernelGGL(istft_kernel<true>, dim3((a.F + 3 + 31) / 32, B), dim3(512), 0, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(reflect_fold_kernel, dim3(B), dim3(256), 0, s, a.edge, a.out, a.N);
+  return hipGetLastError();
 }
 
 hipError_t launch_mel(const MelArgs& a, int B, hipStream_t s) {
@@ -181,7 +276,7 @@ hipError_t launch_stft(const StftArgs& a, int B, hipStream_t s) {
   return hipGetLastError();
 }
 hipError_t launch_istft(const IstftArgs& a, int B, hipStream_t s) {
-  hipLaunchKernelGGL(istft_kernel, dim3((a.F + 3 + 31) / 32, B), dim3(512), 0, s, a);
+  hipLaunchKernelGGL(istft_kernel<false>, dim3((a.F + 3 + 31) / 32, B), dim3(512), 0, s, a);
   return hipGetLastError();
 }
 

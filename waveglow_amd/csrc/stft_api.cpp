@@ -13,14 +13,19 @@ struct StftArgs {
   float* mag;
 };
 struct MelArgs {
-  const float* mag; const float* basis; float* mel; int n_mel, F;
+  const float* mag; const float* basis; float* mel; int n_mel, F; float* pre;
 };
 hipError_t launch_mel(const MelArgs& a, int B, hipStream_t s);
 struct IstftArgs {
-  const float* rec; const float* invA; const float* win_sq; float* out; int N, F, Fs;
+  const float* rec; const float* invA; const float* win_sq; float* out; int N, F, Fs; float* edge;
+};
+struct MelBwdArgs {
+  const float* g; const float* pre; const float* mag; const float* rec; const float* basis; float* gX; int n_mel, F, Fs;
 };
 hipError_t launch_stft(const StftArgs& a, int B, hipStream_t s);
 hipError_t launch_istft(const IstftArgs& a, int B, hipStream_t s);
+hipError_t launch_mel_bwd(const MelBwdArgs& a, int B, hipStream_t s);
+hipError_t launch_stft_grad(const IstftArgs& a, int B, hipStream_t s);
 }  // namespace wg
 using namespace wg;
 
@@ -29,6 +34,7 @@ int wg_set_error(int code, const char* msg);   // api.cpp
 struct wg_stft {
   int device;
   float *d_fwdA = nullptr, *d_invA = nullptr, *d_win = nullptr;
+  float* d_fwdT = nullptr;   // forward basis in the inverse's polyphase pack: A operand of the transposed conv-STFT
 };
 
 #define HIP_TRY2(expr)                                                      \
@@ -47,6 +53,7 @@ int wg_stft_create(const float* fwd_basis, const float* inv_basis, const float* 
   // basis row c of the library = interleaved (re_k, im_k): c = 2k -> reference row k, c = 2k+1 -> row 513 + k
   auto ref_row = [](int c) { return (c & 1) ? kCut + (c >> 1) : (c >> 1); };
   std::vector<float> fa((size_t)(kRows / 32) * (kFL / 2) * 64, 0.f), ia((size_t)8 * 4 * (kRows / 2) * 64, 0.f);
+  std::vector<float> ft(ia.size(), 0.f);
   for (int mt = 0; mt < kRows / 32; ++mt)
     for (int ks = 0; ks < kFL / 2; ++ks)
       for (int lane = 0; lane < 64; ++lane) {
@@ -58,8 +65,11 @@ int wg_stft_create(const float* fwd_basis, const float* inv_basis, const float* 
       for (int ks = 0; ks < kRows / 2; ++ks)
         for (int lane = 0; lane < 64; ++lane) {
           const int r = w * 32 + (lane & 31), c = 2 * ks + (lane >> 5);
-          if (c < 2 * kCut)
-            ia[(((size_t)w * 4 + j) * (kRows / 2) + ks) * 64 + lane] = inv_basis[(size_t)ref_row(c) * kFL + r + kHop * j];
+          if (c < 2 * kCut) {
+            const size_t i = (((size_t)w * 4 + j) * (kRows / 2) + ks) * 64 + lane;
+            ia[i] = inv_basis[(size_t)ref_row(c) * kFL + r + kHop * j];
+            ft[i] = fwd_basis[(size_t)ref_row(c) * kFL + r + kHop * j];
+          }
         }
   wg_stft* h = new wg_stft();
   h->device = device_id;
@@ -72,9 +82,11 @@ int wg_stft_create(const float* fwd_basis, const float* inv_basis, const float* 
   HIP_TRY2(hipMalloc((void**)&h->d_fwdA, fa.size() * 4));
   HIP_TRY2(hipMalloc((void**)&h->d_invA, ia.size() * 4));
   HIP_TRY2(hipMalloc((void**)&h->d_win, kFL * 4));
+  HIP_TRY2(hipMalloc((void**)&h->d_fwdT, ft.size() * 4));
   HIP_TRY2(hipMemcpy(h->d_fwdA, fa.data(), fa.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY2(hipMemcpy(h->d_invA, ia.data(), ia.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY2(hipMemcpy(h->d_win, win_sq, kFL * 4, hipMemcpyHostToDevice));
+  HIP_TRY2(hipMemcpy(h->d_fwdT, ft.data(), ft.size() * 4, hipMemcpyHostToDevice));
   *out = h;
   return WG_OK;
 }
@@ -84,6 +96,7 @@ int wg_stft_destroy(wg_stft* h) {
   if (h->d_fwdA) (void)hipFree(h->d_fwdA);
   if (h->d_invA) (void)hipFree(h->d_invA);
   if (h->d_win) (void)hipFree(h->d_win);
+  if (h->d_fwdT) (void)hipFree(h->d_fwdT);
   delete h;
   return WG_OK;
 }
@@ -133,6 +146,70 @@ int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* 
   HIP_TRY2(launch_stft(a, B, s));
   MelArgs m{(const float*)workspace, mel_basis, mel_out, n_mel, F};
   HIP_TRY2(launch_mel(m, B, s));
+  return WG_OK;
+}
+
+// Mel-gradient workspace, in floats: [rec | gX | edge] (zeroed by the call that fills it) then [mag | pre].
+// rec and gX are [B][1056][Fs], edge [B][1024], mag [B][513][F], pre [B][128][F] (sized for the largest n_mel).
+struct MelGradLayout {
+  int F, Fs;
+  size_t rec, gX, edge, mag, pre, total;   // float offsets; total in floats
+};
+static MelGradLayout mel_grad_layout(int B, int n_samples) {
+  MelGradLayout L;
+  L.F = n_samples / kHop + 1;
+  L.Fs = frames_padded(L.F);
+  const size_t plane = (size_t)B * kRows * L.Fs;
+  L.rec = 0;
+  L.gX = plane;
+  L.edge = 2 * plane;
+  L.mag = L.edge + (size_t)B * kFL;
+  L.pre = L.mag + (size_t)B * kCut * L.F;
+  L.total = L.pre + (size_t)B * 128 * L.F;
+  return L;
+}
+
+size_t wg_stft_mel_grad_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples) {
+  if (!h || B < 1 || n_samples < kFL / 2 + 1) return 0;          // reflect padding needs n_samples > filter/2
+  return mel_grad_layout(B, n_samples).total * 4;
+}
+
+static int mel_grad_check(wg_stft* h, const float* mel_basis, int32_t n_mel, const void* in, const void* out, int32_t B,
+                          int32_t n_samples, void* workspace, size_t workspace_bytes) {
+  if (!h || !mel_basis || !in || !out || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
+  const size_t need = wg_stft_mel_grad_workspace_bytes(h, B, n_samples);
+  if (!need || n_mel < 1 || n_mel > 128) return wg_set_error(WG_ERR_INVALID, "bad B / n_samples / n_mel");
+  if (workspace_bytes < need) return wg_set_error(WG_ERR_WORKSPACE, "mel gradient workspace too small");
+  return WG_OK;
+}
+
+int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out,
+                              int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = mel_grad_check(h, mel_basis, n_mel, audio, mel_out, B, n_samples, workspace, workspace_bytes);
+  if (rc != WG_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const MelGradLayout L = mel_grad_layout(B, n_samples);
+  float* ws = (float*)workspace;
+  HIP_TRY2(hipMemsetAsync(ws + L.rec, 0, (L.gX - L.rec) * 4, s));  // zero lead/tail columns and pad rows of rec
+  StftArgs a{audio, h->d_fwdA, nullptr, 0.0f, ws + L.rec, nullptr, n_samples, L.F, L.Fs, ws + L.mag};
+  HIP_TRY2(launch_stft(a, B, s));
+  MelArgs m{ws + L.mag, mel_basis, mel_out, n_mel, L.F, ws + L.pre};
+  HIP_TRY2(launch_mel(m, B, s));
+  return WG_OK;
+}
+
+int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
+                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = mel_grad_check(h, mel_basis, n_mel, g_mel, audio_grad_out, B, n_samples, workspace, workspace_bytes);
+  if (rc != WG_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const MelGradLayout L = mel_grad_layout(B, n_samples);
+  float* ws = (float*)workspace;
+  HIP_TRY2(hipMemsetAsync(ws + L.gX, 0, (L.mag - L.gX) * 4, s));   // gX pads and uncovered edge positions are zero
+  MelBwdArgs m{g_mel, ws + L.pre, ws + L.mag, ws + L.rec, mel_basis, ws + L.gX, n_mel, L.F, L.Fs};
+  HIP_TRY2(launch_mel_bwd(m, B, s));
+  IstftArgs t{ws + L.gX, h->d_fwdT, nullptr, audio_grad_out, n_samples, L.F, L.Fs, ws + L.edge};
+  HIP_TRY2(launch_stft_grad(t, B, s));
   return WG_OK;
 }
 

@@ -4,6 +4,10 @@
 ``librosa.filters.mel`` (taco_stft.py:66-73) is restated below (Slaney scale, Slaney area normalisation -- librosa's
 defaults ``htk=False, norm='slaney'``); librosa is absent here, so this front-end is pinned only against
 ``oracle/stft_oracle.py`` (numpy fp64 restatement), not against reference outputs: **parity unpinned**.
+
+``TacotronSTFT.mel_spectrogram_differentiable`` is the same front-end with an autograd graph back to the audio (the
+reference detaches at taco_stft.py:99): ``wg_stft_mel_forward_saved`` keeps the spectrum, and ``wg_stft_mel_backward``
+runs the mel / magnitude chain rule in one row kernel and the transposed conv-STFT as an fp32 MFMA GEMM.
 """
 from __future__ import annotations
 
@@ -75,6 +79,39 @@ def dynamic_range_decompression(x, C_=1):
   return torch.exp(x) / C_
 
 
+class _MelFn(torch.autograd.Function):
+  """Inputs: the TacotronSTFT module and the audio [B, N].  The forward keeps the library's workspace (spectrum,
+  magnitudes, pre-log sums) on ctx; the backward writes its d (re, im) to a separate part of that workspace, so the
+  saved state survives and a second backward under retain_graph gives the same gradient."""
+
+  @staticmethod
+  def forward(ctx, taco, y):
+    y = y.contiguous()
+    B, N = y.shape
+    lib = taco.lib
+    nbytes = lib.wg_stft_mel_grad_workspace_bytes(taco._h, B, N)
+    if nbytes == 0:
+      raise _lib.WgError(f"mel front-end: audio of {N} samples is too short (reflect padding needs > 512)")
+    mel = torch.empty((B, taco.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=y.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
+    stream = torch.cuda.current_stream(y.device).cuda_stream
+    _lib.check(lib.wg_stft_mel_forward_saved(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, y.data_ptr(),
+                                             mel.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    ctx.taco, ctx.ws, ctx.dims = taco, ws, (B, N)
+    return mel
+
+  @staticmethod
+  def backward(ctx, g_mel):
+    taco, ws = ctx.taco, ctx.ws
+    B, N = ctx.dims
+    g = g_mel.to(torch.float32).contiguous()
+    gy = torch.empty((B, N), dtype=torch.float32, device=ws.device)
+    stream = torch.cuda.current_stream(ws.device).cuda_stream
+    _lib.check(taco.lib.wg_stft_mel_backward(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, g.data_ptr(),
+                                             gy.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    return None, gy
+
+
 class TacotronSTFT(torch.nn.Module):
   def __init__(self, hparams, device):
     super().__init__()
@@ -110,6 +147,10 @@ class TacotronSTFT(torch.nn.Module):
     """(B, T) in [-1, 1] -> (B, n_mel_channels, T // hop + 1)   (taco_stft.py:84-104)"""
     assert float(y.min()) >= FLOAT32_64_MIN_WAV and float(y.max()) <= FLOAT32_64_MAX_WAV   # taco_stft.py:95-97
     y = y.to(self.device, torch.float32).contiguous()
+    return self._mel(y)
+
+  def _mel(self, y: torch.Tensor) -> torch.Tensor:
+    """wg_stft_mel on contiguous fp32 audio [B, N] on the module's device; no graph."""
     B, N = y.shape
     nbytes = self.lib.wg_stft_mel_workspace_bytes(self._h, B, N)
     if nbytes == 0:
@@ -121,6 +162,24 @@ class TacotronSTFT(torch.nn.Module):
     _lib.check(self.lib.wg_stft_mel(self._h, self.mel_basis.data_ptr(), self.n_mel_channels, y.data_ptr(),
                                     out.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     return out
+
+  def mel_spectrogram_differentiable(self, y: torch.Tensor) -> torch.Tensor:
+    """``mel_spectrogram(y)`` with an autograd graph back to ``y`` (taco_stft.py:84-104 without the detach at :99).
+
+    ``y`` [B, N] fp32 on the module's device, any N > 512 -> [B, n_mel_channels, N // 256 + 1], bit-identical to
+    ``mel_spectrogram``.  No range assert and no host synchronisation: generated audio may leave [-1, 1].  With grad
+    mode on and ``y.requires_grad`` the result's graph leads to ``y``; otherwise it is the same tensor without one.
+    ``mel_basis`` is a constant.  Other devices, CPU tensors and other dtypes raise WgError."""
+    if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or \
+        _lib.device_index(y.device) != _lib.device_index(self.device):
+      raise _lib.WgError(f"mel_spectrogram_differentiable: audio must be on {self.device} (no CPU fallback)")
+    if y.dtype != torch.float32:
+      raise _lib.WgError(f"mel_spectrogram_differentiable takes float32 audio, got {y.dtype}")
+    if y.dim() != 2:
+      raise _lib.WgError(f"mel_spectrogram_differentiable takes audio [B, N], got shape {tuple(y.shape)}")
+    if torch.is_grad_enabled() and y.requires_grad:
+      return _MelFn.apply(self, y)
+    return self._mel(y.detach().contiguous())
 
   def get_wav_tensor_from_file(self, wav_path) -> torch.Tensor:
     wav, sampling_rate = wav_to_float32(wav_path)
