@@ -253,6 +253,19 @@ typedef struct wg_train_grads {
 
 size_t wg_train_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len);
 
+/* Flags of the flag-taking training entry points (the forms without flags are flags = 0).
+ * WG_TRAIN_RECOMPUTE: activation recomputation.  The workspace keeps the layer planes (X / T / S / A / d pre) of two flow
+ *   slots (flow k in slot k & 1) instead of every flow, plus every flow's fp32 state as before; the backward replays each
+ *   flow's forward into its slot just before that flow's data-gradient chain (the last two flows the forward ran are still
+ *   there and are not replayed) and computes d spect flow by flow into an fp32 accumulator.  About 0.2x the workspace at
+ *   256 channels for about one more forward pass of the WN layers.  Outputs of the forwards and every gradient except those
+ *   that go through d spect (upsample weight / bias, d mel: summation order, <= 3e-5 relative) are bit-identical to flags = 0.
+ *   A workspace keeps one layout from its forward to its backward: the workspace of a recompute call must be smaller than
+ *   the full-save size and at least the recompute size; a call whose flags do not match the size it is given returns
+ *   WG_ERR_INVALID, as does the flag at a depth where two slots already hold every flow. */
+#define WG_TRAIN_RECOMPUTE 1
+size_t wg_train_workspace_bytes_ex(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, int32_t flags);
+
 /* The stacked weight matrices in NATURAL channel order, fp32, as the caller's autograd packing produces them every step
  * (waveglow_amd/train.py: pack_weights; reference modules: WN.in_layers / cond_layer / res_skip_layers / end,
  * model.py:85-113, upsample model.py:145-150). */
@@ -306,6 +319,10 @@ int32_t wg_wn_waves(int32_t n_channels);
 int wg_train_forward(wg_handle* h, const wg_train_weights* w, const void* mel, const void* audio, float* z,
                      float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* wg_train_forward with flags (WG_TRAIN_RECOMPUTE, workspace of wg_train_workspace_bytes_ex with the same flags). */
+int wg_train_forward_flags(wg_handle* h, const wg_train_weights* w, const void* mel, const void* audio, float* z,
+                           float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
+                           void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
 
 /* Backward of the last wg_train_forward on this workspace.  g_z [B][8][L] (or null), g_log_s[k] [B][h_k][L]
  * (null entries = zero) are the gradients of the returned tensors; `scale` multiplies them on entry (fp16 gradient
@@ -339,6 +356,12 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* w, const wg_train
                          const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
                          int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
                          int32_t flow_hi, int32_t flow_lo, void* stream);
+/* wg_train_backward_ex with the flags of the forward it belongs to.  With WG_TRAIN_RECOMPUTE every call of a flow range
+ * replays the flows of its range; the call with flow_lo == 0 finishes d spect (upsample gradients, g_mel). */
+int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_z,
+                               const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
+                               int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
+                               int32_t flow_hi, int32_t flow_lo, int32_t flags, void* stream);
 
 /* Differentiable synthesis: WaveGlow.infer with injected noise (src/waveglow/model.py:223-273) with saved state, and its
  * backward w.r.t. mel and the noise (the weights are constants).  Both run on the training workspace of the same
@@ -352,6 +375,11 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* w, const wg_train
 int wg_train_infer_forward(wg_handle* h, const wg_train_weights* w, const void* mel, const void* z_init,
                            const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
                            int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, void* stream);
+/* wg_train_infer_forward with flags (WG_TRAIN_RECOMPUTE: workspace of wg_train_workspace_bytes_ex with the same flags). */
+int wg_train_infer_forward_flags(wg_handle* h, const wg_train_weights* w, const void* mel, const void* z_init,
+                                 const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
+                                 int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
+                                 void* stream);
 
 /* Backward of the last wg_train_infer_forward on this workspace.  g_audio [B][256 n_frames] fp32 is the gradient of the
  * returned audio; `scale` multiplies it on entry (fp16 gradient planes) and is divided out of every result.  Outputs,
@@ -361,6 +389,10 @@ int wg_train_infer_forward(wg_handle* h, const wg_train_weights* w, const void* 
 int wg_train_infer_backward(wg_handle* h, const wg_train_weights* w, const float* g_audio, float scale, float sigma,
                             float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
                             int32_t n_frames, void* workspace, size_t workspace_bytes, void* stream);
+/* wg_train_infer_backward with the flags of its forward (WG_TRAIN_RECOMPUTE: flows 2.. are replayed; still one stream). */
+int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* w, const float* g_audio, float scale, float sigma,
+                                  float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
+                                  int32_t n_frames, void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
 
 /* Diagnostic builds only (-DWG_STAMPS): device buffer of n_tiles*8 uint64 that the WN-layer kernel fills with
  * s_memtime stamps at its phase boundaries (last launch wins).  A no-op pointer in the shipped library. */

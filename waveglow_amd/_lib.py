@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WAVEGLOW_AMD_LIB", os.path.join(_HERE, "csrc", "libwaveglow_amd.so"))
 
 WG_F32, WG_F16 = 0, 1
+WG_TRAIN_RECOMPUTE = 1          # flag of the wg_train_*_flags entry points (include/waveglow_amd.h)
 
 
 class WgConfig(C.Structure):
@@ -72,6 +73,7 @@ SIGNATURES = {
                             C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_macs_per_group_step": (C.c_double, [C.c_void_p]),
   "wg_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+  "wg_train_workspace_bytes_ex": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
   "wg_wn_waves": (C.c_int32, [C.c_int32]),
   "wg_train_pack": (C.c_int, [C.c_void_p, C.POINTER(WgTrainPlain), C.POINTER(WgTrainWeights), C.c_void_p]),
   "wg_train_param_count": (C.c_int32, [C.c_void_p, C.c_int32]),
@@ -85,6 +87,9 @@ SIGNATURES = {
   "wg_train_forward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
+  "wg_train_forward_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_size_t, C.c_int32, C.c_void_p]),
   "wg_train_backward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
                                   C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -94,12 +99,22 @@ SIGNATURES = {
   "wg_train_backward_ex": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
                                      C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p]),
+  "wg_train_backward_ex_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
+                                           C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_void_p]),
   "wg_train_infer_forward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_train_infer_backward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_float, C.c_float,
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_train_infer_forward_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.c_void_p, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+  "wg_train_infer_backward_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_float, C.c_float,
+                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
   "wg_stft_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stft_destroy": (C.c_int, [C.c_void_p]),
   "wg_stft_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),

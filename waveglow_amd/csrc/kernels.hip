@@ -1655,6 +1655,55 @@ hipError_t launch_cond_fold(const float* w_cond, const float* w_up, _Float16* ou
 // =============================================================================================
 // Flow step (both directions) + next WN start.  64 rows per workgroup, 256 threads.
 // =============================================================================================
+// ---- WN.start of the next flow (model.py:117): x[P] = sum_j Wst[P][j] a0[j] + b[P], fp16, position-major, for the FL_ROWS
+// rows from row0; s_a0[rl] = (a0_0..a0_3) of row row0 + rl (after a barrier).  Shared by flow_kernel and start_replay_kernel,
+// whose x_0 planes must be bit-identical.
+// piece = (chunk cc, row, 8-position group g8) = 16 contiguous bytes; idx = cc*2048 + row*8 + g8, so
+// consecutive threads write consecutive bytes and a thread's g8 is fixed: its 8x4 weights sit in registers.
+template <int FL_ROWS>
+__device__ __forceinline__ void start_rows(const float4* s_a0, size_t row0, size_t nrows, int L, const RowGeom& g,
+                                           const float* __restrict__ wstart, const float* __restrict__ bstart, int C, int h,
+                                           _Float16* x) {
+  const int tid = threadIdx.x;
+  const int g8 = tid & 7;
+  // plane rows of this thread's 8 rows (one per pass), once for all chunks: phase-major row of (b, t = 32q + p), see RowGeom
+  unsigned prow[8];
+  unsigned ok = 0;
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int rl = it * (FL_ROWS / 8) + (tid >> 3);
+    const size_t row = row0 + rl;
+    prow[it] = 0;
+    if (row >= nrows) continue;
+    const unsigned r32 = (unsigned)row;
+    const int b = (int)(r32 / (unsigned)L), t = (int)(r32 - (unsigned)b * (unsigned)L);
+    if (g.frames != nullptr && t >= 32 * g.frames[b]) continue;      // padding column of a ragged batch
+    prow[it] = (unsigned)kRowPad + (unsigned)(t & 31) * (unsigned)g.Rp + (unsigned)b * (unsigned)g.Fp + (unsigned)g.Gf + (unsigned)(t >> 5);
+    ok |= 1u << it;
+  }
+  for (int cc = 0; cc < C / 64; ++cc) {
+    const int P0 = cc * 64 + g8 * 8;
+    float w[8][4], bs[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      bs[e] = bstart[P0 + e];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[e][j] = (j < h) ? wstart[(P0 + e) * h + j] : 0.0f;
+    }
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      if (!((ok >> it) & 1u)) continue;
+      const int rl = it * (FL_ROWS / 8) + (tid >> 3);
+      const float4 a0 = s_a0[rl];
+      half8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        o[e] = (_Float16)fmaf(w[e][3], a0.w, fmaf(w[e][2], a0.z, fmaf(w[e][1], a0.y, fmaf(w[e][0], a0.x, bs[e]))));
+      *(half8*)(x + ((size_t)cc * g.R + prow[it]) * 64 + g8 * 8) = o;
+    }
+  }
+}
+
 // FL_ROWS rows per workgroup = threads per workgroup: 256, or 64 for small workloads (a single utterance of 500 frames
 // is 16 000 rows: 63 workgroups of 256 left three quarters of the chip idle, 21 us per launch x 13 launches).
 template <int FL_ROWS>
@@ -1815,48 +1864,21 @@ __global__ void __launch_bounds__(FL_ROWS) flow_kernel(const FlowArgs a) {
   }
   if (a.last || a.skip_x) return;
   __syncthreads();
+  start_rows<FL_ROWS>(s_a0, row0, nrows, L, a.g, a.wstart, a.bstart, a.C, a.h_next, a.x);
+}
 
-  // ---- WN.start of the next flow (model.py:117): x[P] = sum_j Wst[P][j] a0[j] + b[P], fp16, position-major.
-  // piece = (chunk cc, row, 8-position group g8) = 16 contiguous bytes; idx = cc*2048 + row*8 + g8, so
-  // consecutive threads write consecutive bytes and a thread's g8 is fixed: its 8x4 weights sit in registers.
-  const int C = a.C, h = a.h_next;
-  const int g8 = tid & 7;
-  // plane rows of this thread's 8 rows (one per pass), once for all chunks: phase-major row of (b, t = 32q + p), see RowGeom
-  unsigned prow[8];
-  unsigned ok = 0;
-#pragma unroll
-  for (int it = 0; it < 8; ++it) {
-    const int rl = it * (FL_ROWS / 8) + (tid >> 3);
-    const size_t row = row0 + rl;
-    prow[it] = 0;
-    if (row >= nrows) continue;
-    const unsigned r32 = (unsigned)row;
-    const int b = (int)(r32 / (unsigned)L), t = (int)(r32 - (unsigned)b * (unsigned)L);
-    if (a.g.frames != nullptr && t >= 32 * a.g.frames[b]) continue;      // padding column of a ragged batch
-    prow[it] = (unsigned)kRowPad + (unsigned)(t & 31) * (unsigned)a.g.Rp + (unsigned)b * (unsigned)a.g.Fp + (unsigned)a.g.Gf + (unsigned)(t >> 5);
-    ok |= 1u << it;
-  }
-  for (int cc = 0; cc < C / 64; ++cc) {
-    const int P0 = cc * 64 + g8 * 8;
-    float w[8][4], bs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      bs[e] = a.bstart[P0 + e];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w[e][j] = (j < h) ? a.wstart[(P0 + e) * h + j] : 0.0f;
-    }
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      if (!((ok >> it) & 1u)) continue;
-      const int rl = it * (FL_ROWS / 8) + (tid >> 3);
-      const float4 a0 = s_a0[rl];
-      half8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        o[e] = (_Float16)fmaf(w[e][3], a0.w, fmaf(w[e][2], a0.z, fmaf(w[e][1], a0.y, fmaf(w[e][0], a0.x, bs[e]))));
-      *(half8*)(a.x + ((size_t)cc * a.g.R + prow[it]) * 64 + g8 * 8) = o;
-    }
-  }
+// x_0 planes of one flow from its saved state (WG_TRAIN_RECOMPUTE, train_api.cpp): the start half of flow_kernel alone,
+// a0 = Z[row][0..3] -- the same four floats flow_kernel kept in s_a0 when it wrote Z -- through the same start_rows.
+template <int FL_ROWS>
+__global__ void __launch_bounds__(FL_ROWS) start_replay_kernel(const FlowArgs a) {
+  __shared__ float4 s_a0[FL_ROWS];
+  const int L = a.g.L;
+  const size_t nrows = (size_t)a.g.B * L;
+  const size_t row0 = (size_t)blockIdx.x * FL_ROWS;
+  const size_t row = row0 + threadIdx.x;
+  if (row < nrows) s_a0[threadIdx.x] = *(const float4*)(a.Z + row * 8);
+  __syncthreads();
+  start_rows<FL_ROWS>(s_a0, row0, nrows, L, a.g, a.wstart, a.bstart, a.C, a.h_next, a.x);
 }
 
 hipError_t launch_flow(const FlowArgs& a, hipStream_t s) {
@@ -1866,6 +1888,18 @@ hipError_t launch_flow(const FlowArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(flow_kernel<64>, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, s, a);
   } else {
     hipLaunchKernelGGL(flow_kernel<256>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_start_replay(const FlowArgs& a, hipStream_t s) {
+  const size_t nrows = (size_t)a.g.B * a.g.L;
+  if (nrows >= (1ull << 31) || (size_t)a.g.R >= (1ull << 31)) return hipErrorInvalidValue;
+  if (!a.Z || !a.x || !a.wstart || !a.bstart || a.h_next < 1 || a.h_next > 4) return hipErrorInvalidValue;
+  if (nrows < 256 * 256) {
+    hipLaunchKernelGGL(start_replay_kernel<64>, dim3((unsigned)((nrows + 63) / 64)), dim3(64), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(start_replay_kernel<256>, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, a);
   }
   return hipGetLastError();
 }

@@ -74,9 +74,10 @@ __device__ __forceinline__ bool column_valid(const RowGeom& g, int p, int rr, in
 constexpr int PG_WAVES = 4;
 constexpr int PG_THREADS = 64 * PG_WAVES;
 
-template <int CT, int MT>
-__global__ void __launch_bounds__(PG_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
-plane_gemm_kernel(const PGemmArgs a) {
+// ACC: the epilogue of PGemmArgs::acc (a kernel of its own, plane_gemm_acc_kernel: its loads of the accumulator tile
+// cost registers that the plain epilogue does not need)
+template <int CT, int MT, bool ACC>
+__device__ __forceinline__ void plane_gemm_body(const PGemmArgs& a) {
   constexpr int BN = 32 * CT;    // tile width in rows = B-tile rows: CT 16-byte pieces per thread
   __shared__ __attribute__((aligned(16))) _Float16 sB[2][BN * 64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -206,17 +207,50 @@ plane_gemm_kernel(const PGemmArgs a) {
       const bool valid = column_valid(g, p, rr, b, t);
       const size_t prow = (size_t)kRowPad + (size_t)p * g.Rp + rr;
       const size_t addr = ((size_t)(P0 >> 6) * g.R + prow) * 64 + (P0 & 63);
-      half8 o0, o1;
+      if (ACC) {
+        // fp32 accumulator planes: the lane's 16 positions are 64 contiguous bytes at the same element offset
+        float4* ap = (float4*)(a.acc + addr);
+        half8 o0, o1;
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        float v = acc[mt][ct][j];
-        if (a.bias) v += a.bias[P0 + j];
-        if (!valid) v = 0.0f;
-        if (j < 8) o0[j] = (_Float16)v; else o1[j - 8] = (_Float16)v;
+        for (int q = 0; q < 4; ++q) {
+          float4 o = a.acc_in ? ap[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+          o.x = valid ? (a.acc_in ? o.x + acc[mt][ct][4 * q] : acc[mt][ct][4 * q]) : 0.0f;
+          o.y = valid ? (a.acc_in ? o.y + acc[mt][ct][4 * q + 1] : acc[mt][ct][4 * q + 1]) : 0.0f;
+          o.z = valid ? (a.acc_in ? o.z + acc[mt][ct][4 * q + 2] : acc[mt][ct][4 * q + 2]) : 0.0f;
+          o.w = valid ? (a.acc_in ? o.w + acc[mt][ct][4 * q + 3] : acc[mt][ct][4 * q + 3]) : 0.0f;
+          ap[q] = o;
+          if (q < 2) {
+            o0[4 * q] = (_Float16)o.x; o0[4 * q + 1] = (_Float16)o.y; o0[4 * q + 2] = (_Float16)o.z; o0[4 * q + 3] = (_Float16)o.w;
+          } else {
+            o1[4 * q - 8] = (_Float16)o.x; o1[4 * q - 7] = (_Float16)o.y; o1[4 * q - 6] = (_Float16)o.z; o1[4 * q - 5] = (_Float16)o.w;
+          }
+        }
+        if (a.o0) { *(half8*)(a.o0 + addr) = o0; *(half8*)(a.o0 + addr + 8) = o1; }
+      } else {
+        half8 o0, o1;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          float v = acc[mt][ct][j];
+          if (a.bias) v += a.bias[P0 + j];
+          if (!valid) v = 0.0f;
+          if (j < 8) o0[j] = (_Float16)v; else o1[j - 8] = (_Float16)v;
+        }
+        *(half8*)(a.o0 + addr) = o0; *(half8*)(a.o0 + addr + 8) = o1;
       }
-      *(half8*)(a.o0 + addr) = o0; *(half8*)(a.o0 + addr + 8) = o1;
     }
   }
+}
+
+template <int CT, int MT>
+__global__ void __launch_bounds__(PG_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
+plane_gemm_kernel(const PGemmArgs a) {
+  plane_gemm_body<CT, MT, false>(a);
+}
+
+template <int CT, int MT>
+__global__ void __launch_bounds__(PG_THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
+plane_gemm_acc_kernel(const PGemmArgs a) {
+  plane_gemm_body<CT, MT, true>(a);
 }
 
 namespace {
@@ -259,7 +293,8 @@ int plane_gemm_tile_cols(const RowGeom& g, int m_groups, int mt) {
 }
 
 hipError_t launch_plane_gemm(const PGemmArgs& a, hipStream_t s) {
-  if (a.g.Rp % 128 || a.n_runs < 1 || a.n_runs > kMaxRuns || a.M < 1 || !a.o0) return hipErrorInvalidValue;
+  if (a.g.Rp % 128 || a.n_runs < 1 || a.n_runs > kMaxRuns || a.M < 1 || !(a.o0 || a.acc)) return hipErrorInvalidValue;
+  if (a.acc && a.bias) return hipErrorInvalidValue;     // the accumulating epilogue has no bias term
   int k = 0;
   for (int i = 0; i < a.n_runs; ++i) k += a.run[i].n_chunks * 64;
   if (k != a.ktot) return hipErrorInvalidValue;
@@ -268,7 +303,18 @@ hipError_t launch_plane_gemm(const PGemmArgs& a, hipStream_t s) {
   if (const char* e = getenv("WG_TRAIN_MT"))
     if (atoi(e) == 1) mt = 1;
   const int m_groups = (a.M + 32 * PG_WAVES * mt - 1) / (32 * PG_WAVES * mt);
-  const int ct = plane_gemm_tile_cols(a.g, m_groups, mt);
+  int ct = plane_gemm_tile_cols(a.g, m_groups, mt);
+  if (a.acc) {
+    // the accumulating epilogue: at most 2 column tiles with all 640 rows in one workgroup (3 x 5 spills registers)
+    if (mt == 5 && ct > 2) ct = 2;
+    dim3 grid(kPhases * (a.g.Rp / (32 * ct)), m_groups);
+    if (mt == 5) hipLaunchKernelGGL((plane_gemm_acc_kernel<2, 5>), grid, dim3(PG_THREADS), 0, s, a);
+    else if (ct == 6) hipLaunchKernelGGL((plane_gemm_acc_kernel<6, 1>), grid, dim3(PG_THREADS), 0, s, a);
+    else if (ct == 4) hipLaunchKernelGGL((plane_gemm_acc_kernel<4, 1>), grid, dim3(PG_THREADS), 0, s, a);
+    else if (ct == 3) hipLaunchKernelGGL((plane_gemm_acc_kernel<3, 1>), grid, dim3(PG_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((plane_gemm_acc_kernel<2, 1>), grid, dim3(PG_THREADS), 0, s, a);
+    return hipGetLastError();
+  }
   dim3 grid(kPhases * (a.g.Rp / (32 * ct)), m_groups);
   if (mt == 5) {
     if (ct == 3) hipLaunchKernelGGL((plane_gemm_kernel<3, 5>), grid, dim3(PG_THREADS), 0, s, a);

@@ -62,9 +62,10 @@ size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 bool is_early(const wg_config& c, int k) { return k % c.n_early_every == 0 && k > 0; }
 
 struct TrainWs {
-  // fp16 planes (elements)
-  _Float16 *X, *T, *S, *A;      // [FL] x C/64 chunks each (plane_c elements per fl)
-  _Float16 *GP;                 // [FL] x 2C/64 chunks, contiguous: the K operand of the cond_layer dgrad
+  // fp16 planes (elements).  Layer planes: one set per layer of `slots` flows -- every flow (full save), or two flow slots
+  // k & 1 (WG_TRAIN_RECOMPUTE: the backward replays a flow's forward into its slot), see plane_layer
+  _Float16 *X, *T, *S, *A;      // [slots * n_layers] x C/64 chunks each (plane_c elements per layer)
+  _Float16 *GP;                 // [slots * n_layers] x 2C/64 chunks, contiguous: the K operand of the cond_layer dgrad
   _Float16 *GXL;                // [n_layers] x C/64 chunks: d x_i of the flow in flight (one buffer per layer: see chains)
   _Float16 *GO[2], *SP, *MELP, *GSP;   // d out plane (per flow parity), spectrogram planes, mel planes, d spect planes
   float *Zpost, *OUT;           // [n_flows][B*L*8]
@@ -73,24 +74,29 @@ struct TrainWs {
   float *part[2], *part2[2];    // column-sum partials of the two weight-gradient jobs (two sets)
   float *ext[2], *extb[2];      // d (W_end W_skip) partials [n_slabs][16][C] and their column sums [n_slabs][16]
   float *slab_up, *part3;       // d upsample slabs (one per phase) / partials of the row kernels of a flow and of d upsample
+  float *DSP;                   // WG_TRAIN_RECOMPUTE only: fp32 d spect accumulator planes [M8/64][R][64] (per-flow GEMMs)
+  float *OUTs;                  // WG_TRAIN_RECOMPUTE only: [B*L*8] skip sums of the replayed flows (OUT[k] is saved state)
+  int slots;                    // flows whose layer planes the workspace holds at once
   size_t plane_c;               // elements of one C-channel plane set
   size_t rows8;                 // B*L*8
   size_t zero_bytes;            // prefix that `fresh` clears (all planes)
   size_t bytes;
 };
 
-TrainWs carve(const wg_config& c, const RowGeom& g, const int* n_slabs, char* base) {
+TrainWs carve(const wg_config& c, const RowGeom& g, const int* n_slabs, char* base, bool recompute) {
   TrainWs w;
-  const int C = c.n_channels, FL = c.n_flows * c.n_layers, M8 = c.n_mel_channels * 8;
+  const int C = c.n_channels, M8 = c.n_mel_channels * 8;
+  w.slots = recompute ? 2 : c.n_flows;
+  const int SL = w.slots * c.n_layers;             // layers with planes of their own
   const size_t chunk = (size_t)g.R * 64;           // elements of one 64-channel plane
   w.plane_c = (size_t)(C / 64) * chunk;
   size_t off = 0;
   auto take = [&](size_t bytes) { char* p = base + off; off += align_up(bytes); return p; };
-  w.X = (_Float16*)take((size_t)FL * w.plane_c * 2);
-  w.T = (_Float16*)take((size_t)FL * w.plane_c * 2);
-  w.S = (_Float16*)take((size_t)FL * w.plane_c * 2);
-  w.A = (_Float16*)take((size_t)FL * w.plane_c * 2);
-  w.GP = (_Float16*)take((size_t)FL * 2 * w.plane_c * 2);
+  w.X = (_Float16*)take((size_t)SL * w.plane_c * 2);
+  w.T = (_Float16*)take((size_t)SL * w.plane_c * 2);
+  w.S = (_Float16*)take((size_t)SL * w.plane_c * 2);
+  w.A = (_Float16*)take((size_t)SL * w.plane_c * 2);
+  w.GP = (_Float16*)take((size_t)SL * 2 * w.plane_c * 2);
   w.GXL = (_Float16*)take((size_t)c.n_layers * w.plane_c * 2);
   w.GO[0] = (_Float16*)take(chunk * 2);
   w.GO[1] = (_Float16*)take(chunk * 2);
@@ -102,6 +108,8 @@ TrainWs carve(const wg_config& c, const RowGeom& g, const int* n_slabs, char* ba
   w.Zpost = (float*)take((size_t)c.n_flows * w.rows8 * 4);
   w.OUT = (float*)take((size_t)c.n_flows * w.rows8 * 4);
   w.GZ = (float*)take(w.rows8 * 4);
+  w.DSP = recompute ? (float*)take((size_t)(M8 / 64) * chunk * 4) : nullptr;     // every entry it reads it has written
+  w.OUTs = recompute ? (float*)take(w.rows8 * 4) : nullptr;
   const int cc = C / 64, mc = M8 / 64;
   const size_t t1 = (size_t)wgrad_tiles(2 * cc, 3 * cc + mc), t2 = (size_t)wgrad_tiles(cc, cc);
   for (int q = 0; q < 2; ++q) {
@@ -129,7 +137,11 @@ struct Ctx {
   int halves;      // 2: the batch runs as two independent half-batch chains (see setup)
   int n_slabs[2];  // row ranges of the two jobs of a weight-gradient launch (see setup)
   bool serial;     // WG_TRAIN_SERIAL=1: everything on the caller's stream (profiling of single kernels, A/B runs)
+  bool recompute;  // WG_TRAIN_RECOMPUTE: two flow slots of layer planes, the backward replays the others (see carve)
 };
+
+// index of the plane set of layer i of flow k: its own (full save) or its flow slot's (WG_TRAIN_RECOMPUTE)
+size_t plane_layer(const Ctx& x, int k, int i) { return (size_t)(x.recompute ? (k & 1) : k) * x.nl + i; }
 
 // sets rc_ and returns from the enclosing function on a HIP error of an ordering call
 #define TR_ORDER(expr)                                                                       \
@@ -147,8 +159,11 @@ hipError_t order_after(wg_handle* h, hipStream_t from, hipStream_t to) {
   return r != hipSuccess ? r : hipStreamWaitEvent(to, e, 0);
 }
 
-int setup(wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes, Ctx& x) {
+int setup(wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes, int32_t flags,
+          Ctx& x) {
   if (!h) return wg_set_error(WG_ERR_INVALID, "null handle");
+  if (flags & ~WG_TRAIN_RECOMPUTE) return wg_set_error(WG_ERR_INVALID, "unknown wg_train flags");
+  x.recompute = (flags & WG_TRAIN_RECOMPUTE) != 0;
   x.c = wg_internal_config(h);
   x.ck = wg_internal_flow_channels(h);
   const wg_config& c = *x.c;
@@ -209,8 +224,20 @@ int setup(wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, void* wo
     x.n_slabs[0] = (int)s1;
     x.n_slabs[1] = (int)s2;
   }
-  x.w = carve(c, x.g, x.n_slabs, (char*)workspace);
-  if (workspace && x.w.bytes > workspace_bytes) return wg_set_error(WG_ERR_WORKSPACE, "training workspace too small");
+  x.w = carve(c, x.g, x.n_slabs, (char*)workspace, x.recompute);
+  // A workspace keeps one layout from its forward to its backward.  The two sizes tell the layouts apart: a recompute
+  // workspace is smaller than a full-save one, so a call whose flags do not match the size it is given is refused.
+  const size_t full = x.recompute ? carve(c, x.g, x.n_slabs, nullptr, false).bytes : x.w.bytes;
+  const size_t rec = x.recompute ? x.w.bytes : carve(c, x.g, x.n_slabs, nullptr, true).bytes;
+  if (x.recompute && rec >= full)
+    return wg_set_error(WG_ERR_INVALID, "WG_TRAIN_RECOMPUTE saves no memory at this depth (two flow slots hold every layer)");
+  if (workspace) {
+    if (x.recompute && workspace_bytes >= full)
+      return wg_set_error(WG_ERR_INVALID, "WG_TRAIN_RECOMPUTE with a full-save training workspace: flags and workspace size do not match");
+    if (!x.recompute && workspace_bytes < full && rec < full && workspace_bytes >= rec)
+      return wg_set_error(WG_ERR_INVALID, "training workspace of the WG_TRAIN_RECOMPUTE size without the flag: flags and workspace size do not match");
+    if (x.w.bytes > workspace_bytes) return wg_set_error(WG_ERR_WORKSPACE, "training workspace too small");
+  }
   if ((size_t)x.g.R * 128 >= (1ull << 32)) return wg_set_error(WG_ERR_INVALID, "plane too large for 32-bit offsets");
   x.C = c.n_channels;
   x.nl = c.n_layers;
@@ -304,10 +331,11 @@ int spect_planes(const Ctx& x, const wg_train_weights* wt, const void* mel, hipS
   return WG_OK;
 }
 
-// The WN of flow k with saved activations (X / T / S / A planes of its layers), its output accumulated into OUT[k]
-// (initialised by the flow step before it).  The flow step's writes on `s` come first; sB (the second chain, = s for one)
-// is joined back into `s` at the end.
-int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int k, int BNw, hipStream_t s, hipStream_t sB) {
+// The WN of flow k with saved activations (X / T / S / A planes of its layers, plane_layer), its output accumulated into
+// `out` = OUT[k] (initialised by the flow step before it; a replay passes the scratch OUTs).  The flow step's writes on `s`
+// come first; sB (the second chain, = s for one) is joined back into `s` at the end.
+int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int k, int BNw, float* out, hipStream_t s,
+                    hipStream_t sB) {
   const wg_config& c = *x.c;
   const RowGeom& g = x.g;
   const TrainWs& w = x.w;
@@ -320,8 +348,9 @@ int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int 
   TR_ORDER(order_after(h, s, sB));
   for (int i = 0; i < nl; ++i) {
     const int fl = k * nl + i, d = 1 << i;
-    const _Float16* Xi = w.X + (size_t)fl * w.plane_c;
-    _Float16* Ai = w.A + (size_t)fl * w.plane_c;
+    const size_t pl = plane_layer(x, k, i);
+    const _Float16* Xi = w.X + pl * w.plane_c;
+    _Float16* Ai = w.A + pl * w.plane_c;
     // ONE fused launch per layer (kernels.hip: wn_layer_kernel<..., TR = true>): in_layers[i] + cond_layer slice as one
     // K-extended GEMM, gate in registers (tanh / sigmoid / acts saved as planes for the backward pass), res rows +
     // residual add -> x_{i+1}, skip rows folded through WN.end -> OUT   (model.py:123-137)
@@ -330,14 +359,14 @@ int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int 
     a.x_in = Xi;
     a.x_tap = Xi;
     a.x_chunks_per_tap = cc;
-    a.x_out = (i < nl - 1) ? w.X + (size_t)(fl + 1) * w.plane_c : nullptr;
+    a.x_out = (i < nl - 1) ? w.X + (pl + 1) * w.plane_c : nullptr;
     a.wA1 = (const _Float16*)wt->a1 + (size_t)fl * a1_n;
     a.wA1c = (const _Float16*)wt->a1c + (size_t)fl * a1c_n;
     a.bias1 = wt->b1 + (size_t)fl * 2 * C;
     a.wA2 = (const _Float16*)wt->a2 + (size_t)fl * a2_n;
     a.bias2 = wt->b2 + (size_t)fl * C;
     a.wEs = (const _Float16*)wt->es + (size_t)fl * es_n;
-    a.out = w.OUT + (size_t)k * w.rows8;
+    a.out = out;
     a.g = g;
     a.dil = d;
     a.n_cond_steps = mc;
@@ -345,8 +374,8 @@ int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int 
     a.has_res = i < nl - 1;
     a.n_cu = x.n_cu;
     a.sp = w.SP;
-    a.save_t = w.T + (size_t)fl * w.plane_c;
-    a.save_s = w.S + (size_t)fl * w.plane_c;
+    a.save_t = w.T + pl * w.plane_c;
+    a.save_s = w.S + pl * w.plane_c;
     a.save_a = Ai;
     for (int half = 0; half < x.halves; ++half) {
       hipStream_t sh = half ? sB : s;
@@ -354,6 +383,51 @@ int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int 
     }
   }
   TR_ORDER(order_after(h, sB, s));
+  return WG_OK;
+}
+
+// WG_TRAIN_RECOMPUTE: flow k's forward once more, into its plane slot.  x_0 comes from the saved state Zpost[k] (the
+// post-1x1 state in the training direction, the state entering inverse step k in synthesis) through start_replay, which
+// shares flow_kernel's x_0 arithmetic; then wn_flow_forward's launches with the forward's tile width (fwd_block_n) and
+// half-batch split, their skip sums into the scratch OUTs.  X / T / S / A come out bit-identical to the forward's.
+// chains: the second half-batch chain on its own stream, as in the forward (false: both halves on `s`, same launches).
+int replay_flow(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int k, bool chains, hipStream_t s) {
+  hipStream_t sB = s;
+  if (chains && x.halves == 2 && !x.serial) {
+    sB = wg_internal_aux_stream(h, 0);
+    if (!sB) return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
+  }
+  FlowArgs f;
+  memset(&f, 0, sizeof f);
+  f.g = x.g;
+  f.C = x.C;
+  f.Z = x.w.Zpost + (size_t)k * x.w.rows8;
+  f.h_next = x.ck[k] / 2;
+  f.wstart = wt->wstart[k];
+  f.bstart = wt->bstart[k];
+  f.x = x.w.X + plane_layer(x, k, 0) * x.w.plane_c;
+  TR_TRY(launch_start_replay(f, s));
+  return wn_flow_forward(h, x, wt, k, fwd_block_n(x), x.w.OUTs, s, sB);
+}
+
+// WG_TRAIN_RECOMPUTE: d spect += cond_layer^T d pre over the layers of flow k -- K = n_layers * 2C of its slot's GP planes
+// (contiguous) against the matching K range of wct -- in the fp32 DSP planes: stored by the first flow of the backward,
+// added by the others; the last one also writes the loss-scaled fp16 GSP planes that dmel and the d upsample job read.
+int dspect_flow(const Ctx& x, const wg_train_weights* wt, int k, bool first, bool last, hipStream_t s) {
+  const int cc = x.C / 64;
+  PGemmArgs a;
+  memset(&a, 0, sizeof a);
+  a.n_runs = 1;
+  a.run[0] = run_of(x.w.GP + plane_layer(x, k, 0) * 2 * x.w.plane_c, x.nl * 2 * cc, 0);
+  a.n_blk = x.M8 / 32;
+  a.A = (const _Float16*)wt->wct + (size_t)k * x.nl * 2 * cc * a.n_blk * 2048;     // K offset of flow k's first layer
+  a.ktot = x.nl * 2 * x.C;
+  a.M = x.M8;
+  a.g = x.g;
+  a.acc = x.w.DSP;
+  a.acc_in = !first;
+  a.o0 = last ? x.w.GSP : nullptr;
+  TR_TRY(launch_plane_gemm(a, s));
   return WG_OK;
 }
 
@@ -396,24 +470,35 @@ int wg_train_pack(wg_handle* h, const wg_train_plain* in, const wg_train_weights
 }
 
 size_t wg_train_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len) {
+  return wg_train_workspace_bytes_ex(h, B, n_frames, audio_len, 0);
+}
+
+size_t wg_train_workspace_bytes_ex(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, int32_t flags) {
   Ctx x;
-  if (setup(const_cast<wg_handle*>(h), B, n_frames, audio_len, nullptr, 0, x) != WG_OK) return 0;
+  if (setup(const_cast<wg_handle*>(h), B, n_frames, audio_len, nullptr, 0, flags, x) != WG_OK) return 0;
   return x.w.bytes;
 }
 
 int wg_train_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* audio, float* z,
                      float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
                      void* workspace, size_t workspace_bytes, void* stream) {
+  return wg_train_forward_flags(h, wt, mel, audio, z, log_s, B, n_frames, audio_len, fresh, workspace, workspace_bytes, 0,
+                                stream);
+}
+
+int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* audio, float* z,
+                           float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
+                           void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
   if (!wt || !mel || !audio || !z || !log_s || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
   Ctx x;
-  int rc = setup(h, B, n_frames, audio_len, workspace, workspace_bytes, x);
+  int rc = setup(h, B, n_frames, audio_len, workspace, workspace_bytes, flags, x);
   if (rc) return rc;
   if ((rc = check_weights(wt, x.c->n_flows))) return rc;
   const wg_config& c = *x.c;
   const RowGeom& g = x.g;
   TrainWs& w = x.w;
   hipStream_t s = (hipStream_t)stream;
-  const int C = x.C, nl = x.nl;
+  const int C = x.C;
   // second chain (the caller's stream is the first): see setup
   hipStream_t sB = s;
   if (x.halves == 2 && !x.serial) {
@@ -458,14 +543,14 @@ int wg_train_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, 
       f.wstart = wt->wstart[k];
       f.bstart = wt->bstart[k];
       f.out_init = wt->out_init[k];
-      f.x = w.X + (size_t)(k * nl) * w.plane_c;
+      f.x = w.X + plane_layer(x, k, 0) * w.plane_c;      // flow k's slot (WG_TRAIN_RECOMPUTE: k & 1)
       z_ch += f.n_peel;
     }
     // (measured and dropped: each chain running its own half of the flow step, so that the chains never meet -- they
     //  drift apart and the forward pass took 0.2-1.0 ms longer than with this join per flow)
     TR_TRY(launch_flow(f, s));
     if (f.last) break;
-    if ((rc = wn_flow_forward(h, x, wt, k, BNw, s, sB))) return rc;
+    if ((rc = wn_flow_forward(h, x, wt, k, BNw, w.OUT + (size_t)k * w.rows8, s, sB))) return rc;
   }
   return WG_OK;
 }
@@ -493,10 +578,18 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
                          const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
                          int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
                          int32_t flow_hi, int32_t flow_lo, void* stream) {
+  return wg_train_backward_ex_flags(h, wt, gr, g_z, g_log_s, scale, audio, g_mel, g_audio, B, n_frames, audio_len, workspace,
+                                    workspace_bytes, flow_hi, flow_lo, 0, stream);
+}
+
+int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_z,
+                               const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
+                               int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
+                               int32_t flow_hi, int32_t flow_lo, int32_t flags, void* stream) {
   if (!wt || !audio || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
   if (!(scale > 0.f)) return wg_set_error(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
-  int rc = setup(h, B, n_frames, audio_len, workspace, workspace_bytes, x);
+  int rc = setup(h, B, n_frames, audio_len, workspace, workspace_bytes, flags, x);
   if (rc) return rc;
   if ((rc = check_weights(wt, x.c->n_flows)) || (gr && (rc = check_grads(gr, x.c->n_flows)))) return rc;
   if (g_mel && !wt->wupt) return wg_set_error(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
@@ -568,7 +661,12 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
   //                    sW's second job of layer i-1: the next flow's layer-i launch waits for that job (w_done[i-1]);
   //   GO[k & 1]        written by flow k's pre kernel on s, read by the chains and by all of flow k's jobs on sW: the pre
   //                    kernel of flow k-2 waits for the last of them (w_flow[k & 1]);
-  //   GP, X, T, S, A   one set per layer of the whole model: no reuse inside a call.
+  //   GP, X, T, S, A   full save: one set per layer of the whole model, no reuse inside a call.  WG_TRAIN_RECOMPUTE: one
+  //                    set per layer of flow slot k & 1, read by flow k's chain launches (s / sB, joined into s at the
+  //                    end of the flow) and by its weight-gradient jobs and d spect GEMM on sW (X, A, GP): the replay of
+  //                    flow k-2 into the slot runs on s behind the same w_flow[k & 1] wait as its pre kernel.  The
+  //                    forward leaves flows n_flows-1 and n_flows-2 in their slots: they are not replayed.  Across the
+  //                    calls of a flow range everything is joined into s at the end of a call.
   if (pg) TR_ORDER(order_after(h, s, sW));
   // A layer's slabs are reduced by a launch of its own on a third stream (sR, lowest priority too): it is HBM-bound and
   // small in registers and LDS, so its workgroups run beside the NEXT layer's weight-gradient workgroups (MFMA / L2-bound,
@@ -608,15 +706,17 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
     _Float16* const GOk = w.GO[k & 1];
     fb.GO = GOk;
     TR_ORDER(wait_for(s, w_flow[k & 1]));
+    if (x.recompute && k < c.n_flows - 2 && (rc = replay_flow(h, x, wt, k, true, s))) return rc;
     TR_TRY(launch_flow_bwd_pre(fb, s));
     TR_ORDER(order_after(h, s, sB));
 
     _Float16* gx = nullptr;                     // gx = d x_{i+1} (null: zero, the last layer has no res output)
     for (int i = nl - 1; i >= 0; --i) {
       const int fl = k * nl + i, d = 1 << i;
-      const _Float16* Xi = w.X + (size_t)fl * w.plane_c;
-      const _Float16* Ai = w.A + (size_t)fl * w.plane_c;
-      _Float16* GPi = w.GP + (size_t)fl * 2 * w.plane_c;
+      const size_t pl = plane_layer(x, k, i);
+      const _Float16* Xi = w.X + pl * w.plane_c;
+      const _Float16* Ai = w.A + pl * w.plane_c;
+      _Float16* GPi = w.GP + pl * 2 * w.plane_c;
       // Fused (round 3): the d x launch of layer i + 1 has already produced d pre of this layer behind its own result
       // (wn_layer_kernel MODE 4: the d x tile goes through LDS into the next GEMM instead of out to the planes and back in
       // through a launch of its own); only a flow's last layer, which has no d x above it, runs MODE 3 alone.
@@ -643,8 +743,8 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
         a.g = g;
         a.M = c.n_mel_channels;
         a.n_cu = n_cu;
-        a.in0 = w.T + (size_t)fl * w.plane_c;
-        a.in1 = w.S + (size_t)fl * w.plane_c;
+        a.in0 = w.T + pl * w.plane_c;
+        a.in1 = w.S + pl * w.plane_c;
         a.out0 = GPi;
         for (int half = 0; half < bh; ++half) {
           hipStream_t sh = half ? sB : s;
@@ -735,9 +835,9 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
         if (kind == 4) {      // ... and d acts + gate derivative of layer i - 1 on the tile (see above)
           a.wat_prev = wat + (size_t)(fl - 1) * wat_n;
           a.gout = GOk;
-          a.t_prev = w.T + (size_t)(fl - 1) * w.plane_c;
-          a.s_prev = w.S + (size_t)(fl - 1) * w.plane_c;
-          a.dpre_prev = w.GP + (size_t)(fl - 1) * 2 * w.plane_c;
+          a.t_prev = w.T + (pl - 1) * w.plane_c;
+          a.s_prev = w.S + (pl - 1) * w.plane_c;
+          a.dpre_prev = w.GP + (pl - 1) * 2 * w.plane_c;
         }
         for (int half = 0; half < bh; ++half) {
           hipStream_t sh = half ? sB : s;
@@ -747,8 +847,13 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
         gx = gxi;
       }
     }
+    // WG_TRAIN_RECOMPUTE: this flow's share of d spect while its slot still holds its d pre planes -- on sW behind the
+    // flow's last weight-gradient job, so that w_flow covers it; without parameter gradients on s behind the chains
+    const bool dspect = x.recompute && (pg || g_mel);
+    if (dspect && pg && (rc = dspect_flow(x, wt, k, k == c.n_flows - 1, k == 0, sW))) return rc;
     if (pg) TR_ORDER(mark(sW, w_flow[k & 1], 10 + (k & 1)));
     TR_ORDER(order_after(h, sB, s));
+    if (dspect && !pg && (rc = dspect_flow(x, wt, k, k == c.n_flows - 1, k == 0, s))) return rc;
     if (pg) {
       StartWgradArgs a;
       a.g = g;
@@ -792,7 +897,9 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
     }
     return WG_OK;
   }
-  {
+  if (x.recompute) {
+    if (pg) TR_ORDER(order_after(h, sW, s));    // flow 0's d spect GEMM wrote GSP on sW
+  } else {
     // d spect = sum over every layer of cond_layer^T d pre: ONE GEMM with K = FL*2C over the kept d pre planes
     PGemmArgs a;
     memset(&a, 0, sizeof a);
@@ -847,6 +954,8 @@ int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_trai
 // kernels, with the state that enters every inverse step saved, and its backward w.r.t. mel and the noise.
 //   workspace: Zpost[k] = the state y entering inverse step k (step n_flows-1: sigma z_init), OUT[k] = (b | s) of WN_k,
 //   X / T / S / A planes of flow k's layers as in the training forward; the backward keeps GP of every layer for d spect.
+//   WG_TRAIN_RECOMPUTE: as in the training direction, two flow slots; the forward leaves flows 1 and 0 in them, the
+//   backward (ascending) replays flows 2.. into theirs and runs d spect flow by flow.
 // ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -858,12 +967,12 @@ int n_early_flows(const wg_config& c) {
 
 // common checks and geometry of both calls: audio_len = 256 n_frames (infer's trim, model.py:228)
 int infer_setup(wg_handle* h, const wg_train_weights* wt, int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace,
-                size_t workspace_bytes, Ctx& x, const float** winv) {
+                size_t workspace_bytes, int32_t flags, Ctx& x, const float** winv) {
   const wg_config* c = wg_internal_config(h);
   if (!c) return wg_set_error(WG_ERR_INVALID, "null handle");
   if (n_frames < 1) return wg_set_error(WG_ERR_INVALID, "bad n_frames");
   if (c->n_flows > 64) return wg_set_error(WG_ERR_INVALID, "too many flows");
-  int rc = setup(h, B, n_frames, n_frames * c->upsample_stride, workspace, workspace_bytes, x);
+  int rc = setup(h, B, n_frames, n_frames * c->upsample_stride, workspace, workspace_bytes, flags, x);
   if (rc) return rc;
   if ((rc = check_weights(wt, c->n_flows))) return rc;
   if (n_z_early != n_early_flows(*c)) return wg_set_error(WG_ERR_INVALID, "wrong number of early-noise tensors");
@@ -882,7 +991,7 @@ void infer_next(const Ctx& x, const wg_train_weights* wt, int j, FlowArgs& f) {
   f.out_init = wt->out_init[j];
   f.Z_w = x.w.Zpost + (size_t)j * x.w.rows8;
   f.out_w = x.w.OUT + (size_t)j * x.w.rows8;
-  f.x = x.w.X + (size_t)(j * x.nl) * x.w.plane_c;
+  f.x = x.w.X + plane_layer(x, j, 0) * x.w.plane_c;
   f.skip_x = 0;
   f.a0p = nullptr;
 }
@@ -892,11 +1001,19 @@ void infer_next(const Ctx& x, const wg_train_weights* wt, int j, FlowArgs& f) {
 int wg_train_infer_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* z_init,
                            const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
                            int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, void* stream) {
+  return wg_train_infer_forward_flags(h, wt, mel, z_init, z_early, n_z_early, sigma, audio, B, n_frames, fresh, workspace,
+                                      workspace_bytes, 0, stream);
+}
+
+int wg_train_infer_forward_flags(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* z_init,
+                                 const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
+                                 int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
+                                 void* stream) {
   if (!wt || !mel || !z_init || !audio || !workspace || (n_z_early > 0 && !z_early))
     return wg_set_error(WG_ERR_INVALID, "null argument");
   Ctx x;
   const float* winv[64];
-  int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, x, winv);
+  int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, flags, x, winv);
   if (rc) return rc;
   for (int i = 0; i < n_z_early; ++i)
     if (!z_early[i]) return wg_set_error(WG_ERR_INVALID, "null early-noise tensor");
@@ -929,7 +1046,7 @@ int wg_train_infer_forward(wg_handle* h, const wg_train_weights* wt, const void*
   }
   int ze = 0;
   for (int k = c.n_flows - 1; k >= 0; --k) {
-    if ((rc = wn_flow_forward(h, x, wt, k, BNw, s, sB))) return rc;
+    if ((rc = wn_flow_forward(h, x, wt, k, BNw, x.w.OUT + (size_t)k * x.w.rows8, s, sB))) return rc;
     // inverse coupling, W_k^-1, early noise in front   (model.py:253-271); the input state stays in Zpost[k]
     FlowArgs f = base();
     f.Z = x.w.Zpost + (size_t)k * x.w.rows8;
@@ -959,11 +1076,18 @@ int wg_train_infer_forward(wg_handle* h, const wg_train_weights* wt, const void*
 int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const float* g_audio, float scale, float sigma,
                             float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
                             int32_t n_frames, void* workspace, size_t workspace_bytes, void* stream) {
+  return wg_train_infer_backward_flags(h, wt, g_audio, scale, sigma, g_mel, g_z_init, g_z_early, n_z_early, B, n_frames,
+                                       workspace, workspace_bytes, 0, stream);
+}
+
+int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, const float* g_audio, float scale, float sigma,
+                                  float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
+                                  int32_t n_frames, void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
   if (!wt || !g_audio || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
   if (!(scale > 0.f)) return wg_set_error(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
   const float* winv[64];
-  int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, x, winv);
+  int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, flags, x, winv);
   if (rc) return rc;
   if (g_mel && !wt->wupt) return wg_set_error(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
   const wg_config& c = *x.c;
@@ -997,9 +1121,11 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const floa
     return n;
   };
   // Ascending flow order: the gradient enters at the audio, the output of inverse step 0.  Everything runs on `s`, so the
-  // GO plane, GXL and GZ are reused in stream order (GO[k & 1] only keeps the training direction's plane names).
+  // GO plane, GXL and GZ are reused in stream order (GO[k & 1] only keeps the training direction's plane names), and so
+  // are the flow slots of WG_TRAIN_RECOMPUTE: flow k's replay follows every reader of flow k-2's planes.
   for (int k = 0; k < c.n_flows; ++k) {
     const int ck = x.ck[k];
+    if (x.recompute && k >= 2 && (rc = replay_flow(h, x, wt, k, false, s))) return rc;
     InvBwdArgs ib;
     memset(&ib, 0, sizeof ib);
     ib.g = g;
@@ -1020,7 +1146,8 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const floa
     _Float16* gx = nullptr;                     // d x_{i+1} (null: the last layer has no res output)
     for (int i = nl - 1; i >= 0; --i) {
       const int fl = k * nl + i, d = 1 << i;
-      _Float16* GPi = w.GP + (size_t)fl * 2 * w.plane_c;
+      const size_t pl = plane_layer(x, k, i);
+      _Float16* GPi = w.GP + pl * 2 * w.plane_c;
       if (!fuse || i == nl - 1) {
         // d acts = W_res^T d x_{i+1} + (W_end W_skip_i)^T d out ; gate derivative -> d pre   (wn_layer_kernel MODE 3)
         WnLayerArgs a;
@@ -1044,8 +1171,8 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const floa
         a.g = g;
         a.M = c.n_mel_channels;
         a.n_cu = x.n_cu;
-        a.in0 = w.T + (size_t)fl * w.plane_c;
-        a.in1 = w.S + (size_t)fl * w.plane_c;
+        a.in0 = w.T + pl * w.plane_c;
+        a.in1 = w.S + pl * w.plane_c;
         a.out0 = GPi;
         TR_PROF(s, 5, TR_TRY(launch_part(a, g, BNw, 0, 1, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, 3, bn, s); })));
       }
@@ -1069,9 +1196,9 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const floa
         if (kind == 4) {
           a.wat_prev = wat + (size_t)(fl - 1) * wat_n;
           a.gout = GOk;
-          a.t_prev = w.T + (size_t)(fl - 1) * w.plane_c;
-          a.s_prev = w.S + (size_t)(fl - 1) * w.plane_c;
-          a.dpre_prev = w.GP + (size_t)(fl - 1) * 2 * w.plane_c;
+          a.t_prev = w.T + (pl - 1) * w.plane_c;
+          a.s_prev = w.S + (pl - 1) * w.plane_c;
+          a.dpre_prev = w.GP + (pl - 1) * 2 * w.plane_c;
         }
         TR_PROF(s, 5, TR_TRY(launch_part(a, g, BNw, 0, 1, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, kind, bn, s); })));
         gx = gxi;
@@ -1087,9 +1214,11 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const floa
       ib.g_peel = g_z_early ? g_z_early[early_index(k + 1)] : nullptr;
     }
     TR_TRY(launch_inv_bwd_post(ib, s));
+    // WG_TRAIN_RECOMPUTE: this flow's share of d spect before the slot is replayed for flow k+2
+    if (x.recompute && g_mel && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, s))) return rc;
   }
   if (!g_mel) return WG_OK;
-  {
+  if (!x.recompute) {
     // d spect = sum over every layer of cond_layer^T d pre: ONE GEMM with K = FL*2C over the kept d pre planes
     PGemmArgs a;
     memset(&a, 0, sizeof a);

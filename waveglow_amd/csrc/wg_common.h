@@ -175,6 +175,9 @@ hipError_t launch_zero_fill(void* p, size_t bytes, hipStream_t s);   // 16-byte 
 hipError_t launch_cond_fold(const float* w_cond, const float* w_up, _Float16* out, int C, int NW, int M, int n_layers,
                             int up_kernel, float tanh_scale, float sigm_scale, int frag16, hipStream_t s);
 hipError_t launch_flow(const FlowArgs& a, hipStream_t s);
+// x_0 planes (FlowArgs::x) of a flow from its saved state FlowArgs::Z (a0 = Z[:, :h_next]) with wstart / bstart: the
+// values flow_kernel wrote when it produced Z, bit for bit (training direction, WG_TRAIN_RECOMPUTE)
+hipError_t launch_start_replay(const FlowArgs& a, hipStream_t s);
 hipError_t launch_wn_layer(const WnLayerArgs& a, int C, int bn, hipStream_t s);   // bn = 128 (default) or 64
 hipError_t launch_wn_layer_train(const WnLayerArgs& a, int C, int bn, hipStream_t s);   // training forward (a.sp, a.save_*)
 hipError_t launch_wn_plain(const WnLayerArgs& a, int C, int kind, int bn, hipStream_t s);   // backward dgrad GEMMs (kind 2 / 3)

@@ -38,7 +38,11 @@ struct PGemmArgs {
   int M;                    // number of matrix rows
   const float* bias;        // fp32, pos order, or null
   RowGeom g;
-  _Float16* o0;             // output planes [M/64][R][64]
+  _Float16* o0;             // output planes [M/64][R][64], or null with `acc`
+  // Optional fp32 accumulator planes [M/64][R][64] (the per-flow d spect GEMMs of WG_TRAIN_RECOMPUTE): the result, plus
+  // what acc holds when acc_in, is stored to acc -- and to o0 as fp16 when o0 is non-null.  null: o0 alone, as above.
+  float* acc;
+  int acc_in;
 };
 
 // Weight gradient dW[m][k'] = sum over rows of G[row][m] * X[row (+ shift)][k'] (train.hip: wgrad_kernel).

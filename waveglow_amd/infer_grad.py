@@ -28,35 +28,37 @@ from .train import _ptr, _SlotGuard, _Weights, canonical_params, nonfinite_messa
 
 
 class _InferFn(torch.autograd.Function):
-  """Inputs: model, sigma, loss scale (0 = automatic), weight-norm flag, number of early-noise tensors, mel, z_init,
+  """Inputs: model, sigma, loss scale (0 = automatic), weight-norm flag, wg_train flags (``WG_TRAIN_RECOMPUTE``: activation
+  recomputation, the backward runs with its forward's flags), number of early-noise tensors, mel, z_init,
   z_early..., then the module's parameters in the library's canonical order (constants: never differentiated, but the
   library reads them through ``wg_train_prepare``).  Output: audio [B, 256 T] fp32.  backward() returns only what
   ``ctx.needs_input_grad`` asks for among mel, z_init and the z_early entries."""
 
-  N_META = 5      # model, sigma, scale, wn, n_early
+  N_META = 6      # model, sigma, scale, wn, flags, n_early
 
   @staticmethod
-  def forward(ctx, model, sigma, scale, wn, n_early, mel, z_init, *rest):
+  def forward(ctx, model, sigma, scale, wn, flags, n_early, mel, z_init, *rest):
     z_early, params = rest[:n_early], rest[n_early:]
     eng = model._get_engine(mel.device)          # finalised with the current weights: the W^-1 of infer
     lib = eng.lib
     B, M, T = mel.shape
     flow_c = model.flow_channels()
     stream = torch.cuda.current_stream(mel.device).cuda_stream
-    want_mel = ctx.needs_input_grad[5]
+    want_mel = ctx.needs_input_grad[6]
     wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=want_mel)
     S = 256 * T
-    nbytes = lib.wg_train_workspace_bytes(eng.handle, B, T, S)
+    nbytes = lib.wg_train_workspace_bytes_ex(eng.handle, B, T, S, flags)
     if nbytes == 0:
       raise _lib.WgError(lib.wg_last_error().decode())
-    slot, fresh = eng.train_workspace(nbytes, (B, T, S, nbytes))      # held until this graph's backward has run
+    slot, fresh = eng.train_workspace(nbytes, (B, T, S), flags)      # held until this graph's backward has run
     ws = slot["ws"]
     audio = torch.empty((B, S), dtype=torch.float32, device=mel.device)
     ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
-    _lib.check(lib.wg_train_infer_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
-                                          float(sigma), _ptr(audio), B, T, 1 if fresh else 0, _ptr(ws), ws.numel(),
-                                          C.c_void_p(stream)))
+    _lib.check(lib.wg_train_infer_forward_flags(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
+                                                float(sigma), _ptr(audio), B, T, 1 if fresh else 0, _ptr(ws), ws.numel(),
+                                                flags, C.c_void_p(stream)))
     ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.guard = model, wts, ws, (B, M, T), _SlotGuard(slot)
+    ctx.flags = flags
     ctx.sigma, ctx.n_early, ctx.n_params = float(sigma), n_early, len(params)
     ctx.sig = eng.signature
     ctx.z_shapes = [tuple(z_init.shape)] + [tuple(z.shape) for z in z_early]
@@ -81,8 +83,8 @@ class _InferFn(torch.autograd.Function):
     dev = ctx.ws.device
     ne = ctx.n_early
     need = ctx.needs_input_grad
-    want_mel, want_zi = need[5], need[6]
-    want_ze = list(need[7:7 + ne])
+    want_mel, want_zi = need[6], need[7]
+    want_ze = list(need[8:8 + ne])
     poison = os.environ.get("WG_TRAIN_POISON_GRADS") == "1"
     new = (lambda sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)) if poison else \
         (lambda sh: torch.empty(sh, dtype=torch.float32, device=dev))
@@ -93,10 +95,10 @@ class _InferFn(torch.autograd.Function):
     ze = (C.c_void_p * max(1, ne))(*[(g.data_ptr() if g is not None else None) for g in g_ze])
     stream = torch.cuda.current_stream(dev).cuda_stream
     try:
-      _lib.check(lib.wg_train_infer_backward(eng.handle, C.byref(ctx.wts.struct), _ptr(ga), C.c_float(ctx.scale),
-                                             C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
-                                             _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws), ctx.ws.numel(),
-                                             C.c_void_p(stream)))
+      _lib.check(lib.wg_train_infer_backward_flags(eng.handle, C.byref(ctx.wts.struct), _ptr(ga), C.c_float(ctx.scale),
+                                                   C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
+                                                   _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws),
+                                                   ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
     finally:
       ctx.guard.release()
       ctx.wts = None
@@ -110,10 +112,10 @@ class _InferFn(torch.autograd.Function):
 
 
 def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_early: List[torch.Tensor], sigma: float,
-                         grad_scale: float = 0.0) -> torch.Tensor:
+                         grad_scale: float = 0.0, recompute: bool = False) -> torch.Tensor:
   """``model.infer_with_noise(spect, z_init, z_early, sigma)`` (fp32) with an autograd graph back to ``spect``, ``z_init``
   and every ``z_early[i]`` that requires grad.  Without grad mode, or when none of them requires grad, exactly
-  ``infer_with_noise`` (nothing is saved)."""
+  ``infer_with_noise`` (nothing is saved).  ``recompute``: activation recomputation (``WG_TRAIN_RECOMPUTE``)."""
   ins = [spect, z_init] + list(z_early)
   for t in ins:
     if t.device.type != "cuda":
@@ -141,4 +143,5 @@ def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_ear
     return model.infer_with_noise(spect, z_init, z_early, sigma)
   _names, tensors, wn = canonical_params(model, eng)
   ins = [t.contiguous() for t in ins]
-  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, n_early, *ins, *tensors)
+  flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
+  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, flags, n_early, *ins, *tensors)

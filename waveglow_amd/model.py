@@ -183,23 +183,35 @@ class _Engine:
     return ws
 
 
-  def train_workspace(self, nbytes: int, key: Tuple[int, ...]) -> Tuple[dict, bool]:
+  def train_workspace(self, nbytes: int, key: Tuple[int, ...], flags: int = 0) -> Tuple[dict, bool]:
     """A workspace of the training direction (saved activations) that no pending backward still needs.
     ``fresh`` tells the library to clear it (guard rows must read as zero; they stay zero as long as the geometry
     ``key`` does not change).  Normally there is exactly one; a second forward() before the first backward()
-    (gradient accumulation over micro-batches, two losses) gets another one instead of clobbering the first."""
+    (gradient accumulation over micro-batches, two losses) gets another one instead of clobbering the first.
+    The pool is keyed by the wg_train ``flags`` as well (a ``WG_TRAIN_RECOMPUTE`` workspace has its own layout and size,
+    and the library refuses one of the other mode): workspaces of both modes live side by side, so alternating modes
+    reallocate nothing."""
     pool = self._train_pool
-    pool[:] = [e for e in pool if e["key"] == key and e["ws"].numel() >= nbytes]   # geometry changed: drop the old ones
+    pool[:] = [e for e in pool if e["key"] == key]          # geometry changed: drop the old ones (of both modes)
     for e in pool:
-      if not e["busy"]:
+      if e["flags"] == flags and e["ws"].numel() == nbytes and not e["busy"]:
         e["busy"] = True
         return e, False
-    e = {"key": key, "ws": torch.empty(nbytes, dtype=torch.uint8, device=self.device), "busy": True}
+    e = {"key": key, "flags": flags, "ws": torch.empty(nbytes, dtype=torch.uint8, device=self.device), "busy": True}
     pool.append(e)
     return e, True
 
 
 class WaveGlow(nn.Module):
+  # Activation recomputation for the training direction (``forward`` under autograd) and ``infer_differentiable``: the
+  # training workspace keeps the WN layer planes of two flows instead of all of them (about 0.2x its size at 256
+  # channels) and ``backward()`` recomputes each flow's planes from its saved state, in HIP, just before that flow's
+  # backward (about one more forward pass of the WN layers).  Read when the forward runs; its autograd node keeps the mode
+  # it ran with.  Results equal the default mode's bit for bit except the gradients that go through the upsample (upsample
+  # weight / bias, mel): their summation order differs (~1e-6 relative).  ``gradient_workspace_bytes`` sizes both modes.
+  # (``model.grad_scale``, the loss scale of the fp16 gradient planes, is read at the same points.)
+  recompute_activations: bool = False
+
   def __init__(self, hparams: HParams):
     super().__init__()
     self.upsample = nn.ConvTranspose1d(hparams.n_mel_channels, hparams.n_mel_channels, 1024, stride=256)
@@ -372,7 +384,10 @@ class WaveGlow(nn.Module):
     that requires grad raises ``WgError`` (``model.requires_grad_(False)``).  Without grad mode, or when no input requires
     grad, this is ``infer_with_noise``.  The fp16 gradient planes take ``model.grad_scale`` as loss scale (default:
     2^round(log2(audio.numel())), for a loss normalised by the number of samples); ``model.grad_finite`` is set by the
-    backward pass.  Takes the training direction's widths (n_channels 64 / 128 / 256 / 512, n_mel_channels % 16 == 0)."""
+    backward pass.  Takes the training direction's widths (n_channels 64 / 128 / 256 / 512, n_mel_channels % 16 == 0).
+    ``model.recompute_activations = True`` keeps the WN layer planes of two flows instead of twelve between this call and
+    ``backward()``, which recomputes the others flow by flow (``gradient_workspace_bytes`` gives both sizes): the way to
+    take gradients through whole utterances."""
     B, _, T = spect.shape
     L = T * 256 // self.n_group
     if z_init is None:
@@ -383,20 +398,23 @@ class WaveGlow(nn.Module):
         if k % self.n_early_every == 0 and k > 0:
           z_early.append(torch.empty((B, self.n_early_size, L), dtype=spect.dtype, device=spect.device).normal_())
     from .infer_grad import infer_differentiable
-    return infer_differentiable(self, spect, z_init, list(z_early), sigma, float(getattr(self, "grad_scale", 0.0)))
+    return infer_differentiable(self, spect, z_init, list(z_early), sigma, float(getattr(self, "grad_scale", 0.0)),
+                                bool(self.recompute_activations))
 
   def forward(self, forward_input):
     """model.py:178-221: (mel [B,M,F], audio [B,S]) -> (z [B,8,L], [log_s_k], [log_det_W_k]).
     With grad mode on and trainable parameters, or a ``mel`` / ``audio`` that requires grad (a frozen model used as a
     likelihood loss), this is the training direction (waveglow_amd/train.py: saved activations, ``loss.backward()`` runs
     the library's backward pass and fills ``mel.grad`` / ``audio.grad`` too); otherwise the lighter inference-only pass.
-    A shape the training direction does not take raises ``WgError`` there -- never a silent no-grad pass."""
+    A shape the training direction does not take raises ``WgError`` there -- never a silent no-grad pass.
+    In the training direction ``model.recompute_activations = True`` saves the WN layer planes of two flows only and
+    ``backward()`` recomputes the others (about 0.2x the saved state at 256 channels; ``gradient_workspace_bytes``)."""
     spect, audio = forward_input
     if torch.is_grad_enabled() and (spect.requires_grad or audio.requires_grad
                                     or any(p.requires_grad for p in self.parameters())):
       from .train import train_forward
       # grad_scale: loss scale of the fp16 gradient planes (0 = automatic, 2^round(log2 N) for the reference's mean loss)
-      return train_forward(self, spect, audio, float(getattr(self, "grad_scale", 0.0)))
+      return train_forward(self, spect, audio, float(getattr(self, "grad_scale", 0.0)), bool(self.recompute_activations))
     eng = self._get_engine(spect.device)
     io = self._io_dtype(spect)
     assert audio.dtype == spect.dtype and audio.device == spect.device
@@ -426,6 +444,25 @@ class WaveGlow(nn.Module):
       z = z.to(spect.dtype)
       log_s = [t.to(spect.dtype) for t in log_s]
     return z, log_s, log_det_list
+
+  def gradient_workspace_bytes(self, batch_size: int, n_frames: int, audio_len: Optional[int] = None,
+                               recompute: Optional[bool] = None) -> int:
+    """Bytes of the saved state that one outstanding training-direction forward (or ``infer_differentiable`` call) holds
+    until its ``backward()``: the library's own figure (``wg_train_workspace_bytes_ex``), for sizing batches.
+    ``audio_len`` None: ``256 * n_frames`` (the geometry of ``infer_differentiable``); it is cropped to a multiple of
+    n_group as ``forward`` crops the audio.  ``recompute`` None: ``self.recompute_activations``."""
+    dev = next(self.parameters()).device
+    eng = self._get_engine(dev, need_weights=False)
+    if audio_len is None:
+      audio_len = 256 * n_frames
+    audio_len -= audio_len % self.n_group
+    if recompute is None:
+      recompute = bool(self.recompute_activations)
+    flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
+    n = int(eng.lib.wg_train_workspace_bytes_ex(eng.handle, int(batch_size), int(n_frames), int(audio_len), flags))
+    if n == 0:
+      raise _lib.WgError(eng.lib.wg_last_error().decode())
+    return n
 
   @staticmethod
   def remove_weightnorm(model: "WaveGlow") -> "WaveGlow":

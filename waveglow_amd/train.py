@@ -417,14 +417,15 @@ def flow_backward_schedule(n_flows: int, run_flow, bufs, group=None) -> None:
 
 
 class _TrainFn(torch.autograd.Function):
-  """Inputs: mel, audio and the module's parameters in the library's canonical order (``canonical_params``); outputs
-  (z, log_s...).  backward() returns what ``ctx.needs_input_grad`` asks for: d mel / d audio (written by the library
+  """Inputs: mel, audio, the loss scale, the weight-norm flag, the wg_train flags (``WG_TRAIN_RECOMPUTE``: activation
+  recomputation; the backward runs with the flags of its own forward) and the module's parameters in the library's
+  canonical order (``canonical_params``); outputs (z, log_s...).  backward() returns what ``ctx.needs_input_grad`` asks for: d mel / d audio (written by the library
   into tensors of their own), and one gradient per parameter, each a view of ONE flat buffer the library fills --
   or, when no parameter needs one (a frozen model used as a loss), no parameter gradient at all: the library then runs
   the data-gradient chain alone (include/waveglow_amd.h: wg_train_backward_ex)."""
 
   @staticmethod
-  def forward(ctx, model, mel, audio, scale, wn, *params):
+  def forward(ctx, model, mel, audio, scale, wn, flags, *params):
     eng = model._get_engine(mel.device, need_weights=False)
     lib = eng.lib
     B, M, F_ = mel.shape
@@ -437,15 +438,16 @@ class _TrainFn(torch.autograd.Function):
     wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=ctx.needs_input_grad[1])
     z = torch.empty((B, model.n_group, L), dtype=torch.float32, device=mel.device)
     log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=mel.device) for c in flow_c]
-    nbytes = lib.wg_train_workspace_bytes(eng.handle, B, F_, S)
+    nbytes = lib.wg_train_workspace_bytes_ex(eng.handle, B, F_, S, flags)
     if nbytes == 0:
       raise _lib.WgError(lib.wg_last_error().decode())
-    slot, fresh = eng.train_workspace(nbytes, (B, F_, S, nbytes))             # held until this graph's backward has run
+    slot, fresh = eng.train_workspace(nbytes, (B, F_, S), flags)             # held until this graph's backward has run
     ws = slot["ws"]
     ls = (C.c_void_p * len(log_s))(*[t.data_ptr() for t in log_s])
-    _lib.check(lib.wg_train_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(audio), _ptr(z), ls, B, F_, S,
-                                    1 if fresh else 0, _ptr(ws), ws.numel(), C.c_void_p(stream)))
+    _lib.check(lib.wg_train_forward_flags(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(audio), _ptr(z), ls, B, F_, S,
+                                          1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
     ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.audio, ctx.guard = model, wts, ws, (B, F_, S), audio, _SlotGuard(slot)
+    ctx.flags = flags
     ctx.scale = float(scale) if scale else float(2.0 ** round(math.log2(z.numel())))
     ctx.shapes = [t.shape for t in params]
     return (z, *log_s)
@@ -463,7 +465,7 @@ class _TrainFn(torch.autograd.Function):
     nf = model.n_flows
     hp = model._hp
     want_mel, want_audio = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-    want_params = any(ctx.needs_input_grad[5:])
+    want_params = any(ctx.needs_input_grad[6:])
     poison = os.environ.get("WG_TRAIN_POISON_GRADS") == "1"
     # input gradients: every entry is written by the library (NaN first under WG_TRAIN_POISON_GRADS=1, tests)
     new = (lambda *sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)) if poison else \
@@ -483,18 +485,18 @@ class _TrainFn(torch.autograd.Function):
     # input gradients stay local (as under torch DDP); only parameter gradients are averaged over the ranks
     group = _ddp_group(model) if want_params else None
     if group is None:
-      _lib.check(lib.wg_train_backward_ex(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
-                                          _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(),
-                                          nf - 1, 0, C.c_void_p(stream)))
+      _lib.check(lib.wg_train_backward_ex_flags(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
+                                                _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(),
+                                                nf - 1, 0, ctx.flags, C.c_void_p(stream)))
     else:
       # Data parallel: the backward pass is cut at flow boundaries and every flow's gradients -- ONE contiguous region
       # of the flat buffer -- are all-reduced right behind it (flow_backward_schedule).  What follows (weight-norm
       # backward, the fold's chain rule: wg_train_param_grads) is linear in these gradients, so averaging here equals
       # averaging the parameter gradients (the logdet term of the 1x1 weights is identical on every rank).
       def run_flow(k):
-        _lib.check(lib.wg_train_backward_ex(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
-                                            _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(), k, k,
-                                            C.c_void_p(stream)))
+        _lib.check(lib.wg_train_backward_ex_flags(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr,
+                                                  C.c_float(ctx.scale), _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S,
+                                                  _ptr(ctx.ws), ctx.ws.numel(), k, k, ctx.flags, C.c_void_p(stream)))
       flow_backward_schedule(nf, run_flow, bufs, group)
     ctx.guard.release()
     # Overflow of the fp16 gradient planes (the automatic scale 2^round(log2 N) assumes the reference's MEAN loss; a
@@ -509,7 +511,7 @@ class _TrainFn(torch.autograd.Function):
       raise _lib.WgError(nonfinite_message(ctx.scale))
     ctx.wts = None
     if not want_params:
-      return (None, g_mel, g_audio, None, None, *([None] * len(ctx.shapes)))
+      return (None, g_mel, g_audio, None, None, None, *([None] * len(ctx.shapes)))
     # one gradient per parameter, views of one flat buffer in the canonical order
     sizes = [math.prod(sh) for sh in ctx.shapes]
     flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
@@ -518,7 +520,7 @@ class _TrainFn(torch.autograd.Function):
     _lib.check(lib.wg_train_param_grads(eng.handle, wts.params, wts.wn, C.byref(gstruct), _ptr(wts.aux), wts.aux.numel(),
                                         _ptr(flat), C.c_void_p(stream)))
     grads = [v.view(sh) for v, sh in zip(flat.split(sizes), ctx.shapes)]
-    return (None, g_mel, g_audio, None, None, *grads)
+    return (None, g_mel, g_audio, None, None, None, *grads)
 
 
 def nonfinite_message(scale: float) -> str:
@@ -527,10 +529,11 @@ def nonfinite_message(scale: float) -> str:
           "set model.grad_scale (currently %s) so that scale * |dL/dz| stays below 65504" % (("%g" % scale) if scale else "automatic"))
 
 
-def train_forward(model, mel: torch.Tensor, audio: torch.Tensor, grad_scale: float = 0.0):
+def train_forward(model, mel: torch.Tensor, audio: torch.Tensor, grad_scale: float = 0.0, recompute: bool = False):
   """(z, [log_s_k], [log_det_W_k]) with an autograd graph back to the module's parameters and to ``mel`` / ``audio``
   (model.py:178-221).  The crop to a multiple of n_group and ``.contiguous()`` are torch ops in front of the autograd
-  node: dropped trailing samples get a zero gradient and the input gradients the inputs' own shapes."""
+  node: dropped trailing samples get a zero gradient and the input gradients the inputs' own shapes.  ``recompute``:
+  activation recomputation (``WG_TRAIN_RECOMPUTE``, ``WaveGlow.recompute_activations``)."""
   if mel.device.type != "cuda":
     raise _lib.WgError("waveglow_amd runs on MI355X only: there is no CPU fallback")
   if mel.dtype != torch.float32 or audio.dtype != torch.float32:
@@ -547,7 +550,8 @@ def train_forward(model, mel: torch.Tensor, audio: torch.Tensor, grad_scale: flo
                        f"{eng.KERNEL_WIDTHS} and mel counts that are multiples of 16 only (inference and the no-grad forward "
                        "zero-pad the others)")
   _names, tensors, wn = canonical_params(model, eng)
-  out = _TrainFn.apply(model, mel, audio, grad_scale, wn, *tensors)
+  flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
+  out = _TrainFn.apply(model, mel, audio, grad_scale, wn, flags, *tensors)
   z, log_s = out[0], list(out[1:])
   L = S // model.n_group
   return z, log_s, _log_det_w(model, B * L)
