@@ -226,6 +226,12 @@ typedef struct wg_train_weights {
    * s = W_up[i = 32 blk + r][o][8p + g + 256j] for the spectrogram channel (o, g) = 8o + g at d spect plane position
    * 64t + 32h + 8s + e (zero for i >= n_mel).  wg_train_pack / wg_train_prepare fill it when it is non-null. */
   const void* wupt;
+  /* Optional (null: not filled, not read): n_flows pointers to [c_k][c_k] fp32 row-major W_k^-1 of the 1x1 matrices.
+   * wg_train_prepare fills them when the member is non-null: an fp64 Gauss-Jordan elimination with partial pivoting on the
+   * device, rounded to fp32 (a singular or non-finite matrix gives non-finite entries, never a host sync).  The synthesis
+   * calls (wg_train_infer_*) then take the inverses from here instead of from the finalised handle, so a model whose
+   * weights move every optimiser step needs no wg_finalize between steps. */
+  const float* const* winv;
 } wg_train_weights;
 
 /* Gradients: fp32 device buffers in NATURAL channel order, w.r.t. the matrices of wg_train_plain (dw1, dw2, dwes, dwup)
@@ -364,10 +370,11 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* w, const wg
                                int32_t flow_hi, int32_t flow_lo, int32_t flags, void* stream);
 
 /* Differentiable synthesis: WaveGlow.infer with injected noise (src/waveglow/model.py:223-273) with saved state, and its
- * backward w.r.t. mel and the noise (the weights are constants).  Both run on the training workspace of the same
+ * backward w.r.t. mel and the noise (and, through wg_train_infer_backward_params, the weights).  Both run on the training workspace of the same
  * geometry, wg_train_workspace_bytes(h, B, n_frames, 256 * n_frames) (infer's trim to 256 T samples is forward's crop to
- * audio_len), and on the wg_train_weights of wg_train_prepare (with wupt for g_mel).  The inverse 1x1 matrices are those
- * wg_infer uses: the handle must be finalised with the same weights (WG_ERR_STATE otherwise).
+ * audio_len), and on the wg_train_weights of wg_train_prepare (with wupt for g_mel).  The inverse 1x1 matrices are
+ * w->winv when it is given; otherwise those wg_infer uses: the handle must then be finalised with the same weights
+ * (WG_ERR_STATE otherwise).
  *
  * Forward: mel [B][n_mel][n_frames] fp32, z_init [B][c_last][L] fp32, z_early[i] [B][n_early_size][L] fp32 in descending
  * flow order (as wg_infer), audio [B][256 n_frames] fp32 out; L = 32 n_frames.  `fresh` as for wg_train_forward.  The
@@ -393,6 +400,21 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* w, const float
 int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* w, const float* g_audio, float scale, float sigma,
                                   float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
                                   int32_t n_frames, void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
+
+/* wg_train_infer_backward_flags plus the gradients of the weights through synthesis (the vocoder trained on a loss on its
+ * own output).  grads null: exactly wg_train_infer_backward_flags, launch by launch.  Otherwise the packed gradients of
+ * wg_train_grads are filled as wg_train_backward fills them -- dw1 | db1 | dw2 | db2 | dwes per layer, dstart, dout_init per
+ * flow, the upsample tail -- and dw1x1[k] = - sum over rows of (W_k^-T d w) (x) w for the inverse 1x1 step w = W_k^-1 u
+ * (an [8][8] record, rows / columns >= c_k zero; this direction has no logdet term); wg_train_param_grads turns them into
+ * one gradient per parameter.  Every entry is written except dw2 / db2 of the last layer of each flow.  The d spect GEMM
+ * runs when g_mel or grads is given.  The forward must have run on the same wg_train_weights; with a moving model that
+ * means one prepared with winv.  Flows in ascending order.  With grads the weight-gradient launches and their reductions
+ * run on two low-priority streams the handle owns, forked from `stream` inside the call and joined back into it before it
+ * returns, as in wg_train_backward (WG_TRAIN_SERIAL=1: everything on `stream`; same results bit for bit).  Enqueue-only. */
+int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_audio,
+                                   float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
+                                   int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace, size_t workspace_bytes,
+                                   int32_t flags, void* stream);
 
 /* Diagnostic builds only (-DWG_STAMPS): device buffer of n_tiles*8 uint64 that the WN-layer kernel fills with
  * s_memtime stamps at its phase boundaries (last launch wins).  A no-op pointer in the shipped library. */

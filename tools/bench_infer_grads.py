@@ -9,7 +9,16 @@ line per mode:
   c  for comparison: the frozen training direction, WaveGlow.forward + WaveGlowLoss + backward with d mel and d audio
      (tools/bench_input_grads.py mode c)
 
-  python tools/bench_infer_grads.py [--batch 32] [--frames 63] [--steps 5] [--warmup 2] [--modes pfmzc] [--rounds 1]
+  python tools/bench_infer_grads.py [--batch 32] [--frames 63] [--steps 5] [--warmup 2] [--modes pfmzc] [--rounds 1] [--weights [--weights-modes w,wr,ws,fs]]
+
+``--weights`` adds, after the modes above in every round, the weight-gradient path (``infer_differentiable(...,
+weight_grads=True)``, gradients for all 686 parameters, no input gradient) on the same model made trainable for the
+duration -- one model, one engine: a second engine's streams would share the process's hardware queues with the first's
+and the weight-gradient stream would no longer run beside the chain:
+
+  w   forward + backward, full save            wr  the same with activation recomputation
+  ws  forward of the step after a weight change (the 1x1 inverses follow on the device, no engine re-finalisation)
+  fs  for comparison: forward of the frozen path (mode f) after the same weight change (re-finalises the inference engine)
 
 The first line also reports wg_train_workspace_bytes of the synthesis geometry.  ``--headroom`` adds one line on the fp16
 gradient planes: for loss = mean(audio * r), r ~ N(0, 1), the automatic loss scale, the largest |d z| / |d mel| it gives,
@@ -62,6 +71,39 @@ def run_mode(model, mel, zi, ze, wav, mode, sigma, steps, warmup):
   return {"mode": mode, "ms_forward": t_f / steps, "ms_backward": t_b / steps, "ms_fwd_plus_bwd": (t_f + t_b) / steps}
 
 
+def run_weights(model, mel, zi, ze, mode, sigma, steps, warmup):
+  """``--weights`` modes (see the module docstring): the model is trainable for w / wr / ws, frozen again afterwards."""
+  ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+  t_f = t_b = 0.0
+  model.recompute_activations = mode == "wr"
+  model.requires_grad_(mode != "fs")
+  for it in range(warmup + steps):
+    if mode in ("ws", "fs"):
+      with torch.no_grad():
+        model.upsample.bias.add_(0.0)           # what an optimiser step does to the parameter versions
+    m = mel.detach().requires_grad_(mode == "fs")
+    model.zero_grad(set_to_none=True)
+    torch.cuda.synchronize()
+    ev[0].record()
+    audio = model.infer_differentiable(m, sigma, z_init=zi, z_early=ze, weight_grads=mode != "fs")
+    ev[1].record()
+    if mode in ("w", "wr"):
+      audio.backward(torch.full_like(audio, 1.0 / audio.numel()))
+    del audio
+    ev[2].record()
+    torch.cuda.synchronize()
+    if it >= warmup:
+      t_f += ev[0].elapsed_time(ev[1])
+      t_b += ev[1].elapsed_time(ev[2])
+  model.recompute_activations = False
+  model.zero_grad(set_to_none=True)
+  model.requires_grad_(False)
+  out = {"mode": mode, "ms_forward": t_f / steps}
+  if mode in ("w", "wr"):
+    out.update(ms_backward=t_b / steps, ms_fwd_plus_bwd=(t_f + t_b) / steps)
+  return out
+
+
 def headroom(model, mel, zi, ze, sigma):
   r = torch.randn(mel.shape[0], 256 * mel.shape[2], device=mel.device, generator=torch.Generator(device=mel.device).manual_seed(1))
 
@@ -101,6 +143,8 @@ def main():
   ap.add_argument("--modes", default="pfmzc")
   ap.add_argument("--rounds", type=int, default=1)
   ap.add_argument("--headroom", action="store_true")
+  ap.add_argument("--weights", action="store_true")
+  ap.add_argument("--weights-modes", default="w,wr,ws,fs", help="comma-separated subset of the --weights modes")
   a = ap.parse_args()
   hp = HParams()
   model = WaveGlow(hp)
@@ -114,12 +158,16 @@ def main():
   n_early = sum(1 for k in range(hp.n_flows) if k % hp.n_early_every == 0 and k > 0)
   ze = [torch.randn(B, hp.n_early_size, L, device="cuda:0", generator=gen) for _ in range(n_early)]
   wav = (torch.rand(B, 256 * T - 128, generator=torch.Generator().manual_seed(3)) * 0.6 - 0.3).cuda()   # 16000 at T = 63
-  eng = model._get_engine(mel.device)
+  eng = model._get_engine(mel.device, need_weights=bool(a.modes))      # --modes "": the frozen engine stays unfinalised
   ws = int(eng.lib.wg_train_workspace_bytes(eng.handle, B, T, 256 * T))
   print(json.dumps({"workspace_bytes": ws, "bytes_per_output_sample": ws / (B * 256 * T), "batch": B, "frames": T}), flush=True)
   for r in range(a.rounds):
     for mode in a.modes:
       out = run_mode(model, mel, zi, ze, wav, mode, a.sigma, a.steps, a.warmup)
+      out.update(round=r, batch=B, frames=T)
+      print(json.dumps(out), flush=True)
+    for mode in ([m for m in a.weights_modes.split(",") if m in ("w", "wr", "ws", "fs")] if a.weights else ()):
+      out = run_weights(model, mel, zi, ze, mode, a.sigma, a.steps, a.warmup)
       out.update(round=r, batch=B, frames=T)
       print(json.dumps(out), flush=True)
   if a.headroom:

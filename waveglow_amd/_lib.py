@@ -24,9 +24,11 @@ class WgConfig(C.Structure):
 
 class WgTrainWeights(C.Structure):
   """wg_train_weights (include/waveglow_amd.h): device pointers; wstart .. w1x1 are arrays of n_flows pointers, wupt is
-  optional (null unless the mel input gradient is wanted)."""
+  optional (null unless the mel input gradient is wanted), winv (array of n_flows pointers) too (null unless synthesis
+  takes W^-1 from the per-call weights)."""
   _fields_ = [(n, C.c_void_p) for n in (
-    "a1", "a1c", "b1", "a2", "b2", "es", "wat", "wbt", "wct", "wup", "bup", "wstart", "bstart", "out_init", "w1x1", "wupt")]
+    "a1", "a1c", "b1", "a2", "b2", "es", "wat", "wbt", "wct", "wup", "bup", "wstart", "bstart", "out_init", "w1x1", "wupt",
+    "winv")]
 
 
 class WgTrainPlain(C.Structure):
@@ -115,6 +117,10 @@ SIGNATURES = {
   "wg_train_infer_backward_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_float, C.c_float,
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32,
                                               C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+  "wg_train_infer_backward_params": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
+                                               C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
+                                               C.c_void_p]),
   "wg_stft_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stft_destroy": (C.c_int, [C.c_void_p]),
   "wg_stft_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),

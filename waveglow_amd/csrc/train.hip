@@ -1427,12 +1427,85 @@ __global__ void __launch_bounds__(FB_ROWS) inv_bwd_post_kernel(const InvBwdArgs 
   gp[1] = make_float4(gw[4], gw[5], gw[6], gw[7]);
 }
 
+// d W_k of inverse step k (InvDwArgs): the row's g_v = W^-T g and w = W^-1 u, then the [8][8] outer products of the
+// workgroup's rows summed in a fixed order, as flow_bwd_post_kernel sums its dw_partial (slab_reduce adds the workgroups'
+// partials in a fixed order too: bitwise reproducible).
+__global__ void __launch_bounds__(FB_ROWS) inv_dw1x1_kernel(const InvDwArgs a) {
+  __shared__ float s_g[FB_ROWS][9];
+  __shared__ float s_w[FB_ROWS][9];
+  const int L = a.g.L;
+  const size_t nrows = (size_t)a.g.B * L;
+  const size_t row = (size_t)blockIdx.x * FB_ROWS + threadIdx.x;
+  const int h = a.h, c = a.c;
+  float gv[kMaxGroup], wv[kMaxGroup];
+#pragma unroll
+  for (int j = 0; j < kMaxGroup; ++j) { gv[j] = 0.0f; wv[j] = 0.0f; }
+  if (row < nrows) {
+    const unsigned r32 = (unsigned)row;
+    const int b = (int)(r32 / (unsigned)L), t = (int)(r32 - (unsigned)b * (unsigned)L);
+    float g[kMaxGroup], y[kMaxGroup], o[kMaxGroup], u[kMaxGroup];
+    {
+      const float4* yp = (const float4*)(a.Y + row * 8);
+      const float4* op = (const float4*)(a.OUT + row * 8);
+      const float4 y0 = yp[0], y1 = yp[1], o0 = op[0], o1 = op[1];
+      y[0] = y0.x; y[1] = y0.y; y[2] = y0.z; y[3] = y0.w; y[4] = y1.x; y[5] = y1.y; y[6] = y1.z; y[7] = y1.w;
+      o[0] = o0.x; o[1] = o0.y; o[2] = o0.z; o[3] = o0.w; o[4] = o1.x; o[5] = o1.y; o[6] = o1.z; o[7] = o1.w;
+    }
+    if (a.g_audio) {
+      const float4* gp = (const float4*)(a.g_audio + (size_t)b * L * 8 + (size_t)t * 8);
+      const float4 g0 = gp[0], g1 = gp[1];
+      g[0] = g0.x; g[1] = g0.y; g[2] = g0.z; g[3] = g0.w; g[4] = g1.x; g[5] = g1.y; g[6] = g1.z; g[7] = g1.w;
+#pragma unroll
+      for (int j = 0; j < kMaxGroup; ++j) g[j] *= a.scale;
+    } else {
+      const float4* gp = (const float4*)(a.GZ + row * 8);
+      const float4 g0 = gp[0], g1 = gp[1];
+      g[0] = g0.x; g[1] = g0.y; g[2] = g0.z; g[3] = g0.w; g[4] = g1.x; g[5] = g1.y; g[6] = g1.z; g[7] = g1.w;
+    }
+#pragma unroll
+    for (int j = 0; j < kMaxGroup; ++j) {                  // u = (y0 | (y1 - b) e^-s)   (model.py:253-255)
+      u[j] = (j < h) ? y[j] : 0.0f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (j >= h && j - h == q && q < h) u[j] = (y[j] - o[q]) * expf(-o[j]);
+    }
+#pragma unroll
+    for (int r = 0; r < kMaxGroup; ++r) {
+      float sg = 0.0f, sw = 0.0f;
+#pragma unroll
+      for (int q = 0; q < kMaxGroup; ++q)
+        if (r < c && q < c) {
+          sg = fmaf(a.winv[q * c + r], g[q], sg);          // (W^-1)^T g
+          sw = fmaf(a.winv[r * c + q], u[q], sw);          // W^-1 u   (model.py:259)
+        }
+      gv[r] = sg;
+      wv[r] = sw;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kMaxGroup; ++j) {
+    s_g[threadIdx.x][j] = gv[j];
+    s_w[threadIdx.x][j] = wv[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int rr = threadIdx.x >> 3, cc = threadIdx.x & 7;
+    float s = 0.0f;
+    for (int i = 0; i < FB_ROWS; ++i) s = fmaf(s_g[i][rr], s_w[i][cc], s);
+    a.partial[(size_t)blockIdx.x * 64 + threadIdx.x] = -s;
+  }
+}
+
 hipError_t launch_inv_bwd_pre(const InvBwdArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(inv_bwd_pre_kernel, dim3(flow_bwd_workgroups(a.g)), dim3(FB_ROWS), 0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_inv_bwd_post(const InvBwdArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(inv_bwd_post_kernel, dim3(flow_bwd_workgroups(a.g)), dim3(FB_ROWS), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_inv_dw1x1(const InvDwArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(inv_dw1x1_kernel, dim3(flow_bwd_workgroups(a.g)), dim3(FB_ROWS), 0, s, a);
   return hipGetLastError();
 }
 

@@ -431,6 +431,156 @@ int dspect_flow(const Ctx& x, const wg_train_weights* wt, int k, bool first, boo
   return WG_OK;
 }
 
+// where entry fl of a per-layer gradient tensor lives: dense, or in interleaved per-layer records (wg_train_grads)
+size_t grad_ofs(const wg_train_grads* gr, int nl, int fl, size_t dense) {
+  return gr->layer_stride ? (size_t)(fl / nl) * (size_t)gr->flow_stride + (size_t)(fl % nl) * (size_t)gr->layer_stride
+                          : (size_t)fl * dense;
+}
+
+// Weight-gradient sequencing shared by the two backward directions (wg_train_backward_ex_flags: descending flows,
+// wg_train_infer_backward_params: ascending flows; both put the launches on the low-priority streams sW / sR).  A layer's
+// slabs are reduced by a launch of its own on sR beside the NEXT layer's weight-gradient launch on sW.
+// Two slab sets: launch n + 2 on sW waits for the reduction of launch n (r_done), the reduction of launch n for launch n
+// itself (l_done).  serial: one stream, no marks.
+struct WgradSeq {
+  hipStream_t sW, sR;
+  bool serial;
+  int n_layer;
+  hipEvent_t l_done[2], r_done[2];
+};
+WgradSeq wgrad_seq(hipStream_t sW, hipStream_t sR, bool serial) {
+  WgradSeq q;
+  q.sW = sW; q.sR = sR; q.serial = serial; q.n_layer = 0;
+  q.l_done[0] = q.l_done[1] = q.r_done[0] = q.r_done[1] = nullptr;
+  return q;
+}
+// (marks are waited on one or two flows / launches after their record: events of their own, wg_internal_mark_event,
+//  slots 0-9 = w_done[layer], 10-11 = w_flow[parity], 12-13 = l_done[set], 14-15 = r_done[set]; a null entry = not recorded
+//  in this call, nothing to wait for)
+hipError_t mark_on(wg_handle* h, bool serial, hipStream_t st, hipEvent_t& e, int slot) {
+  e = nullptr;
+  if (serial) return hipSuccess;
+  e = wg_internal_mark_event(h, slot);
+  return e ? hipEventRecord(e, st) : hipErrorOutOfMemory;
+}
+hipError_t wait_on(hipStream_t st, hipEvent_t e) { return e ? hipStreamWaitEvent(st, e, 0) : hipSuccess; }
+
+// The weight gradients of layer i of flow k, once d pre of the layer (GP) and gx = d x_{i+1} (null: the flow's last layer)
+// are on q.sW's side of the stream order:
+// d W1 = d pre x [x taps | spect]^T, d b1;
+// d W2 = d x_{i+1} x acts^T, d b2  and  d (W_end W_skip_i) = d out x acts^T  share the X operand (acts): one
+// job with the d out plane as the `extra` 16 rows (the last layer has no d x: the d out plane stands in as the
+// job's G as well, and that part of the result is not used).
+// Both jobs in ONE launch over the same slab partition (train.hip: wgrad_kernel), then the reduction of everything the
+// launch left behind; layer 0 also leaves d out_init of the flow.
+int layer_wgrad(wg_handle* h, const Ctx& x, const wg_train_grads* gr, WgradSeq& q, int k, int i, const _Float16* gx,
+                const _Float16* GOk, float inv) {
+  const RowGeom& g = x.g;
+  const TrainWs& w = x.w;
+  const int C = x.C, nl = x.nl, K1 = x.K1;
+  const int cc = C / 64, mc = x.M8 / 64;
+  const int fl = k * nl + i, d = 1 << i;
+  const size_t pl = plane_layer(x, k, i);
+  const _Float16* Xi = w.X + pl * w.plane_c;
+  const _Float16* Ai = w.A + pl * w.plane_c;
+  const _Float16* GPi = w.GP + pl * 2 * w.plane_c;
+  const int* const n_slabs = x.n_slabs;
+  hipStream_t sW = q.sW, sR = q.sR;
+  WgradJob jb[2];
+  const int set = q.n_layer & 1;
+  ++q.n_layer;
+  memset(jb, 0, sizeof jb);
+  jb[0].G = GPi;
+  jb[0].m_chunks = 2 * cc;
+  jb[0].n_runs = 4;
+  jb[0].run[0] = run_of(Xi, cc, -d);
+  jb[0].run[1] = run_of(Xi, cc, 0);
+  jb[0].run[2] = run_of(Xi, cc, d);
+  jb[0].run[3] = run_of(w.SP, mc, 0);
+  jb[0].k_chunks = 3 * cc + mc;
+  jb[0].slabs = w.slab[set];
+  jb[0].bias_out = w.part[set];
+  jb[1].G = gx ? gx : GOk;
+  jb[1].m_chunks = gx ? cc : 1;
+  jb[1].G_extra = GOk;
+  jb[1].n_runs = 1;
+  jb[1].run[0] = run_of(Ai, cc, 0);
+  jb[1].k_chunks = cc;
+  jb[1].slabs = w.slab2[set];
+  jb[1].bias_out = w.part2[set];
+  jb[1].extra_out = w.ext[set];
+  jb[1].extra_bias_out = w.extb[set];
+  TR_ORDER(wait_on(sW, q.r_done[set]));          // the reduction of the launch before last has read this slab set
+  TR_PROF(sW, 6, TR_TRY(launch_wgrad(jb, 2, g, n_slabs, sW)));
+  TR_ORDER(mark_on(h, q.serial, sW, q.l_done[set], 12 + set));
+  // ---- reduction of everything this launch left behind, in NATURAL channel order (SlabSeg: perm bit 0 = rows are
+  // channels, bit 1 = columns are)
+  SlabSeg seg[kMaxSlabSegs];
+  int n_seg = 0;
+  const size_t n1 = (size_t)2 * C * K1;
+  auto add_flat = [&](int job, const float* slabs, size_t stride, size_t n, float* out, int row_len, int perm) {
+    seg[n_seg++] = make_seg(slabs, n_slabs[job], stride, n, inv, out, row_len, perm);
+  };
+  auto add_blocked = [&](int job, const float* slabs, int m_ch, int k_ch, float* out) {
+    SlabSeg sg = make_seg(slabs, n_slabs[job], (size_t)wgrad_tiles(m_ch, k_ch) * kWgradTileFloats,
+                          (size_t)wgrad_tiles(m_ch, k_ch) * kWgradTileFloats, inv, out, k_ch * 64, 3);
+    sg.blocked = 1; sg.m_chunks = m_ch; sg.k_chunks = k_ch; sg.n_groups = 1;
+    seg[n_seg++] = sg;
+  };
+  add_blocked(0, w.slab[set], 2 * cc, 3 * cc + mc, gr->dw1 + grad_ofs(gr, nl, fl, n1));
+  add_flat(0, w.part[set], (size_t)2 * C, (size_t)2 * C, gr->db1 + grad_ofs(gr, nl, fl, (size_t)2 * C), 2 * C, 2);
+  if (gx) {
+    add_blocked(1, w.slab2[set], cc, cc, gr->dw2 + grad_ofs(gr, nl, fl, (size_t)C * C));
+    add_flat(1, w.part2[set], (size_t)C, (size_t)C, gr->db2 + grad_ofs(gr, nl, fl, (size_t)C), C, 2);
+  }
+  add_flat(1, w.ext[set], (size_t)16 * C, (size_t)8 * C, gr->dwes + grad_ofs(gr, nl, fl, (size_t)8 * C), C, 2);
+  // d out_init = sum over columns of (d b | d log_s), once per flow
+  if (i == 0) add_flat(1, w.extb[set], 16, 8, gr->dout_init[k], 0, 0);
+  TR_ORDER(wait_on(sR, q.l_done[set]));
+  TR_TRY(launch_slab_reduce_multi(seg, n_seg, sR));
+  TR_ORDER(mark_on(h, q.serial, sR, q.r_done[set], 14 + set));
+  return WG_OK;
+}
+
+// d Wstart / d bstart of flow k from d x_0 (gx) and the state whose first h_k channels entered the start conv
+int start_wgrad(const Ctx& x, const wg_train_grads* gr, int k, const _Float16* gx, const float* Zpost, float inv, hipStream_t s) {
+  StartWgradArgs a;
+  a.g = x.g;
+  a.C = x.C;
+  a.h = x.ck[k] / 2;
+  a.GX = gx;
+  a.Zpost = Zpost;
+  a.partial = x.w.part3;
+  TR_TRY(launch_start_wgrad(a, s));
+  const SlabSeg sg = make_seg(x.w.part3, start_wgrad_workgroups(x.g), (size_t)5 * x.C, (size_t)5 * x.C, inv, gr->dstart[k], x.C, 2);
+  TR_TRY(launch_slab_reduce_multi(&sg, 1, s));
+  return WG_OK;
+}
+
+// d upsample: per phase, d spect (GSP) x mel frames q..q-3 (no sum over phases: one slab = one phase = one result)
+int upsample_wgrad(const Ctx& x, const wg_train_grads* gr, float inv, hipStream_t s) {
+  const TrainWs& w = x.w;
+  const int M8 = x.M8, mc = M8 / 64;
+  WgradJob a;
+  memset(&a, 0, sizeof a);
+  a.G = w.GSP;
+  a.m_chunks = mc;
+  a.n_runs = 4;
+  for (int j = 0; j < 4; ++j) a.run[j] = run_of(w.MELP, 2, -32 * j);
+  a.k_chunks = 8;
+  a.slabs = w.slab_up;
+  a.bias_out = w.part3;
+  const int up_slabs = kPhases;
+  TR_TRY(launch_wgrad(&a, 1, x.g, &up_slabs, s));
+  SlabSeg sg[2];
+  const size_t tile_n = (size_t)wgrad_tiles(mc, 8) * kWgradTileFloats;
+  sg[0] = make_seg(w.slab_up, kPhases, tile_n, tile_n, inv, gr->dwup, 512, 1);      // rows to natural order, columns are mel taps
+  sg[0].blocked = 1; sg[0].m_chunks = mc; sg[0].k_chunks = 8; sg[0].n_groups = kPhases; sg[0].out_group_stride = (size_t)M8 * 512;
+  sg[1] = make_seg(w.part3, kPhases, M8, M8, inv, gr->dbup, M8, 2);
+  TR_TRY(launch_slab_reduce_multi(sg, 2, s));
+  return WG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -600,8 +750,8 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
   const RowGeom& g = x.g;
   TrainWs& w = x.w;
   hipStream_t s = (hipStream_t)stream;
-  const int C = x.C, nl = x.nl, M8 = x.M8, K1 = x.K1, FL = x.FL;
-  const int cc = C / 64, mc = M8 / 64;
+  const int C = x.C, nl = x.nl, M8 = x.M8, FL = x.FL;
+  const int cc = C / 64;
   const float inv = 1.0f / scale;
   const _Float16* wat = (const _Float16*)wt->wat;
   const _Float16* wbt = (const _Float16*)wt->wbt;
@@ -625,7 +775,6 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     if (pg && !(sW = wg_internal_aux_stream(h, 1))) return wg_set_error(WG_ERR_HIP, "cannot create the weight-gradient stream");
     if (pg && !(sR = wg_internal_aux_stream(h, 2))) return wg_set_error(WG_ERR_HIP, "cannot create the slab-reduction stream");
   }
-  const int* const n_slabs = x.n_slabs;
   bool fuse = true;                       // WG_TRAIN_NO_FUSE=1 (tests, A/B): d acts + gate derivative as launches of their own
   if (const char* e = getenv("WG_TRAIN_NO_FUSE")) fuse = !(*e == '1');
   int BNw = wn_block_n(C);
@@ -641,10 +790,6 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
   // where entry fl of a per-layer gradient tensor lives: dense, or in interleaved per-layer records (wg_train_grads)
   if (pg && ((gr->layer_stride == 0) != (gr->flow_stride == 0) || gr->layer_stride < 0 || gr->flow_stride < 0))
     return wg_set_error(WG_ERR_INVALID, "wg_train_grads: layer_stride and flow_stride must both be 0 or both positive");
-  auto gofs = [&](int fl, size_t dense) -> size_t {
-    return gr->layer_stride ? (size_t)(fl / nl) * (size_t)gr->flow_stride + (size_t)(fl % nl) * (size_t)gr->layer_stride
-                            : (size_t)fl * dense;
-  };
 
   if (flow_lo < 0 || flow_hi >= c.n_flows || flow_lo > flow_hi) return wg_set_error(WG_ERR_INVALID, "bad flow range");
   // channel offsets of the peeled outputs in z (model.py:201-203, :220): early outputs of the flows <= k
@@ -672,20 +817,13 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
   // small in registers and LDS, so its workgroups run beside the NEXT layer's weight-gradient workgroups (MFMA / L2-bound,
   // one per CU).  Two slab sets: launch n + 2 on sW waits for the reduction of launch n (r_done), the reduction of launch
   // n for launch n itself (l_done).
-  int n_layer = 0;
-  // (marks are waited on one or two flows / launches after their record: events of their own, wg_internal_mark_event,
-  //  slots 0-9 = w_done[layer], 10-11 = w_flow[parity], 12-13 = l_done[set], 14-15 = r_done[set]; a null entry = not recorded
-  //  in this call, nothing to wait for)
+  WgradSeq wq = wgrad_seq(sW, sR, x.serial);
+  // (marks: see mark_on)
   hipEvent_t w_done[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t w_flow[2] = {nullptr, nullptr}, l_done[2] = {nullptr, nullptr}, r_done[2] = {nullptr, nullptr};
+  hipEvent_t w_flow[2] = {nullptr, nullptr};
   if (nl > 10) return wg_set_error(WG_ERR_INVALID, "more than 10 layers");
-  auto mark = [&](hipStream_t st, hipEvent_t& e, int slot) -> hipError_t {
-    e = nullptr;
-    if (x.serial) return hipSuccess;
-    e = wg_internal_mark_event(h, slot);
-    return e ? hipEventRecord(e, st) : hipErrorOutOfMemory;
-  };
-  auto wait_for = [&](hipStream_t st, hipEvent_t e) -> hipError_t { return e ? hipStreamWaitEvent(st, e, 0) : hipSuccess; };
+  auto mark = [&](hipStream_t st, hipEvent_t& e, int slot) -> hipError_t { return mark_on(h, x.serial, st, e, slot); };
+  auto wait_for = [&](hipStream_t st, hipEvent_t e) -> hipError_t { return wait_on(st, e); };
 
   for (int k = flow_hi; k >= flow_lo; --k) {
     const int ck = x.ck[k], hk = ck / 2;
@@ -714,8 +852,6 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     for (int i = nl - 1; i >= 0; --i) {
       const int fl = k * nl + i, d = 1 << i;
       const size_t pl = plane_layer(x, k, i);
-      const _Float16* Xi = w.X + pl * w.plane_c;
-      const _Float16* Ai = w.A + pl * w.plane_c;
       _Float16* GPi = w.GP + pl * 2 * w.plane_c;
       // Fused (round 3): the d x launch of layer i + 1 has already produced d pre of this layer behind its own result
       // (wn_layer_kernel MODE 4: the d x tile goes through LDS into the next GEMM instead of out to the planes and back in
@@ -755,64 +891,8 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
       if (pg) {
         TR_ORDER(order_after(h, s, sW));
         TR_ORDER(order_after(h, sB, sW));
-        // d W1 = d pre x [x taps | spect]^T, d b1;
-        // d W2 = d x_{i+1} x acts^T, d b2  and  d (W_end W_skip_i) = d out x acts^T  share the X operand (acts): one
-        // job with the d out plane as the `extra` 16 rows (the last layer has no d x: the d out plane stands in as the
-        // job's G as well, and that part of the result is not used).
-        // Both jobs in ONE launch over the same slab partition (train.hip: wgrad_kernel).
-        WgradJob jb[2];
-        const int set = n_layer & 1;
-        ++n_layer;
-        memset(jb, 0, sizeof jb);
-        jb[0].G = GPi;
-        jb[0].m_chunks = 2 * cc;
-        jb[0].n_runs = 4;
-        jb[0].run[0] = run_of(Xi, cc, -d);
-        jb[0].run[1] = run_of(Xi, cc, 0);
-        jb[0].run[2] = run_of(Xi, cc, d);
-        jb[0].run[3] = run_of(w.SP, mc, 0);
-        jb[0].k_chunks = 3 * cc + mc;
-        jb[0].slabs = w.slab[set];
-        jb[0].bias_out = w.part[set];
-        jb[1].G = gx ? gx : GOk;
-        jb[1].m_chunks = gx ? cc : 1;
-        jb[1].G_extra = GOk;
-        jb[1].n_runs = 1;
-        jb[1].run[0] = run_of(Ai, cc, 0);
-        jb[1].k_chunks = cc;
-        jb[1].slabs = w.slab2[set];
-        jb[1].bias_out = w.part2[set];
-        jb[1].extra_out = w.ext[set];
-        jb[1].extra_bias_out = w.extb[set];
-        TR_ORDER(wait_for(sW, r_done[set]));          // the reduction of the launch before last has read this slab set
-        TR_PROF(sW, 6, TR_TRY(launch_wgrad(jb, 2, g, n_slabs, sW)));
-        TR_ORDER(mark(sW, l_done[set], 12 + set));
-        // ---- reduction of everything this launch left behind, in NATURAL channel order (SlabSeg: perm bit 0 = rows are
-        // channels, bit 1 = columns are)
-        SlabSeg seg[kMaxSlabSegs];
-        int n_seg = 0;
-        const size_t n1 = (size_t)2 * C * K1;
-        auto add_flat = [&](int job, const float* slabs, size_t stride, size_t n, float* out, int row_len, int perm) {
-          seg[n_seg++] = make_seg(slabs, n_slabs[job], stride, n, inv, out, row_len, perm);
-        };
-        auto add_blocked = [&](int job, const float* slabs, int m_ch, int k_ch, float* out) {
-          SlabSeg q = make_seg(slabs, n_slabs[job], (size_t)wgrad_tiles(m_ch, k_ch) * kWgradTileFloats,
-                               (size_t)wgrad_tiles(m_ch, k_ch) * kWgradTileFloats, inv, out, k_ch * 64, 3);
-          q.blocked = 1; q.m_chunks = m_ch; q.k_chunks = k_ch; q.n_groups = 1;
-          seg[n_seg++] = q;
-        };
-        add_blocked(0, w.slab[set], 2 * cc, 3 * cc + mc, gr->dw1 + gofs(fl, n1));
-        add_flat(0, w.part[set], (size_t)2 * C, (size_t)2 * C, gr->db1 + gofs(fl, (size_t)2 * C), 2 * C, 2);
-        if (gx) {
-          add_blocked(1, w.slab2[set], cc, cc, gr->dw2 + gofs(fl, (size_t)C * C));
-          add_flat(1, w.part2[set], (size_t)C, (size_t)C, gr->db2 + gofs(fl, (size_t)C), C, 2);
-        }
-        add_flat(1, w.ext[set], (size_t)16 * C, (size_t)8 * C, gr->dwes + gofs(fl, (size_t)8 * C), C, 2);
-        // d out_init = sum over columns of (d b | d log_s), once per flow
-        if (i == 0) add_flat(1, w.extb[set], 16, 8, gr->dout_init[k], 0, 0);
-        TR_ORDER(wait_for(sR, l_done[set]));
-        TR_TRY(launch_slab_reduce_multi(seg, n_seg, sR));
-        TR_ORDER(mark(sR, r_done[set], 14 + set));
+        // d W1 / d b1, d W2 / d b2, d (W_end W_skip_i) of the layer (and d out_init with layer 0) and their reduction
+        if ((rc = layer_wgrad(h, x, gr, wq, k, i, gx, GOk, inv))) return rc;
         TR_ORDER(mark(sW, w_done[i], i));
       }
       {
@@ -854,18 +934,7 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     if (pg) TR_ORDER(mark(sW, w_flow[k & 1], 10 + (k & 1)));
     TR_ORDER(order_after(h, sB, s));
     if (dspect && !pg && (rc = dspect_flow(x, wt, k, k == c.n_flows - 1, k == 0, s))) return rc;
-    if (pg) {
-      StartWgradArgs a;
-      a.g = g;
-      a.C = C;
-      a.h = hk;
-      a.GX = gx;
-      a.Zpost = fb.Zpost;
-      a.partial = w.part3;
-      TR_TRY(launch_start_wgrad(a, s));
-      const SlabSeg sg = make_seg(w.part3, start_wgrad_workgroups(g), (size_t)5 * C, (size_t)5 * C, inv, gr->dstart[k], C, 2);
-      TR_TRY(launch_slab_reduce_multi(&sg, 1, s));
-    }
+    if (pg && (rc = start_wgrad(x, gr, k, gx, fb.Zpost, inv, s))) return rc;
     fb.GX = gx;
     fb.wstart = wt->wstart[k];
     fb.w1x1 = wt->w1x1[k];
@@ -926,23 +995,7 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     TR_TRY(launch_dmel(a, s));
   }
   if (pg) {
-    WgradJob a;   // d upsample: per phase, d spect x mel frames q..q-3 (no sum over phases: one slab = one phase = one result)
-    memset(&a, 0, sizeof a);
-    a.G = w.GSP;
-    a.m_chunks = mc;
-    a.n_runs = 4;
-    for (int j = 0; j < 4; ++j) a.run[j] = run_of(w.MELP, 2, -32 * j);
-    a.k_chunks = 8;
-    a.slabs = w.slab_up;
-    a.bias_out = w.part3;
-    const int up_slabs = kPhases;
-    TR_TRY(launch_wgrad(&a, 1, g, &up_slabs, s));
-    SlabSeg sg[2];
-    const size_t tile_n = (size_t)wgrad_tiles(mc, 8) * kWgradTileFloats;
-    sg[0] = make_seg(w.slab_up, kPhases, tile_n, tile_n, inv, gr->dwup, 512, 1);      // rows to natural order, columns are mel taps
-    sg[0].blocked = 1; sg[0].m_chunks = mc; sg[0].k_chunks = 8; sg[0].n_groups = kPhases; sg[0].out_group_stride = (size_t)M8 * 512;
-    sg[1] = make_seg(w.part3, kPhases, M8, M8, inv, gr->dbup, M8, 2);
-    TR_TRY(launch_slab_reduce_multi(sg, 2, s));
+    if ((rc = upsample_wgrad(x, gr, inv, s))) return rc;
     TR_ORDER(order_after(h, sW, s));      // every gradient of the call is final on the caller's stream
     TR_ORDER(order_after(h, sR, s));
   }
@@ -976,9 +1029,14 @@ int infer_setup(wg_handle* h, const wg_train_weights* wt, int32_t n_z_early, int
   if (rc) return rc;
   if ((rc = check_weights(wt, c->n_flows))) return rc;
   if (n_z_early != n_early_flows(*c)) return wg_set_error(WG_ERR_INVALID, "wrong number of early-noise tensors");
-  for (int k = 0; k < c->n_flows; ++k)
-    if (!(winv[k] = wg_internal_winv(h, k)))
+  // W_k^-1: the per-call weights' own (wg_train_prepare inverted them on the device), else the finalised handle's
+  for (int k = 0; k < c->n_flows; ++k) {
+    if (wt->winv) {
+      if (!(winv[k] = wt->winv[k])) return wg_set_error(WG_ERR_INVALID, "wg_train_weights.winv has a null per-flow pointer");
+    } else if (!(winv[k] = wg_internal_winv(h, k))) {
       return wg_set_error(WG_ERR_STATE, "wg_finalize has not been called: the synthesis direction uses the handle's W^-1");
+    }
+  }
   return WG_OK;
 }
 
@@ -1083,6 +1141,14 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const floa
 int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, const float* g_audio, float scale, float sigma,
                                   float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
                                   int32_t n_frames, void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
+  return wg_train_infer_backward_params(h, wt, nullptr, g_audio, scale, sigma, g_mel, g_z_init, g_z_early, n_z_early, B,
+                                        n_frames, workspace, workspace_bytes, flags, stream);
+}
+
+int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_audio,
+                                   float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
+                                   int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace, size_t workspace_bytes,
+                                   int32_t flags, void* stream) {
   if (!wt || !g_audio || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
   if (!(scale > 0.f)) return wg_set_error(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
@@ -1090,12 +1156,46 @@ int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, cons
   int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, flags, x, winv);
   if (rc) return rc;
   if (g_mel && !wt->wupt) return wg_set_error(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
+  // gr == null: the data-gradient chain alone, the launches of wg_train_infer_backward_flags before this entry point existed.
+  // Otherwise the packed weight gradients as well, flow by flow behind the data gradients they are made of: per layer the
+  // training direction's weight-gradient launch and slab reduction (layer_wgrad), per flow d start (the saved state Y is the
+  // WN input, as Zpost is in the training direction), d out_init and d W_k of the inverse 1x1, after the last flow d upsample.
+  const bool pg = gr != nullptr;
+  if (pg && (rc = check_grads(gr, x.c->n_flows))) return rc;
+  if (pg && ((gr->layer_stride == 0) != (gr->flow_stride == 0) || gr->layer_stride < 0 || gr->flow_stride < 0))
+    return wg_set_error(WG_ERR_INVALID, "wg_train_grads: layer_stride and flow_stride must both be 0 or both positive");
   const wg_config& c = *x.c;
   const RowGeom& g = x.g;
   TrainWs& w = x.w;
   hipStream_t s = (hipStream_t)stream;
   const int C = x.C, nl = x.nl, M8 = x.M8, FL = x.FL;
   const int cc = C / 64;
+  const float inv = 1.0f / scale;
+  // Streams, as in wg_train_backward_ex_flags: the caller's stream `s` carries the data-gradient chain and every row kernel,
+  // sW (lowest priority) the weight-gradient launches (and the per-flow d spect GEMMs of WG_TRAIN_RECOMPUTE), sR their slab
+  // reductions; nothing downstream in the call waits for them, they fill the CUs the chain leaves idle, and everything is
+  // joined back into `s` before the call returns.  Without parameter gradients, or with WG_TRAIN_SERIAL=1: all three are `s`.
+  // What orders the reuse of shared buffers -- the flows ascend here, but every reuse is by the NEXT flow processed (GXL) or
+  // the one after it (GO, flow slots), so the marks are the training direction's with k + 1 / k + 2 for k - 1 / k - 2:
+  //   GXL[i] (d x_i)   written by the d x launch of layer i on s, read by sW's second job of layer i-1: flow k+1's layer-i
+  //                    launch waits for flow k's job (w_done[i-1], not yet re-marked by flow k+1 at that point);
+  //   GO[k & 1]        written by flow k's pre kernel on s, read by all of flow k's jobs on sW: the pre kernel of flow k+2
+  //                    waits for the last of them (w_flow[k & 1]);
+  //   flow slot k & 1  (WG_TRAIN_RECOMPUTE: X / T / S / A / GP) read by flow k's jobs and d spect GEMM on sW: the replay of
+  //                    flow k+2 into it runs on s behind the same w_flow[k & 1] wait;
+  //   GZ, part3        row kernels and their reductions, on s alone;
+  //   GP (full save)   one set per layer of the model, written on s, read by the final d spect GEMM on s.
+  hipStream_t sW = s, sR = s;
+  const bool serial = x.serial || !pg;
+  if (!serial) {
+    if (!(sW = wg_internal_aux_stream(h, 1))) return wg_set_error(WG_ERR_HIP, "cannot create the weight-gradient stream");
+    if (!(sR = wg_internal_aux_stream(h, 2))) return wg_set_error(WG_ERR_HIP, "cannot create the slab-reduction stream");
+  }
+  WgradSeq wq = wgrad_seq(sW, sR, serial);
+  hipEvent_t w_done[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t w_flow[2] = {nullptr, nullptr};
+  if (pg && nl > 10) return wg_set_error(WG_ERR_INVALID, "more than 10 layers");
+  if (pg) TR_ORDER(order_after(h, s, sW));
   const _Float16* wat = (const _Float16*)wt->wat;
   const _Float16* wbt = (const _Float16*)wt->wbt;
   // fragment tensors of the two dgrad GEMMs, as in wg_train_backward_ex
@@ -1120,11 +1220,12 @@ int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, cons
     for (int q = c.n_flows - 1; q > k; --q) n += is_early(c, q);
     return n;
   };
-  // Ascending flow order: the gradient enters at the audio, the output of inverse step 0.  Everything runs on `s`, so the
-  // GO plane, GXL and GZ are reused in stream order (GO[k & 1] only keeps the training direction's plane names), and so
-  // are the flow slots of WG_TRAIN_RECOMPUTE: flow k's replay follows every reader of flow k-2's planes.
+  // Ascending flow order: the gradient enters at the audio, the output of inverse step 0.  Without parameter gradients
+  // everything runs on `s`, so the GO plane, GXL and GZ are reused in stream order, and so are the flow slots of
+  // WG_TRAIN_RECOMPUTE: flow k's replay follows every reader of flow k-2's planes.  With them: the marks above.
   for (int k = 0; k < c.n_flows; ++k) {
     const int ck = x.ck[k];
+    TR_ORDER(wait_on(s, w_flow[k & 1]));
     if (x.recompute && k >= 2 && (rc = replay_flow(h, x, wt, k, false, s))) return rc;
     InvBwdArgs ib;
     memset(&ib, 0, sizeof ib);
@@ -1141,6 +1242,24 @@ int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, cons
     ib.GZ = w.GZ;
     _Float16* const GOk = w.GO[k & 1];
     ib.GO = GOk;
+    if (pg) {
+      // d W_k = - sum g_v (x) w, from the step's incoming gradient: before the pre kernel overwrites GZ in place
+      InvDwArgs dw;
+      memset(&dw, 0, sizeof dw);
+      dw.g = g;
+      dw.c = ck;
+      dw.h = ck / 2;
+      dw.scale = scale;
+      dw.Y = ib.Y;
+      dw.OUT = ib.OUT;
+      dw.winv = ib.winv;
+      dw.g_audio = ib.g_audio;
+      dw.GZ = w.GZ;
+      dw.partial = w.part3;
+      TR_TRY(launch_inv_dw1x1(dw, s));
+      const SlabSeg sg = make_seg(w.part3, flow_bwd_workgroups(g), 64, 64, inv, gr->dw1x1[k], 0, 0);
+      TR_TRY(launch_slab_reduce_multi(&sg, 1, s));
+    }
     TR_TRY(launch_inv_bwd_pre(ib, s));
     // the WN data-gradient chain of flow k: wg_train_backward_ex's launches without parameter gradients, one chain
     _Float16* gx = nullptr;                     // d x_{i+1} (null: the last layer has no res output)
@@ -1176,6 +1295,12 @@ int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, cons
         a.out0 = GPi;
         TR_PROF(s, 5, TR_TRY(launch_part(a, g, BNw, 0, 1, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, 3, bn, s); })));
       }
+      if (pg) {
+        // the weight-gradient stream continues once the chain has written d pre of this layer (and d x_{i+1} before it)
+        TR_ORDER(order_after(h, s, sW));
+        if ((rc = layer_wgrad(h, x, gr, wq, k, i, gx, GOk, inv))) return rc;
+        TR_ORDER(mark_on(h, serial, sW, w_done[i], i));
+      }
       {
         // d x_i = d x_{i+1} + sum_tap W_in[tap]^T d pre (MODE 2), fused with layer i-1's d acts + gate derivative (MODE 4)
         WnLayerArgs a;
@@ -1200,6 +1325,7 @@ int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, cons
           a.s_prev = w.S + (pl - 1) * w.plane_c;
           a.dpre_prev = w.GP + (pl - 1) * 2 * w.plane_c;
         }
+        if (i > 0) TR_ORDER(wait_on(s, w_done[i - 1]));     // the previous flow's reader of GXL[i]
         TR_PROF(s, 5, TR_TRY(launch_part(a, g, BNw, 0, 1, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, kind, bn, s); })));
         gx = gxi;
       }
@@ -1213,12 +1339,19 @@ int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, cons
       ib.n_peel = c.n_early_size;
       ib.g_peel = g_z_early ? g_z_early[early_index(k + 1)] : nullptr;
     }
+    // WG_TRAIN_RECOMPUTE: this flow's share of d spect before the slot is replayed for flow k+2 -- with parameter gradients
+    // on sW behind the flow's last weight-gradient job, so that w_flow covers it; otherwise on s behind the chain
+    const bool dspect = x.recompute && (g_mel || pg);
+    if (dspect && pg && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, sW))) return rc;
+    if (pg) TR_ORDER(mark_on(h, serial, sW, w_flow[k & 1], 10 + (k & 1)));
+    if (pg && (rc = start_wgrad(x, gr, k, gx, ib.Y, inv, s))) return rc;
     TR_TRY(launch_inv_bwd_post(ib, s));
-    // WG_TRAIN_RECOMPUTE: this flow's share of d spect before the slot is replayed for flow k+2
-    if (x.recompute && g_mel && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, s))) return rc;
+    if (dspect && !pg && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, s))) return rc;
   }
-  if (!g_mel) return WG_OK;
-  if (!x.recompute) {
+  if (!g_mel && !pg) return WG_OK;
+  if (x.recompute) {
+    if (pg) TR_ORDER(order_after(h, sW, s));    // the last flow's d spect GEMM wrote GSP on sW
+  } else {
     // d spect = sum over every layer of cond_layer^T d pre: ONE GEMM with K = FL*2C over the kept d pre planes
     PGemmArgs a;
     memset(&a, 0, sizeof a);
@@ -1232,16 +1365,21 @@ int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, cons
     a.o0 = w.GSP;
     TR_TRY(launch_plane_gemm(a, s));
   }
-  {
+  if (g_mel) {
     DmelArgs a;                           // d mel = the upsample's transpose applied to d spect (train.hip: dmel_kernel)
     a.g = g;
     a.GSP = w.GSP;
     a.wupt = (const _Float16*)wt->wupt;
     a.M = c.n_mel_channels;
     a.M8 = M8;
-    a.inv_scale = 1.0f / scale;
+    a.inv_scale = inv;
     a.g_mel = g_mel;
     TR_TRY(launch_dmel(a, s));
+  }
+  if (pg) {
+    if ((rc = upsample_wgrad(x, gr, inv, s))) return rc;
+    TR_ORDER(order_after(h, sW, s));      // every gradient of the call is final on the caller's stream
+    TR_ORDER(order_after(h, sR, s));
   }
   return WG_OK;
 }
@@ -1353,6 +1491,7 @@ int prep_args(wg_handle* h, const void* const* params, int weight_normed, const 
       tab[prep_slot_n(FL, nf, SEC_O_BSTART, k)] = const_cast<float*>(wt->bstart[k]);
       tab[prep_slot_n(FL, nf, SEC_O_OINIT, k)] = const_cast<float*>(wt->out_init[k]);
       tab[prep_slot_n(FL, nf, SEC_O_W1X1, k)] = const_cast<float*>(wt->w1x1[k]);
+      if (wt->winv) tab[prep_slot_n(FL, nf, SEC_O_WINV, k)] = const_cast<float*>(wt->winv[k]);
     }
     if (gr) {
       tab[prep_slot_n(FL, nf, SEC_G_DSTART, k)] = gr->dstart[k];
@@ -1374,6 +1513,7 @@ int prep_args(wg_handle* h, const void* const* params, int weight_normed, const 
   for (int k = 0; k < nf; ++k) { a.ck[k] = ck[k]; a.hk[k] = ck[k] / 2; }
   for (int q = 0; q < 4; ++q) a.n_scale[q] = L.n_scale[q];
   if (wt) { a.b1 = const_cast<float*>(wt->b1); a.b2 = const_cast<float*>(wt->b2); a.bup = const_cast<float*>(wt->bup); }
+  a.want_winv = wt && wt->winv;
   if (gr) {
     a.dw1 = gr->dw1; a.db1 = gr->db1; a.dw2 = gr->dw2; a.db2 = gr->db2; a.dwes = gr->dwes; a.dwup = gr->dwup; a.dbup = gr->dbup;
     a.layer_stride = gr->layer_stride; a.flow_stride = gr->flow_stride;
@@ -1413,6 +1553,9 @@ int wg_train_prepare(wg_handle* h, const void* const* params, int32_t weight_nor
   if (!out->a1 || !out->a1c || !out->b1 || !out->a2 || !out->b2 || !out->es || !out->wat || !out->wbt || !out->wct || !out->wup ||
       !out->bup || !out->wstart || !out->bstart || !out->out_init || !out->w1x1)
     return wg_set_error(WG_ERR_INVALID, "wg_train_prepare: wg_train_weights has a null member");
+  if (out->winv && h)
+    for (int k = 0; k < wg_internal_config(h)->n_flows; ++k)
+      if (!out->winv[k]) return wg_set_error(WG_ERR_INVALID, "wg_train_prepare: wg_train_weights.winv has a null per-flow pointer");
   hipStream_t s = (hipStream_t)stream;
   PrepArgs pa;
   int rc = prep_args(h, params, weight_normed, out, nullptr, aux, aux_bytes, nullptr, s, pa);

@@ -180,12 +180,50 @@ __global__ void __launch_bounds__(256) small_prep_kernel(const PrepArgs a) {
   }
 }
 
+// W_k^-1 of the 1x1 matrices (c_k <= 8) for the synthesis direction of a model whose weights move every optimiser step
+// (wg_train_weights.winv): Gauss-Jordan with partial pivoting in fp64 on the augmented [8][16] matrix, the c_k x c_k block
+// in the corner of an identity; rounded to fp32, row-major [c_k][c_k] as FlowArgs::winv / InvBwdArgs::winv read it.  One
+// workgroup per flow, its first lane does the 8 elimination steps (LDS holds the matrix: rows are indexed dynamically).
+// A singular matrix divides by a zero pivot and a nan never wins a pivot comparison: the result is non-finite, the loop
+// bounds are fixed.
+__global__ void __launch_bounds__(64) inv1x1_kernel(const PrepArgs a) {
+  __shared__ double m[8][16];
+  if (threadIdx.x != 0) return;
+  const int k = blockIdx.x, c = a.ck[k];
+  float* out = (float*)a.tab[prep_slot(a, SEC_O_WINV, k)];
+  const float* W = (const float*)a.tab[prep_slot(a, SEC_CV_W, k)];
+  if (!out || c < 1 || c > 8) return;
+  for (int r = 0; r < 8; ++r)
+    for (int j = 0; j < 8; ++j) {
+      m[r][j] = (r < c && j < c) ? (double)W[r * c + j] : (r == j ? 1.0 : 0.0);
+      m[r][8 + j] = r == j ? 1.0 : 0.0;
+    }
+  for (int col = 0; col < 8; ++col) {
+    int piv = col;
+    double best = fabs(m[col][col]);
+    for (int r = col + 1; r < 8; ++r)
+      if (fabs(m[r][col]) > best) { best = fabs(m[r][col]); piv = r; }
+    if (piv != col)
+      for (int j = 0; j < 16; ++j) { const double t = m[col][j]; m[col][j] = m[piv][j]; m[piv][j] = t; }
+    const double inv = 1.0 / m[col][col];
+    for (int j = 0; j < 16; ++j) m[col][j] *= inv;
+    for (int r = 0; r < 8; ++r) {
+      if (r == col) continue;
+      const double f = m[r][col];
+      for (int j = 0; j < 16; ++j) m[r][j] -= f * m[col][j];
+    }
+  }
+  for (int r = 0; r < c; ++r)
+    for (int j = 0; j < c; ++j) out[r * c + j] = (float)m[r][8 + j];
+}
+
 hipError_t launch_prepare(const PrepArgs& a, hipStream_t s) {
   const long long rows = (long long)a.FL * 2 * a.C * 2 + (long long)a.nf * 2 * a.C * a.nl + (long long)a.nf * a.C;
   hipLaunchKernelGGL(rownorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, a);
   hipLaunchKernelGGL(end_prep_kernel, dim3(a.nf), dim3(256), 0, s, a);
   hipLaunchKernelGGL(wes_fold_kernel, dim3(a.FL), dim3(256), 0, s, a);
   hipLaunchKernelGGL(small_prep_kernel, dim3(512), dim3(256), 0, s, a);
+  if (a.want_winv) hipLaunchKernelGGL(inv1x1_kernel, dim3(a.nf), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

@@ -148,6 +148,22 @@ struct InvBwdArgs {
   int last;                 // k == n_flows-1: the state is sigma * z_init
 };
 
+// d W_k of inverse step k (train.hip: inv_dw1x1_kernel).  The step computes w = W_k^-1 u with u = (y0 | (y1 - b) e^-s);
+// with g = d w and g_v = W_k^-T g:  d W_k = - sum over rows of g_v (x) w  (no logdet term in this direction).  Runs BEFORE
+// the step's inv_bwd_pre_kernel, which overwrites GZ in place.
+struct InvDwArgs {
+  RowGeom g;
+  int c, h;                 // c_k, h_k
+  float scale;              // loss scale (applied to g_audio; GZ already carries it)
+  const float* Y;           // [B*L][8] state entering inverse step k
+  const float* OUT;         // [B*L][8] (b | s) of WN_k
+  const float* winv;        // [c][c] W_k^-1 row-major
+  const float* g_audio;     // k == 0: [B][8L] d audio (unscaled); otherwise null and d w comes from GZ
+  const float* GZ;          // [B*L][8] d w (scaled)
+  float* partial;           // [flow_bwd_workgroups][64]: per-workgroup partial of d W[r][cc] as an [8][8] record (scaled;
+                            // rows / columns >= c_k are zeros)
+};
+
 struct StartWgradArgs {
   RowGeom g;
   int C, h;
@@ -170,6 +186,7 @@ enum PrepSec : int {
   SEC_UP_W, SEC_UP_B,                    // upsample.weight [M][M][1024], upsample.bias [M]                              x 1
   SEC_O_WSTART, SEC_O_BSTART, SEC_O_OINIT, SEC_O_W1X1,      // outputs of prepare (wg_train_weights per-flow pointers)   x n_flows
   SEC_G_DSTART, SEC_G_DOINIT, SEC_G_DW1X1,                  // packed gradients (wg_train_grads per-flow pointers)       x n_flows
+  SEC_O_WINV,                                               // optional output of prepare (wg_train_weights.winv)        x n_flows
   SEC_COUNT
 };
 constexpr int kPrepMaxFlows = 32;
@@ -185,6 +202,7 @@ struct PrepArgs {
   int C, M8, nl, nf, FL;
   int hk[kPrepMaxFlows], ck[kPrepMaxFlows];
   int n_scale[4];            // rows of the four weight-normed module classes (in_layers, cond_layer, res_skip_layers, start)
+  int want_winv;             // launch_prepare also inverts the 1x1 matrices into the SEC_O_WINV buffers (inv1x1_kernel)
 };
 __host__ __device__ inline int prep_sec_len(int FL, int nf, int sec) {
   return sec <= SEC_RS_B ? FL : (sec == SEC_UP_W || sec == SEC_UP_B) ? 1 : nf;
@@ -244,6 +262,7 @@ hipError_t launch_flow_bwd_post(const FlowBwdArgs& a, hipStream_t s);
 int flow_bwd_workgroups(const RowGeom& g);
 hipError_t launch_inv_bwd_pre(const InvBwdArgs& a, hipStream_t s);
 hipError_t launch_inv_bwd_post(const InvBwdArgs& a, hipStream_t s);
+hipError_t launch_inv_dw1x1(const InvDwArgs& a, hipStream_t s);
 hipError_t launch_start_wgrad(const StartWgradArgs& a, hipStream_t s);
 int start_wgrad_workgroups(const RowGeom& g);
 

@@ -3,13 +3,19 @@
 Reference: src/waveglow/model.py:223-273 (``infer``; the reference ends it with ``.data``, so its output never carries a
 graph).  Here the output of the frozen vocoder carries one back to ``mel`` and to the noise, so that a waveform-domain loss
 (a multi-resolution STFT loss, a discriminator) can train an acoustic model, or optimise a mel or a noise tensor, through
-it.  The weights are constants: a parameter that requires grad is refused, never silently dropped.
+it.  By default the weights are constants: a parameter that requires grad is refused, never silently dropped.  With
+``weight_grads=True`` the graph reaches the vocoder's own parameters as well (fine-tuning WaveGlow on a loss on what it
+synthesises): the backward then also runs the training direction's weight-gradient launches, flow by flow, and
+``wg_train_param_grads``; the inverse 1x1 matrices come from the per-call weights (inverted on the device by
+``wg_train_prepare``), so an optimiser step costs no re-finalisation of the inference engine.
 
 * ``wg_train_infer_forward``: the same 12 WN stacks as the training direction (``wg_train_forward``), in inverse flow
   order, with the training kernels' saved activations and the state that enters every inverse step; the inverse 1x1
   matrices are the fp64-computed ones ``infer`` uses (the engine is finalised with the current weights);
 * ``wg_train_infer_backward``: ascending flow order, two row kernels per flow around the training direction's WN
-  data-gradient chain, then the d spect GEMM and the transposed upsample for ``d mel``.
+  data-gradient chain, then the d spect GEMM and the transposed upsample for ``d mel``;
+* ``wg_train_infer_backward_params``: the same plus the packed weight gradients (``GradBuffers``), among them
+  ``d W_k = - sum (W_k^-T d w) (x) w`` of every inverse 1x1 step.
 
 The binding mirrors ``_TrainFn`` (waveglow_amd/train.py): ``_Weights`` from ``wg_train_prepare``, one training workspace
 per outstanding graph, the fp16 loss scale and ``model.grad_finite``.  There is no fallback: CPU tensors raise.
@@ -24,28 +30,31 @@ from typing import List
 import torch
 
 from . import _lib
-from .train import _ptr, _SlotGuard, _Weights, canonical_params, nonfinite_message
+from .train import GradBuffers, _ddp_group, _ptr, _SlotGuard, _Weights, canonical_params, nonfinite_message
 
 
 class _InferFn(torch.autograd.Function):
   """Inputs: model, sigma, loss scale (0 = automatic), weight-norm flag, wg_train flags (``WG_TRAIN_RECOMPUTE``: activation
-  recomputation, the backward runs with its forward's flags), number of early-noise tensors, mel, z_init,
-  z_early..., then the module's parameters in the library's canonical order (constants: never differentiated, but the
-  library reads them through ``wg_train_prepare``).  Output: audio [B, 256 T] fp32.  backward() returns only what
-  ``ctx.needs_input_grad`` asks for among mel, z_init and the z_early entries."""
+  recomputation, the backward runs with its forward's flags), number of early-noise tensors, the weight-gradient mode, mel,
+  z_init, z_early..., then the module's parameters in the library's canonical order (the library reads them through
+  ``wg_train_prepare``; without the weight-gradient mode they are constants: never differentiated).  Output: audio
+  [B, 256 T] fp32.  backward() returns only what ``ctx.needs_input_grad`` asks for among mel, z_init, the z_early entries
+  and -- in the weight-gradient mode -- the parameters, each parameter gradient a view of ONE flat buffer (as ``_TrainFn``)."""
 
-  N_META = 6      # model, sigma, scale, wn, flags, n_early
+  N_META = 7      # model, sigma, scale, wn, flags, n_early, wgrads
 
   @staticmethod
-  def forward(ctx, model, sigma, scale, wn, flags, n_early, mel, z_init, *rest):
+  def forward(ctx, model, sigma, scale, wn, flags, n_early, wgrads, mel, z_init, *rest):
     z_early, params = rest[:n_early], rest[n_early:]
-    eng = model._get_engine(mel.device)          # finalised with the current weights: the W^-1 of infer
+    # frozen: finalised with the current weights, the W^-1 of infer.  Weight-gradient mode: the weights move every step,
+    # W^-1 comes with the per-call weights and the inference engine is left alone
+    eng = model._get_engine(mel.device, need_weights=not wgrads)
     lib = eng.lib
     B, M, T = mel.shape
     flow_c = model.flow_channels()
     stream = torch.cuda.current_stream(mel.device).cuda_stream
-    want_mel = ctx.needs_input_grad[6]
-    wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=want_mel)
+    want_mel = ctx.needs_input_grad[_InferFn.N_META]
+    wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=want_mel, want_winv=wgrads)
     S = 256 * T
     nbytes = lib.wg_train_workspace_bytes_ex(eng.handle, B, T, S, flags)
     if nbytes == 0:
@@ -58,10 +67,11 @@ class _InferFn(torch.autograd.Function):
                                                 float(sigma), _ptr(audio), B, T, 1 if fresh else 0, _ptr(ws), ws.numel(),
                                                 flags, C.c_void_p(stream)))
     ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.guard = model, wts, ws, (B, M, T), _SlotGuard(slot)
-    ctx.flags = flags
+    ctx.flags, ctx.wgrads = flags, wgrads
     ctx.sigma, ctx.n_early, ctx.n_params = float(sigma), n_early, len(params)
-    ctx.sig = eng.signature
+    ctx.sig = model._weights_signature() if wgrads else eng.signature
     ctx.z_shapes = [tuple(z_init.shape)] + [tuple(z.shape) for z in z_early]
+    ctx.shapes = [t.shape for t in params]
     # the automatic scale assumes a loss normalised by the number of samples (|d loss / d audio| ~ 1 / N)
     ctx.scale = float(scale) if scale else float(2.0 ** round(math.log2(audio.numel())))
     return audio
@@ -73,7 +83,8 @@ class _InferFn(torch.autograd.Function):
       raise _lib.WgError("the saved state of this infer_differentiable call is gone: backward() already ran for it "
                          "(retain_graph is not supported)")
     eng = model._engine
-    if eng is None or eng.signature != ctx.sig or model._weights_signature() != ctx.sig:
+    stale = eng is None or model._weights_signature() != ctx.sig or (not ctx.wgrads and eng.signature != ctx.sig)
+    if stale:
       ctx.wts = None
       ctx.guard.release()
       raise _lib.WgError("the vocoder's weights changed between infer_differentiable and backward(): the saved state "
@@ -83,8 +94,11 @@ class _InferFn(torch.autograd.Function):
     dev = ctx.ws.device
     ne = ctx.n_early
     need = ctx.needs_input_grad
-    want_mel, want_zi = need[6], need[7]
-    want_ze = list(need[8:8 + ne])
+    nm = _InferFn.N_META
+    want_mel, want_zi = need[nm], need[nm + 1]
+    want_ze = list(need[nm + 2:nm + 2 + ne])
+    need_p = list(need[nm + 2 + ne:])
+    want_params = ctx.wgrads and any(need_p)
     poison = os.environ.get("WG_TRAIN_POISON_GRADS") == "1"
     new = (lambda sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)) if poison else \
         (lambda sh: torch.empty(sh, dtype=torch.float32, device=dev))
@@ -94,28 +108,52 @@ class _InferFn(torch.autograd.Function):
     ga = g_audio.float().contiguous() if g_audio is not None else torch.zeros((B, 256 * T), dtype=torch.float32, device=dev)
     ze = (C.c_void_p * max(1, ne))(*[(g.data_ptr() if g is not None else None) for g in g_ze])
     stream = torch.cuda.current_stream(dev).cuda_stream
+    hp = model._hp
+    bufs = GradBuffers(hp.n_channels, hp.n_layers, model.n_flows, hp.n_mel_channels * 8, dev) if want_params else None
+    gstruct, _keep = bufs.struct() if want_params else (None, None)
+    flat = None
     try:
-      _lib.check(lib.wg_train_infer_backward_flags(eng.handle, C.byref(ctx.wts.struct), _ptr(ga), C.c_float(ctx.scale),
-                                                   C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
-                                                   _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws),
-                                                   ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
+      if ctx.wgrads:
+        _lib.check(lib.wg_train_infer_backward_params(eng.handle, C.byref(ctx.wts.struct),
+                                                      C.byref(gstruct) if want_params else None, _ptr(ga),
+                                                      C.c_float(ctx.scale), C.c_float(ctx.sigma),
+                                                      _ptr(g_mel) if want_mel else None, _ptr(g_zi) if want_zi else None, ze,
+                                                      ne, B, T, _ptr(ctx.ws), ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
+      else:
+        _lib.check(lib.wg_train_infer_backward_flags(eng.handle, C.byref(ctx.wts.struct), _ptr(ga), C.c_float(ctx.scale),
+                                                     C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
+                                                     _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws),
+                                                     ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
+      if want_params:
+        # one gradient per parameter, views of one flat buffer in the canonical order (no logdet term in this direction)
+        sizes = [math.prod(sh) for sh in ctx.shapes]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        if poison:
+          flat.fill_(float("nan"))
+        wts = ctx.wts
+        _lib.check(lib.wg_train_param_grads(eng.handle, wts.params, wts.wn, C.byref(gstruct), _ptr(wts.aux), wts.aux.numel(),
+                                            _ptr(flat), C.c_void_p(stream)))
     finally:
       ctx.guard.release()
       ctx.wts = None
     # overflow of the fp16 gradient planes (see infer_differentiable: grad_scale), or inf / nan inputs
-    outs = [t for t in [g_mel, g_zi] + g_ze if t is not None]
+    outs = [t for t in [bufs.flat if want_params else None, g_mel, g_zi] + g_ze if t is not None]
     sums = [t.sum() for t in outs]
     model.grad_finite = torch.isfinite(torch.stack(sums)).all() if len(sums) > 1 else torch.isfinite(sums[0])
     if os.environ.get("WG_TRAIN_CHECK_FINITE") == "1" and not bool(model.grad_finite):
       raise _lib.WgError(nonfinite_message(ctx.scale))
-    return (None,) * _InferFn.N_META + (g_mel, g_zi, *g_ze) + (None,) * ctx.n_params
+    if not want_params:
+      return (None,) * nm + (g_mel, g_zi, *g_ze) + (None,) * ctx.n_params
+    grads = [v.view(sh) if w else None for v, sh, w in zip(flat.split(sizes), ctx.shapes, need_p)]
+    return (None,) * nm + (g_mel, g_zi, *g_ze, *grads)
 
 
 def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_early: List[torch.Tensor], sigma: float,
-                         grad_scale: float = 0.0, recompute: bool = False) -> torch.Tensor:
+                         grad_scale: float = 0.0, recompute: bool = False, weight_grads: bool = False) -> torch.Tensor:
   """``model.infer_with_noise(spect, z_init, z_early, sigma)`` (fp32) with an autograd graph back to ``spect``, ``z_init``
-  and every ``z_early[i]`` that requires grad.  Without grad mode, or when none of them requires grad, exactly
-  ``infer_with_noise`` (nothing is saved).  ``recompute``: activation recomputation (``WG_TRAIN_RECOMPUTE``)."""
+  and every ``z_early[i]`` that requires grad -- and, with ``weight_grads``, to every parameter that requires grad.
+  Without grad mode, or when nothing requires grad, exactly ``infer_with_noise`` (nothing is saved).  ``recompute``:
+  activation recomputation (``WG_TRAIN_RECOMPUTE``)."""
   ins = [spect, z_init] + list(z_early)
   for t in ins:
     if t.device.type != "cuda":
@@ -134,14 +172,19 @@ def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_ear
   n_early = sum(1 for k in range(model.n_flows) if k % model.n_early_every == 0 and k > 0)
   if len(z_early) != n_early or any(tuple(z.shape) != (B, model.n_early_size, L) for z in z_early):
     raise _lib.WgError(f"z_early: expected {n_early} tensors of shape {(B, model.n_early_size, L)}")
+  if weight_grads and _ddp_group(model) is not None:
+    raise _lib.WgError("infer_differentiable(weight_grads=True) does not average gradients over a process group "
+                       "(enable_data_parallel covers the training direction only): unset model.ddp_group and reduce the "
+                       "parameter gradients yourself")
   if not torch.is_grad_enabled():
     return model.infer_with_noise(spect, z_init, z_early, sigma)
-  if any(p.requires_grad for p in model.parameters()):
+  trainable = any(p.requires_grad for p in model.parameters())
+  if trainable and not weight_grads:
     raise _lib.WgError("infer_differentiable treats the vocoder's weights as constants and gives no weight gradients: "
-                       "freeze the model first (model.requires_grad_(False))")
-  if not any(t.requires_grad for t in ins):
+                       "freeze the model first (model.requires_grad_(False)) or ask for them (weight_grads=True)")
+  if not trainable and not any(t.requires_grad for t in ins):
     return model.infer_with_noise(spect, z_init, z_early, sigma)
   _names, tensors, wn = canonical_params(model, eng)
   ins = [t.contiguous() for t in ins]
   flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
-  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, flags, n_early, *ins, *tensors)
+  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, flags, n_early, bool(weight_grads), *ins, *tensors)

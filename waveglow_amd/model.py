@@ -376,13 +376,17 @@ class WaveGlow(nn.Module):
     return self.infer_with_noise(spect, z_init, z_early, sigma)
 
   def infer_differentiable(self, spect: torch.Tensor, sigma: float = 1.0, z_init: Optional[torch.Tensor] = None,
-                           z_early: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+                           z_early: Optional[List[torch.Tensor]] = None, *, weight_grads: bool = False) -> torch.Tensor:
     """``infer_with_noise(spect, z_init, z_early, sigma)`` at fp32 I/O (model.py:223-273) whose output carries an autograd
     graph back to ``spect`` and to the noise: ``loss.backward()`` fills ``spect.grad`` / ``z_init.grad`` /
     ``z_early[i].grad`` for those that require grad (waveglow_amd/infer_grad.py).  Noise that is not given is drawn as
-    ``infer`` draws it (same shapes, device RNG, same order).  The weights are constants: with grad mode on, a parameter
-    that requires grad raises ``WgError`` (``model.requires_grad_(False)``).  Without grad mode, or when no input requires
-    grad, this is ``infer_with_noise``.  The fp16 gradient planes take ``model.grad_scale`` as loss scale (default:
+    ``infer`` draws it (same shapes, device RNG, same order).  By default the weights are constants: with grad mode on, a
+    parameter that requires grad raises ``WgError`` (``model.requires_grad_(False)``).  ``weight_grads=True`` makes the
+    graph reach every parameter that requires grad as well -- ``loss.backward()`` gives each its ``.grad`` (weight-normed
+    ``(g, v)`` pairs or dense weights, ``end``, ``convinv``, ``upsample``), so an optimiser can train the vocoder on a loss
+    on its own output; the 1x1 inverses then follow the weights on the device (no re-finalised inference engine after an
+    optimiser step).  Gradient averaging over ``model.ddp_group`` is not done for this path: it raises ``WgError``.
+    Without grad mode, or when nothing requires grad, this is ``infer_with_noise``.  The fp16 gradient planes take ``model.grad_scale`` as loss scale (default:
     2^round(log2(audio.numel())), for a loss normalised by the number of samples); ``model.grad_finite`` is set by the
     backward pass.  Takes the training direction's widths (n_channels 64 / 128 / 256 / 512, n_mel_channels % 16 == 0).
     ``model.recompute_activations = True`` keeps the WN layer planes of two flows instead of twelve between this call and
@@ -399,7 +403,7 @@ class WaveGlow(nn.Module):
           z_early.append(torch.empty((B, self.n_early_size, L), dtype=spect.dtype, device=spect.device).normal_())
     from .infer_grad import infer_differentiable
     return infer_differentiable(self, spect, z_init, list(z_early), sigma, float(getattr(self, "grad_scale", 0.0)),
-                                bool(self.recompute_activations))
+                                bool(self.recompute_activations), bool(weight_grads))
 
   def forward(self, forward_input):
     """model.py:178-221: (mel [B,M,F], audio [B,S]) -> (z [B,8,L], [log_s_k], [log_det_W_k]).

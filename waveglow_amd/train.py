@@ -250,7 +250,8 @@ class _Weights:
   orders).  ``pack_weights`` / ``wn_forward_fragments`` / ``plain_fragments`` / ``to_fragments`` above are the same
   computation written as torch ops: the tests hold the library to them."""
 
-  def __init__(self, model, tensors, wn: bool, flow_c: List[int], eng, stream, want_wupt: bool = False):
+  def __init__(self, model, tensors, wn: bool, flow_c: List[int], eng, stream, want_wupt: bool = False,
+               want_winv: bool = False):
     hp = model._hp
     Cc, nf, nl = hp.n_channels, model.n_flows, hp.n_layers
     M8 = hp.n_mel_channels * 8
@@ -276,11 +277,18 @@ class _Weights:
     self.w1x1 = [small[k, 5 * Cc + 8:5 * Cc + 8 + c * c] for k, c in enumerate(flow_c)]
     arr = lambda ts: (C.c_void_p * nf)(*[t.data_ptr() for t in ts])
     self._arrs = [arr(self.wstart), arr(self.bstart), arr(self.out_init), arr(self.w1x1)]
+    # W_k^-1 for synthesis with moving weights (infer_differentiable(weight_grads=True)): inverted by wg_train_prepare
+    self.winv = None
+    if want_winv:
+      self._winv = f32(nf, 64)
+      self.winv = [self._winv[k, :c * c] for k, c in enumerate(flow_c)]
+      self._arrs.append(arr(self.winv))
     self.struct = _lib.WgTrainWeights(_ptr(self.a1), _ptr(self.a1c), _ptr(self.b1), _ptr(self.a2), _ptr(self.b2), _ptr(self.es),
                                       _ptr(self.wat), _ptr(self.wbt), _ptr(self.wct), _ptr(self.wup), _ptr(self.bup),
                                       C.cast(self._arrs[0], C.c_void_p), C.cast(self._arrs[1], C.c_void_p),
                                       C.cast(self._arrs[2], C.c_void_p), C.cast(self._arrs[3], C.c_void_p),
-                                      _ptr(self.wupt) if want_wupt else None)
+                                      _ptr(self.wupt) if want_wupt else None,
+                                      C.cast(self._arrs[4], C.c_void_p) if want_winv else None)
     self.wn = int(wn)
     self.params = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
     self.aux = torch.empty(eng.lib.wg_train_prepare_bytes(eng.handle), dtype=torch.uint8, device=dev)
