@@ -181,6 +181,36 @@ int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel,
 int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
                          int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Multi-resolution STFT loss (spectral convergence + log-magnitude L1), fp32, with its backward ------------------
+ * For resolution r = (n_fft, hop, win): X = STFT(x) with reflect padding by n_fft/2 and the window of `win` samples
+ * centred in n_fft, M = sqrt(max(re^2 + im^2, eps)); sc_r = |M(y) - M(x)|_F / |M(y)|_F over the whole batch,
+ * mag_r = mean |log M(y) - log M(x)|; sc = mean_r sc_r, mag = mean_r mag_r.
+ * wg_stftloss_create: 1..8 resolutions; n_fft a multiple of 32 in [32, 2048], 1 <= hop <= n_fft, 1 <= win <= n_fft;
+ *   fwd_basis[r] is the windowed Fourier basis [2*(n_fft/2+1)][n_fft] (real rows, then imaginary rows), HOST pointers,
+ *   packed once.  device_id < 0 makes a planning handle (no device work, fwd_basis may be null): workspace sizes only.
+ * wg_stftloss_workspace_bytes: 0 unless B >= 1 and n_samples > max n_fft / 2.  saved = 0 sizes wg_stftloss_forward,
+ *   saved = 1 sizes wg_stftloss_forward_saved + wg_stftloss_backward (one workspace serves both).
+ * wg_stftloss_forward[_saved]: audio, target [B][n_samples] fp32 device -> out3 = {sc, mag, factor_sc sc + factor_mag
+ *   mag} fp32 device.  _saved also keeps the prediction's (re, im), M(target) and the two norms in the workspace.
+ * wg_stftloss_backward: g_out3 [3] fp32 DEVICE = d loss / d out3 -> audio_grad_out [B][n_samples] = d loss / d audio
+ *   (no gradient under the clamp, sign(0) = 0).  Reads the workspace of a forward_saved call with the same factors, B
+ *   and n_samples and leaves its saved state intact, so it may run more than once.
+ * Sums are reduced in a fixed order (no floating-point atomics): results are bit-reproducible.  Enqueue-only; argument
+ * checks run before any device work. */
+typedef struct wg_stftloss wg_stftloss;
+int wg_stftloss_create(int32_t n_res, const int32_t* n_fft, const int32_t* hop, const int32_t* win,
+                       const float* const* fwd_basis, float eps, int32_t device_id, wg_stftloss** out);
+int wg_stftloss_destroy(wg_stftloss* h);
+size_t wg_stftloss_workspace_bytes(const wg_stftloss* h, int32_t B, int32_t n_samples, int32_t saved);
+int wg_stftloss_forward(wg_stftloss* h, const float* audio, const float* target, float factor_sc, float factor_mag,
+                        float* out3, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int wg_stftloss_forward_saved(wg_stftloss* h, const float* audio, const float* target, float factor_sc,
+                              float factor_mag, float* out3, int32_t B, int32_t n_samples, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, float factor_mag, float* audio_grad_out,
+                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Training direction: WaveGlow.forward under autograd and loss.backward() ---------------------------------------
  * (src/waveglow/model.py:178-221, train.py:190-199).  Weights change every optimiser step, so they are NOT taken from
  * the handle: the caller passes device buffers.  Every fp16 matrix below is given as [rows][K] in "(pos,pos)" order

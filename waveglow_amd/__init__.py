@@ -18,6 +18,9 @@ def __getattr__(name):
   if name in ("TacotronSTFT", "TSTFTHParams"):
     from . import taco_stft
     return getattr(taco_stft, name)
+  if name == "MultiResolutionSTFTLoss":
+    from .stft_loss import MultiResolutionSTFTLoss
+    return MultiResolutionSTFTLoss
   if name == "Denoiser":
     from .denoiser import Denoiser
     return Denoiser

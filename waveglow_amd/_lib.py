@@ -134,6 +134,16 @@ SIGNATURES = {
                                           C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stft_mel_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stftloss_create": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_void_p), C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
+  "wg_stftloss_destroy": (C.c_int, [C.c_void_p]),
+  "wg_stftloss_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+  "wg_stftloss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stftloss_forward_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                          C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stftloss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_debug_set_stamp_buffer": (C.c_int, [C.c_void_p, C.c_void_p]),
   "wg_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
   "wg_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),

@@ -1,0 +1,171 @@
+"""Multi-resolution STFT loss (spectral convergence + log-magnitude L1, as in Parallel WaveGAN) computed by the HIP
+library (``wg_stftloss_*``): conv-STFTs at run-time geometry on exact-fp32 MFMA, device-side reductions in a fixed
+order, and the matching backward.  The waveform-domain loss that ``WaveGlow.infer_differentiable`` is built for.
+
+For one resolution ``(n_fft, hop, win)``: ``X = STFT(x)`` with reflect padding by ``n_fft / 2`` and the periodic window
+of ``win`` samples centred in ``n_fft`` (``torch.stft(x, n_fft, hop, win, hann_window(win), center=True,
+pad_mode="reflect")``), ``M = sqrt(max(re^2 + im^2, eps))``,
+
+  sc_r  = ||M(y) - M(x)||_F / ||M(y)||_F        (norms over the whole batch)
+  mag_r = mean |log M(y) - log M(x)|            (over all B K F elements)
+
+and ``loss = factor_sc * mean_r sc_r + factor_mag * mean_r mag_r``.  No torch / CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+from scipy.signal import get_window
+
+from . import _lib
+
+MAX_RESOLUTIONS, MAX_FFT = 8, 2048
+
+
+def forward_basis(n_fft: int, win_length: int, window: str = "hann") -> np.ndarray:
+  """The windowed Fourier basis [2 * (n_fft / 2 + 1), n_fft] fp32, real rows then imaginary rows: the forward basis of
+  ``denoiser.stft_bases(n_fft, hop, win_length, window)``, value for value, without its pseudo-inverse."""
+  fb = np.fft.fft(np.eye(n_fft))
+  cutoff = n_fft // 2 + 1
+  fb = np.vstack([np.real(fb[:cutoff]), np.imag(fb[:cutoff])])
+  win = get_window(window, win_length, fftbins=True)
+  lpad = (n_fft - win_length) // 2
+  win = np.pad(win, (lpad, n_fft - win_length - lpad))
+  return np.ascontiguousarray(fb * win, dtype=np.float32)
+
+
+def check_geometry(fft_sizes, hop_sizes, win_lengths):
+  """Raise WgError unless the resolutions are ones the kernels support (see MultiResolutionSTFTLoss)."""
+  if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
+    raise _lib.WgError("fft_sizes, hop_sizes and win_lengths must have the same length")
+  if not 1 <= len(fft_sizes) <= MAX_RESOLUTIONS:
+    raise _lib.WgError(f"1 to {MAX_RESOLUTIONS} resolutions are supported, got {len(fft_sizes)}")
+  for n, h, w in zip(fft_sizes, hop_sizes, win_lengths):
+    if n < 32 or n > MAX_FFT or n % 32:
+      raise _lib.WgError(f"n_fft must be a multiple of 32 in [32, {MAX_FFT}], got {n}")
+    if not 1 <= h <= n:
+      raise _lib.WgError(f"hop must be in [1, n_fft], got {h} for n_fft {n}")
+    if not 1 <= w <= n:
+      raise _lib.WgError(f"win_length must be in [1, n_fft], got {w} for n_fft {n}")
+
+
+class _LossFn(torch.autograd.Function):
+  """Inputs: the module, prediction and target [B, N].  Output: the device vector (sc, mag, loss).  The forward keeps
+  the library's workspace on ctx; the backward writes only to that workspace's scratch part, so a second backward under
+  retain_graph gives the same bits."""
+
+  @staticmethod
+  def forward(ctx, crit, x, y):
+    B, N = x.shape
+    out, ws = crit._run(x, y, saved=True)
+    ctx.crit, ctx.ws, ctx.dims = crit, ws, (B, N)
+    return out
+
+  @staticmethod
+  def backward(ctx, g_out):
+    crit, ws = ctx.crit, ctx.ws
+    B, N = ctx.dims
+    g = g_out.to(torch.float32).contiguous()
+    gx = torch.empty((B, N), dtype=torch.float32, device=ws.device)
+    stream = torch.cuda.current_stream(ws.device).cuda_stream
+    _lib.check(crit.lib.wg_stftloss_backward(crit._h, g.data_ptr(), crit.factor_sc, crit.factor_mag, gx.data_ptr(), B, N,
+                                             ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    return None, gx, None
+
+
+class MultiResolutionSTFTLoss(torch.nn.Module):
+  """``crit(audio, target)`` -> 0-dim fp32 loss on the device with a graph back to ``audio``; ``crit.terms(audio,
+  target)`` -> ``(sc, mag)``.
+
+  ``audio``, ``target``: fp32 ``[B, N]`` on the module's device, same shape, ``N > max(fft_sizes) / 2``; anything else
+  raises WgError.  Only ``audio`` gets a gradient (a ``target`` that requires grad raises WgError); the clamp at ``eps``
+  passes no gradient where ``re^2 + im^2 < eps`` and ``sign(0) = 0``, as in plain torch.  Without grad mode, or when
+  ``audio`` does not require grad, the same values come back with no graph and nothing saved.  No host synchronisation
+  in forward or backward; values and gradients are bit-reproducible (fixed-order reductions, no atomics).
+
+  Supported geometries: 1 to 8 resolutions, each with ``n_fft`` a multiple of 32 in [32, 2048], ``1 <= hop <= n_fft``
+  (it need not divide ``n_fft``) and ``1 <= win_length <= n_fft``; ``window`` is any name ``scipy.signal.get_window``
+  knows.  Everything else raises WgError at construction."""
+
+  def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240),
+               window="hann", factor_sc=1.0, factor_mag=1.0, eps=1e-7, device="cuda"):
+    super().__init__()
+    device = torch.device(device)
+    if device.type != "cuda":
+      raise _lib.WgError("the STFT loss runs on the GPU library only")
+    fft_sizes, hop_sizes, win_lengths = (tuple(int(v) for v in t) for t in (fft_sizes, hop_sizes, win_lengths))
+    check_geometry(fft_sizes, hop_sizes, win_lengths)
+    if not eps > 0:
+      raise _lib.WgError(f"eps must be positive, got {eps}")
+    self.resolutions = tuple(zip(fft_sizes, hop_sizes, win_lengths))
+    self.factor_sc, self.factor_mag, self.eps = float(factor_sc), float(factor_mag), float(eps)
+    self.device = device
+    self.lib = _lib.load()
+    n = len(fft_sizes)
+    bases = [forward_basis(nf, w, window) for nf, _, w in self.resolutions]
+    arr = lambda v: (C.c_int32 * n)(*v)
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bases])
+    self._h = C.c_void_p()
+    _lib.check(self.lib.wg_stftloss_create(n, arr(fft_sizes), arr(hop_sizes), arr(win_lengths), ptrs, self.eps,
+                                           _lib.device_index(device), C.byref(self._h)))
+
+  def __del__(self):
+    try:
+      if getattr(self, "_h", None):
+        self.lib.wg_stftloss_destroy(self._h)
+    except Exception:
+      pass
+
+  def workspace_bytes(self, B: int, N: int) -> int:
+    """Bytes one forward with a graph keeps until its backward (0 when N <= max(fft_sizes) / 2): per resolution the
+    prediction's (re, im) [B, n_fft, F] and M(target) [B, n_fft / 2 + 1, F] (F rounded up to 64), the per-workgroup
+    sums, and one frame-gradient scratch [B, F, win] that the backward reuses for every resolution."""
+    return int(self.lib.wg_stftloss_workspace_bytes(self._h, B, N, 1))
+
+  def _check(self, x, y):
+    for name, t in (("audio", x), ("target", y)):
+      if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or \
+          _lib.device_index(t.device) != _lib.device_index(self.device):
+        raise _lib.WgError(f"MultiResolutionSTFTLoss: {name} must be on {self.device} (no CPU fallback)")
+      if t.dtype != torch.float32:
+        raise _lib.WgError(f"MultiResolutionSTFTLoss takes float32 {name}, got {t.dtype}")
+      if t.dim() != 2:
+        raise _lib.WgError(f"MultiResolutionSTFTLoss takes {name} [B, N], got shape {tuple(t.shape)}")
+    if x.shape != y.shape:
+      raise _lib.WgError(f"audio {tuple(x.shape)} and target {tuple(y.shape)} differ in shape")
+    if y.requires_grad:
+      raise _lib.WgError("MultiResolutionSTFTLoss: only audio gets a gradient; detach the target")
+    need = max(n for n, _, _ in self.resolutions) // 2
+    if x.shape[0] < 1 or x.shape[1] <= need:
+      raise _lib.WgError(f"audio of {x.shape[1]} samples is too short (reflect padding needs > {need})")
+
+  def _run(self, x, y, saved):
+    """One library call on contiguous fp32 [B, N]: (out3, workspace)."""
+    x, y = x.detach().contiguous(), y.detach().contiguous()
+    B, N = x.shape
+    nbytes = self.lib.wg_stftloss_workspace_bytes(self._h, B, N, 1 if saved else 0)
+    if nbytes == 0:
+      raise _lib.WgError(f"MultiResolutionSTFTLoss: unsupported batch {B} x {N}")
+    out = torch.empty(3, dtype=torch.float32, device=x.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    fn = self.lib.wg_stftloss_forward_saved if saved else self.lib.wg_stftloss_forward
+    _lib.check(fn(self._h, x.data_ptr(), y.data_ptr(), self.factor_sc, self.factor_mag, out.data_ptr(), B, N,
+                  ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    return out, ws
+
+  def _out3(self, audio, target):
+    self._check(audio, target)
+    if torch.is_grad_enabled() and audio.requires_grad:
+      return _LossFn.apply(self, audio, target)
+    return self._run(audio, target, saved=False)[0]
+
+  def terms(self, audio: torch.Tensor, target: torch.Tensor):
+    """(sc, mag): the spectral-convergence and log-magnitude terms, each averaged over the resolutions."""
+    out = self._out3(audio, target)
+    return out[0], out[1]
+
+  def forward(self, audio: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    return self._out3(audio, target)[2]
