@@ -437,26 +437,57 @@ size_t grad_ofs(const wg_train_grads* gr, int nl, int fl, size_t dense) {
                           : (size_t)fl * dense;
 }
 
-// Weight-gradient sequencing shared by the two backward directions (wg_train_backward_ex_flags: descending flows,
-// wg_train_infer_backward_params: ascending flows; both put the launches on the low-priority streams sW / sR).  A layer's
-// slabs are reduced by a launch of its own on sR beside the NEXT layer's weight-gradient launch on sW.
-// Two slab sets: launch n + 2 on sW waits for the reduction of launch n (r_done), the reduction of launch n for launch n
-// itself (l_done).  serial: one stream, no marks.
-struct WgradSeq {
-  hipStream_t sW, sR;
-  bool serial;
-  int n_layer;
-  hipEvent_t l_done[2], r_done[2];
+// ---------------------------------------------------------------------------------------------
+// What the two backward drivers share (wg_train_backward_ex_flags: training direction, flows descending;
+// wg_train_infer_backward_params: synthesis direction, flows ascending): the plan of one call, the WN data-gradient chain
+// of one flow (wn_flow_backward) and the d spect tail behind the last flow (dspect_finish).
+//
+// Streams of one backward call.  The caller's stream `s` carries chain 0 (d acts / gate derivative and d x of the first
+// half of the batch, or of all of it) and the row kernels of every flow; sB carries chain 1 (the second half, see setup:
+// training direction only); sW (lowest priority) carries the weight-gradient launches (and the per-flow d spect GEMMs of
+// WG_TRAIN_RECOMPUTE) and sR (lowest priority too) their slab reductions, which nothing downstream in the same call waits
+// for: they fill the CUs the chains leave idle.  Everything is joined back into `s` before the call returns, so the caller
+// sees the usual stream semantics.  Without parameter gradients sW = sR = s; WG_TRAIN_SERIAL=1: all four are `s`.
+// (Two chains pay in the forward pass, -23 % per layer at config 4; in the backward pass the weight-gradient stream
+//  already fills the idle CUs and a second chain measured +0.7 ms per step: off unless WG_TRAIN_BWD_HALVES=2, tests.)
+//
+// Buffers the streams share and what orders their reuse.  Every reuse is by the NEXT flow processed (k - 1 descending,
+// k + 1 ascending) or by the one AFTER it (k -+ 2: the same parity), so the rules hold for both loop directions:
+//   GXL[i] (d x_i)   written by the chains' d x launch of layer i, read by their layer i-1 launches (same stream) and by
+//                    sW's second job of layer i-1: the next flow's layer-i launch waits for that job (w_done[i-1], not yet
+//                    re-marked by the next flow at that point: its layer i-1 comes later);
+//   GO[k & 1]        written by flow k's pre kernel on s, read by the chains and by all of flow k's jobs on sW: the pre
+//                    kernel of the flow after the next waits for the last of them (w_flow[k & 1]);
+//   GP, X, T, S, A   full save: one set per layer of the whole model, no reuse inside a call (GP is read by the final
+//                    d spect GEMM on s).  WG_TRAIN_RECOMPUTE: one set per layer of flow slot k & 1, read by flow k's chain
+//                    launches (s / sB, joined into s at the end of the flow) and by its weight-gradient jobs and d spect
+//                    GEMM on sW (X, A, GP): the replay of the flow after the next into the slot runs on s behind the same
+//                    w_flow[k & 1] wait as its pre kernel.  The forward leaves the first two flows of the backward in
+//                    their slots: they are not replayed;
+//   slab sets        a layer's slabs are reduced by a launch of its own on sR -- HBM-bound and small in registers and LDS,
+//                    so its workgroups run beside the NEXT layer's weight-gradient workgroups on sW (MFMA / L2-bound, one
+//                    per CU).  Two sets: launch n + 2 on sW waits for the reduction of launch n (r_done), the reduction of
+//                    launch n for launch n itself (l_done);
+//   GZ, part3        row kernels and their reductions, on s alone.
+// Without parameter gradients everything but chain 1 runs on `s` and is reused in stream order.  Across the calls of a flow
+// range (training direction) everything is joined into s at the end of a call.
+// Marks are waited on one or two flows / launches after their record: events of their own (wg_internal_mark_event, slots
+// 0-9 = w_done[layer], 10-11 = w_flow[parity], 12-13 = l_done[set], 14-15 = r_done[set]); a null entry = not recorded in
+// this call, nothing to wait for.
+// ---------------------------------------------------------------------------------------------
+struct BwdPlan {
+  const _Float16 *wat, *wbt;       // fragment tensors of the two dgrad GEMMs (include/waveglow_amd.h: wat, wbt)
+  size_t kstep_n, wat_n, wbt_n;    // their elements per 64-deep K-step and per layer
+  bool fuse;                       // false (WG_TRAIN_NO_FUSE=1: tests, A/B): d acts + gate derivative as launches of their own
+  int BNw;                         // tile width of the chain launches
+  int bh;                          // chains: 1, or the forward's 2 half-batch chains
+  float inv;                       // 1 / loss scale
+  hipStream_t s, sB, sW, sR;
+  bool serial;                     // sW = sR = s: no marks
+  int n_wgrad;                     // weight-gradient launches so far (slab set = its parity)
+  hipEvent_t w_done[10], w_flow[2], l_done[2], r_done[2];
 };
-WgradSeq wgrad_seq(hipStream_t sW, hipStream_t sR, bool serial) {
-  WgradSeq q;
-  q.sW = sW; q.sR = sR; q.serial = serial; q.n_layer = 0;
-  q.l_done[0] = q.l_done[1] = q.r_done[0] = q.r_done[1] = nullptr;
-  return q;
-}
-// (marks are waited on one or two flows / launches after their record: events of their own, wg_internal_mark_event,
-//  slots 0-9 = w_done[layer], 10-11 = w_flow[parity], 12-13 = l_done[set], 14-15 = r_done[set]; a null entry = not recorded
-//  in this call, nothing to wait for)
+
 hipError_t mark_on(wg_handle* h, bool serial, hipStream_t st, hipEvent_t& e, int slot) {
   e = nullptr;
   if (serial) return hipSuccess;
@@ -465,16 +496,55 @@ hipError_t mark_on(wg_handle* h, bool serial, hipStream_t st, hipEvent_t& e, int
 }
 hipError_t wait_on(hipStream_t st, hipEvent_t e) { return e ? hipStreamWaitEvent(st, e, 0) : hipSuccess; }
 
+// tile width of the backward chain launches: the forward's, or WG_TRAIN_BWD_BN (A/B runs of the backward alone)
+int bwd_block_n(const Ctx& x) {
+  if (const char* e = getenv("WG_TRAIN_BWD_BN")) {
+    const int f = atoi(e);
+    if (f == 64 || (f == 128 && wn_block_n(x.C) == 128)) return f;
+  }
+  return fwd_block_n(x);
+}
+
+// The plan of one backward call on stream `s`; gr null: no parameter gradients.  second_chain: the training direction,
+// which may run the forward's two half-batch chains (WG_TRAIN_BWD_HALVES=2).  The environment is read on every call.
+int bwd_plan(wg_handle* h, const Ctx& x, const wg_train_weights* wt, const wg_train_grads* gr, float scale, hipStream_t s,
+             bool second_chain, BwdPlan& p) {
+  if (gr && ((gr->layer_stride == 0) != (gr->flow_stride == 0) || gr->layer_stride < 0 || gr->flow_stride < 0))
+    return wg_set_error(WG_ERR_INVALID, "wg_train_grads: layer_stride and flow_stride must both be 0 or both positive");
+  memset(&p, 0, sizeof p);
+  const int cc = x.C / 64, NW = wn_waves(x.C), MBw = x.C / (32 * NW);
+  p.wat = (const _Float16*)wt->wat;
+  p.wbt = (const _Float16*)wt->wbt;
+  p.kstep_n = (size_t)2 * NW * MBw * 2 * 64 * 8;
+  p.wat_n = (size_t)(cc + 1) * p.kstep_n;
+  p.wbt_n = (size_t)(6 * cc) * p.kstep_n;
+  const char* e = getenv("WG_TRAIN_NO_FUSE");
+  p.fuse = !(e && *e == '1');
+  p.BNw = bwd_block_n(x);
+  p.bh = 1;
+  if (second_chain && (e = getenv("WG_TRAIN_BWD_HALVES")) && atoi(e) == 2) p.bh = x.halves;
+  p.inv = 1.0f / scale;
+  p.s = p.sB = p.sW = p.sR = s;
+  p.serial = x.serial || !gr;
+  if (p.bh == 2 && !x.serial && !(p.sB = wg_internal_aux_stream(h, 0)))
+    return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
+  if (!p.serial) {
+    if (!(p.sW = wg_internal_aux_stream(h, 1))) return wg_set_error(WG_ERR_HIP, "cannot create the weight-gradient stream");
+    if (!(p.sR = wg_internal_aux_stream(h, 2))) return wg_set_error(WG_ERR_HIP, "cannot create the slab-reduction stream");
+  }
+  return WG_OK;
+}
+
 // The weight gradients of layer i of flow k, once d pre of the layer (GP) and gx = d x_{i+1} (null: the flow's last layer)
-// are on q.sW's side of the stream order:
+// are on sW's side of the stream order:
 // d W1 = d pre x [x taps | spect]^T, d b1;
 // d W2 = d x_{i+1} x acts^T, d b2  and  d (W_end W_skip_i) = d out x acts^T  share the X operand (acts): one
 // job with the d out plane as the `extra` 16 rows (the last layer has no d x: the d out plane stands in as the
 // job's G as well, and that part of the result is not used).
 // Both jobs in ONE launch over the same slab partition (train.hip: wgrad_kernel), then the reduction of everything the
 // launch left behind; layer 0 also leaves d out_init of the flow.
-int layer_wgrad(wg_handle* h, const Ctx& x, const wg_train_grads* gr, WgradSeq& q, int k, int i, const _Float16* gx,
-                const _Float16* GOk, float inv) {
+int layer_wgrad(wg_handle* h, const Ctx& x, BwdPlan& p, const wg_train_grads* gr, int k, int i, const _Float16* gx,
+                const _Float16* GOk) {
   const RowGeom& g = x.g;
   const TrainWs& w = x.w;
   const int C = x.C, nl = x.nl, K1 = x.K1;
@@ -485,10 +555,10 @@ int layer_wgrad(wg_handle* h, const Ctx& x, const wg_train_grads* gr, WgradSeq& 
   const _Float16* Ai = w.A + pl * w.plane_c;
   const _Float16* GPi = w.GP + pl * 2 * w.plane_c;
   const int* const n_slabs = x.n_slabs;
-  hipStream_t sW = q.sW, sR = q.sR;
+  hipStream_t sW = p.sW, sR = p.sR;
+  const float inv = p.inv;
   WgradJob jb[2];
-  const int set = q.n_layer & 1;
-  ++q.n_layer;
+  const int set = p.n_wgrad++ & 1;
   memset(jb, 0, sizeof jb);
   jb[0].G = GPi;
   jb[0].m_chunks = 2 * cc;
@@ -510,9 +580,9 @@ int layer_wgrad(wg_handle* h, const Ctx& x, const wg_train_grads* gr, WgradSeq& 
   jb[1].bias_out = w.part2[set];
   jb[1].extra_out = w.ext[set];
   jb[1].extra_bias_out = w.extb[set];
-  TR_ORDER(wait_on(sW, q.r_done[set]));          // the reduction of the launch before last has read this slab set
+  TR_ORDER(wait_on(sW, p.r_done[set]));          // the reduction of the launch before last has read this slab set
   TR_PROF(sW, 6, TR_TRY(launch_wgrad(jb, 2, g, n_slabs, sW)));
-  TR_ORDER(mark_on(h, q.serial, sW, q.l_done[set], 12 + set));
+  TR_ORDER(mark_on(h, p.serial, sW, p.l_done[set], 12 + set));
   // ---- reduction of everything this launch left behind, in NATURAL channel order (SlabSeg: perm bit 0 = rows are
   // channels, bit 1 = columns are)
   SlabSeg seg[kMaxSlabSegs];
@@ -536,9 +606,9 @@ int layer_wgrad(wg_handle* h, const Ctx& x, const wg_train_grads* gr, WgradSeq& 
   add_flat(1, w.ext[set], (size_t)16 * C, (size_t)8 * C, gr->dwes + grad_ofs(gr, nl, fl, (size_t)8 * C), C, 2);
   // d out_init = sum over columns of (d b | d log_s), once per flow
   if (i == 0) add_flat(1, w.extb[set], 16, 8, gr->dout_init[k], 0, 0);
-  TR_ORDER(wait_on(sR, q.l_done[set]));
+  TR_ORDER(wait_on(sR, p.l_done[set]));
   TR_TRY(launch_slab_reduce_multi(seg, n_seg, sR));
-  TR_ORDER(mark_on(h, q.serial, sR, q.r_done[set], 14 + set));
+  TR_ORDER(mark_on(h, p.serial, sR, p.r_done[set], 14 + set));
   return WG_OK;
 }
 
@@ -579,6 +649,140 @@ int upsample_wgrad(const Ctx& x, const wg_train_grads* gr, float inv, hipStream_
   sg[1] = make_seg(w.part3, kPhases, M8, M8, inv, gr->dbup, M8, 2);
   TR_TRY(launch_slab_reduce_multi(sg, 2, s));
   return WG_OK;
+}
+
+// The WN data-gradient chain of flow k, last layer to first, once the flow's pre kernel has written GOk = GO[k & 1] on p.s:
+// per layer d pre and d x_i on the p.bh chains (p.s, p.sB), and with parameter gradients the layer's weight-gradient job
+// on p.sW behind them.  Chain 1 is joined back into p.s at the end; gx returns d x_0 (GXL[0]).
+int wn_flow_backward(wg_handle* h, const Ctx& x, BwdPlan& p, const wg_train_grads* gr, int k, const _Float16* GOk,
+                     const _Float16*& gx) {
+  const RowGeom& g = x.g;
+  const TrainWs& w = x.w;
+  const int C = x.C, nl = x.nl, cc = C / 64;
+  TR_ORDER(order_after(h, p.s, p.sB));
+  gx = nullptr;                               // gx = d x_{i+1} (null: zero, the last layer has no res output)
+  for (int i = nl - 1; i >= 0; --i) {
+    const int fl = k * nl + i, d = 1 << i;
+    const size_t pl = plane_layer(x, k, i);
+    _Float16* GPi = w.GP + pl * 2 * w.plane_c;
+    WnLayerArgs a;
+    // Fused (round 3): the d x launch of layer i + 1 has already produced d pre of this layer behind its own result
+    // (wn_layer_kernel MODE 4: the d x tile goes through LDS into the next GEMM instead of out to the planes and back in
+    // through a launch of its own); only a flow's last layer, which has no d x above it, runs MODE 3 alone.
+    if (!p.fuse || i == nl - 1) {
+      // d acts = W_res^T d x_{i+1} + (W_end W_skip_i)^T d out ; gate derivative -> d pre   (wn_layer_kernel MODE 3)
+      memset(&a, 0, sizeof a);
+      const _Float16* Am = p.wat + (size_t)fl * p.wat_n;
+      if (gx) {
+        a.x_tap = gx;
+        a.x_chunks_per_tap = cc;
+        a.sp = GOk;
+        a.n_cond_steps = 1;
+        a.wA1 = Am;
+        a.wA1c = Am + (size_t)cc * p.kstep_n;
+      } else {
+        a.x_tap = GOk;                     // last layer of a flow: no d x_{i+1}, the d out plane alone
+        a.x_chunks_per_tap = 1;
+        a.n_cond_steps = 0;
+        a.wA1 = Am + (size_t)cc * p.kstep_n;
+        a.wA1c = a.wA1;
+      }
+      a.dil = 0;
+      a.g = g;
+      a.M = x.c->n_mel_channels;
+      a.n_cu = x.n_cu;
+      a.in0 = w.T + pl * w.plane_c;
+      a.in1 = w.S + pl * w.plane_c;
+      a.out0 = GPi;
+      for (int half = 0; half < p.bh; ++half) {
+        hipStream_t sh = half ? p.sB : p.s;
+        TR_PROF(sh, 5, TR_TRY(launch_part(a, g, p.BNw, half, p.bh, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, 3, bn, sh); })));
+      }
+    }
+    if (gr) {
+      // the weight-gradient stream continues once every chain has written its part of d pre (and of d x_{i+1} before it)
+      TR_ORDER(order_after(h, p.s, p.sW));
+      if (p.sB != p.s) TR_ORDER(order_after(h, p.sB, p.sW));
+      // d W1 / d b1, d W2 / d b2, d (W_end W_skip_i) of the layer (and d out_init with layer 0) and their reduction
+      if (int rc = layer_wgrad(h, x, p, gr, k, i, gx, GOk)) return rc;
+      TR_ORDER(mark_on(h, p.serial, p.sW, p.w_done[i], i));
+    }
+    // d x_i = d x_{i+1} + sum_tap W_in[tap]^T d pre(t - (tap-1) d)   (wn_layer_kernel MODE 2: taps at +d, 0, -d)
+    memset(&a, 0, sizeof a);
+    a.x_tap = GPi;
+    a.x_chunks_per_tap = 2 * cc;
+    a.n_cond_steps = 0;
+    a.wA1 = p.wbt + (size_t)fl * p.wbt_n;
+    a.wA1c = a.wA1;
+    a.dil = -d;
+    a.g = g;
+    a.M = x.c->n_mel_channels;
+    a.n_cu = x.n_cu;
+    a.in0 = gx;
+    _Float16* const gxi = w.GXL + (size_t)i * w.plane_c;
+    a.out0 = gxi;
+    const int kind = (p.fuse && i > 0) ? 4 : 2;
+    if (kind == 4) {      // ... and d acts + gate derivative of layer i - 1 on the tile (see above)
+      a.wat_prev = p.wat + (size_t)(fl - 1) * p.wat_n;
+      a.gout = GOk;
+      a.t_prev = w.T + (pl - 1) * w.plane_c;
+      a.s_prev = w.S + (pl - 1) * w.plane_c;
+      a.dpre_prev = w.GP + (pl - 1) * 2 * w.plane_c;
+    }
+    for (int half = 0; half < p.bh; ++half) {
+      hipStream_t sh = half ? p.sB : p.s;
+      if (gr && i > 0) TR_ORDER(wait_on(sh, p.w_done[i - 1]));     // GXL[i]: see BwdPlan
+      TR_PROF(sh, 5, TR_TRY(launch_part(a, g, p.BNw, half, p.bh, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, kind, bn, sh); })));
+    }
+    gx = gxi;
+  }
+  TR_ORDER(order_after(h, p.sB, p.s));
+  return WG_OK;
+}
+
+// every gradient of the call is final on the caller's stream
+int join_wgrad_streams(wg_handle* h, const BwdPlan& p) {
+  TR_ORDER(order_after(h, p.sW, p.s));
+  TR_ORDER(order_after(h, p.sR, p.s));
+  return WG_OK;
+}
+
+// Behind the last flow: d spect (GSP planes) -> d mel and, with parameter gradients, d upsample; then the final joins.
+int dspect_finish(wg_handle* h, const Ctx& x, const BwdPlan& p, const wg_train_weights* wt, const wg_train_grads* gr,
+                  float* g_mel) {
+  const TrainWs& w = x.w;
+  hipStream_t s = p.s;
+  if (x.recompute) {
+    TR_ORDER(order_after(h, p.sW, s));      // the last flow's d spect GEMM (dspect_flow) wrote GSP on sW
+  } else {
+    // d spect = sum over every layer of cond_layer^T d pre: ONE GEMM with K = FL*2C over the kept d pre planes
+    const int C = x.C, FL = x.FL;
+    PGemmArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_runs = 1;
+    a.run[0] = run_of(w.GP, FL * 2 * (C / 64), 0);
+    a.A = (const _Float16*)wt->wct;
+    a.ktot = FL * 2 * C;
+    a.n_blk = x.M8 / 32;
+    a.M = x.M8;
+    a.g = x.g;
+    a.o0 = w.GSP;
+    TR_TRY(launch_plane_gemm(a, s));
+  }
+  if (g_mel) {
+    DmelArgs a;                             // d mel = the upsample's transpose applied to d spect (train.hip: dmel_kernel)
+    a.g = x.g;
+    a.GSP = w.GSP;
+    a.wupt = (const _Float16*)wt->wupt;
+    a.M = x.c->n_mel_channels;
+    a.M8 = x.M8;
+    a.inv_scale = p.inv;
+    a.g_mel = g_mel;
+    TR_TRY(launch_dmel(a, s));
+  }
+  if (!gr) return WG_OK;
+  if (int rc = upsample_wgrad(x, gr, p.inv, s)) return rc;
+  return join_wgrad_streams(h, p);
 }
 
 }  // namespace
@@ -750,48 +954,10 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
   const RowGeom& g = x.g;
   TrainWs& w = x.w;
   hipStream_t s = (hipStream_t)stream;
-  const int C = x.C, nl = x.nl, M8 = x.M8, FL = x.FL;
-  const int cc = C / 64;
-  const float inv = 1.0f / scale;
-  const _Float16* wat = (const _Float16*)wt->wat;
-  const _Float16* wbt = (const _Float16*)wt->wbt;
-  // fragment tensors of the two dgrad GEMMs (include/waveglow_amd.h: wat, wbt): elements per 64-deep K-step and per layer
-  const int NW = wn_waves(C), MBw = C / (32 * NW);
-  const size_t kstep_n = (size_t)2 * NW * MBw * 2 * 64 * 8;
-  const size_t wat_n = (size_t)(cc + 1) * kstep_n, wbt_n = (size_t)(6 * cc) * kstep_n;
-  const int n_cu = x.n_cu;
-  // Streams of one backward call.  The caller's stream `s` carries chain 0 (d acts / gate derivative and d x of the
-  // first half of the batch) and the row kernels of every flow; sB carries chain 1 (the second half, see setup); sW
-  // (lowest priority) carries the weight-gradient launches and their slab reductions, which nothing downstream in
-  // the same call waits for: they fill the CUs the chains leave idle.  Everything is joined back into `s` before the
-  // call returns, so the caller sees the usual stream semantics.  WG_TRAIN_SERIAL=1: all three are `s`.
-  // (Two chains pay in the forward pass, -23 % per layer at config 4; in the backward pass the weight-gradient stream
-  //  already fills the idle CUs and a second chain measured +0.7 ms per step: off unless WG_TRAIN_BWD_HALVES=2, tests.)
-  int bh = 1;
-  if (const char* e = getenv("WG_TRAIN_BWD_HALVES")) bh = (atoi(e) == 2) ? x.halves : 1;
-  hipStream_t sB = s, sW = s, sR = s;
-  if (!x.serial) {
-    if (bh == 2 && !(sB = wg_internal_aux_stream(h, 0))) return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
-    if (pg && !(sW = wg_internal_aux_stream(h, 1))) return wg_set_error(WG_ERR_HIP, "cannot create the weight-gradient stream");
-    if (pg && !(sR = wg_internal_aux_stream(h, 2))) return wg_set_error(WG_ERR_HIP, "cannot create the slab-reduction stream");
-  }
-  bool fuse = true;                       // WG_TRAIN_NO_FUSE=1 (tests, A/B): d acts + gate derivative as launches of their own
-  if (const char* e = getenv("WG_TRAIN_NO_FUSE")) fuse = !(*e == '1');
-  int BNw = wn_block_n(C);
-  if (BNw == 128 && (int64_t)kPhases * (g.Rp / 128) < (int64_t)n_cu) BNw = 64;
-  if (const char* e = getenv("WG_FORCE_BN")) {
-    const int f = atoi(e);
-    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
-  }
-  if (const char* e = getenv("WG_TRAIN_BWD_BN")) {      // A/B runs: tile width of the backward launches alone
-    const int f = atoi(e);
-    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
-  }
-  // where entry fl of a per-layer gradient tensor lives: dense, or in interleaved per-layer records (wg_train_grads)
-  if (pg && ((gr->layer_stride == 0) != (gr->flow_stride == 0) || gr->layer_stride < 0 || gr->flow_stride < 0))
-    return wg_set_error(WG_ERR_INVALID, "wg_train_grads: layer_stride and flow_stride must both be 0 or both positive");
-
+  BwdPlan p;                                // streams, marks and what orders the reuse of shared buffers: see BwdPlan
+  if ((rc = bwd_plan(h, x, wt, gr, scale, s, true, p))) return rc;
   if (flow_lo < 0 || flow_hi >= c.n_flows || flow_lo > flow_hi) return wg_set_error(WG_ERR_INVALID, "bad flow range");
+  if (x.nl > 10) return wg_set_error(WG_ERR_INVALID, "more than 10 layers");
   // channel offsets of the peeled outputs in z (model.py:201-203, :220): early outputs of the flows <= k
   auto early_channels_upto = [&](int k) {
     int n = 0;
@@ -800,37 +966,14 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     return n;
   };
   int z_final_ch0 = early_channels_upto(flow_hi);
-
-  // Buffers the streams share and what orders their reuse:
-  //   GXL[i] (d x_i)   written by the chains' d x launch of layer i, read by their layer i-1 launches (same stream) and by
-  //                    sW's second job of layer i-1: the next flow's layer-i launch waits for that job (w_done[i-1]);
-  //   GO[k & 1]        written by flow k's pre kernel on s, read by the chains and by all of flow k's jobs on sW: the pre
-  //                    kernel of flow k-2 waits for the last of them (w_flow[k & 1]);
-  //   GP, X, T, S, A   full save: one set per layer of the whole model, no reuse inside a call.  WG_TRAIN_RECOMPUTE: one
-  //                    set per layer of flow slot k & 1, read by flow k's chain launches (s / sB, joined into s at the
-  //                    end of the flow) and by its weight-gradient jobs and d spect GEMM on sW (X, A, GP): the replay of
-  //                    flow k-2 into the slot runs on s behind the same w_flow[k & 1] wait as its pre kernel.  The
-  //                    forward leaves flows n_flows-1 and n_flows-2 in their slots: they are not replayed.  Across the
-  //                    calls of a flow range everything is joined into s at the end of a call.
-  if (pg) TR_ORDER(order_after(h, s, sW));
-  // A layer's slabs are reduced by a launch of its own on a third stream (sR, lowest priority too): it is HBM-bound and
-  // small in registers and LDS, so its workgroups run beside the NEXT layer's weight-gradient workgroups (MFMA / L2-bound,
-  // one per CU).  Two slab sets: launch n + 2 on sW waits for the reduction of launch n (r_done), the reduction of launch
-  // n for launch n itself (l_done).
-  WgradSeq wq = wgrad_seq(sW, sR, x.serial);
-  // (marks: see mark_on)
-  hipEvent_t w_done[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t w_flow[2] = {nullptr, nullptr};
-  if (nl > 10) return wg_set_error(WG_ERR_INVALID, "more than 10 layers");
-  auto mark = [&](hipStream_t st, hipEvent_t& e, int slot) -> hipError_t { return mark_on(h, x.serial, st, e, slot); };
-  auto wait_for = [&](hipStream_t st, hipEvent_t e) -> hipError_t { return wait_on(st, e); };
+  TR_ORDER(order_after(h, s, p.sW));
 
   for (int k = flow_hi; k >= flow_lo; --k) {
     const int ck = x.ck[k], hk = ck / 2;
     FlowBwdArgs fb;
     memset(&fb, 0, sizeof fb);
     fb.g = g;
-    fb.C = C;
+    fb.C = x.C;
     fb.c = ck;
     fb.h = hk;
     fb.scale = scale;
@@ -841,101 +984,17 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     fb.from_z = (k == c.n_flows - 1);
     fb.z_ch0 = early_channels_upto(c.n_flows - 1);
     fb.GZ = w.GZ;
-    _Float16* const GOk = w.GO[k & 1];
-    fb.GO = GOk;
-    TR_ORDER(wait_for(s, w_flow[k & 1]));
+    fb.GO = w.GO[k & 1];
+    TR_ORDER(wait_on(s, p.w_flow[k & 1]));
     if (x.recompute && k < c.n_flows - 2 && (rc = replay_flow(h, x, wt, k, true, s))) return rc;
     TR_TRY(launch_flow_bwd_pre(fb, s));
-    TR_ORDER(order_after(h, s, sB));
-
-    _Float16* gx = nullptr;                     // gx = d x_{i+1} (null: zero, the last layer has no res output)
-    for (int i = nl - 1; i >= 0; --i) {
-      const int fl = k * nl + i, d = 1 << i;
-      const size_t pl = plane_layer(x, k, i);
-      _Float16* GPi = w.GP + pl * 2 * w.plane_c;
-      // Fused (round 3): the d x launch of layer i + 1 has already produced d pre of this layer behind its own result
-      // (wn_layer_kernel MODE 4: the d x tile goes through LDS into the next GEMM instead of out to the planes and back in
-      // through a launch of its own); only a flow's last layer, which has no d x above it, runs MODE 3 alone.
-      if (!fuse || i == nl - 1) {
-        // d acts = W_res^T d x_{i+1} + (W_end W_skip_i)^T d out ; gate derivative -> d pre   (wn_layer_kernel MODE 3)
-        WnLayerArgs a;
-        memset(&a, 0, sizeof a);
-        const _Float16* Am = wat + (size_t)fl * wat_n;
-        if (gx) {
-          a.x_tap = gx;
-          a.x_chunks_per_tap = cc;
-          a.sp = GOk;
-          a.n_cond_steps = 1;
-          a.wA1 = Am;
-          a.wA1c = Am + (size_t)cc * kstep_n;
-        } else {
-          a.x_tap = GOk;                     // last layer of a flow: no d x_{i+1}, the d out plane alone
-          a.x_chunks_per_tap = 1;
-          a.n_cond_steps = 0;
-          a.wA1 = Am + (size_t)cc * kstep_n;
-          a.wA1c = a.wA1;
-        }
-        a.dil = 0;
-        a.g = g;
-        a.M = c.n_mel_channels;
-        a.n_cu = n_cu;
-        a.in0 = w.T + pl * w.plane_c;
-        a.in1 = w.S + pl * w.plane_c;
-        a.out0 = GPi;
-        for (int half = 0; half < bh; ++half) {
-          hipStream_t sh = half ? sB : s;
-          TR_PROF(sh, 5, TR_TRY(launch_part(a, g, BNw, half, bh, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, 3, bn, sh); })));
-        }
-      }
-      // the weight-gradient stream continues once both chains have written their half of d pre (and of d x_{i+1} before it)
-      if (pg) {
-        TR_ORDER(order_after(h, s, sW));
-        TR_ORDER(order_after(h, sB, sW));
-        // d W1 / d b1, d W2 / d b2, d (W_end W_skip_i) of the layer (and d out_init with layer 0) and their reduction
-        if ((rc = layer_wgrad(h, x, gr, wq, k, i, gx, GOk, inv))) return rc;
-        TR_ORDER(mark(sW, w_done[i], i));
-      }
-      {
-        // d x_i = d x_{i+1} + sum_tap W_in[tap]^T d pre(t - (tap-1) d)   (wn_layer_kernel MODE 2: taps at +d, 0, -d)
-        WnLayerArgs a;
-        memset(&a, 0, sizeof a);
-        a.x_tap = GPi;
-        a.x_chunks_per_tap = 2 * cc;
-        a.n_cond_steps = 0;
-        a.wA1 = wbt + (size_t)fl * wbt_n;
-        a.wA1c = a.wA1;
-        a.dil = -d;
-        a.g = g;
-        a.M = c.n_mel_channels;
-        a.n_cu = n_cu;
-        a.in0 = gx;
-        _Float16* const gxi = w.GXL + (size_t)i * w.plane_c;
-        a.out0 = gxi;
-        const int kind = (fuse && i > 0) ? 4 : 2;
-        if (kind == 4) {      // ... and d acts + gate derivative of layer i - 1 on the tile (see above)
-          a.wat_prev = wat + (size_t)(fl - 1) * wat_n;
-          a.gout = GOk;
-          a.t_prev = w.T + (pl - 1) * w.plane_c;
-          a.s_prev = w.S + (pl - 1) * w.plane_c;
-          a.dpre_prev = w.GP + (pl - 1) * 2 * w.plane_c;
-        }
-        for (int half = 0; half < bh; ++half) {
-          hipStream_t sh = half ? sB : s;
-          if (i > 0) TR_ORDER(wait_for(sh, w_done[i - 1]));     // the previous flow's reader of GXL[i] (not yet re-marked: layer i-1 of this flow comes later)
-          TR_PROF(sh, 5, TR_TRY(launch_part(a, g, BNw, half, bh, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, kind, bn, sh); })));
-        }
-        gx = gxi;
-      }
-    }
+    if ((rc = wn_flow_backward(h, x, p, gr, k, fb.GO, fb.GX))) return rc;
     // WG_TRAIN_RECOMPUTE: this flow's share of d spect while its slot still holds its d pre planes -- on sW behind the
-    // flow's last weight-gradient job, so that w_flow covers it; without parameter gradients on s behind the chains
+    // flow's last weight-gradient job, so that w_flow covers it (without parameter gradients sW is s: behind the chains)
     const bool dspect = x.recompute && (pg || g_mel);
-    if (dspect && pg && (rc = dspect_flow(x, wt, k, k == c.n_flows - 1, k == 0, sW))) return rc;
-    if (pg) TR_ORDER(mark(sW, w_flow[k & 1], 10 + (k & 1)));
-    TR_ORDER(order_after(h, sB, s));
-    if (dspect && !pg && (rc = dspect_flow(x, wt, k, k == c.n_flows - 1, k == 0, s))) return rc;
-    if (pg && (rc = start_wgrad(x, gr, k, gx, fb.Zpost, inv, s))) return rc;
-    fb.GX = gx;
+    if (dspect && (rc = dspect_flow(x, wt, k, k == c.n_flows - 1, k == 0, p.sW))) return rc;
+    if (pg) TR_ORDER(mark_on(h, p.serial, p.sW, p.w_flow[k & 1], 10 + (k & 1)));
+    if (pg && (rc = start_wgrad(x, gr, k, fb.GX, fb.Zpost, p.inv, s))) return rc;
     fb.wstart = wt->wstart[k];
     fb.w1x1 = wt->w1x1[k];
     if (k > 0) {
@@ -955,52 +1014,15 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
       TR_TRY(launch_flow_bwd_post(fb, s));
     }
     if (pg) {
-      const SlabSeg sg = make_seg(w.part3, flow_bwd_workgroups(g), 64, 64, inv, gr->dw1x1[k], 0, 0);
+      const SlabSeg sg = make_seg(w.part3, flow_bwd_workgroups(g), 64, 64, p.inv, gr->dw1x1[k], 0, 0);
       TR_TRY(launch_slab_reduce_multi(&sg, 1, s));
     }
   }
-  if (flow_lo > 0 || !(pg || g_mel)) {    // the upsample / mel gradients need the d pre planes of every flow
-    if (pg) {
-      TR_ORDER(order_after(h, sW, s));    // every gradient of the call is final on the caller's stream
-      TR_ORDER(order_after(h, sR, s));
-    }
-    return WG_OK;
-  }
-  if (x.recompute) {
-    if (pg) TR_ORDER(order_after(h, sW, s));    // flow 0's d spect GEMM wrote GSP on sW
-  } else {
-    // d spect = sum over every layer of cond_layer^T d pre: ONE GEMM with K = FL*2C over the kept d pre planes
-    PGemmArgs a;
-    memset(&a, 0, sizeof a);
-    a.n_runs = 1;
-    a.run[0] = run_of(w.GP, FL * 2 * cc, 0);
-    a.A = (const _Float16*)wt->wct;
-    a.ktot = FL * 2 * C;
-    a.n_blk = M8 / 32;
-    a.M = M8;
-    a.g = g;
-    a.o0 = w.GSP;
-    TR_TRY(launch_plane_gemm(a, s));
-  }
-  if (g_mel) {
-    // d mel = the upsample's transpose applied to d spect (train.hip: dmel_kernel)
-    DmelArgs a;
-    a.g = g;
-    a.GSP = w.GSP;
-    a.wupt = (const _Float16*)wt->wupt;
-    a.M = c.n_mel_channels;
-    a.M8 = M8;
-    a.inv_scale = inv;
-    a.g_mel = g_mel;
-    TR_TRY(launch_dmel(a, s));
-  }
-  if (pg) {
-    if ((rc = upsample_wgrad(x, gr, inv, s))) return rc;
-    TR_ORDER(order_after(h, sW, s));      // every gradient of the call is final on the caller's stream
-    TR_ORDER(order_after(h, sR, s));
-  }
-  return WG_OK;
+  // the upsample / mel gradients need the d pre planes of every flow
+  if (flow_lo > 0 || !(pg || g_mel)) return join_wgrad_streams(h, p);
+  return dspect_finish(h, x, p, wt, gr, g_mel);
 }
+
 
 // ---------------------------------------------------------------------------------------------
 // Differentiable synthesis (include/waveglow_amd.h: wg_train_infer_*): WaveGlow.infer (model.py:223-273) on the training
@@ -1156,81 +1178,35 @@ int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, con
   int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, flags, x, winv);
   if (rc) return rc;
   if (g_mel && !wt->wupt) return wg_set_error(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
-  // gr == null: the data-gradient chain alone, the launches of wg_train_infer_backward_flags before this entry point existed.
-  // Otherwise the packed weight gradients as well, flow by flow behind the data gradients they are made of: per layer the
-  // training direction's weight-gradient launch and slab reduction (layer_wgrad), per flow d start (the saved state Y is the
-  // WN input, as Zpost is in the training direction), d out_init and d W_k of the inverse 1x1, after the last flow d upsample.
+  // gr == null: the data-gradient chain alone.  Otherwise the packed weight gradients as well, flow by flow behind the data
+  // gradients they are made of: per layer the training direction's weight-gradient launch and slab reduction (layer_wgrad),
+  // per flow d start (the saved state Y is the WN input, as Zpost is in the training direction), d out_init and d W_k of the
+  // inverse 1x1, after the last flow d upsample.
   const bool pg = gr != nullptr;
   if (pg && (rc = check_grads(gr, x.c->n_flows))) return rc;
-  if (pg && ((gr->layer_stride == 0) != (gr->flow_stride == 0) || gr->layer_stride < 0 || gr->flow_stride < 0))
-    return wg_set_error(WG_ERR_INVALID, "wg_train_grads: layer_stride and flow_stride must both be 0 or both positive");
   const wg_config& c = *x.c;
   const RowGeom& g = x.g;
   TrainWs& w = x.w;
   hipStream_t s = (hipStream_t)stream;
-  const int C = x.C, nl = x.nl, M8 = x.M8, FL = x.FL;
-  const int cc = C / 64;
-  const float inv = 1.0f / scale;
-  // Streams, as in wg_train_backward_ex_flags: the caller's stream `s` carries the data-gradient chain and every row kernel,
-  // sW (lowest priority) the weight-gradient launches (and the per-flow d spect GEMMs of WG_TRAIN_RECOMPUTE), sR their slab
-  // reductions; nothing downstream in the call waits for them, they fill the CUs the chain leaves idle, and everything is
-  // joined back into `s` before the call returns.  Without parameter gradients, or with WG_TRAIN_SERIAL=1: all three are `s`.
-  // What orders the reuse of shared buffers -- the flows ascend here, but every reuse is by the NEXT flow processed (GXL) or
-  // the one after it (GO, flow slots), so the marks are the training direction's with k + 1 / k + 2 for k - 1 / k - 2:
-  //   GXL[i] (d x_i)   written by the d x launch of layer i on s, read by sW's second job of layer i-1: flow k+1's layer-i
-  //                    launch waits for flow k's job (w_done[i-1], not yet re-marked by flow k+1 at that point);
-  //   GO[k & 1]        written by flow k's pre kernel on s, read by all of flow k's jobs on sW: the pre kernel of flow k+2
-  //                    waits for the last of them (w_flow[k & 1]);
-  //   flow slot k & 1  (WG_TRAIN_RECOMPUTE: X / T / S / A / GP) read by flow k's jobs and d spect GEMM on sW: the replay of
-  //                    flow k+2 into it runs on s behind the same w_flow[k & 1] wait;
-  //   GZ, part3        row kernels and their reductions, on s alone;
-  //   GP (full save)   one set per layer of the model, written on s, read by the final d spect GEMM on s.
-  hipStream_t sW = s, sR = s;
-  const bool serial = x.serial || !pg;
-  if (!serial) {
-    if (!(sW = wg_internal_aux_stream(h, 1))) return wg_set_error(WG_ERR_HIP, "cannot create the weight-gradient stream");
-    if (!(sR = wg_internal_aux_stream(h, 2))) return wg_set_error(WG_ERR_HIP, "cannot create the slab-reduction stream");
-  }
-  WgradSeq wq = wgrad_seq(sW, sR, serial);
-  hipEvent_t w_done[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t w_flow[2] = {nullptr, nullptr};
-  if (pg && nl > 10) return wg_set_error(WG_ERR_INVALID, "more than 10 layers");
-  if (pg) TR_ORDER(order_after(h, s, sW));
-  const _Float16* wat = (const _Float16*)wt->wat;
-  const _Float16* wbt = (const _Float16*)wt->wbt;
-  // fragment tensors of the two dgrad GEMMs, as in wg_train_backward_ex
-  const int NW = wn_waves(C), MBw = C / (32 * NW);
-  const size_t kstep_n = (size_t)2 * NW * MBw * 2 * 64 * 8;
-  const size_t wat_n = (size_t)(cc + 1) * kstep_n, wbt_n = (size_t)(6 * cc) * kstep_n;
-  bool fuse = true;                       // WG_TRAIN_NO_FUSE=1: as in wg_train_backward_ex
-  if (const char* e = getenv("WG_TRAIN_NO_FUSE")) fuse = !(*e == '1');
-  int BNw = wn_block_n(C);
-  if (BNw == 128 && (int64_t)kPhases * (g.Rp / 128) < (int64_t)x.n_cu) BNw = 64;
-  if (const char* e = getenv("WG_FORCE_BN")) {
-    const int f = atoi(e);
-    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
-  }
-  if (const char* e = getenv("WG_TRAIN_BWD_BN")) {
-    const int f = atoi(e);
-    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
-  }
+  BwdPlan p;                                // one chain on `s`; streams, marks and buffer reuse: see BwdPlan
+  if ((rc = bwd_plan(h, x, wt, gr, scale, s, false, p))) return rc;
+  if (pg && x.nl > 10) return wg_set_error(WG_ERR_INVALID, "more than 10 layers");
+  TR_ORDER(order_after(h, s, p.sW));
   // index in z_early (descending flow order) of early flow k
   auto early_index = [&](int k) {
     int n = 0;
     for (int q = c.n_flows - 1; q > k; --q) n += is_early(c, q);
     return n;
   };
-  // Ascending flow order: the gradient enters at the audio, the output of inverse step 0.  Without parameter gradients
-  // everything runs on `s`, so the GO plane, GXL and GZ are reused in stream order, and so are the flow slots of
-  // WG_TRAIN_RECOMPUTE: flow k's replay follows every reader of flow k-2's planes.  With them: the marks above.
+  // Ascending flow order: the gradient enters at the audio, the output of inverse step 0.
   for (int k = 0; k < c.n_flows; ++k) {
     const int ck = x.ck[k];
-    TR_ORDER(wait_on(s, w_flow[k & 1]));
+    TR_ORDER(wait_on(s, p.w_flow[k & 1]));
     if (x.recompute && k >= 2 && (rc = replay_flow(h, x, wt, k, false, s))) return rc;
     InvBwdArgs ib;
     memset(&ib, 0, sizeof ib);
     ib.g = g;
-    ib.C = C;
+    ib.C = x.C;
     ib.c = ck;
     ib.h = ck / 2;
     ib.scale = scale;
@@ -1240,8 +1216,7 @@ int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, con
     ib.winv = winv[k];
     ib.g_audio = k == 0 ? g_audio : nullptr;
     ib.GZ = w.GZ;
-    _Float16* const GOk = w.GO[k & 1];
-    ib.GO = GOk;
+    ib.GO = w.GO[k & 1];
     if (pg) {
       // d W_k = - sum g_v (x) w, from the step's incoming gradient: before the pre kernel overwrites GZ in place
       InvDwArgs dw;
@@ -1257,80 +1232,11 @@ int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, con
       dw.GZ = w.GZ;
       dw.partial = w.part3;
       TR_TRY(launch_inv_dw1x1(dw, s));
-      const SlabSeg sg = make_seg(w.part3, flow_bwd_workgroups(g), 64, 64, inv, gr->dw1x1[k], 0, 0);
+      const SlabSeg sg = make_seg(w.part3, flow_bwd_workgroups(g), 64, 64, p.inv, gr->dw1x1[k], 0, 0);
       TR_TRY(launch_slab_reduce_multi(&sg, 1, s));
     }
     TR_TRY(launch_inv_bwd_pre(ib, s));
-    // the WN data-gradient chain of flow k: wg_train_backward_ex's launches without parameter gradients, one chain
-    _Float16* gx = nullptr;                     // d x_{i+1} (null: the last layer has no res output)
-    for (int i = nl - 1; i >= 0; --i) {
-      const int fl = k * nl + i, d = 1 << i;
-      const size_t pl = plane_layer(x, k, i);
-      _Float16* GPi = w.GP + pl * 2 * w.plane_c;
-      if (!fuse || i == nl - 1) {
-        // d acts = W_res^T d x_{i+1} + (W_end W_skip_i)^T d out ; gate derivative -> d pre   (wn_layer_kernel MODE 3)
-        WnLayerArgs a;
-        memset(&a, 0, sizeof a);
-        const _Float16* Am = wat + (size_t)fl * wat_n;
-        if (gx) {
-          a.x_tap = gx;
-          a.x_chunks_per_tap = cc;
-          a.sp = GOk;
-          a.n_cond_steps = 1;
-          a.wA1 = Am;
-          a.wA1c = Am + (size_t)cc * kstep_n;
-        } else {
-          a.x_tap = GOk;
-          a.x_chunks_per_tap = 1;
-          a.n_cond_steps = 0;
-          a.wA1 = Am + (size_t)cc * kstep_n;
-          a.wA1c = a.wA1;
-        }
-        a.dil = 0;
-        a.g = g;
-        a.M = c.n_mel_channels;
-        a.n_cu = x.n_cu;
-        a.in0 = w.T + pl * w.plane_c;
-        a.in1 = w.S + pl * w.plane_c;
-        a.out0 = GPi;
-        TR_PROF(s, 5, TR_TRY(launch_part(a, g, BNw, 0, 1, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, 3, bn, s); })));
-      }
-      if (pg) {
-        // the weight-gradient stream continues once the chain has written d pre of this layer (and d x_{i+1} before it)
-        TR_ORDER(order_after(h, s, sW));
-        if ((rc = layer_wgrad(h, x, gr, wq, k, i, gx, GOk, inv))) return rc;
-        TR_ORDER(mark_on(h, serial, sW, w_done[i], i));
-      }
-      {
-        // d x_i = d x_{i+1} + sum_tap W_in[tap]^T d pre (MODE 2), fused with layer i-1's d acts + gate derivative (MODE 4)
-        WnLayerArgs a;
-        memset(&a, 0, sizeof a);
-        a.x_tap = GPi;
-        a.x_chunks_per_tap = 2 * cc;
-        a.n_cond_steps = 0;
-        a.wA1 = wbt + (size_t)fl * wbt_n;
-        a.wA1c = a.wA1;
-        a.dil = -d;
-        a.g = g;
-        a.M = c.n_mel_channels;
-        a.n_cu = x.n_cu;
-        a.in0 = gx;
-        _Float16* const gxi = w.GXL + (size_t)i * w.plane_c;
-        a.out0 = gxi;
-        const int kind = (fuse && i > 0) ? 4 : 2;
-        if (kind == 4) {
-          a.wat_prev = wat + (size_t)(fl - 1) * wat_n;
-          a.gout = GOk;
-          a.t_prev = w.T + (pl - 1) * w.plane_c;
-          a.s_prev = w.S + (pl - 1) * w.plane_c;
-          a.dpre_prev = w.GP + (pl - 1) * 2 * w.plane_c;
-        }
-        if (i > 0) TR_ORDER(wait_on(s, w_done[i - 1]));     // the previous flow's reader of GXL[i]
-        TR_PROF(s, 5, TR_TRY(launch_part(a, g, BNw, 0, 1, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, kind, bn, s); })));
-        gx = gxi;
-      }
-    }
-    ib.GX = gx;
+    if ((rc = wn_flow_backward(h, x, p, gr, k, ib.GO, ib.GX))) return rc;
     ib.wstart = wt->wstart[k];
     ib.last = (k == c.n_flows - 1);
     if (ib.last) {
@@ -1340,48 +1246,16 @@ int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, con
       ib.g_peel = g_z_early ? g_z_early[early_index(k + 1)] : nullptr;
     }
     // WG_TRAIN_RECOMPUTE: this flow's share of d spect before the slot is replayed for flow k+2 -- with parameter gradients
-    // on sW behind the flow's last weight-gradient job, so that w_flow covers it; otherwise on s behind the chain
+    // on sW behind the flow's last weight-gradient job, so that w_flow covers it; otherwise on s behind the post kernel
     const bool dspect = x.recompute && (g_mel || pg);
-    if (dspect && pg && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, sW))) return rc;
-    if (pg) TR_ORDER(mark_on(h, serial, sW, w_flow[k & 1], 10 + (k & 1)));
-    if (pg && (rc = start_wgrad(x, gr, k, gx, ib.Y, inv, s))) return rc;
+    if (dspect && pg && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, p.sW))) return rc;
+    if (pg) TR_ORDER(mark_on(h, p.serial, p.sW, p.w_flow[k & 1], 10 + (k & 1)));
+    if (pg && (rc = start_wgrad(x, gr, k, ib.GX, ib.Y, p.inv, s))) return rc;
     TR_TRY(launch_inv_bwd_post(ib, s));
     if (dspect && !pg && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, s))) return rc;
   }
   if (!g_mel && !pg) return WG_OK;
-  if (x.recompute) {
-    if (pg) TR_ORDER(order_after(h, sW, s));    // the last flow's d spect GEMM wrote GSP on sW
-  } else {
-    // d spect = sum over every layer of cond_layer^T d pre: ONE GEMM with K = FL*2C over the kept d pre planes
-    PGemmArgs a;
-    memset(&a, 0, sizeof a);
-    a.n_runs = 1;
-    a.run[0] = run_of(w.GP, FL * 2 * cc, 0);
-    a.A = (const _Float16*)wt->wct;
-    a.ktot = FL * 2 * C;
-    a.n_blk = M8 / 32;
-    a.M = M8;
-    a.g = g;
-    a.o0 = w.GSP;
-    TR_TRY(launch_plane_gemm(a, s));
-  }
-  if (g_mel) {
-    DmelArgs a;                           // d mel = the upsample's transpose applied to d spect (train.hip: dmel_kernel)
-    a.g = g;
-    a.GSP = w.GSP;
-    a.wupt = (const _Float16*)wt->wupt;
-    a.M = c.n_mel_channels;
-    a.M8 = M8;
-    a.inv_scale = inv;
-    a.g_mel = g_mel;
-    TR_TRY(launch_dmel(a, s));
-  }
-  if (pg) {
-    if ((rc = upsample_wgrad(x, gr, inv, s))) return rc;
-    TR_ORDER(order_after(h, sW, s));      // every gradient of the call is final on the caller's stream
-    TR_ORDER(order_after(h, sR, s));
-  }
-  return WG_OK;
+  return dspect_finish(h, x, p, wt, gr, g_mel);
 }
 
 }  // extern "C"

@@ -17,20 +17,21 @@ synthesises): the backward then also runs the training direction's weight-gradie
 * ``wg_train_infer_backward_params``: the same plus the packed weight gradients (``GradBuffers``), among them
   ``d W_k = - sum (W_k^-T d w) (x) w`` of every inverse 1x1 step.
 
-The binding mirrors ``_TrainFn`` (waveglow_amd/train.py): ``_Weights`` from ``wg_train_prepare``, one training workspace
-per outstanding graph, the fp16 loss scale and ``model.grad_finite``.  There is no fallback: CPU tensors raise.
+The binding uses ``_TrainFn``'s plumbing (waveglow_amd/train.py): ``_Weights`` from ``wg_train_prepare``, one training
+workspace per outstanding graph (``request_workspace``), the fp16 loss scale and ``model.grad_finite``
+(``set_grad_finite``), ``param_grad_views``.  Its own: the stale-weights check.  There is no fallback: CPU tensors raise.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import List
 
 import torch
 
 from . import _lib
-from .train import GradBuffers, _ddp_group, _ptr, _SlotGuard, _Weights, canonical_params, nonfinite_message
+from .train import (GradBuffers, _ddp_group, _ptr, _SlotGuard, _Weights, canonical_params, new_grad, param_grad_views,
+                    request_workspace, set_grad_finite)
 
 
 class _InferFn(torch.autograd.Function):
@@ -56,10 +57,7 @@ class _InferFn(torch.autograd.Function):
     want_mel = ctx.needs_input_grad[_InferFn.N_META]
     wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=want_mel, want_winv=wgrads)
     S = 256 * T
-    nbytes = lib.wg_train_workspace_bytes_ex(eng.handle, B, T, S, flags)
-    if nbytes == 0:
-      raise _lib.WgError(lib.wg_last_error().decode())
-    slot, fresh = eng.train_workspace(nbytes, (B, T, S), flags)      # held until this graph's backward has run
+    slot, fresh = request_workspace(eng, B, T, S, flags)             # held until this graph's backward has run
     ws = slot["ws"]
     audio = torch.empty((B, S), dtype=torch.float32, device=mel.device)
     ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
@@ -99,19 +97,16 @@ class _InferFn(torch.autograd.Function):
     want_ze = list(need[nm + 2:nm + 2 + ne])
     need_p = list(need[nm + 2 + ne:])
     want_params = ctx.wgrads and any(need_p)
-    poison = os.environ.get("WG_TRAIN_POISON_GRADS") == "1"
-    new = (lambda sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)) if poison else \
-        (lambda sh: torch.empty(sh, dtype=torch.float32, device=dev))
-    g_mel = new((B, M, T)) if want_mel else None
-    g_zi = new(ctx.z_shapes[0]) if want_zi else None
-    g_ze = [new(ctx.z_shapes[1 + i]) if w else None for i, w in enumerate(want_ze)]
+    g_mel = new_grad((B, M, T), dev) if want_mel else None
+    g_zi = new_grad(ctx.z_shapes[0], dev) if want_zi else None
+    g_ze = [new_grad(ctx.z_shapes[1 + i], dev) if w else None for i, w in enumerate(want_ze)]
     ga = g_audio.float().contiguous() if g_audio is not None else torch.zeros((B, 256 * T), dtype=torch.float32, device=dev)
     ze = (C.c_void_p * max(1, ne))(*[(g.data_ptr() if g is not None else None) for g in g_ze])
     stream = torch.cuda.current_stream(dev).cuda_stream
     hp = model._hp
     bufs = GradBuffers(hp.n_channels, hp.n_layers, model.n_flows, hp.n_mel_channels * 8, dev) if want_params else None
     gstruct, _keep = bufs.struct() if want_params else (None, None)
-    flat = None
+    views = None
     try:
       if ctx.wgrads:
         _lib.check(lib.wg_train_infer_backward_params(eng.handle, C.byref(ctx.wts.struct),
@@ -124,27 +119,15 @@ class _InferFn(torch.autograd.Function):
                                                      C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
                                                      _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws),
                                                      ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
-      if want_params:
-        # one gradient per parameter, views of one flat buffer in the canonical order (no logdet term in this direction)
-        sizes = [math.prod(sh) for sh in ctx.shapes]
-        flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-        if poison:
-          flat.fill_(float("nan"))
-        wts = ctx.wts
-        _lib.check(lib.wg_train_param_grads(eng.handle, wts.params, wts.wn, C.byref(gstruct), _ptr(wts.aux), wts.aux.numel(),
-                                            _ptr(flat), C.c_void_p(stream)))
+      if want_params:      # (no logdet term in this direction)
+        views = param_grad_views(eng, ctx.wts, gstruct, ctx.shapes, stream)
     finally:
       ctx.guard.release()
       ctx.wts = None
-    # overflow of the fp16 gradient planes (see infer_differentiable: grad_scale), or inf / nan inputs
-    outs = [t for t in [bufs.flat if want_params else None, g_mel, g_zi] + g_ze if t is not None]
-    sums = [t.sum() for t in outs]
-    model.grad_finite = torch.isfinite(torch.stack(sums)).all() if len(sums) > 1 else torch.isfinite(sums[0])
-    if os.environ.get("WG_TRAIN_CHECK_FINITE") == "1" and not bool(model.grad_finite):
-      raise _lib.WgError(nonfinite_message(ctx.scale))
+    set_grad_finite(model, [bufs.flat if want_params else None, g_mel, g_zi] + g_ze, ctx.scale)
     if not want_params:
       return (None,) * nm + (g_mel, g_zi, *g_ze) + (None,) * ctx.n_params
-    grads = [v.view(sh) if w else None for v, sh, w in zip(flat.split(sizes), ctx.shapes, need_p)]
+    grads = [v if w else None for v, w in zip(views, need_p)]
     return (None,) * nm + (g_mel, g_zi, *g_ze, *grads)
 
 
@@ -169,7 +152,7 @@ def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_ear
   L = T * 256 // model.n_group
   if tuple(z_init.shape) != (B, model.n_remaining_channels, L):
     raise _lib.WgError(f"z_init: expected shape {(B, model.n_remaining_channels, L)}, got {tuple(z_init.shape)}")
-  n_early = sum(1 for k in range(model.n_flows) if k % model.n_early_every == 0 and k > 0)
+  n_early = model.n_early_flows()
   if len(z_early) != n_early or any(tuple(z.shape) != (B, model.n_early_size, L) for z in z_early):
     raise _lib.WgError(f"z_early: expected {n_early} tensors of shape {(B, model.n_early_size, L)}")
   if weight_grads and _ddp_group(model) is not None:

@@ -60,11 +60,6 @@ class WN(nn.Module):
       self.res_skip_layers.append(wn(nn.Conv1d(self.n_channels, rs, 1), name="weight"))
 
 
-def _dense_weight(conv: nn.Module) -> torch.Tensor:
-  """``conv.weight`` -- for a weight-normed module this evaluates g*v/||v|| exactly as torch does."""
-  return conv.weight
-
-
 class _Engine:
   """Owns one wg_handle and the packed device weights derived from a module's parameters."""
 
@@ -237,18 +232,19 @@ class WaveGlow(nn.Module):
 
   # ------------------------------------------------------------------ engine plumbing
   def dense_state(self) -> Dict[str, torch.Tensor]:
-    """Weight-norm-folded tensors under the 470-key names (what remove_weightnorm would leave)."""
+    """Weight-norm-folded tensors under the 470-key names (what remove_weightnorm would leave): ``conv.weight`` of a
+    weight-normed module evaluates g*v/||v|| exactly as torch does."""
     out = {"upsample.weight": self.upsample.weight, "upsample.bias": self.upsample.bias}
     for k in range(self.n_flows):
       out[f"convinv.{k}.conv.weight"] = self.convinv[k].conv.weight
       wn, p = self.WN[k], f"WN.{k}."
       for name, mod in (("start", wn.start), ("cond_layer", wn.cond_layer), ("end", wn.end)):
-        out[p + name + ".weight"] = _dense_weight(mod)
+        out[p + name + ".weight"] = mod.weight
         out[p + name + ".bias"] = mod.bias
       for i in range(wn.n_layers):
-        out[p + f"in_layers.{i}.weight"] = _dense_weight(wn.in_layers[i])
+        out[p + f"in_layers.{i}.weight"] = wn.in_layers[i].weight
         out[p + f"in_layers.{i}.bias"] = wn.in_layers[i].bias
-        out[p + f"res_skip_layers.{i}.weight"] = _dense_weight(wn.res_skip_layers[i])
+        out[p + f"res_skip_layers.{i}.weight"] = wn.res_skip_layers[i].weight
         out[p + f"res_skip_layers.{i}.bias"] = wn.res_skip_layers[i].bias
     return out
 
@@ -263,6 +259,23 @@ class WaveGlow(nn.Module):
         c -= self.n_early_size
       out.append(c)
     return out
+
+  def n_early_flows(self) -> int:
+    """Flows k > 0 with k % n_early_every == 0: channels leave in front of them (model.py:201-203), noise enters in infer."""
+    return sum(1 for k in range(1, self.n_flows) if k % self.n_early_every == 0)
+
+  def _draw_noise(self, spect: torch.Tensor, z_init: Optional[torch.Tensor] = None,
+                  z_early: Optional[List[torch.Tensor]] = None) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """(z_init, z_early) of ``infer`` (model.py:243, :266-268); what is given is kept.  The rest is drawn with the device
+    RNG in the tensor dtype, in the reference's order: [B,n_rem,L], then [B,n_early,L] per early-output flow for descending k."""
+    B, _, T = spect.shape
+    L = T * 256 // self.n_group
+    draw = lambda c: torch.empty((B, c, L), dtype=spect.dtype, device=spect.device).normal_()
+    if z_init is None:
+      z_init = draw(self.n_remaining_channels)
+    if z_early is None:
+      z_early = [draw(self.n_early_size) for _ in range(self.n_early_flows())]
+    return z_init, z_early
 
   def _get_engine(self, device: torch.device, need_weights: bool = True) -> _Engine:
     if device.type != "cuda":
@@ -364,16 +377,8 @@ class WaveGlow(nn.Module):
     return out.clone()
 
   def infer(self, spect: torch.Tensor, sigma: float = 1.0) -> torch.Tensor:
-    """model.py:223-274.  Noise is drawn with the device RNG in the tensor dtype, in the reference's
-    order: [B,n_rem,L], then [B,n_early,L] per early-output flow for descending k."""
-    B, _, T = spect.shape
-    L = T * 256 // self.n_group
-    z_init = torch.empty((B, self.n_remaining_channels, L), dtype=spect.dtype, device=spect.device).normal_()
-    z_early = []
-    for k in reversed(range(self.n_flows)):
-      if k % self.n_early_every == 0 and k > 0:
-        z_early.append(torch.empty((B, self.n_early_size, L), dtype=spect.dtype, device=spect.device).normal_())
-    return self.infer_with_noise(spect, z_init, z_early, sigma)
+    """model.py:223-274, with the noise of ``_draw_noise``."""
+    return self.infer_with_noise(spect, *self._draw_noise(spect), sigma)
 
   def infer_differentiable(self, spect: torch.Tensor, sigma: float = 1.0, z_init: Optional[torch.Tensor] = None,
                            z_early: Optional[List[torch.Tensor]] = None, *, weight_grads: bool = False) -> torch.Tensor:
@@ -392,15 +397,7 @@ class WaveGlow(nn.Module):
     ``model.recompute_activations = True`` keeps the WN layer planes of two flows instead of twelve between this call and
     ``backward()``, which recomputes the others flow by flow (``gradient_workspace_bytes`` gives both sizes): the way to
     take gradients through whole utterances."""
-    B, _, T = spect.shape
-    L = T * 256 // self.n_group
-    if z_init is None:
-      z_init = torch.empty((B, self.n_remaining_channels, L), dtype=spect.dtype, device=spect.device).normal_()
-    if z_early is None:
-      z_early = []
-      for k in reversed(range(self.n_flows)):
-        if k % self.n_early_every == 0 and k > 0:
-          z_early.append(torch.empty((B, self.n_early_size, L), dtype=spect.dtype, device=spect.device).normal_())
+    z_init, z_early = self._draw_noise(spect, z_init, z_early)
     from .infer_grad import infer_differentiable
     return infer_differentiable(self, spect, z_init, list(z_early), sigma, float(getattr(self, "grad_scale", 0.0)),
                                 bool(self.recompute_activations), bool(weight_grads))
@@ -431,11 +428,7 @@ class WaveGlow(nn.Module):
       audio = audio[:, :S].contiguous()
     L = S // self.n_group
     z = torch.empty((B, self.n_group, L), dtype=torch.float32, device=spect.device)
-    log_s, c = [], self.n_group
-    for k in range(self.n_flows):
-      if k % self.n_early_every == 0 and k > 0:
-        c -= self.n_early_size
-      log_s.append(torch.empty((B, c // 2, L), dtype=torch.float32, device=spect.device))
+    log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=spect.device) for c in self.flow_channels()]
     log_det = (C.c_float * self.n_flows)()
     nbytes = eng.lib.wg_forward_workspace_bytes(eng.handle, B, F_, S)
     ws = eng.workspace("fwd", nbytes, (B, F_, S))

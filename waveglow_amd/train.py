@@ -12,8 +12,10 @@ weight-normed parameters).  Everything that touches a weight, an activation or a
 * ``wg_train_param_grads``: packed gradients -> one gradient per parameter (weight-norm backward, the fold's chain rule) in
   ONE flat buffer; autograd gets views of it.
 
-This file is the binding: the autograd node (``_TrainFn``), buffer allocation, the data-parallel schedule.  What is left
-to torch is ``logdet`` of the twelve 1x1 weights (model.py:63) and the optimiser.  ``pack_weights`` /
+This file is the binding: the autograd node (``_TrainFn``), buffer allocation, the data-parallel schedule, and the
+plumbing that ``_TrainFn`` shares with the synthesis direction's node (waveglow_amd/infer_grad.py): ``request_workspace``,
+``new_grad``, ``set_grad_finite``, ``param_grad_views``.  What is left to torch is ``logdet`` of the twelve 1x1 weights
+(model.py:63) and the optimiser.  ``pack_weights`` /
 ``wn_forward_fragments`` / ``plain_fragments`` / ``to_fragments`` are the library's packing written as torch ops -- the
 checker of tests/test_gpu_train.py::test_prepare_matches_torch_packing and tests/test_host_cpu.py, not on the product path.
 
@@ -338,6 +340,44 @@ def enable_data_parallel(model, group=None, force: bool = False) -> bool:
   return True
 
 
+def request_workspace(eng, B: int, n_frames: int, audio_len: int, flags: int) -> Tuple[dict, bool]:
+  """(slot, fresh) of ``_Engine.train_workspace`` for one forward of either direction: the saved state of its graph, of the
+  library's own size for the geometry and the wg_train ``flags``.  The caller hands the slot to a ``_SlotGuard``."""
+  nbytes = eng.lib.wg_train_workspace_bytes_ex(eng.handle, B, n_frames, audio_len, flags)
+  if nbytes == 0:
+    raise _lib.WgError(eng.lib.wg_last_error().decode())
+  return eng.train_workspace(nbytes, (B, n_frames, audio_len), flags)
+
+
+def new_grad(shape, device) -> torch.Tensor:
+  """An fp32 gradient tensor the library fills: not cleared -- every entry is written (GradBuffers names the exception) --
+  or, under WG_TRAIN_POISON_GRADS=1 (tests), NaN first, so an entry the library leaves out cannot go unnoticed."""
+  t = torch.empty(shape, dtype=torch.float32, device=device)
+  return t.fill_(float("nan")) if os.environ.get("WG_TRAIN_POISON_GRADS") == "1" else t
+
+
+def set_grad_finite(model, tensors, scale: float) -> None:
+  """Overflow of the fp16 gradient planes (the automatic scale 2^round(log2 N) assumes a loss normalised by N, the
+  reference's MEAN loss; another normalisation needs model.grad_scale) or inf / nan inputs: every gradient tensor of a
+  backward (None entries aside) is checked, on the device.  model.grad_finite is read by waveglow_amd.training.train()
+  before the optimiser step; WG_TRAIN_CHECK_FINITE=1 raises here (one host sync per step).
+  (one reduction per tensor: inf / nan anywhere makes a sum non-finite, and 8.6e7 finite fp32 values cannot overflow it)"""
+  sums = [t.sum() for t in tensors if t is not None]
+  model.grad_finite = torch.isfinite(torch.stack(sums)).all() if len(sums) > 1 else torch.isfinite(sums[0])
+  if os.environ.get("WG_TRAIN_CHECK_FINITE") == "1" and not bool(model.grad_finite):
+    raise _lib.WgError(nonfinite_message(scale))
+
+
+def param_grad_views(eng, wts, gstruct, shapes, stream) -> List[torch.Tensor]:
+  """Packed gradients (``GradBuffers.struct``) -> one gradient per parameter of ``wts``, in the canonical order: views of
+  ONE flat buffer that ``wg_train_param_grads`` fills (weight-norm backward, the fold's chain rule)."""
+  sizes = [math.prod(sh) for sh in shapes]
+  flat = new_grad(sum(sizes), wts.aux.device)
+  _lib.check(eng.lib.wg_train_param_grads(eng.handle, wts.params, wts.wn, C.byref(gstruct), _ptr(wts.aux), wts.aux.numel(),
+                                          _ptr(flat), C.c_void_p(stream)))
+  return [v.view(sh) for v, sh in zip(flat.split(sizes), shapes)]
+
+
 class GradBuffers:
   """All gradients of one backward pass in ONE flat fp32 buffer, laid out so that everything that becomes final
   with flow k's backward is contiguous (few, large messages -- xGMI rings are per-link bound):
@@ -358,11 +398,8 @@ class GradBuffers:
     self.flow_stride = nl * self.rec + sum(small)
     n_tail = 32 * M8 * 512 + M8
     # Not zero-filled (352 MB per step at 256 channels): the library writes every entry except dw2 / db2 of the last
-    # layer of each flow (no res rows there, model.py:106-110), which are cleared below.  WG_TRAIN_POISON_GRADS=1
-    # (tests) starts from NaN instead, so an entry the library leaves out cannot go unnoticed.
-    self.flat = torch.empty(nf * self.flow_stride + n_tail, dtype=torch.float32, device=device)
-    if os.environ.get("WG_TRAIN_POISON_GRADS") == "1":
-      self.flat.fill_(float("nan"))
+    # layer of each flow (no res rows there, model.py:106-110), which are cleared below.
+    self.flat = new_grad(nf * self.flow_stride + n_tail, device)
     self.regions = [self.flat[k * self.flow_stride:(k + 1) * self.flow_stride] for k in range(nf)]
     self.tail = self.flat[nf * self.flow_stride:]
     st = lambda shape, strides, off: self.flat.as_strided(shape, strides, off)
@@ -446,10 +483,7 @@ class _TrainFn(torch.autograd.Function):
     wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=ctx.needs_input_grad[1])
     z = torch.empty((B, model.n_group, L), dtype=torch.float32, device=mel.device)
     log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=mel.device) for c in flow_c]
-    nbytes = lib.wg_train_workspace_bytes_ex(eng.handle, B, F_, S, flags)
-    if nbytes == 0:
-      raise _lib.WgError(lib.wg_last_error().decode())
-    slot, fresh = eng.train_workspace(nbytes, (B, F_, S), flags)             # held until this graph's backward has run
+    slot, fresh = request_workspace(eng, B, F_, S, flags)                    # held until this graph's backward has run
     ws = slot["ws"]
     ls = (C.c_void_p * len(log_s))(*[t.data_ptr() for t in log_s])
     _lib.check(lib.wg_train_forward_flags(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(audio), _ptr(z), ls, B, F_, S,
@@ -474,12 +508,8 @@ class _TrainFn(torch.autograd.Function):
     hp = model._hp
     want_mel, want_audio = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
     want_params = any(ctx.needs_input_grad[6:])
-    poison = os.environ.get("WG_TRAIN_POISON_GRADS") == "1"
-    # input gradients: every entry is written by the library (NaN first under WG_TRAIN_POISON_GRADS=1, tests)
-    new = (lambda *sh: torch.full(sh, float("nan"), dtype=torch.float32, device=dev)) if poison else \
-        (lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev))
-    g_mel = new(B, hp.n_mel_channels, F_) if want_mel else None
-    g_audio = new(B, S) if want_audio else None
+    g_mel = new_grad((B, hp.n_mel_channels, F_), dev) if want_mel else None
+    g_audio = new_grad((B, S), dev) if want_audio else None
     bufs = GradBuffers(hp.n_channels, hp.n_layers, nf, hp.n_mel_channels * 8, dev) if want_params else None
     gstruct, _keep = bufs.struct() if want_params else (None, None)
     gs_ptr = C.byref(gstruct) if want_params else None
@@ -507,28 +537,13 @@ class _TrainFn(torch.autograd.Function):
                                                   _ptr(ctx.ws), ctx.ws.numel(), k, k, ctx.flags, C.c_void_p(stream)))
       flow_backward_schedule(nf, run_flow, bufs, group)
     ctx.guard.release()
-    # Overflow of the fp16 gradient planes (the automatic scale 2^round(log2 N) assumes the reference's MEAN loss; a
-    # loss with another normalisation needs model.grad_scale) or inf / nan inputs: every gradient tensor is checked,
-    # on the device.  model.grad_finite is read by waveglow_amd.training.train() before the optimiser step;
-    # WG_TRAIN_CHECK_FINITE=1 raises here (one host sync per step).
-    # (one reduction per tensor: inf / nan anywhere makes a sum non-finite, and 8.6e7 finite fp32 values cannot overflow it)
-    sums = [t.sum() for t in (bufs.flat if want_params else None, g_mel, g_audio) if t is not None]
-    model.grad_finite = torch.isfinite(torch.stack(sums)).all() if len(sums) > 1 else torch.isfinite(sums[0])
-    if os.environ.get("WG_TRAIN_CHECK_FINITE") == "1" and not bool(model.grad_finite):
+    try:
+      set_grad_finite(model, (bufs.flat if want_params else None, g_mel, g_audio), ctx.scale)
+    finally:
       ctx.wts = None
-      raise _lib.WgError(nonfinite_message(ctx.scale))
-    ctx.wts = None
     if not want_params:
       return (None, g_mel, g_audio, None, None, None, *([None] * len(ctx.shapes)))
-    # one gradient per parameter, views of one flat buffer in the canonical order
-    sizes = [math.prod(sh) for sh in ctx.shapes]
-    flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-    if poison:
-      flat.fill_(float("nan"))
-    _lib.check(lib.wg_train_param_grads(eng.handle, wts.params, wts.wn, C.byref(gstruct), _ptr(wts.aux), wts.aux.numel(),
-                                        _ptr(flat), C.c_void_p(stream)))
-    grads = [v.view(sh) for v, sh in zip(flat.split(sizes), ctx.shapes)]
-    return (None, g_mel, g_audio, None, None, None, *grads)
+    return (None, g_mel, g_audio, None, None, None, *param_grad_views(eng, wts, gstruct, ctx.shapes, stream))
 
 
 def nonfinite_message(scale: float) -> str:
