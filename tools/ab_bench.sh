@@ -1,11 +1,11 @@
 #!/bin/bash
 # A/B two builds of the library on ONE box, interleaved (rule 24): tools/ab_bench.sh "<-D flags of variant B>" [bench args]
 # A = the in-tree library, B = the same sources with the extra flags.  Prints ms/step + avg wn_layer launch per run.
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd $(dirname $0)/.. && pwd)
 FLAGS=$1; shift
 LIB=$ROOT/gpurun_out/lib_variantB.so
 mkdir -p $ROOT/gpurun_out
-(cd $ROOT/waveglow_amd/csrc && hipcc -O3 --offload-arch=gfx950 -std=c++17 -shared -fPIC -Wno-unused-value $FLAGS -o $LIB kernels.hip stft.hip train.hip train_prep.hip api.cpp stft_api.cpp train_api.cpp) || exit 1
+(cd $ROOT && python -m waveglow_amd.build -o $LIB $FLAGS) || exit 1
 for round in 1 2 3; do
   for v in A B; do
     if [ $v = A ]; then unset WAVEGLOW_AMD_LIB; else export WAVEGLOW_AMD_LIB=$LIB; fi

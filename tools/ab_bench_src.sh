@@ -1,11 +1,14 @@
 #!/bin/bash
-# A/B the in-tree library (A) against a build of another source directory (B) on ONE box, interleaved.
-# usage: tools/ab_bench_src.sh <dir with the csrc of variant B> [bench args]
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+# A/B the in-tree library (A) against a build of another checkout of this repository (B) on ONE box, interleaved.
+# usage: tools/ab_bench_src.sh <root of the checkout of variant B> [bench args]     (B is built by its own waveglow_amd.build,
+# which has the command line from the commit that removed the ablation switches on; an older checkout builds nothing and is refused)
+ROOT=$(cd $(dirname $0)/.. && pwd)
 SRC=$1; shift
 LIB=$ROOT/gpurun_out/lib_variantB.so
 mkdir -p $ROOT/gpurun_out
-(cd $SRC && hipcc -O3 --offload-arch=gfx950 -std=c++17 -shared -fPIC -Wno-unused-value -o $LIB kernels.hip stft.hip train.hip train_prep.hip api.cpp stft_api.cpp train_api.cpp) || exit 1
+rm -f $LIB
+(cd $SRC && python -m waveglow_amd.build -o $LIB) || exit 1
+[ -f $LIB ] || { echo "$SRC: python -m waveglow_amd.build built no library (a checkout without the build command line?)"; exit 1; }
 for round in 1 2 3; do
   for v in A B; do
     if [ $v = A ]; then unset WAVEGLOW_AMD_LIB; else export WAVEGLOW_AMD_LIB=$LIB; fi

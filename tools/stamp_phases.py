@@ -11,21 +11,23 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-csrc = os.path.join(ROOT, "waveglow_amd", "csrc")
-lib = os.path.join(ROOT, "gpurun_out", "libwaveglow_amd_stamps.so")
-os.makedirs(os.path.dirname(lib), exist_ok=True)
-extra = [f for f in sys.argv[2:] if f.startswith("-D") and f != "-DNONE"]
-if os.environ.get("WG_STAMP_LIB"):          # prebuilt with tools/build_variant.sh <name> "-DWG_STAMPS ..."
+# waveglow_amd._lib reads WAVEGLOW_AMD_LIB when the package is first imported: the variant is built in a child process and the
+# variable is set before anything of the package is imported here
+if os.environ.get("WG_STAMP_LIB"):          # prebuilt with tools/build_variant.sh <name> "-DWG_STAMPS"
   lib = os.path.abspath(os.environ["WG_STAMP_LIB"])
 else:
-  subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value",
-                  "-DWG_STAMPS"] + extra + ["-o", lib, "kernels.hip", "stft.hip", "train.hip", "train_prep.hip", "api.cpp", "stft_api.cpp", "train_api.cpp"], cwd=csrc, check=True)
+  lib = os.path.join(ROOT, "build_variants", "libwaveglow_amd_stamps.so")
+  os.makedirs(os.path.dirname(lib), exist_ok=True)
+  subprocess.run([sys.executable, "-m", "waveglow_amd.build", "-o", lib, "-DWG_STAMPS"], cwd=ROOT, check=True)
 os.environ["WAVEGLOW_AMD_LIB"] = lib
 
 import torch  # noqa: E402
 from waveglow_amd import synthetic  # noqa: E402
 from waveglow_amd.hparams import HParams  # noqa: E402
 from waveglow_amd.model import WaveGlow  # noqa: E402
+from waveglow_amd import _lib  # noqa: E402
+
+assert _lib.LIB_PATH == lib, (_lib.LIB_PATH, lib)
 
 C = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 B, T = (16, 864)
@@ -53,6 +55,8 @@ with torch.no_grad():
   m.infer(mel, 0.6)
   torch.cuda.synchronize()
 st = buf.view(n_tiles, 8).cpu().double()
+if not bool((st != 0).any()):
+  sys.exit(f"no stamp was written: {_lib.LIB_PATH} is not a -DWG_STAMPS build")
 if os.environ.get("WG_STAMP_LAYOUT", "pipe") == "pipe":
   # pipelined epilogue: stamps 0 top, 1 K loop start, 2 K loop end, 3 / 5 / 6 / 7 end of phases 0..3, 4 end of the last phase
   order = [0, 1, 2, 3, 5, 6, 7, 4]

@@ -1,25 +1,17 @@
 // Host side of libwaveglow_amd: C ABI (include/waveglow_amd.h), weight packing, launch sequencing.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <string>
-#include <vector>
 
-#include "../../include/waveglow_amd.h"
-#include "wg_common.h"
+#include "wg_host.h"
 
 using namespace wg;
 
 namespace {
-
 thread_local std::string g_err;
+}
 
-int fail(int code, const char* fmt, ...) {
+int wg::fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -29,18 +21,7 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) return fail(WG_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
-  } while (0)
-
-struct HostTensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-};
-
-size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+namespace {
 
 // fp64 Gauss-Jordan inverse with partial pivoting; also log|det| and sign.
 bool invert(const std::vector<double>& A, int n, std::vector<double>& inv, double& logabsdet, int& sign) {
@@ -85,95 +66,23 @@ bool invert(const std::vector<double>& A, int n, std::vector<double>& inv, doubl
 constexpr float kTanhScale = 2.8853900817779268f;    // 2*log2(e)
 constexpr float kSigmScale = -1.4426950408889634f;   // -log2(e)
 
-struct LayerOffsets {
-  size_t wA1, bias1, wA2, bias2, wEs;
-  size_t wA1f = 0;   // layer 0 only: in_layers[0] o start folded onto the a0 plane, one gathered K-step ([tap][8] along K)
-  size_t wA1x = 0, wA1fx = 0;   // the same two as 16x16x32 fragments (wn_frag16: the 128-column tile's K loop)
-};
-struct FlowOffsets {
-  std::vector<LayerOffsets> layers;
-  size_t wstart, bstart, out_init, winv, wfwd;
-  size_t wStA = 0;   // start weights as the A fragment of the first layer's residual step (wn_res_a0)
-  int c, h;
-  double logdet;   // log|det W_k|, NaN when det < 0 (torch.logdet semantics, model.py:63)
-};
-
-}  // namespace
-
-struct wg_handle {
-  wg_config cfg;
-  int device;
-  int NS;                 // n_mel * n_group
-  std::vector<int> c_k;   // remaining channels per flow (model.py:160-176)
-  std::vector<std::string> expected;
-  std::map<std::string, HostTensor> tensors;
-  bool finalized = false;
-  char* d_blob = nullptr;
-  size_t blob_bytes = 0;
-  char* d_cond = nullptr;   // derived: folded cond_layer o upsample A fragments [flow][layer][phase]...
-  char* d_cond16 = nullptr; // ... as 16x16x32 fragments (wn_frag16), same sizes
-  size_t cond_layer_bytes = 0, cond_flow_bytes = 0;
-  std::vector<FlowOffsets> flows;
-  int n_cu = 256;         // multiProcessorCount, read in wg_finalize
-  int force_bn = 0;       // WG_FORCE_BN=64|128 (tests): pin the WN tile width instead of choosing by workload size
-  bool fold_start = true; // WG_NO_START_FOLD=1 (tests / A-B runs): first WN layer reads x_0 like every other layer
-  unsigned long long* dbg_stamps = nullptr;   // diagnostic builds only
-  // profiling
-  bool prof = false;
-  unsigned prof_mask = ~0u;
-  std::vector<hipEvent_t> ev;
-  std::vector<int> ev_class;
-  size_t ev_used = 0;
-  double prof_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int64_t prof_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // library-owned streams of the training direction (independent chains of one call run side by side, joined back into
-  // the caller's stream before the call returns) and a ring of ordering events for them
-  hipStream_t aux[3] = {nullptr, nullptr, nullptr};
-  std::vector<hipEvent_t> sync_ev;
-  size_t sync_next = 0;
-  // events of wg_train_backward's long-lived marks (recorded on one stream, waited on one or two flows later): a pool of
-  // their own, one event per role, so that no number of ring events consumed in between can re-record one under a wait
-  hipEvent_t mark_ev[16] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // pinned staging buffers for small host -> device table uploads (wg_train_prepare / wg_train_param_grads): a rotating set,
-  // each guarded by an event recorded behind its copy, so a buffer is never rewritten while a copy out of it is pending
-  static constexpr int kPins = 4;
-  void* pin[kPins] = {nullptr, nullptr, nullptr, nullptr};
-  size_t pin_bytes[kPins] = {0, 0, 0, 0};
-  hipEvent_t pin_ev[kPins] = {nullptr, nullptr, nullptr, nullptr};
-  int pin_next = 0;
-};
-
-namespace {
+// fp16 hi / lo split of a weight (v ~ hi + lo): the two parts ride as two rows / lane halves of one fp16 MFMA operand.
+// hi is v rounded ONCE to fp16 (written as one conversion from double: hipcc merges a double -> float -> fp16 chain into it
+// in some contexts and not in others, so spelling the chain would make the packed bits depend on the surrounding code); lo
+// is what fp32 has left.
+_Float16 f16_split(double v, bool lo_part) {
+  const _Float16 hi = (_Float16)v;
+  return lo_part ? (_Float16)((float)v - (float)hi) : hi;
+}
 
 std::vector<int> flow_channels(const wg_config& c) {
   std::vector<int> out;
   int rem = c.n_group;
   for (int k = 0; k < c.n_flows; ++k) {
-    if (k % c.n_early_every == 0 && k > 0) rem -= c.n_early_size;
+    if (is_early(c, k)) rem -= c.n_early_size;
     out.push_back(rem);
   }
   return out;
-}
-
-bool is_early(const wg_config& c, int k) { return k % c.n_early_every == 0 && k > 0; }
-
-RowGeom make_geom(const wg_config& c, int B, int L, int T) {
-  RowGeom g;
-  g.frames = nullptr;
-  g.B = B;
-  g.L = L;
-  g.F = (L + kPhases - 1) / kPhases;
-  // guard frames: a dilated tap reaches (phase + dilation) >> 5 frames past an utterance's ends; dilation <= 2^(n_layers-1)
-  // (model.py:97): 4 frames up to 8 layers, 8 / 16 for 9 / 10 layers
-  const int max_dil = 1 << (c.n_layers - 1);
-  g.Gf = (kPhases - 1 + max_dil) / kPhases;
-  if (g.Gf < 4) g.Gf = 4;
-  g.Fp = g.Gf + g.F + g.Gf;
-  g.Rp = (B * g.Fp + 127) / 128 * 128;
-  g.R = kPhases * g.Rp + 2 * kRowPad;
-  g.T = T;
-  return g;
 }
 
 struct Workspace {
@@ -205,8 +114,7 @@ const HostTensor* find(const wg_handle* h, const std::string& name) {
   return it == h->tensors.end() ? nullptr : &it->second;
 }
 
-// WG_DEBUG_SYNC=1: synchronise after every launch and name it on stderr (fault localisation only)
-static bool dbg_sync() { static int v = -1; if (v < 0) { const char* e = getenv("WG_DEBUG_SYNC"); v = e && *e == '1'; } return v == 1; }
+// WG_DEBUG_SYNC=1 (dbg_sync): synchronise after every launch and name it on stderr
 #define WG_DBG(stream, what) do { if (dbg_sync()) { hipError_t _e = hipStreamSynchronize(stream); fprintf(stderr, "[wg] %s -> %s\n", what, hipGetErrorString(_e)); fflush(stderr); } } while (0)
 
 struct Prof {
@@ -235,19 +143,7 @@ struct Prof {
 
 namespace wg { extern unsigned long long* g_wgrad_stamps; }   // train.hip
 
-int wg_set_error(int code, const char* msg) { return fail(code, "%s", msg); }
-
-// accessors for the other translation units of the library (train_api.cpp)
-const wg_config* wg_internal_config(const wg_handle* h) { return h ? &h->cfg : nullptr; }
-const int* wg_internal_flow_channels(const wg_handle* h) { return h ? h->c_k.data() : nullptr; }
-int wg_internal_device(const wg_handle* h) { return h ? h->device : -1; }
-int wg_internal_n_cu(const wg_handle* h) { return h ? h->n_cu : 256; }   // of the HANDLE's device (wg_create)
-wg::RowGeom wg_internal_geom(const wg_handle* h, int B, int L, int T) { return make_geom(h->cfg, B, L, T); }
-// W_k^-1 of the finalised handle on the device (fp32 of the fp64 inverse, the matrix wg_infer uses), null before wg_finalize
-const float* wg_internal_winv(const wg_handle* h, int k) {
-  if (!h || !h->finalized || k < 0 || k >= (int)h->flows.size()) return nullptr;
-  return (const float*)(h->d_blob + h->flows[k].winv);
-}
+// ---- services of the handle for the other translation units (prototypes in wg_host.h)
 // one profiling event of class cls on stream s (a no-op unless wg_profile_enable is on); events come in begin/end pairs
 void wg_internal_prof_event(wg_handle* h, void* s, int cls) {
   if (!h || !h->prof || !((h->prof_mask >> cls) & 1u)) return;
@@ -434,22 +330,45 @@ static int check_shape(const wg_handle* h, const std::string& name, std::initial
   return WG_OK;
 }
 
-int wg_finalize(wg_handle* h) {
-  if (!h) return fail(WG_ERR_INVALID, "null handle");
+// wg_finalize, first half: checks the tensors and packs every host-packed weight into `blob` (pure host arithmetic; the
+// offsets go to h->flows)
+static int build_blob(wg_handle* h, std::vector<char>& blob) {
   const wg_config& c = h->cfg;
   const int C = c.n_channels, M = c.n_mel_channels, NS = h->NS, NL = c.n_layers;
   const int NW = wn_waves(C), MB = C / (32 * NW), MT = 2 * MB, CC = C / 64, K2 = C / 16, nKx = 3 * CC;
-  std::vector<char> blob;
   auto reserve = [&](size_t bytes) {
     size_t off = align_up(blob.size());
     blob.resize(off + bytes, 0);
     return off;
   };
   int rc;
-  // ---- upsample weights: folded into the conditioning GEMM on the device below (cond_fold_kernel)
+  // ---- upsample weights: folded into the conditioning GEMM on the device (finalize_device: cond_fold_kernel)
   const HostTensor *upw, *upb;
   if ((rc = check_shape(h, "upsample.weight", {M, M, c.upsample_kernel}, &upw))) return rc;
   if ((rc = check_shape(h, "upsample.bias", {M}, &upb))) return rc;
+  // GEMM-1 A fragments of the 32x32x16 MFMA, [half K-step u][NW][MT][2 k16][64 lanes][8]; wave w owns 32-channel blocks
+  // w*MB .. w*MB+MB-1: M-tiles mt < MB are their tanh rows, mt >= MB their sigmoid rows (+C).  value(m, ksx, kk) is the
+  // unscaled weight of row m at K index kk of K-step ksx (a double is scaled in double and rounded once to fp16, see
+  // f16_split); K indices from k_live up carry no weight and stay zero.
+  auto pack32 = [&](size_t off, int n_half, int k_live, auto&& value) {
+    _Float16* dst = (_Float16*)(blob.data() + off);
+    for (int u = 0; u < n_half; ++u)
+      for (int w = 0; w < NW; ++w)
+        for (int mt = 0; mt < MT; ++mt)
+          for (int k2 = 0; k2 < 2; ++k2)
+            for (int lane = 0; lane < 64; ++lane) {
+              const int ksx = u >> 1, k16 = (u & 1) * 2 + k2;
+              const int r = lane & 31, hh = lane >> 5;
+              const bool tanh_row = mt < MB;
+              const int m = (tanh_row ? 0 : C) + 32 * (w * MB + (tanh_row ? mt : mt - MB)) + r;
+              const float rs = tanh_row ? kTanhScale : kSigmScale;   // gate pre-scale (kernels.hip gate_act)
+              _Float16* d = dst + (((((size_t)u * NW + w) * MT + mt) * 2 + k2) * 64 + lane) * 8;
+              for (int j = 0; j < 8; ++j) {
+                const int kk = k16 * 16 + 8 * hh + j;
+                if (kk < k_live) d[j] = (_Float16)(value(m, ksx, kk) * rs);
+              }
+            }
+  };
   h->flows.assign(c.n_flows, FlowOffsets());
   for (int k = 0; k < c.n_flows; ++k) {
     FlowOffsets& fo = h->flows[k];
@@ -505,8 +424,7 @@ int wg_finalize(wg_handle* h) {
           const int ch = 32 * w + (lane & 31);
           for (int j = 0; j < 8; ++j) {
             const float v = j < hk ? wst->data[(size_t)ch * hk + j] : j == 4 ? bst->data[ch] : 0.0f;
-            const _Float16 hi = (_Float16)v;
-            d[((size_t)w * 64 + lane) * 8 + j] = lane < 32 ? hi : (_Float16)(v - (float)hi);
+            d[((size_t)w * 64 + lane) * 8 + j] = f16_split(v, lane >= 32);
           }
         }
     }
@@ -523,30 +441,13 @@ int wg_finalize(wg_handle* h) {
       if ((rc = check_shape(h, p + "in_layers." + is + ".bias", {2 * C}, &bin))) return rc;
       if ((rc = check_shape(h, p + "res_skip_layers." + is + ".weight", {RS, C, 1}, &wrs))) return rc;
       if ((rc = check_shape(h, p + "res_skip_layers." + is + ".bias", {RS}, &brs))) return rc;
-      // GEMM1 tap A fragments [2*3C/64 half K-steps][NW][MT][2 k16][64 lanes][8]; wave w owns 32-channel blocks
-      // w*MB .. w*MB+MB-1: M-tiles mt < MB are their tanh rows, mt >= MB their sigmoid rows (+C)
+      // the three taps: K-step ksx = (tap, 64-channel chunk), K index kk = position inside the chunk
+      auto tap_weight = [&](int m, int ksx, int kk) {
+        const int tap = ksx / CC, cc = ksx % CC;
+        return win->data[((size_t)m * C + pos_to_chan(cc * 64 + kk)) * 3 + tap];
+      };
       lo.wA1 = reserve((size_t)nKx * 2 * NW * MT * 2 * 64 * 8 * 2);
-      {
-        _Float16* dst = (_Float16*)(blob.data() + lo.wA1);
-        for (int u = 0; u < 2 * nKx; ++u)
-          for (int w = 0; w < NW; ++w)
-            for (int mt = 0; mt < MT; ++mt)
-              for (int k2 = 0; k2 < 2; ++k2)
-                for (int lane = 0; lane < 64; ++lane) {
-                  const int ksx = u >> 1, k16 = (u & 1) * 2 + k2;
-                  const int r = lane & 31, hh = lane >> 5;
-                  const bool tanh_row = mt < MB;
-                  const int m = (tanh_row ? 0 : C) + 32 * (w * MB + (tanh_row ? mt : mt - MB)) + r;
-                  const float rs = tanh_row ? kTanhScale : kSigmScale;   // gate pre-scale (kernels.hip gate_act)
-                  _Float16* d = dst + (((((size_t)u * NW + w) * MT + mt) * 2 + k2) * 64 + lane) * 8;
-                  for (int j = 0; j < 8; ++j) {
-                    const int kk = k16 * 16 + 8 * hh + j;
-                    const int tap = ksx / CC, cc = ksx % CC;
-                    const int ch = pos_to_chan(cc * 64 + kk);
-                    d[j] = (_Float16)(win->data[((size_t)m * C + ch) * 3 + tap] * rs);
-                  }
-                }
-      }
+      pack32(lo.wA1, 2 * nKx, 64, tap_weight);
       const bool f16 = wn_frag16(C, wn_block_n(C));
       // 16x16x32 fragments [half K-step u][wave][tile m][64 lanes = (row i = lane & 15, K group lane >> 4)][8]: tile m of
       // wave w = rows 32 w + 16 (m & 1) + i of the tanh (m < 2) / sigmoid half; K = 32 (u & 1) + 8 (lane >> 4) + j of the step
@@ -564,10 +465,7 @@ int wg_finalize(wg_handle* h) {
       };
       if (f16) {
         lo.wA1x = reserve((size_t)nKx * 2 * NW * 4 * 64 * 8 * 2);
-        pack16(lo.wA1x, 2 * nKx, [&](int m, int ksx, int kk) {
-          const int tap = ksx / CC, cc = ksx % CC;
-          return win->data[((size_t)m * C + pos_to_chan(cc * 64 + kk)) * 3 + tap];
-        });
+        pack16(lo.wA1x, 2 * nKx, tap_weight);
       }
       if (i == 0) {
         // in_layers[0] o start (model.py:117, :123): column kk of tap `tap` on the a0 plane row (a0 | 1 | 0...):
@@ -585,23 +483,7 @@ int wg_finalize(wg_handle* h) {
         // ONE K-step for the three taps (wn_layer_kernel A0G): K index kk = 8 tap + j against a B tile whose 16-byte chunk
         // `tap` is the first chunk (a0 | 1 | 0 0 0) of that tap's a0-plane row
         lo.wA1f = reserve((size_t)2 * NW * MT * 2 * 64 * 8 * 2);
-        _Float16* dst = (_Float16*)(blob.data() + lo.wA1f);
-        for (int u = 0; u < 2; ++u)
-          for (int w = 0; w < NW; ++w)
-            for (int mt = 0; mt < MT; ++mt)
-              for (int k2 = 0; k2 < 2; ++k2)
-                for (int lane = 0; lane < 64; ++lane) {
-                  const int k16 = u * 2 + k2;
-                  const int r = lane & 31, hh = lane >> 5;
-                  const bool tanh_row = mt < MB;
-                  const int m = (tanh_row ? 0 : C) + 32 * (w * MB + (tanh_row ? mt : mt - MB)) + r;
-                  const float rs = tanh_row ? kTanhScale : kSigmScale;
-                  _Float16* d = dst + (((((size_t)u * NW + w) * MT + mt) * 2 + k2) * 64 + lane) * 8;
-                  for (int j = 0; j < 8; ++j) {
-                    const int kk = k16 * 16 + 8 * hh + j;          // 8 tap + value index of the gathered tile row
-                    d[j] = (_Float16)(kk < 24 ? (float)(fold[((size_t)m * 3 + (kk >> 3)) * 8 + (kk & 7)] * rs) : 0.0f);
-                  }
-                }
+        pack32(lo.wA1f, 2, 24, [&](int m, int, int kk) { return fold[((size_t)m * 3 + (kk >> 3)) * 8 + (kk & 7)]; });
         if (f16) {
           lo.wA1fx = reserve((size_t)2 * NW * 4 * 64 * 8 * 2);
           pack16(lo.wA1fx, 2, [&](int m, int, int kk) { return kk < 24 ? (float)fold[((size_t)m * 3 + (kk >> 3)) * 8 + (kk & 7)] : 0.0f; });
@@ -657,10 +539,7 @@ int wg_finalize(wg_handle* h) {
             const int row = lane & 15, l4 = lane >> 4;
             for (int j = 0; j < 8; ++j) {
               const int ch = pos_to_chan(32 * s + 8 * l4 + j);
-              const float v = (float)Wes[(size_t)(row & 7) * C + ch];
-              const _Float16 hi = (_Float16)v;
-              const _Float16 lo16 = (_Float16)(v - (float)hi);
-              dst[((size_t)s * 64 + lane) * 8 + j] = row < 8 ? hi : lo16;
+              dst[((size_t)s * 64 + lane) * 8 + j] = f16_split(Wes[(size_t)(row & 7) * C + ch], row >= 8);
             }
           }
       }
@@ -671,11 +550,16 @@ int wg_finalize(wg_handle* h) {
       for (int r = 0; r < 8; ++r) oi[r] = (float)out_bias[r];
     }
   }
-  // the library works on h->device without changing the caller's current device for good
-  struct DeviceGuard {
-    int prev = -1;
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  } dev_guard;
+  return WG_OK;
+}
+
+// wg_finalize, second half: the blob goes to the device, and cond_layer o upsample is folded there, flow by flow
+static int finalize_device(wg_handle* h, const std::vector<char>& blob) {
+  const wg_config& c = h->cfg;
+  const int C = c.n_channels, M = c.n_mel_channels, NS = h->NS, NL = c.n_layers;
+  const int NW = wn_waves(C), MT = 2 * (C / (32 * NW));
+  const HostTensor* upw = find(h, "upsample.weight");
+  DeviceGuard dev_guard;
   HIP_TRY(hipGetDevice(&dev_guard.prev));
   HIP_TRY(hipSetDevice(h->device));
   {
@@ -727,6 +611,13 @@ int wg_finalize(wg_handle* h) {
   }
   h->finalized = true;
   return WG_OK;
+}
+
+int wg_finalize(wg_handle* h) {
+  if (!h) return fail(WG_ERR_INVALID, "null handle");
+  std::vector<char> blob;
+  const int rc = build_blob(h, blob);
+  return rc != WG_OK ? rc : finalize_device(h, blob);
 }
 
 size_t wg_infer_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames) {
@@ -817,8 +708,7 @@ int wg_infer_ragged(wg_handle* h, const void* mel, const int32_t* frames, const 
   if (B < 1 || n_frames < 1) return fail(WG_ERR_INVALID, "bad B/n_frames");
   if (io_dtype != WG_F32 && io_dtype != WG_F16) return fail(WG_ERR_INVALID, "bad io_dtype");
   const wg_config& c = h->cfg;
-  int n_early = 0;
-  for (int k = 0; k < c.n_flows; ++k) n_early += is_early(c, k);
+  const int n_early = n_early_flows(c);
   if (n_z_early != n_early || (n_early && !z_early)) return fail(WG_ERR_INVALID, "expected %d early-noise tensors", n_early);
   const int L = n_frames * c.upsample_stride / c.n_group;
   if ((int64_t)B * L * 8 >= (1ll << 31)) return fail(WG_ERR_INVALID, "batch too large for 32-bit row indexing");

@@ -91,76 +91,27 @@ __device__ __forceinline__ void gload16(half8& dst, const void* sbase, unsigned 
 #define WG_STAMP(i) do {} while (0)
 #endif
 
-constexpr bool kPersistent = true;    // cross-tile prefetch inside a workgroup (see the tile loop of wn_layer_kernel)
-#ifdef WG_DBG_NO_XTILE_DMA
-constexpr bool kXTileDMA = false;
-#else
-constexpr bool kXTileDMA = kPersistent;
-#endif
+// Cross-tile prefetch inside a workgroup: see the tile loop of wn_layer_kernel.
 // (The next tile's A fragments are NOT prefetched under the epilogue: between such an inline-asm load and its
 // wait lies a long stretch of compiler-scheduled code, and hipcc moved the still-in-flight destination registers
 // there -- wrong results.  They are loaded at the tile top: ~1 L2 latency exposed per tile.)
 constexpr int kTilesPerWG = 2;        // tiles per workgroup (template TPW), fully unrolled; 1 for small workloads
-#ifdef WG_NO_PIPE_EPI
-constexpr bool kPipeEpi = false;      // A/B builds: the round-1 epilogue (gate, barrier, GEMM 2, end x skip, stores in sequence)
-#else
-constexpr bool kPipeEpi = true;       // gate of column chunk c overlapped with GEMM 2 of chunk c-1 (see "pipelined epilogue")
-#endif
 // Tried and measured slower on MI355X, kept out of the source: staging B tiles global -> VGPR -> ds_write instead
 // of LDS-DMA (K loop 59.3k vs 57.6k cycles per tile); offsetting the VMEM slots of the two waves of a SIMD
 // (two copies of the loop made hipcc spill).
 
 // Alternating issue priority in the K loop.  The SIMD arbiter favours the older of its two waves: one wave runs a whole
 // K-step ahead of its partner, then idles at the barrier while the partner finishes alone with its load-issue stalls
-// uncovered (with the barrier removed, wave 0 is through the K loop in 28 k cycles and its partner in 44 k).  With kPrio the
+// uncovered (with the barrier removed, wave 0 is through the K loop in 28 k cycles and its partner in 44 k).  With PRIO the
 // two waves of a SIMD take turns at s_setprio 1: waves 4-7 during the deferred sub-step and sub-step 0, waves 0-3 during
 // sub-steps 1 and 2.  Same-box A/B: +0.4 ... +1.2 % on the inference kernel (box dependent), -0.4 ms on the training
 // forward.  Measured and dropped: the other phase (-1.1 %), either group always ahead (-0.1 / -0.3 %), a 1/4 : 3/4 split
 // (-0.4 %); switches in front of sub-step 2 (quarters, 3/4 : 1/4) and any switch in the first-layer variant make hipcc spill.
-#ifdef WG_NO_PRIO
-constexpr bool kPrio = false;         // A/B builds
-#else
-constexpr bool kPrio = true;
-#endif
+// (The priority alternation in the backward dgrad variants: no measurable change, left out.)
 // (Also measured and dropped, round 2: waves 4-7 sleeping 64-192 cycles after every K-loop barrier to de-phase the two
 // groups' loads: -0.5 %; the GEMM-2 weight fragments fetched inside the last K-step instead of phase 0 of the epilogue:
 // phase 0 -1.2 k cycles, K loop +0.9 k, +-0.1 % end to end; both waves' loads moved to different slots by branches inside
 // the load statements: the "+v" ties make hipcc copy fragment registers, and the K loop spills.)
-// q[2] of a K-step is fetched in the load-free slots of the step's own deferred sub-step (behind the DMA pieces) instead of
-// as two loads back to back at the end of the step before, where nothing covers their issue; the step then ends with the
-// counted wait and the barrier alone.  Same-box A/B +0.25 % (0.6143 -> 0.6158), training neutral.
-#ifdef WG_NO_TILE_INTERLEAVE
-constexpr bool kTileInterleave = false;   // A/B builds
-#else
-constexpr bool kTileInterleave = true;
-#endif
-#ifdef WG_NO_Q2_LATE
-constexpr bool kQ2Late = false;       // A/B builds
-#else
-constexpr bool kQ2Late = true;
-#endif
-// DEEP rings: quarter 2 of step ks+1 is fetched in the last slot of step ks's deferred sub-step (its ring slot was freed in
-// sub-step 2 of step ks-1) instead of as two uncovered loads at the end of step ks-1 (-0.3 % on configs[0], same-box).
-#ifdef WG_NO_DEEP_Q2
-constexpr bool kDeepQ2 = false;       // A/B builds
-#else
-constexpr bool kDeepQ2 = true;
-#endif
-// The folded end x skip weight fragments (hi + lo rows, C/32 KiB) are the same for every wave and every tile of a launch:
-// they are staged in LDS once per workgroup and read from there right before their MFMAs, instead of C/32 global 1-KiB
-// loads per wave and tile (8 x redundant through the vector memory path).  Same-box A/B: fetching them one per two slots
-// of the second-to-last phase instead of as a burst gave +0.5 %, the LDS copy another +0.25 % (0.6180 -> 0.6195).
-// (The priority alternation in the backward dgrad variants: no measurable change, left out.)
-#ifdef WG_NO_WES_LDS
-constexpr bool kWesLds = false;       // A/B builds: global loads at the top of the second-to-last phase
-#else
-constexpr bool kWesLds = true;
-#endif
-#ifdef WG_NO_DEEP
-constexpr bool kDeep = false;         // A/B builds: the one-step ring for small workloads too
-#else
-constexpr bool kDeep = true;
-#endif
 
 // 16x16x32 MFMA of the M16 K loop.  (Measured: the same instruction as an asm statement accumulating in place -- hipcc
 // cannot then give a result a fresh destination tuple -- -0.16 % same-box, and hipcc no longer sees the MFMA hazards.)
@@ -229,7 +180,10 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
   constexpr int NAH = MT * 2;            // A fragments per half K-step (packing unit)
   constexpr bool DEFER = (MB == 1);      // defer a step's last sub-step past the barrier (needs spare registers)
   static_assert(BN * 8 % NTHREADS == 0 && MB >= 1 && MB <= 2 && NKX >= 1 && (NTAPS == 1 || NTAPS == 3), "tile geometry");
-  constexpr bool Q2L = !M16 && kQ2Late && DEFER && !DEEP && (NG + NT - 1) / NT == 1 && NT >= NG + MT;   // free slots behind the DMA pieces
+  // q[2] of a K-step is fetched in the load-free slots of the step's own deferred sub-step (behind the DMA pieces) instead of
+  // as two loads back to back at the end of the step before, where nothing covers their issue; the step then ends with the
+  // counted wait and the barrier alone.  Same-box A/B +0.25 % (0.6143 -> 0.6158), training neutral.
+  constexpr bool Q2L = !M16 && DEFER && !DEEP && (NG + NT - 1) / NT == 1 && NT >= NG + MT;   // free slots behind the DMA pieces
   // M16: GEMM 1 on 16x16x32 MFMAs (same tile, same loads, same FLOPs per K-step; the matrix pipe holds a higher clock on
   // them -- DESIGN.md section 3).  A K-step is two 32-deep sub-steps s; quarter g = (s = g >> 1, column half g & 1) runs
   // the wave's four 16-row tiles m (tanh rows 0-15, 16-31, sigmoid rows 0-15, 16-31 of its channel block) against the
@@ -310,7 +264,6 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     return (unsigned)(((mrow[i] - j) * M + (k0 - j * M)) * 2);
   };
   auto stage_B_piece = [&](int p, int jt, int ks, int bufsel, int i) {
-#ifndef WG_DBG_NO_DMA
     const unsigned lds = __builtin_amdgcn_readfirstlane(sB_addr + bufsel * BT_BYTES + (i * NTHREADS + wave * 64) * 16);
     if constexpr (A0G) {
       if (ks < NKX) {
@@ -324,12 +277,8 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     if (ks < NKX) glds16(xstep_src(p, jt, ks), pvoff[i], lds);
     else if constexpr (MODE != 0) glds16(sp_src(p, jt, ks - NKX), pvoff[i], lds);
     else glds16(a.melT, cond_voff(ks - NKX, i), lds);
-#endif
   };
   auto read_B = [&](const char* buf, int nt, int k16) -> half8 {
-#ifdef WG_DBG_NO_LDSREAD
-    half8 z; asm volatile("" : "=v"(z)); return z;
-#endif
     const int n = nt * 32 + ln;
     const int c = (k16 * 2 + lh) ^ swB;
     return *(const half8*)(buf + n * 128 + c * 16);
@@ -348,21 +297,13 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     const char* base = ks < NKX ? (const char*)a.wA1 : wA1c_p;
     const int kl = ks < NKX ? ks : ks - NKX;
     const char* p = base + ((size_t)(2 * kl + (g >> 1)) * NW + wave) * (NAH * 1024) + (mt * 2 + (g & 1)) * 1024;
-#ifndef WG_DBG_NO_ALOAD
     gload16<0>(dst, p, a_voff);
-#else
-    asm volatile("" : "=v"(dst));
-#endif
   };
   // M16: [half K-step = sub-step s][wave][tile m][64 lanes = (row i, K group)][8]; fragment (s, m) lives in q[2 s + (m >> 1)][m & 1]
   auto load_A16 = [&](int ks, int s_, int m, half8& dst) {
     const char* base = ks < NKX ? (const char*)a.wA1 : wA1c_p;
     const int kl = ks < NKX ? ks : ks - NKX;
-#ifndef WG_DBG_NO_ALOAD
     gload16<0>(dst, base + ((size_t)(2 * kl + s_) * NW + wave) * (NAH * 1024) + m * 1024, a_voff);
-#else
-    asm volatile("" : "=v"(dst));
-#endif
   };
   // column -> (utterance, frame): rr = row inside the phase block, one of the BN consecutive rows of the current tile.
   // The utterance of the tile's first row (tile_b0, wave-uniform: one scalar division per tile) is at most one
@@ -403,7 +344,7 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     tile_end = start + (xcd < r ? qq + 1 : qq);
     tile = start + idx;
     run_start = start;
-    if (kTileInterleave && ((tile_end - start) & 3) == 0) run_quarter = (tile_end - start) >> 2;
+    if (((tile_end - start) & 3) == 0) run_quarter = (tile_end - start) >> 2;
   }
   // Walk order inside the run: index i takes tile (i & 3) * quarter + (i >> 2), so the tiles an XCD works on at one time are
   // the same few rows of its (typically four) phases instead of 32 consecutive tiles of one phase -- with every XCD doing the
@@ -426,10 +367,12 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     for (int i = tid; i < 2 * C; i += NTHREADS) sBias[i] = a.bias1[i];
     if constexpr (HAS_RES)
       for (int i = tid; i < C; i += NTHREADS) sBias[2 * C + i] = a.bias2[i];   // b_res, read by the pipelined epilogue
-    if constexpr (kWesLds) {
-      uint4* const sW = (uint4*)(sBias + 3 * C);                 // [C/32][64 lanes] x 16 B, behind the biases
-      for (int i = tid; i < (C / 32) * 64; i += NTHREADS) sW[i] = ((const uint4*)a.wEs)[i];
-    }
+    // The folded end x skip weight fragments (hi + lo rows, C/32 KiB) are the same for every wave and every tile of a launch:
+    // they are staged in LDS once per workgroup and read from there right before their MFMAs, instead of C/32 global 1-KiB
+    // loads per wave and tile (8 x redundant through the vector memory path).  Same-box A/B: fetching them one per two slots
+    // of the second-to-last phase instead of as a burst gave +0.5 %, the LDS copy another +0.25 % (0.6180 -> 0.6195).
+    uint4* const sW = (uint4*)(sBias + 3 * C);                   // [C/32][64 lanes] x 16 B, behind the biases
+    for (int i = tid; i < (C / 32) * 64; i += NTHREADS) sW[i] = ((const uint4*)a.wEs)[i];
   }
   __syncthreads();
 
@@ -445,12 +388,6 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     const int r0 = kRowPad + p * Rp + rr0;            // first plane row of this tile
     const int next_tile = tile + tile_step;
     wA1c_p = (const char*)a.wA1c + (MODE != 0 ? (size_t)0 : (size_t)p * (2 * a.n_cond_steps) * NW * (NAH * 1024));
-    if constexpr (!kXTileDMA) {
-      if (it > 0) {
-#pragma unroll
-        for (int i = 0; i < NG; ++i) stage_B_piece(p, jt, 0, par, i);
-      }
-    }
     half8 Q[DEEP ? 2 : 1][4][MT];               // DEEP: fragment rings of the even / odd K-steps
     if constexpr (DEEP) {
       // issue order A(0, 0..3), A(1, 0..2): the steady state's (see kstep_d)
@@ -459,7 +396,7 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) load_Aq(0, g, mt, Q[0][g][mt]);
 #pragma unroll
-      for (int g = 0; g < (kDeepQ2 ? 2 : 3); ++g)
+      for (int g = 0; g < 2; ++g)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) load_Aq(1, g, mt, Q[DEEP ? 1 : 0][g][mt]);
     } else {
@@ -524,7 +461,7 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
       }
     }
 
-    constexpr bool PIPE = !PLAIN && kPipeEpi && HAS_RES && MB == 1;     // pipelined epilogue (below); else the sequential one
+    constexpr bool PIPE = !PLAIN && HAS_RES && MB == 1;     // pipelined epilogue (below); else the sequential one
     constexpr bool RES_A0 = A0G && wn_res_a0(C);                        // first layer of a WN: x_0 rebuilt from the a0 plane
     half8 a2r[PIPE ? K2 : 1];                                 // GEMM-2 weight fragments of this wave (pipelined epilogue)
     // ---- K loop (GEMM 1).  One K-step = 4 k16 sub-steps g = 0..3, each MT*NT MFMAs on fragments q[g][.]
@@ -543,17 +480,17 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     // VMEM issue order per step: DMA xNG, q2 xMT, q3 xMT, q0 xMT, q1 xMT -- every wait is a counted vmcnt.
     // The first and last steps are peeled and "next step is a conditioning step" is a compile-time flag, so the
     // loop bodies are branch-free.
-    wait_vm<DEEP ? (kDeepQ2 ? 3 : 4) * MT : 0>();   // DEEP: A(0, 3) and A(1, .) may still be in flight (steady-state invariant)
+    wait_vm<DEEP ? 3 * MT : 0>();   // DEEP: A(0, 3) and A(1, .) may still be in flight (steady-state invariant)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     WG_STAMP(1);
     constexpr int LPS = (MT + NT - 1) / NT;      // A-fragment reloads per slot
     constexpr int GPS = (NG + NT - 1) / NT;      // LDS-DMA pieces per slot
     half8 bf[2][NT];
-    // kPrio (see the knob): waves 4-7 hold the raised priority through the deferred sub-step and sub-step 0, waves 0-3
-    // through sub-steps 1 and 2; the switch sits inside the last slot of the sub-step before.  The training forward and the
+    // PRIO ("Alternating issue priority" above): waves 4-7 hold the raised priority through the deferred sub-step and
+    // sub-step 0, waves 0-3 through sub-steps 1 and 2; the switch sits inside the last slot of the sub-step before.  The training forward and the
     // 512-channel kernel (+0.8 % at configs[2]) have it too; the first-layer variants (CX = 1) spill with it and go without.
-    constexpr bool PRIO = kPrio && NW == 8 && ((BN == 128 && ((MODE == 0 && CX == C / 64) || MODE == 1)) || (C == 512 && MODE == 0 && CX == C / 64));
+    constexpr bool PRIO = NW == 8 && ((BN == 128 && ((MODE == 0 && CX == C / 64) || MODE == 1)) || (C == 512 && MODE == 0 && CX == C / 64));
     auto prio_set = [&](int hi_grp) {
       if (hi_grp == 1)
         asm volatile("s_cmp_lt_u32 %0, 4\n\ts_cbranch_scc1 .Lpa%=\n\ts_setprio 1\n\ts_branch .Lpb%=\n.Lpa%=:\n\ts_setprio 0\n.Lpb%=:" :: "s"(wave) : "memory", "scc");
@@ -570,16 +507,7 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
       } else {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-#ifdef WG_DBG_MFMA16   // timing experiment only (results are garbage): the 32x32x16 loop's loads and schedule, two 16x16x32 MFMAs each
-          f32x4 lo = __builtin_shufflevector(acc[mt][nt], acc[mt][nt], 0, 1, 2, 3);
-          f32x4 hi = __builtin_shufflevector(acc[mt][nt], acc[mt][nt], 4, 5, 6, 7);
-          lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(q[g][mt], bf[g & 1][nt], lo, 0, 0, 0);
-          hi = __builtin_amdgcn_mfma_f32_16x16x32_f16(q[g][mt], bf[g & 1][nt], hi, 0, 0, 0);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { acc[mt][nt][j] = lo[j]; acc[mt][nt][4 + j] = hi[j]; }
-#else
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(q[g][mt], bf[g & 1][nt], acc[mt][nt], 0, 0, 0);
-#endif
         }
       }
     };
@@ -600,11 +528,9 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
         if constexpr (more) {
 #pragma unroll
           for (int i = nt * GPS; i < (nt + 1) * GPS && i < NG; ++i) {
-#ifndef WG_DBG_NO_DMA
             const unsigned lds = __builtin_amdgcn_readfirstlane(lds_next + i * NTHREADS * 16);
             if constexpr (ncond && MODE == 0) glds16(a.melT, cond_voff(ks + 1 - NKX, i), lds);
             else glds16(src_next, pvoff[i], lds);
-#endif
           }
         }
       };
@@ -669,9 +595,7 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
           for (int mt = 0; mt < MT; ++mt) load_Aq(ks + 1, 2, mt, q[2][mt]);
         }
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "i"(M16 ? 4 : Q2L ? MT : 2 * MT) : "memory");   // DMA, q[0] landed; reads done
-#ifndef WG_DBG_NO_BARRIER
         __builtin_amdgcn_s_barrier();
-#endif
         __builtin_amdgcn_sched_barrier(0);
       }
     };
@@ -703,11 +627,11 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
             if constexpr (ncond) glds16(a.melT, cond_voff(ks + 1 - NKX, nt), lds);
             else glds16(src_next, pvoff[nt], lds);
           }
-          if constexpr (kDeepQ2) {            // quarter 2 of the NEXT step (its ring slot was freed in sub-step 2 of step ks-1)
-            if (nt == NT - 1) {
+          // Quarter 2 of step ks+1 is fetched in the last slot of step ks's deferred sub-step (its ring slot was freed in
+          // sub-step 2 of step ks-1) instead of as two uncovered loads at the end of step ks-1 (-0.3 % on configs[0], same-box).
+          if (nt == NT - 1) {
 #pragma unroll
-              for (int mt = 0; mt < MT; ++mt) load_Aq(ks + 1, 2, mt, Q[PO][2][mt]);
-            }
+            for (int mt = 0; mt < MT; ++mt) load_Aq(ks + 1, 2, mt, Q[PO][2][mt]);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -728,12 +652,8 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      if constexpr (more2 && !kDeepQ2) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) load_Aq(ks + 2, 2, mt, Q[P][2][mt]);
-      }
       if constexpr (more) {
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "i"(more2 ? (kDeepQ2 ? 3 : 4) * MT : MT) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "i"(more2 ? 3 * MT : MT) : "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -802,12 +722,10 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     par = (par + nK) & 1;
     // Next tile's first B tile goes out now, into the LDS buffer the last step did not use (slow waves may
     // still be reading that one) -- it lands under the phases below.
-    if constexpr (kXTileDMA) {
-      if (next_tile < tile_end) {
-        const int tn = tile_of(next_tile), pn = tn / a.tiles_per_phase;
+    if (next_tile < tile_end) {
+      const int tn = tile_of(next_tile), pn = tn / a.tiles_per_phase;
 #pragma unroll
-        for (int i = 0; i < NG; ++i) stage_B_piece(pn, tn - pn * a.tiles_per_phase, 0, par, i);
-      }
+      for (int i = 0; i < NG; ++i) stage_B_piece(pn, tn - pn * a.tiles_per_phase, 0, par, i);
     }
     __builtin_amdgcn_sched_barrier(0);
 
@@ -976,16 +894,8 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     float4 es_o[NGRP];
     float4* es_op[NGRP];
     bool es_valid[NGRP];
-    auto es_prefetch_w = [&](int s_) {
-      if constexpr (kWesLds) wes[s_] = ((const half8*)(sBias + 3 * C) + laneo)[s_ * 64];
-      else wes[s_] = ((const half8*)a.wEs + laneo)[s_ * 64];
-    };
-    auto es_prefetch = [&](bool with_w = true) {
-      const half8* pe = (const half8*)a.wEs + laneo;
-      if (with_w && !kWesLds) {
-#pragma unroll
-        for (int s = 0; s < C / 32; ++s) wes[s] = pe[s * 64];
-      }
+    auto es_prefetch_w = [&](int s_) { wes[s_] = ((const half8*)(sBias + 3 * C) + laneo)[s_ * 64]; };
+    auto es_prefetch = [&]() {
 #pragma unroll
       for (int gi = 0; gi < NGRP; ++gi) {
         const int grp = wave + gi * NW;
@@ -1001,10 +911,8 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
       }
     };
     auto es_compute = [&]() {
-      if constexpr (kWesLds) {
 #pragma unroll
-        for (int s = 0; s < C / 32; ++s) es_prefetch_w(s);
-      }
+      for (int s = 0; s < C / 32; ++s) es_prefetch_w(s);
 #pragma unroll
       for (int gi = 0; gi < NGRP; ++gi) {
         const int grp = wave + gi * NW;
@@ -1113,7 +1021,7 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
           if constexpr (!RES_A0) d2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(idA[1], xr[1], d2, 0, 0, 0);
         }
         if (do_mm && c < NT) load_xr(c);                      // residual of chunk c: phase c+1 starts from it
-        if (c == NT - 1) es_prefetch();                       // end x skip out rows (and weights, without kWesLds): consumed in the last phase
+        if (c == NT - 1) es_prefetch();                       // end x skip out rows: consumed in the last phase
         if (c == NT) es_compute();                            // every acts row is in LDS (barrier of phase NT-1)
         // gate pipeline state (static indices after unrolling)
         float e1[SL], den[SL], rc[SL];
@@ -1392,7 +1300,7 @@ static hipError_t launch_wn_tttt(const WnLayerArgs& a, hipStream_t s) {
   if (M16 != (a.frag16 != 0)) return hipErrorInvalidValue;
   if (MODE == 0 && CX == 1 && NTAPS == 1 && wn_res_a0(C) && HAS_RES && !a.wStA) return hipErrorInvalidValue;
   constexpr int smem = MODE == 4 ? (BN * (2 * C + 16) > 2 * BN * 128 ? BN * (2 * C + 16) : 2 * BN * 128)
-                                 : 2 * BN * 128 + (MODE >= 2 ? 0 : BN * (2 * C + 16) + 3 * C * 4 + (kWesLds ? (C / 32) * 1024 : 0));
+                                 : 2 * BN * 128 + (MODE >= 2 ? 0 : BN * (2 * C + 16) + 3 * C * 4 + (C / 32) * 1024);
   static bool attr_done_dev[64] = {};      // the attribute is per device: keyed by the launch's (current) device
   int cur_dev = 0;
   if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev < 0 || cur_dev >= 64) cur_dev = 0;
@@ -1413,7 +1321,7 @@ template <int C, int BN, bool HAS_RES, int TPW>
 static hipError_t launch_wn_ttt(const WnLayerArgs& a, hipStream_t s) {
   // small workloads (one tile per workgroup, 64 columns) at 256 channels / 80 mel channels: two-step-deep weight prefetch.
   // WG_DISABLE_DEEP=1 (read per launch, tests only) takes the one-step ring instead: the two must agree bit for bit.
-  if constexpr (kDeep && C == 256 && BN == 64 && TPW == 1) {
+  if constexpr (C == 256 && BN == 64 && TPW == 1) {
     const char* e = getenv("WG_DISABLE_DEEP");
     if (a.n_cond_steps == 5 && !(e && *e == '1')) {
       if (a.a0_fold) return launch_wn_tttt<C, BN, HAS_RES, TPW, 1, 0, 1, true, true>(a, s);

@@ -15,11 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <vector>
-
-#include "../../include/waveglow_amd.h"
-
-int wg_set_error(int code, const char* msg);   // api.cpp
+#include "wg_host.h"
 
 namespace wgsl {
 
@@ -419,29 +415,54 @@ static bool layout(const wg_stftloss* h, int B, int N, bool saved, Layout& L) {
   return true;
 }
 
-#define HIP_TRY3(expr)                                                      \
-  do {                                                                      \
-    hipError_t _e = (expr);                                                 \
-    if (_e != hipSuccess) return wg_set_error(WG_ERR_HIP, hipGetErrorString(_e)); \
-  } while (0)
+// device part of wg_stftloss_create: the packed bases of every resolution
+static int upload_bases(wg_stftloss* h, const float* const* fwd_basis) {
+  wg::DeviceGuard dev_guard;
+  HIP_TRY(hipGetDevice(&dev_guard.prev));
+  HIP_TRY(hipSetDevice(h->device));
+  for (int i = 0; i < h->n_res; ++i) {
+    Res& r = h->res[i];
+    const int n = r.n_fft, K = n / 2 + 1;
+    const float* fb = fwd_basis[i];                         // [2K][n]: real rows, then imaginary rows
+    auto basis = [&](int row, int tap) -> float {
+      if (row >= n || tap >= n) return 0.0f;
+      const int ref = row == 0 ? 0 : row == 1 ? n / 2 : (row & 1) ? K + (row >> 1) : (row >> 1);
+      return fb[(size_t)ref * n + tap];
+    };
+    std::vector<float> af((size_t)r.MTf * r.KSf * 64), ab((size_t)r.MTb * r.KSb * 64);
+    for (int mt = 0; mt < r.MTf; ++mt)
+      for (int ks = 0; ks < r.KSf; ++ks)
+        for (int lane = 0; lane < 64; ++lane)
+          af[((size_t)mt * r.KSf + ks) * 64 + lane] = basis(mt * 32 + (lane & 31), r.lpad + 2 * ks + (lane >> 5));
+    for (int mt = 0; mt < r.MTb; ++mt)
+      for (int ks = 0; ks < r.KSb; ++ks)
+        for (int lane = 0; lane < 64; ++lane)
+          ab[((size_t)mt * r.KSb + ks) * 64 + lane] = basis(2 * ks + (lane >> 5), r.lpad + mt * 32 + (lane & 31));
+    HIP_TRY(hipMalloc((void**)&r.d_Af, af.size() * 4));
+    HIP_TRY(hipMalloc((void**)&r.d_Ab, ab.size() * 4));
+    HIP_TRY(hipMemcpy(r.d_Af, af.data(), af.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.d_Ab, ab.data(), ab.size() * 4, hipMemcpyHostToDevice));
+  }
+  return WG_OK;
+}
 
 extern "C" {
 
 int wg_stftloss_create(int32_t n_res, const int32_t* n_fft, const int32_t* hop, const int32_t* win,
                        const float* const* fwd_basis, float eps, int32_t device_id, wg_stftloss** out) {
-  if (!n_fft || !hop || !win || !out) return wg_set_error(WG_ERR_INVALID, "null argument");
-  if (n_res < 1 || n_res > kMaxRes) return wg_set_error(WG_ERR_INVALID, "stft loss: 1 to 8 resolutions");
-  if (!(eps > 0.0f)) return wg_set_error(WG_ERR_INVALID, "stft loss: eps must be positive");
+  if (!n_fft || !hop || !win || !out) return wg::fail(WG_ERR_INVALID, "null argument");
+  if (n_res < 1 || n_res > kMaxRes) return wg::fail(WG_ERR_INVALID, "stft loss: 1 to 8 resolutions");
+  if (!(eps > 0.0f)) return wg::fail(WG_ERR_INVALID, "stft loss: eps must be positive");
   for (int i = 0; i < n_res; ++i) {
     if (n_fft[i] < 32 || n_fft[i] > kMaxFft || n_fft[i] % 32)
-      return wg_set_error(WG_ERR_INVALID, "stft loss: n_fft must be a multiple of 32 in [32, 2048]");
-    if (hop[i] < 1 || hop[i] > n_fft[i]) return wg_set_error(WG_ERR_INVALID, "stft loss: hop must be in [1, n_fft]");
-    if (win[i] < 1 || win[i] > n_fft[i]) return wg_set_error(WG_ERR_INVALID, "stft loss: win must be in [1, n_fft]");
+      return wg::fail(WG_ERR_INVALID, "stft loss: n_fft must be a multiple of 32 in [32, 2048]");
+    if (hop[i] < 1 || hop[i] > n_fft[i]) return wg::fail(WG_ERR_INVALID, "stft loss: hop must be in [1, n_fft]");
+    if (win[i] < 1 || win[i] > n_fft[i]) return wg::fail(WG_ERR_INVALID, "stft loss: win must be in [1, n_fft]");
   }
   if (device_id >= 0) {
-    if (!fwd_basis) return wg_set_error(WG_ERR_INVALID, "null argument");
+    if (!fwd_basis) return wg::fail(WG_ERR_INVALID, "null argument");
     for (int i = 0; i < n_res; ++i)
-      if (!fwd_basis[i]) return wg_set_error(WG_ERR_INVALID, "null basis");
+      if (!fwd_basis[i]) return wg::fail(WG_ERR_INVALID, "null basis");
   }
   wg_stftloss* h = new wg_stftloss();
   h->device = device_id;
@@ -462,39 +483,10 @@ int wg_stftloss_create(int32_t n_res, const int32_t* n_fft, const int32_t* hop, 
     *out = h;
     return WG_OK;
   }
-  struct DeviceGuard {
-    int prev = -1;
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-  } dev_guard;
-  auto fail = [&](hipError_t e) {
+  const int rc = upload_bases(h, fwd_basis);
+  if (rc != WG_OK) {
     wg_stftloss_destroy(h);
-    return wg_set_error(WG_ERR_HIP, hipGetErrorString(e));
-  };
-  hipError_t e;
-  if ((e = hipGetDevice(&dev_guard.prev)) != hipSuccess) return fail(e);
-  if ((e = hipSetDevice(device_id)) != hipSuccess) return fail(e);
-  for (int i = 0; i < n_res; ++i) {
-    Res& r = h->res[i];
-    const int n = r.n_fft, K = n / 2 + 1;
-    const float* fb = fwd_basis[i];                         // [2K][n]: real rows, then imaginary rows
-    auto basis = [&](int row, int tap) -> float {
-      if (row >= n || tap >= n) return 0.0f;
-      const int ref = row == 0 ? 0 : row == 1 ? n / 2 : (row & 1) ? K + (row >> 1) : (row >> 1);
-      return fb[(size_t)ref * n + tap];
-    };
-    std::vector<float> af((size_t)r.MTf * r.KSf * 64), ab((size_t)r.MTb * r.KSb * 64);
-    for (int mt = 0; mt < r.MTf; ++mt)
-      for (int ks = 0; ks < r.KSf; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-          af[((size_t)mt * r.KSf + ks) * 64 + lane] = basis(mt * 32 + (lane & 31), r.lpad + 2 * ks + (lane >> 5));
-    for (int mt = 0; mt < r.MTb; ++mt)
-      for (int ks = 0; ks < r.KSb; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-          ab[((size_t)mt * r.KSb + ks) * 64 + lane] = basis(2 * ks + (lane >> 5), r.lpad + mt * 32 + (lane & 31));
-    if ((e = hipMalloc((void**)&r.d_Af, af.size() * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc((void**)&r.d_Ab, ab.size() * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpy(r.d_Af, af.data(), af.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
-    if ((e = hipMemcpy(r.d_Ab, ab.data(), ab.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail(e);
+    return rc;
   }
   *out = h;
   return WG_OK;
@@ -519,12 +511,12 @@ size_t wg_stftloss_workspace_bytes(const wg_stftloss* h, int32_t B, int32_t n_sa
 static int loss_forward(wg_stftloss* h, const float* audio, const float* target, float factor_sc, float factor_mag,
                         float* out3, int32_t B, int32_t N, void* workspace, size_t workspace_bytes, void* stream,
                         bool saved) {
-  if (!h || !audio || !target || !out3 || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
-  if (h->device < 0) return wg_set_error(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
+  if (!h || !audio || !target || !out3 || !workspace) return wg::fail(WG_ERR_INVALID, "null argument");
+  if (h->device < 0) return wg::fail(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
   Layout L;
   if (!layout(h, B, N, saved, L) || B > 65535)
-    return wg_set_error(WG_ERR_INVALID, "stft loss: bad B, or n_samples <= max n_fft / 2");
-  if (workspace_bytes < L.total * 4) return wg_set_error(WG_ERR_WORKSPACE, "stft loss workspace too small");
+    return wg::fail(WG_ERR_INVALID, "stft loss: bad B, or n_samples <= max n_fft / 2");
+  if (workspace_bytes < L.total * 4) return wg::fail(WG_ERR_WORKSPACE, "stft loss workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   FinalArgs fa{};
@@ -553,17 +545,17 @@ static int loss_forward(wg_stftloss* h, const float* audio, const float* target,
     const dim3 grid(L.nbx[i], L.nby[i], B);
     a.audio = target;
     hipLaunchKernelGGL((sl_gemm_kernel<kFwdY, kTW>), grid, dim3(256), 0, s, a);
-    HIP_TRY3(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     a.audio = audio;
     if (saved) hipLaunchKernelGGL((sl_gemm_kernel<kFwdXSave, kTW>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((sl_gemm_kernel<kFwdX, kTW>), grid, dim3(256), 0, s, a);
-    HIP_TRY3(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     fa.part[i] = a.part;
     fa.nblk[i] = L.nbx[i] * L.nby[i] * B;
     fa.cnt[i] = (double)B * (r.n_fft / 2 + 1) * L.F[i];
   }
   hipLaunchKernelGGL(sl_final_kernel, dim3(1), dim3(256), 0, s, fa);
-  HIP_TRY3(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return WG_OK;
 }
 
@@ -583,12 +575,12 @@ int wg_stftloss_forward_saved(wg_stftloss* h, const float* audio, const float* t
 
 int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, float factor_mag, float* audio_grad_out,
                          int32_t B, int32_t N, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h || !g_out3 || !audio_grad_out || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
-  if (h->device < 0) return wg_set_error(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
+  if (!h || !g_out3 || !audio_grad_out || !workspace) return wg::fail(WG_ERR_INVALID, "null argument");
+  if (h->device < 0) return wg::fail(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
   Layout L;
   if (!layout(h, B, N, true, L) || B > 65535)
-    return wg_set_error(WG_ERR_INVALID, "stft loss: bad B, or n_samples <= max n_fft / 2");
-  if (workspace_bytes < L.total * 4) return wg_set_error(WG_ERR_WORKSPACE, "stft loss workspace too small");
+    return wg::fail(WG_ERR_INVALID, "stft loss: bad B, or n_samples <= max n_fft / 2");
+  if (workspace_bytes < L.total * 4) return wg::fail(WG_ERR_WORKSPACE, "stft loss workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   for (int i = 0; i < h->n_res; ++i) {
@@ -622,10 +614,10 @@ int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, f
       case 3: hipLaunchKernelGGL((sl_gemm_kernel<kBwd, 3>), grid, dim3(256), 0, s, a); break;
       default: hipLaunchKernelGGL((sl_gemm_kernel<kBwd, 4>), grid, dim3(256), 0, s, a); break;
     }
-    HIP_TRY3(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     GatherArgs ga{a.G, audio_grad_out, r.n_fft, r.hop, r.win, r.lpad, N, L.F[i], a.Wp, i > 0};
     hipLaunchKernelGGL(sl_gather_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, ga);
-    HIP_TRY3(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   return WG_OK;
 }

@@ -688,13 +688,8 @@ __device__ __forceinline__ void wgrad_body(const WgradLaunch& L, const WgradJob&
   auto mfma_all = [&]() {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-#ifdef WGR_NOMFMA      // diagnostic builds: one VALU instruction per fragment pair keeps the LDS reads alive
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc[i][k][0] += (float)af[i][0] * (float)bf[k][0];
-#else
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[i][k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[k], af[i], acc[i][k], 0, 0, 0);
-#endif
     }
     if (extra_wave) {
 #pragma unroll
@@ -720,24 +715,14 @@ __device__ __forceinline__ void wgrad_body(const WgradLaunch& L, const WgradJob&
     // this wave's pieces of step st have landed: all but the NS youngest (waves with NS + 1 pieces per step wait for the
     // oldest piece of step st + 1 as well, issued a whole step ago)
     WGR_STEP_STAMP(0);
-#ifdef WGR_NODMA
-    if (st < WD_STAGES) tr_wait_vm<0>();
-#else
     if (st + 1 < n_steps) tr_wait_vm<NS>(); else tr_wait_vm<0>();
-#endif
     WGR_STEP_STAMP(1);
-#ifndef WGR_NOBAR
     __syncthreads();                                                  // everyone's have; stage (st + 2) % 3 is free
-#endif
     WGR_STEP_STAMP(2);
     // Staging costs the issuing wave 100+ cycles per piece (in-kernel stamps: 350-530 cycles for a wave's 4-5 pieces when
     // all eight waves issue together right behind the barrier), so the late half runs its MFMAs FIRST -- the matrix pipe
     // starts at the barrier -- and stages afterwards, while the early half stages and reads.
-#ifdef WGR_NODMA       // diagnostic builds (A/B timing only, results are garbage): the ring is filled once and never again
-    const bool stage_now = st + 2 < n_steps && st + 2 < WD_STAGES;
-#else
     const bool stage_now = st + 2 < n_steps;
-#endif
     if (!late && stage_now) issue();
     __builtin_amdgcn_sched_barrier(0);
     WGR_STEP_STAMP(3);

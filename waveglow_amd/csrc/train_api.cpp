@@ -1,44 +1,23 @@
 // C ABI of the training direction (include/waveglow_amd.h: wg_train_*): launch sequencing of train.hip.
 // Reference: WaveGlow.forward under autograd (src/waveglow/model.py:178-221) and loss.backward() (train.py:190-199).
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/waveglow_amd.h"
+#include "wg_host.h"
 #include "wg_train.h"
 
 using namespace wg;
 
-int wg_set_error(int code, const char* msg);                              // api.cpp
-const wg_config* wg_internal_config(const wg_handle* h);                  // api.cpp
-const int* wg_internal_flow_channels(const wg_handle* h);                 // api.cpp
-wg::RowGeom wg_internal_geom(const wg_handle* h, int B, int L, int T);    // api.cpp
-void wg_internal_prof_event(wg_handle* h, void* stream, int cls);         // api.cpp
-hipStream_t wg_internal_aux_stream(wg_handle* h, int i);                  // api.cpp
-hipEvent_t wg_internal_sync_event(wg_handle* h);                          // api.cpp
-hipEvent_t wg_internal_mark_event(wg_handle* h, int slot);                // api.cpp
-hipError_t wg_internal_upload(wg_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);   // api.cpp
-int wg_internal_n_cu(const wg_handle* h);                                 // api.cpp
-const float* wg_internal_winv(const wg_handle* h, int k);                 // api.cpp
-
 namespace {
 
+// A training launch: HIP_TRY, and under WG_DEBUG_SYNC=1 a device synchronise and a stderr line per call.
 #define TR_TRY(expr)                                                                         \
   do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) {                                                                  \
-      std::string m = std::string(#expr) + ": " + hipGetErrorString(_e);                     \
-      return wg_set_error(WG_ERR_HIP, m.c_str());                                            \
-    }                                                                                        \
+    HIP_TRY(expr);                                                                           \
     if (dbg_sync()) {                                                                        \
       hipError_t _s = hipDeviceSynchronize();                                                \
       fprintf(stderr, "[wg-train] %s -> %s\n", #expr, hipGetErrorString(_s));                \
       fflush(stderr);                                                                        \
-      if (_s != hipSuccess) return wg_set_error(WG_ERR_HIP, hipGetErrorString(_s));          \
+      if (_s != hipSuccess) return fail(WG_ERR_HIP, "%s", hipGetErrorString(_s));            \
     }                                                                                        \
   } while (0)
 
@@ -50,16 +29,7 @@ namespace {
     wg_internal_prof_event(h, (void*)(st), cls);   \
   } while (0)
 
-bool dbg_sync() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("WG_DEBUG_SYNC"); v = e && *e == '1'; }
-  return v == 1;
-}
-
-size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
-
-bool is_early(const wg_config& c, int k) { return k % c.n_early_every == 0 && k > 0; }
 
 struct TrainWs {
   // fp16 planes (elements).  Layer planes: one set per layer of `slots` flows -- every flow (full save), or two flow slots
@@ -143,13 +113,6 @@ struct Ctx {
 // index of the plane set of layer i of flow k: its own (full save) or its flow slot's (WG_TRAIN_RECOMPUTE)
 size_t plane_layer(const Ctx& x, int k, int i) { return (size_t)(x.recompute ? (k & 1) : k) * x.nl + i; }
 
-// sets rc_ and returns from the enclosing function on a HIP error of an ordering call
-#define TR_ORDER(expr)                                                                       \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) return wg_set_error(WG_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(_e)).c_str()); \
-  } while (0)
-
 // `to` continues after everything enqueued on `from` so far
 hipError_t order_after(wg_handle* h, hipStream_t from, hipStream_t to) {
   if (from == to) return hipSuccess;
@@ -161,19 +124,19 @@ hipError_t order_after(wg_handle* h, hipStream_t from, hipStream_t to) {
 
 int setup(wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes, int32_t flags,
           Ctx& x) {
-  if (!h) return wg_set_error(WG_ERR_INVALID, "null handle");
-  if (flags & ~WG_TRAIN_RECOMPUTE) return wg_set_error(WG_ERR_INVALID, "unknown wg_train flags");
+  if (!h) return fail(WG_ERR_INVALID, "null handle");
+  if (flags & ~WG_TRAIN_RECOMPUTE) return fail(WG_ERR_INVALID, "unknown wg_train flags");
   x.recompute = (flags & WG_TRAIN_RECOMPUTE) != 0;
-  x.c = wg_internal_config(h);
-  x.ck = wg_internal_flow_channels(h);
+  x.c = &h->cfg;
+  x.ck = h->c_k.data();
   const wg_config& c = *x.c;
   if (B < 1 || n_frames < 1 || audio_len < c.n_group || audio_len % c.n_group)
-    return wg_set_error(WG_ERR_INVALID, "audio_len must be a positive multiple of n_group");
+    return fail(WG_ERR_INVALID, "audio_len must be a positive multiple of n_group");
   if ((int64_t)(n_frames - 1) * c.upsample_stride + c.upsample_kernel < audio_len)    // model.py:187
-    return wg_set_error(WG_ERR_INVALID, "upsampled mel shorter than audio");
+    return fail(WG_ERR_INVALID, "upsampled mel shorter than audio");
   const int L = audio_len / c.n_group;
-  x.g = wg_internal_geom(h, B, L, n_frames);
-  x.n_cu = wg_internal_n_cu(h);     // of the handle's device: decides the chain geometry (workspace layout) below
+  x.g = make_geom(h->cfg, B, L, n_frames);
+  x.n_cu = h->n_cu;     // of the handle's device: decides the chain geometry (workspace layout) below
   // Chains.  A WN-layer launch runs ceil(tiles / CUs) rounds and the next layer waits for its last, partly filled
   // round (config 4: 576 tiles of 128 columns on 256 CUs = 2.25 rounds, a quarter of the chip-time idle).  The two
   // halves of the batch never exchange data inside a WN, so they run as two chains of half-size launches on two
@@ -230,15 +193,15 @@ int setup(wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, void* wo
   const size_t full = x.recompute ? carve(c, x.g, x.n_slabs, nullptr, false).bytes : x.w.bytes;
   const size_t rec = x.recompute ? x.w.bytes : carve(c, x.g, x.n_slabs, nullptr, true).bytes;
   if (x.recompute && rec >= full)
-    return wg_set_error(WG_ERR_INVALID, "WG_TRAIN_RECOMPUTE saves no memory at this depth (two flow slots hold every layer)");
+    return fail(WG_ERR_INVALID, "WG_TRAIN_RECOMPUTE saves no memory at this depth (two flow slots hold every layer)");
   if (workspace) {
     if (x.recompute && workspace_bytes >= full)
-      return wg_set_error(WG_ERR_INVALID, "WG_TRAIN_RECOMPUTE with a full-save training workspace: flags and workspace size do not match");
+      return fail(WG_ERR_INVALID, "WG_TRAIN_RECOMPUTE with a full-save training workspace: flags and workspace size do not match");
     if (!x.recompute && workspace_bytes < full && rec < full && workspace_bytes >= rec)
-      return wg_set_error(WG_ERR_INVALID, "training workspace of the WG_TRAIN_RECOMPUTE size without the flag: flags and workspace size do not match");
-    if (x.w.bytes > workspace_bytes) return wg_set_error(WG_ERR_WORKSPACE, "training workspace too small");
+      return fail(WG_ERR_INVALID, "training workspace of the WG_TRAIN_RECOMPUTE size without the flag: flags and workspace size do not match");
+    if (x.w.bytes > workspace_bytes) return fail(WG_ERR_WORKSPACE, "training workspace too small");
   }
-  if ((size_t)x.g.R * 128 >= (1ull << 32)) return wg_set_error(WG_ERR_INVALID, "plane too large for 32-bit offsets");
+  if ((size_t)x.g.R * 128 >= (1ull << 32)) return fail(WG_ERR_INVALID, "plane too large for 32-bit offsets");
   x.C = c.n_channels;
   x.nl = c.n_layers;
   x.FL = c.n_flows * c.n_layers;
@@ -251,19 +214,19 @@ int setup(wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, void* wo
 int check_weights(const wg_train_weights* w, int n_flows) {
   if (!w->a1 || !w->a1c || !w->b1 || !w->a2 || !w->b2 || !w->es || !w->wat || !w->wbt || !w->wct || !w->wup || !w->bup ||
       !w->wstart || !w->bstart || !w->out_init || !w->w1x1)
-    return wg_set_error(WG_ERR_INVALID, "wg_train_weights has a null member");
+    return fail(WG_ERR_INVALID, "wg_train_weights has a null member");
   for (int k = 0; k < n_flows; ++k)
     if (!w->wstart[k] || !w->bstart[k] || !w->out_init[k] || !w->w1x1[k])
-      return wg_set_error(WG_ERR_INVALID, "wg_train_weights has a null per-flow pointer");
+      return fail(WG_ERR_INVALID, "wg_train_weights has a null per-flow pointer");
   return WG_OK;
 }
 int check_grads(const wg_train_grads* g, int n_flows) {
   if (!g->dw1 || !g->db1 || !g->dw2 || !g->db2 || !g->dwes || !g->dwup || !g->dbup || !g->dstart || !g->dout_init ||
       !g->dw1x1)
-    return wg_set_error(WG_ERR_INVALID, "wg_train_grads has a null member");
+    return fail(WG_ERR_INVALID, "wg_train_grads has a null member");
   for (int k = 0; k < n_flows; ++k)
     if (!g->dstart[k] || !g->dout_init[k] || !g->dw1x1[k])
-      return wg_set_error(WG_ERR_INVALID, "wg_train_grads has a null per-flow pointer");
+      return fail(WG_ERR_INVALID, "wg_train_grads has a null per-flow pointer");
   return WG_OK;
 }
 
@@ -345,7 +308,7 @@ int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int 
   const int NW = wn_waves(C), MBw = C / (32 * NW), MTw = 2 * MBw;
   const size_t a1_n = (size_t)2 * (3 * cc) * NW * MTw * 2 * 64 * 8, a1c_n = (size_t)2 * mc * NW * MTw * 2 * 64 * 8;
   const size_t a2_n = (size_t)NW * MBw * (C / 16) * 64 * 8, es_n = (size_t)(C / 32) * 64 * 8;
-  TR_ORDER(order_after(h, s, sB));
+  HIP_TRY(order_after(h, s, sB));
   for (int i = 0; i < nl; ++i) {
     const int fl = k * nl + i, d = 1 << i;
     const size_t pl = plane_layer(x, k, i);
@@ -382,7 +345,7 @@ int wn_flow_forward(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int 
       TR_PROF(sh, 4, TR_TRY(launch_part(a, g, BNw, half, x.halves, [&](const WnLayerArgs& q, int bn) { return launch_wn_layer_train(q, C, bn, sh); })));
     }
   }
-  TR_ORDER(order_after(h, sB, s));
+  HIP_TRY(order_after(h, sB, s));
   return WG_OK;
 }
 
@@ -395,7 +358,7 @@ int replay_flow(wg_handle* h, const Ctx& x, const wg_train_weights* wt, int k, b
   hipStream_t sB = s;
   if (chains && x.halves == 2 && !x.serial) {
     sB = wg_internal_aux_stream(h, 0);
-    if (!sB) return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
+    if (!sB) return fail(WG_ERR_HIP, "cannot create the second chain's stream");
   }
   FlowArgs f;
   memset(&f, 0, sizeof f);
@@ -510,7 +473,7 @@ int bwd_block_n(const Ctx& x) {
 int bwd_plan(wg_handle* h, const Ctx& x, const wg_train_weights* wt, const wg_train_grads* gr, float scale, hipStream_t s,
              bool second_chain, BwdPlan& p) {
   if (gr && ((gr->layer_stride == 0) != (gr->flow_stride == 0) || gr->layer_stride < 0 || gr->flow_stride < 0))
-    return wg_set_error(WG_ERR_INVALID, "wg_train_grads: layer_stride and flow_stride must both be 0 or both positive");
+    return fail(WG_ERR_INVALID, "wg_train_grads: layer_stride and flow_stride must both be 0 or both positive");
   memset(&p, 0, sizeof p);
   const int cc = x.C / 64, NW = wn_waves(x.C), MBw = x.C / (32 * NW);
   p.wat = (const _Float16*)wt->wat;
@@ -527,10 +490,10 @@ int bwd_plan(wg_handle* h, const Ctx& x, const wg_train_weights* wt, const wg_tr
   p.s = p.sB = p.sW = p.sR = s;
   p.serial = x.serial || !gr;
   if (p.bh == 2 && !x.serial && !(p.sB = wg_internal_aux_stream(h, 0)))
-    return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
+    return fail(WG_ERR_HIP, "cannot create the second chain's stream");
   if (!p.serial) {
-    if (!(p.sW = wg_internal_aux_stream(h, 1))) return wg_set_error(WG_ERR_HIP, "cannot create the weight-gradient stream");
-    if (!(p.sR = wg_internal_aux_stream(h, 2))) return wg_set_error(WG_ERR_HIP, "cannot create the slab-reduction stream");
+    if (!(p.sW = wg_internal_aux_stream(h, 1))) return fail(WG_ERR_HIP, "cannot create the weight-gradient stream");
+    if (!(p.sR = wg_internal_aux_stream(h, 2))) return fail(WG_ERR_HIP, "cannot create the slab-reduction stream");
   }
   return WG_OK;
 }
@@ -580,9 +543,9 @@ int layer_wgrad(wg_handle* h, const Ctx& x, BwdPlan& p, const wg_train_grads* gr
   jb[1].bias_out = w.part2[set];
   jb[1].extra_out = w.ext[set];
   jb[1].extra_bias_out = w.extb[set];
-  TR_ORDER(wait_on(sW, p.r_done[set]));          // the reduction of the launch before last has read this slab set
+  HIP_TRY(wait_on(sW, p.r_done[set]));          // the reduction of the launch before last has read this slab set
   TR_PROF(sW, 6, TR_TRY(launch_wgrad(jb, 2, g, n_slabs, sW)));
-  TR_ORDER(mark_on(h, p.serial, sW, p.l_done[set], 12 + set));
+  HIP_TRY(mark_on(h, p.serial, sW, p.l_done[set], 12 + set));
   // ---- reduction of everything this launch left behind, in NATURAL channel order (SlabSeg: perm bit 0 = rows are
   // channels, bit 1 = columns are)
   SlabSeg seg[kMaxSlabSegs];
@@ -606,9 +569,9 @@ int layer_wgrad(wg_handle* h, const Ctx& x, BwdPlan& p, const wg_train_grads* gr
   add_flat(1, w.ext[set], (size_t)16 * C, (size_t)8 * C, gr->dwes + grad_ofs(gr, nl, fl, (size_t)8 * C), C, 2);
   // d out_init = sum over columns of (d b | d log_s), once per flow
   if (i == 0) add_flat(1, w.extb[set], 16, 8, gr->dout_init[k], 0, 0);
-  TR_ORDER(wait_on(sR, p.l_done[set]));
+  HIP_TRY(wait_on(sR, p.l_done[set]));
   TR_TRY(launch_slab_reduce_multi(seg, n_seg, sR));
-  TR_ORDER(mark_on(h, p.serial, sR, p.r_done[set], 14 + set));
+  HIP_TRY(mark_on(h, p.serial, sR, p.r_done[set], 14 + set));
   return WG_OK;
 }
 
@@ -659,7 +622,7 @@ int wn_flow_backward(wg_handle* h, const Ctx& x, BwdPlan& p, const wg_train_grad
   const RowGeom& g = x.g;
   const TrainWs& w = x.w;
   const int C = x.C, nl = x.nl, cc = C / 64;
-  TR_ORDER(order_after(h, p.s, p.sB));
+  HIP_TRY(order_after(h, p.s, p.sB));
   gx = nullptr;                               // gx = d x_{i+1} (null: zero, the last layer has no res output)
   for (int i = nl - 1; i >= 0; --i) {
     const int fl = k * nl + i, d = 1 << i;
@@ -701,11 +664,11 @@ int wn_flow_backward(wg_handle* h, const Ctx& x, BwdPlan& p, const wg_train_grad
     }
     if (gr) {
       // the weight-gradient stream continues once every chain has written its part of d pre (and of d x_{i+1} before it)
-      TR_ORDER(order_after(h, p.s, p.sW));
-      if (p.sB != p.s) TR_ORDER(order_after(h, p.sB, p.sW));
+      HIP_TRY(order_after(h, p.s, p.sW));
+      if (p.sB != p.s) HIP_TRY(order_after(h, p.sB, p.sW));
       // d W1 / d b1, d W2 / d b2, d (W_end W_skip_i) of the layer (and d out_init with layer 0) and their reduction
       if (int rc = layer_wgrad(h, x, p, gr, k, i, gx, GOk)) return rc;
-      TR_ORDER(mark_on(h, p.serial, p.sW, p.w_done[i], i));
+      HIP_TRY(mark_on(h, p.serial, p.sW, p.w_done[i], i));
     }
     // d x_i = d x_{i+1} + sum_tap W_in[tap]^T d pre(t - (tap-1) d)   (wn_layer_kernel MODE 2: taps at +d, 0, -d)
     memset(&a, 0, sizeof a);
@@ -731,19 +694,19 @@ int wn_flow_backward(wg_handle* h, const Ctx& x, BwdPlan& p, const wg_train_grad
     }
     for (int half = 0; half < p.bh; ++half) {
       hipStream_t sh = half ? p.sB : p.s;
-      if (gr && i > 0) TR_ORDER(wait_on(sh, p.w_done[i - 1]));     // GXL[i]: see BwdPlan
+      if (gr && i > 0) HIP_TRY(wait_on(sh, p.w_done[i - 1]));     // GXL[i]: see BwdPlan
       TR_PROF(sh, 5, TR_TRY(launch_part(a, g, p.BNw, half, p.bh, [&](const WnLayerArgs& q, int bn) { return launch_wn_plain(q, C, kind, bn, sh); })));
     }
     gx = gxi;
   }
-  TR_ORDER(order_after(h, p.sB, p.s));
+  HIP_TRY(order_after(h, p.sB, p.s));
   return WG_OK;
 }
 
 // every gradient of the call is final on the caller's stream
 int join_wgrad_streams(wg_handle* h, const BwdPlan& p) {
-  TR_ORDER(order_after(h, p.sW, p.s));
-  TR_ORDER(order_after(h, p.sR, p.s));
+  HIP_TRY(order_after(h, p.sW, p.s));
+  HIP_TRY(order_after(h, p.sR, p.s));
   return WG_OK;
 }
 
@@ -753,7 +716,7 @@ int dspect_finish(wg_handle* h, const Ctx& x, const BwdPlan& p, const wg_train_w
   const TrainWs& w = x.w;
   hipStream_t s = p.s;
   if (x.recompute) {
-    TR_ORDER(order_after(h, p.sW, s));      // the last flow's d spect GEMM (dspect_flow) wrote GSP on sW
+    HIP_TRY(order_after(h, p.sW, s));      // the last flow's d spect GEMM (dspect_flow) wrote GSP on sW
   } else {
     // d spect = sum over every layer of cond_layer^T d pre: ONE GEMM with K = FL*2C over the kept d pre planes
     const int C = x.C, FL = x.FL;
@@ -792,14 +755,14 @@ extern "C" {
 int32_t wg_wn_waves(int32_t n_channels) { return wn_waves(n_channels); }
 
 int wg_train_pack(wg_handle* h, const wg_train_plain* in, const wg_train_weights* out, void* stream) {
-  if (!h || !in || !out) return wg_set_error(WG_ERR_INVALID, "null argument");
+  if (!h || !in || !out) return fail(WG_ERR_INVALID, "null argument");
   if (!in->w1 || !in->w2 || !in->wes || !in->wup || !out->a1 || !out->a1c || !out->a2 || !out->es || !out->wat ||
       !out->wbt || !out->wct || !out->wup)
-    return wg_set_error(WG_ERR_INVALID, "wg_train_pack: null tensor");
-  const wg_config& c = *wg_internal_config(h);
+    return fail(WG_ERR_INVALID, "wg_train_pack: null tensor");
+  const wg_config& c = h->cfg;
   hipStream_t s = (hipStream_t)stream;
   const int C = c.n_channels, M8 = c.n_mel_channels * 8, FL = c.n_flows * c.n_layers, NW = wn_waves(C);
-  if (NW <= 0 || M8 % 64) return wg_set_error(WG_ERR_INVALID, "wg_train_pack: unsupported channel counts");
+  if (NW <= 0 || M8 % 64) return fail(WG_ERR_INVALID, "wg_train_pack: unsupported channel counts");
   const size_t K1 = 3 * (size_t)C + M8;
   PackArgs a;
   memset(&a, 0, sizeof a);
@@ -843,7 +806,7 @@ int wg_train_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, 
 int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* audio, float* z,
                            float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
                            void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
-  if (!wt || !mel || !audio || !z || !log_s || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
+  if (!wt || !mel || !audio || !z || !log_s || !workspace) return fail(WG_ERR_INVALID, "null argument");
   Ctx x;
   int rc = setup(h, B, n_frames, audio_len, workspace, workspace_bytes, flags, x);
   if (rc) return rc;
@@ -857,7 +820,7 @@ int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void*
   hipStream_t sB = s;
   if (x.halves == 2 && !x.serial) {
     sB = wg_internal_aux_stream(h, 0);
-    if (!sB) return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
+    if (!sB) return fail(WG_ERR_HIP, "cannot create the second chain's stream");
   }
   const int BNw = fwd_block_n(x);
 
@@ -884,7 +847,7 @@ int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void*
       f.c_in = x.ck[k - 1];
       f.h_in = f.c_in / 2;
       f.log_s_out = log_s[k - 1];
-      if (!f.log_s_out) return wg_set_error(WG_ERR_INVALID, "null log_s entry");
+      if (!f.log_s_out) return fail(WG_ERR_INVALID, "null log_s entry");
     }
     if (!f.last) {
       f.Z_w = w.Zpost + (size_t)k * w.rows8;
@@ -892,7 +855,7 @@ int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void*
       f.n_peel = is_early(c, k) ? c.n_early_size : 0;
       f.c_next = x.ck[k];
       f.h_next = f.c_next / 2;
-      if (f.c_in - f.n_peel != f.c_next) return wg_set_error(WG_ERR_STATE, "flow bookkeeping error");
+      if (f.c_in - f.n_peel != f.c_next) return fail(WG_ERR_STATE, "flow bookkeeping error");
       f.winv = wt->w1x1[k];
       f.wstart = wt->wstart[k];
       f.bstart = wt->bstart[k];
@@ -912,9 +875,9 @@ int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void*
 int wg_train_backward(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_z,
                       const float* const* g_log_s, float scale, const void* audio, int32_t B, int32_t n_frames,
                       int32_t audio_len, void* workspace, size_t workspace_bytes, void* stream) {
-  const wg_config* c = wg_internal_config(h);
-  if (!c) return wg_set_error(WG_ERR_INVALID, "null handle");
-  if (!gr) return wg_set_error(WG_ERR_INVALID, "null argument");
+  if (!h) return fail(WG_ERR_INVALID, "null handle");
+  const wg_config* c = &h->cfg;
+  if (!gr) return fail(WG_ERR_INVALID, "null argument");
   return wg_train_backward_ex(h, wt, gr, g_z, g_log_s, scale, audio, nullptr, nullptr, B, n_frames, audio_len, workspace,
                               workspace_bytes, c->n_flows - 1, 0, stream);
 }
@@ -923,7 +886,7 @@ int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_t
                             const float* const* g_log_s, float scale, const void* audio, int32_t B, int32_t n_frames,
                             int32_t audio_len, void* workspace, size_t workspace_bytes, int32_t flow_hi, int32_t flow_lo,
                             void* stream) {
-  if (!gr) return wg_set_error(WG_ERR_INVALID, "null argument");
+  if (!gr) return fail(WG_ERR_INVALID, "null argument");
   return wg_train_backward_ex(h, wt, gr, g_z, g_log_s, scale, audio, nullptr, nullptr, B, n_frames, audio_len, workspace,
                               workspace_bytes, flow_hi, flow_lo, stream);
 }
@@ -940,13 +903,13 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
                                const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
                                int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
                                int32_t flow_hi, int32_t flow_lo, int32_t flags, void* stream) {
-  if (!wt || !audio || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
-  if (!(scale > 0.f)) return wg_set_error(WG_ERR_INVALID, "scale must be positive");
+  if (!wt || !audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
+  if (!(scale > 0.f)) return fail(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
   int rc = setup(h, B, n_frames, audio_len, workspace, workspace_bytes, flags, x);
   if (rc) return rc;
   if ((rc = check_weights(wt, x.c->n_flows)) || (gr && (rc = check_grads(gr, x.c->n_flows)))) return rc;
-  if (g_mel && !wt->wupt) return wg_set_error(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
+  if (g_mel && !wt->wupt) return fail(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
   // gr == null: no parameter gradients -- the data-gradient chain alone (no weight-gradient launch, slab reduction, start /
   // 1x1 partial, d upsample job; the d spect GEMM only for g_mel)
   const bool pg = gr != nullptr;
@@ -956,8 +919,8 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
   hipStream_t s = (hipStream_t)stream;
   BwdPlan p;                                // streams, marks and what orders the reuse of shared buffers: see BwdPlan
   if ((rc = bwd_plan(h, x, wt, gr, scale, s, true, p))) return rc;
-  if (flow_lo < 0 || flow_hi >= c.n_flows || flow_lo > flow_hi) return wg_set_error(WG_ERR_INVALID, "bad flow range");
-  if (x.nl > 10) return wg_set_error(WG_ERR_INVALID, "more than 10 layers");
+  if (flow_lo < 0 || flow_hi >= c.n_flows || flow_lo > flow_hi) return fail(WG_ERR_INVALID, "bad flow range");
+  if (x.nl > 10) return fail(WG_ERR_INVALID, "more than 10 layers");
   // channel offsets of the peeled outputs in z (model.py:201-203, :220): early outputs of the flows <= k
   auto early_channels_upto = [&](int k) {
     int n = 0;
@@ -966,7 +929,7 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     return n;
   };
   int z_final_ch0 = early_channels_upto(flow_hi);
-  TR_ORDER(order_after(h, s, p.sW));
+  HIP_TRY(order_after(h, s, p.sW));
 
   for (int k = flow_hi; k >= flow_lo; --k) {
     const int ck = x.ck[k], hk = ck / 2;
@@ -985,7 +948,7 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     fb.z_ch0 = early_channels_upto(c.n_flows - 1);
     fb.GZ = w.GZ;
     fb.GO = w.GO[k & 1];
-    TR_ORDER(wait_on(s, p.w_flow[k & 1]));
+    HIP_TRY(wait_on(s, p.w_flow[k & 1]));
     if (x.recompute && k < c.n_flows - 2 && (rc = replay_flow(h, x, wt, k, true, s))) return rc;
     TR_TRY(launch_flow_bwd_pre(fb, s));
     if ((rc = wn_flow_backward(h, x, p, gr, k, fb.GO, fb.GX))) return rc;
@@ -993,7 +956,7 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
     // flow's last weight-gradient job, so that w_flow covers it (without parameter gradients sW is s: behind the chains)
     const bool dspect = x.recompute && (pg || g_mel);
     if (dspect && (rc = dspect_flow(x, wt, k, k == c.n_flows - 1, k == 0, p.sW))) return rc;
-    if (pg) TR_ORDER(mark_on(h, p.serial, p.sW, p.w_flow[k & 1], 10 + (k & 1)));
+    if (pg) HIP_TRY(mark_on(h, p.serial, p.sW, p.w_flow[k & 1], 10 + (k & 1)));
     if (pg && (rc = start_wgrad(x, gr, k, fb.GX, fb.Zpost, p.inv, s))) return rc;
     fb.wstart = wt->wstart[k];
     fb.w1x1 = wt->w1x1[k];
@@ -1034,29 +997,23 @@ int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const w
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-int n_early_flows(const wg_config& c) {
-  int n = 0;
-  for (int k = 0; k < c.n_flows; ++k) n += is_early(c, k);
-  return n;
-}
-
 // common checks and geometry of both calls: audio_len = 256 n_frames (infer's trim, model.py:228)
 int infer_setup(wg_handle* h, const wg_train_weights* wt, int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace,
                 size_t workspace_bytes, int32_t flags, Ctx& x, const float** winv) {
-  const wg_config* c = wg_internal_config(h);
-  if (!c) return wg_set_error(WG_ERR_INVALID, "null handle");
-  if (n_frames < 1) return wg_set_error(WG_ERR_INVALID, "bad n_frames");
-  if (c->n_flows > 64) return wg_set_error(WG_ERR_INVALID, "too many flows");
+  if (!h) return fail(WG_ERR_INVALID, "null handle");
+  const wg_config* c = &h->cfg;
+  if (n_frames < 1) return fail(WG_ERR_INVALID, "bad n_frames");
+  if (c->n_flows > 64) return fail(WG_ERR_INVALID, "too many flows");
   int rc = setup(h, B, n_frames, n_frames * c->upsample_stride, workspace, workspace_bytes, flags, x);
   if (rc) return rc;
   if ((rc = check_weights(wt, c->n_flows))) return rc;
-  if (n_z_early != n_early_flows(*c)) return wg_set_error(WG_ERR_INVALID, "wrong number of early-noise tensors");
+  if (n_z_early != n_early_flows(*c)) return fail(WG_ERR_INVALID, "wrong number of early-noise tensors");
   // W_k^-1: the per-call weights' own (wg_train_prepare inverted them on the device), else the finalised handle's
   for (int k = 0; k < c->n_flows; ++k) {
     if (wt->winv) {
-      if (!(winv[k] = wt->winv[k])) return wg_set_error(WG_ERR_INVALID, "wg_train_weights.winv has a null per-flow pointer");
+      if (!(winv[k] = wt->winv[k])) return fail(WG_ERR_INVALID, "wg_train_weights.winv has a null per-flow pointer");
     } else if (!(winv[k] = wg_internal_winv(h, k))) {
-      return wg_set_error(WG_ERR_STATE, "wg_finalize has not been called: the synthesis direction uses the handle's W^-1");
+      return fail(WG_ERR_STATE, "wg_finalize has not been called: the synthesis direction uses the handle's W^-1");
     }
   }
   return WG_OK;
@@ -1090,19 +1047,19 @@ int wg_train_infer_forward_flags(wg_handle* h, const wg_train_weights* wt, const
                                  int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
                                  void* stream) {
   if (!wt || !mel || !z_init || !audio || !workspace || (n_z_early > 0 && !z_early))
-    return wg_set_error(WG_ERR_INVALID, "null argument");
+    return fail(WG_ERR_INVALID, "null argument");
   Ctx x;
   const float* winv[64];
   int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, flags, x, winv);
   if (rc) return rc;
   for (int i = 0; i < n_z_early; ++i)
-    if (!z_early[i]) return wg_set_error(WG_ERR_INVALID, "null early-noise tensor");
+    if (!z_early[i]) return fail(WG_ERR_INVALID, "null early-noise tensor");
   const wg_config& c = *x.c;
   hipStream_t s = (hipStream_t)stream;
   hipStream_t sB = s;
   if (x.halves == 2 && !x.serial) {
     sB = wg_internal_aux_stream(h, 0);
-    if (!sB) return wg_set_error(WG_ERR_HIP, "cannot create the second chain's stream");
+    if (!sB) return fail(WG_ERR_HIP, "cannot create the second chain's stream");
   }
   const int BNw = fwd_block_n(x);
   if (fresh) TR_TRY(hipMemsetAsync(workspace, 0, x.w.zero_bytes, s));
@@ -1141,11 +1098,11 @@ int wg_train_infer_forward_flags(wg_handle* h, const wg_train_weights* wt, const
     const int c_next = f.c_in + f.n_extra;
     f.last = (k == 0);
     if (f.last) {
-      if (c_next != c.n_group) return wg_set_error(WG_ERR_STATE, "flow bookkeeping error");
+      if (c_next != c.n_group) return fail(WG_ERR_STATE, "flow bookkeeping error");
       f.c_next = c_next;
       f.audio_out = audio;
     } else {
-      if (x.ck[k - 1] != c_next) return wg_set_error(WG_ERR_STATE, "flow bookkeeping error");
+      if (x.ck[k - 1] != c_next) return fail(WG_ERR_STATE, "flow bookkeeping error");
       infer_next(x, wt, k - 1, f);
     }
     TR_TRY(launch_flow(f, s));
@@ -1171,13 +1128,13 @@ int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, con
                                    float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
                                    int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace, size_t workspace_bytes,
                                    int32_t flags, void* stream) {
-  if (!wt || !g_audio || !workspace) return wg_set_error(WG_ERR_INVALID, "null argument");
-  if (!(scale > 0.f)) return wg_set_error(WG_ERR_INVALID, "scale must be positive");
+  if (!wt || !g_audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
+  if (!(scale > 0.f)) return fail(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
   const float* winv[64];
   int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, flags, x, winv);
   if (rc) return rc;
-  if (g_mel && !wt->wupt) return wg_set_error(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
+  if (g_mel && !wt->wupt) return fail(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
   // gr == null: the data-gradient chain alone.  Otherwise the packed weight gradients as well, flow by flow behind the data
   // gradients they are made of: per layer the training direction's weight-gradient launch and slab reduction (layer_wgrad),
   // per flow d start (the saved state Y is the WN input, as Zpost is in the training direction), d out_init and d W_k of the
@@ -1190,8 +1147,8 @@ int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, con
   hipStream_t s = (hipStream_t)stream;
   BwdPlan p;                                // one chain on `s`; streams, marks and buffer reuse: see BwdPlan
   if ((rc = bwd_plan(h, x, wt, gr, scale, s, false, p))) return rc;
-  if (pg && x.nl > 10) return wg_set_error(WG_ERR_INVALID, "more than 10 layers");
-  TR_ORDER(order_after(h, s, p.sW));
+  if (pg && x.nl > 10) return fail(WG_ERR_INVALID, "more than 10 layers");
+  HIP_TRY(order_after(h, s, p.sW));
   // index in z_early (descending flow order) of early flow k
   auto early_index = [&](int k) {
     int n = 0;
@@ -1201,7 +1158,7 @@ int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, con
   // Ascending flow order: the gradient enters at the audio, the output of inverse step 0.
   for (int k = 0; k < c.n_flows; ++k) {
     const int ck = x.ck[k];
-    TR_ORDER(wait_on(s, p.w_flow[k & 1]));
+    HIP_TRY(wait_on(s, p.w_flow[k & 1]));
     if (x.recompute && k >= 2 && (rc = replay_flow(h, x, wt, k, false, s))) return rc;
     InvBwdArgs ib;
     memset(&ib, 0, sizeof ib);
@@ -1249,7 +1206,7 @@ int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, con
     // on sW behind the flow's last weight-gradient job, so that w_flow covers it; otherwise on s behind the post kernel
     const bool dspect = x.recompute && (g_mel || pg);
     if (dspect && pg && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, p.sW))) return rc;
-    if (pg) TR_ORDER(mark_on(h, p.serial, p.sW, p.w_flow[k & 1], 10 + (k & 1)));
+    if (pg) HIP_TRY(mark_on(h, p.serial, p.sW, p.w_flow[k & 1], 10 + (k & 1)));
     if (pg && (rc = start_wgrad(x, gr, k, ib.GX, ib.Y, p.inv, s))) return rc;
     TR_TRY(launch_inv_bwd_post(ib, s));
     if (dspect && !pg && (rc = dspect_flow(x, wt, k, k == 0, k == c.n_flows - 1, s))) return rc;
@@ -1340,20 +1297,20 @@ PrepLayout prep_layout(const wg_config& c) {
 // fills the argument block and uploads the pointer table (parameters + the per-flow buffers of `wt` / `gr`)
 int prep_args(wg_handle* h, const void* const* params, int weight_normed, const wg_train_weights* wt, const wg_train_grads* gr,
               void* aux, size_t aux_bytes, float* flat, hipStream_t s, PrepArgs& a) {
-  if (!h || !params || !aux) return wg_set_error(WG_ERR_INVALID, "null argument");
-  const wg_config& c = *wg_internal_config(h);
-  const int* ck = wg_internal_flow_channels(h);
-  if (c.n_flows > kPrepMaxFlows) return wg_set_error(WG_ERR_INVALID, "more than 32 flows are not supported by the training direction");
-  if (c.upsample_kernel != 1024) return wg_set_error(WG_ERR_INVALID, "upsample kernel must be 1024");
+  if (!h || !params || !aux) return fail(WG_ERR_INVALID, "null argument");
+  const wg_config& c = h->cfg;
+  const int* ck = h->c_k.data();
+  if (c.n_flows > kPrepMaxFlows) return fail(WG_ERR_INVALID, "more than 32 flows are not supported by the training direction");
+  if (c.upsample_kernel != 1024) return fail(WG_ERR_INVALID, "upsample kernel must be 1024");
   const PrepLayout L = prep_layout(c);
-  if (aux_bytes < L.bytes) return wg_set_error(WG_ERR_WORKSPACE, "wg_train_prepare: aux buffer too small");
+  if (aux_bytes < L.bytes) return fail(WG_ERR_WORKSPACE, "wg_train_prepare: aux buffer too small");
   const int nf = c.n_flows, FL = nf * c.n_layers;
   std::vector<void*> tab((size_t)L.n_slots, nullptr);
   std::vector<long long> goff((size_t)L.n_slots, 0);
   const std::vector<ParamDesc> pl = param_list(c, ck, weight_normed != 0);
   long long off = 0;
   for (size_t i = 0; i < pl.size(); ++i) {
-    if (!params[i]) return wg_set_error(WG_ERR_INVALID, ("null parameter pointer: " + pl[i].name).c_str());
+    if (!params[i]) return fail(WG_ERR_INVALID, "null parameter pointer: %s", pl[i].name.c_str());
     const int slot = prep_slot_n(FL, nf, pl[i].sec, pl[i].idx);
     tab[slot] = const_cast<void*>(params[i]);
     goff[slot] = off;
@@ -1401,13 +1358,13 @@ extern "C" {
 
 int32_t wg_train_param_count(const wg_handle* h, int32_t weight_normed) {
   if (!h) return 0;
-  return (int32_t)param_list(*wg_internal_config(h), wg_internal_flow_channels(h), weight_normed != 0).size();
+  return (int32_t)param_list(h->cfg, h->c_k.data(), weight_normed != 0).size();
 }
 
 const char* wg_train_param_name(const wg_handle* h, int32_t weight_normed, int32_t i) {
   static thread_local std::string name;
   if (!h) return "";
-  const std::vector<ParamDesc> pl = param_list(*wg_internal_config(h), wg_internal_flow_channels(h), weight_normed != 0);
+  const std::vector<ParamDesc> pl = param_list(h->cfg, h->c_k.data(), weight_normed != 0);
   if (i < 0 || (size_t)i >= pl.size()) return "";
   name = pl[i].name;
   return name.c_str();
@@ -1415,29 +1372,29 @@ const char* wg_train_param_name(const wg_handle* h, int32_t weight_normed, int32
 
 int64_t wg_train_param_numel(const wg_handle* h, int32_t weight_normed, int32_t i) {
   if (!h) return 0;
-  const std::vector<ParamDesc> pl = param_list(*wg_internal_config(h), wg_internal_flow_channels(h), weight_normed != 0);
+  const std::vector<ParamDesc> pl = param_list(h->cfg, h->c_k.data(), weight_normed != 0);
   return (i < 0 || (size_t)i >= pl.size()) ? 0 : pl[i].numel;
 }
 
-size_t wg_train_prepare_bytes(const wg_handle* h) { return h ? prep_layout(*wg_internal_config(h)).bytes : 0; }
+size_t wg_train_prepare_bytes(const wg_handle* h) { return h ? prep_layout(h->cfg).bytes : 0; }
 
 int wg_train_prepare(wg_handle* h, const void* const* params, int32_t weight_normed, const wg_train_weights* out, void* aux,
                      size_t aux_bytes, void* stream) {
-  if (!out) return wg_set_error(WG_ERR_INVALID, "null argument");
+  if (!out) return fail(WG_ERR_INVALID, "null argument");
   if (!out->a1 || !out->a1c || !out->b1 || !out->a2 || !out->b2 || !out->es || !out->wat || !out->wbt || !out->wct || !out->wup ||
       !out->bup || !out->wstart || !out->bstart || !out->out_init || !out->w1x1)
-    return wg_set_error(WG_ERR_INVALID, "wg_train_prepare: wg_train_weights has a null member");
+    return fail(WG_ERR_INVALID, "wg_train_prepare: wg_train_weights has a null member");
   if (out->winv && h)
-    for (int k = 0; k < wg_internal_config(h)->n_flows; ++k)
-      if (!out->winv[k]) return wg_set_error(WG_ERR_INVALID, "wg_train_prepare: wg_train_weights.winv has a null per-flow pointer");
+    for (int k = 0; k < h->cfg.n_flows; ++k)
+      if (!out->winv[k]) return fail(WG_ERR_INVALID, "wg_train_prepare: wg_train_weights.winv has a null per-flow pointer");
   hipStream_t s = (hipStream_t)stream;
   PrepArgs pa;
   int rc = prep_args(h, params, weight_normed, out, nullptr, aux, aux_bytes, nullptr, s, pa);
   if (rc) return rc;
   TR_TRY(launch_prepare(pa, s));
-  const wg_config& c = *wg_internal_config(h);
+  const wg_config& c = h->cfg;
   const int C = c.n_channels, M8 = c.n_mel_channels * 8, FL = c.n_flows * c.n_layers, NW = wn_waves(C);
-  if (NW <= 0 || M8 % 64) return wg_set_error(WG_ERR_INVALID, "wg_train_prepare: unsupported channel counts");
+  if (NW <= 0 || M8 % 64) return fail(WG_ERR_INVALID, "wg_train_prepare: unsupported channel counts");
   const size_t K1 = 3 * (size_t)C + M8;
   PackArgs a;
   memset(&a, 0, sizeof a);
@@ -1465,8 +1422,8 @@ int wg_train_prepare(wg_handle* h, const void* const* params, int32_t weight_nor
 
 int wg_train_param_grads(wg_handle* h, const void* const* params, int32_t weight_normed, const wg_train_grads* grads, void* aux,
                          size_t aux_bytes, float* flat, void* stream) {
-  if (!grads || !flat) return wg_set_error(WG_ERR_INVALID, "null argument");
-  int rc = check_grads(grads, wg_internal_config(h) ? wg_internal_config(h)->n_flows : 0);
+  if (!grads || !flat) return fail(WG_ERR_INVALID, "null argument");
+  int rc = check_grads(grads, h ? h->cfg.n_flows : 0);
   if (rc) return rc;
   PrepArgs pa;
   rc = prep_args(h, params, weight_normed, nullptr, grads, aux, aux_bytes, flat, (hipStream_t)stream, pa);

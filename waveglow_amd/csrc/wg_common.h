@@ -52,21 +52,13 @@ struct RowGeom {
                        // t >= 32 * frames[b] of utterance b are padding: never written, so they read as the zero padding
                        // of the convolutions exactly as in a batch-of-one call.  null: every utterance has L columns.
 };
-#ifdef WG_ROWPAD                 // A/B builds only
-constexpr int kRowPad = WG_ROWPAD;
-#else
 constexpr int kRowPad = 16;      // zero slack rows in front of / behind every plane chunk (taps of the first / last tile reach up to
                                  // Gf <= 16 rows past it: the guard rows of a tile read as far outside as its valid rows do)
-#endif
 constexpr int kPhases = 32;
 
 // GEMM 1 of the inference layer on 16x16x32 MFMAs (wn_layer_kernel M16) for this tile shape: its A fragments are packed
 // differently (api.cpp wg_finalize packs both orders when a model can run either tile width)
-#ifdef WG_NO_M16                 // A/B builds only
-constexpr bool wn_frag16(int, int) { return false; }
-#else
 constexpr bool wn_frag16(int C, int BN) { return C == 256 && BN == 128; }
-#endif
 
 // First layer of a WN in the inference kernels: the residual input x_0 = W_start a0 + b_start (model.py:117) is rebuilt from
 // the a0 plane by one MFMA step of the epilogue (weights hi + lo fp16, WnLayerArgs::wStA), so flow_kernel does not write
