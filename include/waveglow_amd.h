@@ -158,6 +158,16 @@ size_t wg_stft_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples);
 int wg_stft_denoise(wg_stft* h, const float* audio, const float* bias_mag, float strength, float* audio_out,
                     float* mag0_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
                     void* stream);
+/* The denoiser for a batch of utterances of DIFFERENT lengths (Denoiser.forward per utterance, denoiser.py:51-57 on
+ * stft.py:134-198): `lens` is a device array of B sample counts, each a multiple of 256 in [1024, n_samples]; n_samples
+ * is the row pitch of audio / audio_out and sizes the workspace as in the uniform call.  Utterance b gets bit for bit what
+ * the uniform call with B = 1 and n_samples = lens[b] gives it: reflect padding about its own last sample, lens[b]/256 + 1
+ * frames, the window-sum-square of those frames, cropping to lens[b]; audio_out[b][lens[b]:] = 0.  lens is read by the
+ * kernels only (enqueue-only, nothing synchronised); a length outside the limits is treated as 0: that row comes out
+ * all zero (its mag0_out row is not written) and nothing is indexed with it. */
+int wg_stft_denoise_ragged(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag, float strength,
+                           float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* Mel front-end, TacotronSTFT.mel_spectrogram (src/waveglow/taco_stft.py:84-104): STFT magnitudes (reflect padding,
  * stft.py:141-152) x mel filterbank -> log(clamp(., 1e-5)).  audio [B][n_samples] fp32 device (any n_samples > 512),
@@ -165,6 +175,14 @@ int wg_stft_denoise(wg_stft* h, const float* audio, const float* bias_mag, float
 size_t wg_stft_mel_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples);
 int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out, int32_t B,
                 int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for a batch of utterances of DIFFERENT lengths (taco_stft.py:84-103 per utterance): `lens` is a device array
+ * of B sample counts, each in (512, n_samples]; n_samples is the row pitch of audio.  mel_out is
+ * [B][n_mel][n_samples/256 + 1]: columns below lens[b]/256 + 1 are bit for bit those of the uniform call on that
+ * utterance alone, the others are 0.  A length outside the limits is treated as 0 (row all zero).  No gradient variant.
+ * Workspace as in the uniform call.  Enqueue-only. */
+int wg_stft_mel_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
+                       float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                       void* stream);
 
 /* Mel front-end with an audio gradient, TacotronSTFT.mel_spectrogram_differentiable (taco_stft.py:84-104 without the
  * detach at :99; conv-STFT of stft.py:135-163).  Same arguments and n_samples rule as wg_stft_mel (n_mel <= 128).
@@ -180,6 +198,19 @@ int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel,
                               int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
 int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
                          int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- PCM finishing of a synthesised batch (src/waveglow/audio_utils.py:36-95, :132-138), no handle -----------------
+ * raw, denoised [B][n_samples] fp32 device (they may be the same array), lens device [B] sample counts (clamped to
+ * [0, n_samples]), n_samples a multiple of 8, arrays 16-byte aligned.  Per utterance b over [0, lens[b]):
+ *   stats_out[b] = {raw min, raw max, raw max|x|, denoised min, denoised max, denoised max|x|, f, 0} (8 floats, device);
+ *     f = 1 when a sample of either signal is NaN or infinite (the host functions' own asserts fail on such input), else 0.
+ *     is_overamp (audio_utils.py:132-138) is raw min < -1 or raw max > 1.
+ *   pcm_out[b] = int16 of convert_wav(normalize_wav(denoised[b])) (audio_utils.py:67-95, :36-64) in float32 arithmetic:
+ *     y = x / peak (IEEE division) unless peak is 1 or 0, then round-half-even of y * 32767; pcm_out[b][lens[b]:] = 0.
+ * Bit for bit the host functions' result.  Workspace: device memory for the per-chunk extrema.  Enqueue-only. */
+size_t wg_wav_finish_workspace_bytes(int32_t B);
+int wg_wav_finish(const float* raw, const float* denoised, const int32_t* lens, int16_t* pcm_out, float* stats_out,
+                  int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Multi-resolution STFT loss (spectral convergence + log-magnitude L1), fp32, with its backward ------------------
  * For resolution r = (n_fft, hop, win): X = STFT(x) with reflect padding by n_fft/2 and the window of `win` samples

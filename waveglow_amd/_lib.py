@@ -126,14 +126,21 @@ SIGNATURES = {
   "wg_stft_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
   "wg_stft_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
                                 C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_denoise_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stft_mel_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
   "wg_stft_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                             C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_mel_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stft_mel_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
   "wg_stft_mel_forward_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stft_mel_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_wav_finish_workspace_bytes": (C.c_size_t, [C.c_int32]),
+  "wg_wav_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                              C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stftloss_create": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_void_p), C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stftloss_destroy": (C.c_int, [C.c_void_p]),

@@ -22,6 +22,7 @@ from pathlib import Path
 
 import numpy as np
 import torch
+from scipy.io.wavfile import write as write_wav
 
 from .audio import float_to_wav, normalize_wav
 from .checkpoint import CheckpointWaveglow
@@ -122,19 +123,26 @@ def synthesize(ns, from_wav: bool = False) -> bool:
   bs = max(1, ns.batch_size)
   for i in range(0, len(todo), bs):
     chunk = todo[i:i + bs]
-    mels = []
-    for mel_path, _ in chunk:
+    if len(chunk) == 1:                                               # the reference-shaped path, one utterance
+      mel_path, wav_path = chunk[0]
       if from_wav:
-        mels.append(taco_stft.get_mel_tensor_from_file(mel_path).unsqueeze(0))
+        mel = taco_stft.get_mel_tensor_from_file(mel_path).unsqueeze(0)
       else:
-        mels.append(torch.FloatTensor(np.load(mel_path)).unsqueeze(0))
-    if len(mels) == 1:
-      results = [synth.infer(mels[0], sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=seed)]
-    else:
-      results = synth.infer_batch(mels, sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=seed)
-    for (_, wav_path), res in zip(chunk, results):
+        mel = torch.FloatTensor(np.load(mel_path)).unsqueeze(0)
+      res = synth.infer(mel, sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=seed)
       wav_path.parent.mkdir(parents=True, exist_ok=True)
       float_to_wav(normalize_wav(res.wav_denoised), wav_path, sample_rate=res.sampling_rate)
+      continue
+    # a batch: one mel call, one launch sequence, int16 samples back from the device (the same bytes as above)
+    if from_wav:
+      mel, frames = taco_stft.get_mel_tensors_from_files([p for p, _ in chunk])
+      mels = [mel[b, :, :frames[b]] for b in range(len(chunk))]
+    else:
+      mels = [torch.FloatTensor(np.load(p)) for p, _ in chunk]
+    results = synth.infer_batch_pcm(mels, sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=seed)
+    for (_, wav_path), res in zip(chunk, results):
+      wav_path.parent.mkdir(parents=True, exist_ok=True)
+      write_wav(filename=wav_path, rate=res.sampling_rate, data=res.pcm)
   return True
 
 

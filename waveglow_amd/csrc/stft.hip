@@ -21,17 +21,32 @@ constexpr int kMT = kRows / 32;        // 33
 // of a B-fragment read (same k, frames 256 apart) hit 32 different banks
 __device__ __forceinline__ int seg_idx(int pos) { return pos + (pos >> 8); }
 
+// Sample count of utterance b in a ragged batch (wg_stft_denoise_ragged, wg_stft_mel_ragged).  A length the entry point
+// does not allow (below min_len, above the row pitch, or with bits of mask set) counts as 0: the row comes out all zero
+// and nothing is indexed with it.
+__device__ __forceinline__ int ragged_len(const int* lens, int b, int pitch, int min_len, int mask) {
+  const int n = lens[b];
+  return (n < min_len || n > pitch || (n & mask)) ? 0 : n;
+}
+__device__ __forceinline__ int ragged_frames(int n) { return n ? n / kHop + 1 : 0; }
+
 __global__ void __launch_bounds__(512) stft_kernel(const StftArgs a) {
   __shared__ float seg[8960 + 40];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int f0 = blockIdx.x * 32, b = blockIdx.y;
   const float* x = a.audio + (size_t)b * a.N;
+  int N = a.N, F = a.F;                                 // this utterance's samples and frames; a.N / a.F are the pitches
+  if (a.lens) {
+    N = ragged_len(a.lens, b, a.N, a.min_len, a.len_mask);
+    F = ragged_frames(N);
+    if (f0 >= F) return;                                // tile wholly behind the utterance: its columns stay zero
+  }
   for (int i = tid; i < 8960; i += 512) {
     int s = f0 * kHop + i - kFL / 2;                    // audio index of padded position (reflect, stft.py:141-147)
     if (s < 0) s = -s;
-    if (s >= a.N) s = 2 * (a.N - 1) - s;
-    seg[seg_idx(i)] = (s >= 0 && s < a.N) ? x[s] : 0.0f;
+    if (s >= N) s = 2 * (N - 1) - s;
+    seg[seg_idx(i)] = (s >= 0 && s < N) ? x[s] : 0.0f;
   }
   __syncthreads();
   constexpr int TPWV = 5;                               // M tiles per wave (wave w: w, w+8, ...; 33 tiles)
@@ -65,7 +80,7 @@ __global__ void __launch_bounds__(512) stft_kernel(const StftArgs a) {
       for (int e = 0; e < 2; ++e) {
         const int bin = row0 / 2 + e;
         float re = acc[t][4 * g + 2 * e], im = acc[t][4 * g + 2 * e + 1];
-        if (bin < kCut && f < a.F) {
+        if (bin < kCut && f < F) {
           const float mag = sqrtf(re * re + im * im);
           if (a.mag0 && f == 0) a.mag0[(size_t)b * kCut + bin] = mag;
           if (a.mag) a.mag[((size_t)b * kCut + bin) * a.F + f] = mag;
@@ -94,6 +109,21 @@ __global__ void __launch_bounds__(512) istft_kernel(const IstftArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // M tile: output phase r in [32w, 32w+32)
   const int q0 = blockIdx.x * 32, b = blockIdx.y;
   const int col = lane & 31, kk = lane >> 5;
+  int N = a.N, F = a.F;                                   // this utterance's samples and frames; a.N is the row pitch
+  if (!kGrad && a.lens) {
+    N = ragged_len(a.lens, b, a.N, kFL, kHop - 1);
+    F = ragged_frames(N);
+    if (q0 * kHop - kFL / 2 >= N) {                       // tile wholly behind the utterance: zeros, no GEMM
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int o = (q0 + col) * kHop + wave * 32 + 8 * g + 4 * kk + e - kFL / 2;
+          if (o < a.N) a.out[(size_t)b * a.N + o] = 0.0f;
+        }
+      return;
+    }
+  }
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -122,11 +152,15 @@ __global__ void __launch_bounds__(512) istft_kernel(const IstftArgs a) {
         continue;
       }
       if (o < 0 || o >= a.N) continue;
+      if (o >= N) {                                       // ragged batch: zeros behind the utterance
+        a.out[(size_t)b * a.N + o] = 0.0f;
+        continue;
+      }
       float ws = 0.0f;                                    // window_sumsquare at n (stft.py:45-95)
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
         const int fr = q - jj;
-        if (fr >= 0 && fr < a.F) ws += a.win_sq[r + kHop * jj];
+        if (fr >= 0 && fr < F) ws += a.win_sq[r + kHop * jj];
       }
       float v = acc[4 * g + e];
       if (ws > 1.17549435e-38f) v /= ws;                  // tiny(float32)
@@ -143,7 +177,16 @@ __global__ void __launch_bounds__(256) mel_kernel(const MelArgs a) {
   float acc[32];
 #pragma unroll
   for (int i = 0; i < 32; ++i) acc[i] = 0.0f;
-  const float* mp = a.mag + (size_t)b * kCut * a.F + (f < a.F ? f : a.F - 1);
+  int F = a.F;                                            // this utterance's frames; a.F is the row pitch
+  if (a.lens) {
+    F = ragged_frames(ragged_len(a.lens, b, a.N, kFL / 2 + 1, 0));
+    if ((int)blockIdx.x * 64 >= F) {                      // block wholly behind the utterance: zeros, magnitudes unread
+      if (f < a.F)
+        for (int m = grp; m < a.n_mel; m += 4) a.mel[((size_t)b * a.n_mel + m) * a.F + f] = 0.0f;
+      return;
+    }
+  }
+  const float* mp = a.mag + (size_t)b * kCut * a.F + (f < F ? f : F - 1);
   for (int k = 0; k < kCut; ++k) {
     const float v = mp[(size_t)k * a.F];
 #pragma unroll
@@ -157,7 +200,7 @@ __global__ void __launch_bounds__(256) mel_kernel(const MelArgs a) {
   for (int i = 0; i < 32; ++i) {
     const int m = grp * per + i;
     if (i < per && m < a.n_mel) {
-      a.mel[((size_t)b * a.n_mel + m) * a.F + f] = logf(fmaxf(acc[i], 1e-5f));
+      a.mel[((size_t)b * a.n_mel + m) * a.F + f] = f < F ? logf(fmaxf(acc[i], 1e-5f)) : 0.0f;
       if (a.pre) a.pre[((size_t)b * a.n_mel + m) * a.F + f] = acc[i];
     }
   }

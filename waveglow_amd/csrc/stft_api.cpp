@@ -73,10 +73,10 @@ size_t wg_stft_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples) {
   return (size_t)B * kRows * frames_padded(F) * 4;
 }
 
-int wg_stft_denoise(wg_stft* h, const float* audio, const float* bias_mag, float strength, float* audio_out,
-                    float* mag0_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                    void* stream) {
-  if (!h || !audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
+// lens == nullptr: every row has n_samples samples.  Otherwise lens is a device array read by the kernels only.
+static int denoise(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag, float strength,
+                   float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
+                   size_t workspace_bytes, void* stream) {
   if (B < 1 || n_samples < kFL || n_samples % kHop)
     return fail(WG_ERR_INVALID, "n_samples must be a multiple of 256 and >= 1024");
   const size_t need = wg_stft_workspace_bytes(h, B, n_samples);
@@ -84,13 +84,30 @@ int wg_stft_denoise(wg_stft* h, const float* audio, const float* bias_mag, float
   hipStream_t s = (hipStream_t)stream;
   const int F = n_samples / kHop + 1, Fs = frames_padded(F);
   HIP_TRY(hipMemsetAsync(workspace, 0, need, s));           // zero lead/tail columns and pad rows
-  StftArgs a{audio, h->d_fwdA, bias_mag, strength, (float*)workspace, mag0_out, n_samples, F, Fs, nullptr};
+  StftArgs a{audio, h->d_fwdA, bias_mag, strength, (float*)workspace, mag0_out, n_samples, F, Fs, nullptr,
+             lens, kFL, kHop - 1};
   HIP_TRY(launch_stft(a, B, s));
   if (audio_out) {
-    IstftArgs b{(const float*)workspace, h->d_invA, h->d_win, audio_out, n_samples, F, Fs};
+    IstftArgs b{(const float*)workspace, h->d_invA, h->d_win, audio_out, n_samples, F, Fs, nullptr, lens};
     HIP_TRY(launch_istft(b, B, s));
   }
   return WG_OK;
+}
+
+int wg_stft_denoise(wg_stft* h, const float* audio, const float* bias_mag, float strength, float* audio_out,
+                    float* mag0_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  if (!h || !audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
+  return denoise(h, audio, nullptr, bias_mag, strength, audio_out, mag0_out, B, n_samples, workspace, workspace_bytes,
+                 stream);
+}
+
+int wg_stft_denoise_ragged(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag, float strength,
+                           float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  if (!h || !audio || !lens || !workspace) return fail(WG_ERR_INVALID, "null argument");
+  return denoise(h, audio, lens, bias_mag, strength, audio_out, mag0_out, B, n_samples, workspace, workspace_bytes,
+                 stream);
 }
 
 size_t wg_stft_mel_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples) {
@@ -98,19 +115,32 @@ size_t wg_stft_mel_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_sample
   return (size_t)B * kCut * (n_samples / kHop + 1) * 4;
 }
 
-int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out, int32_t B,
-                int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h || !mel_basis || !audio || !mel_out || !workspace) return fail(WG_ERR_INVALID, "null argument");
+static int mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
+               float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
   const size_t need = wg_stft_mel_workspace_bytes(h, B, n_samples);
   if (!need || n_mel < 1 || n_mel > 128) return fail(WG_ERR_INVALID, "bad B / n_samples / n_mel");
   if (workspace_bytes < need) return fail(WG_ERR_WORKSPACE, "mel workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int F = n_samples / kHop + 1;                             // stft.py:141-152: reflect pad filter/2 both sides
-  StftArgs a{audio, h->d_fwdA, nullptr, 0.0f, nullptr, nullptr, n_samples, F, 0, (float*)workspace};
+  StftArgs a{audio, h->d_fwdA, nullptr, 0.0f, nullptr, nullptr, n_samples, F, 0, (float*)workspace,
+             lens, kFL / 2 + 1, 0};
   HIP_TRY(launch_stft(a, B, s));
-  MelArgs m{(const float*)workspace, mel_basis, mel_out, n_mel, F};
+  MelArgs m{(const float*)workspace, mel_basis, mel_out, n_mel, F, nullptr, lens, n_samples};
   HIP_TRY(launch_mel(m, B, s));
   return WG_OK;
+}
+
+int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out, int32_t B,
+                int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h || !mel_basis || !audio || !mel_out || !workspace) return fail(WG_ERR_INVALID, "null argument");
+  return mel(h, mel_basis, n_mel, audio, nullptr, mel_out, B, n_samples, workspace, workspace_bytes, stream);
+}
+
+int wg_stft_mel_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
+                       float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+  if (!h || !mel_basis || !audio || !lens || !mel_out || !workspace) return fail(WG_ERR_INVALID, "null argument");
+  return mel(h, mel_basis, n_mel, audio, lens, mel_out, B, n_samples, workspace, workspace_bytes, stream);
 }
 
 // Mel-gradient workspace, in floats: [rec | gX | edge] (zeroed by the call that fills it) then [mag | pre].

@@ -18,6 +18,8 @@ struct StftArgs {
   float* mag0;             // optional [B][513]: magnitude of frame 0
   int N, F, Fs;
   float* mag;              // optional [B][513][F]: all magnitudes (mel front-end); rec may then be null
+  const int* lens;         // ragged batch: device [B] sample counts (N is then the row pitch, F the frames of N) or null
+  int min_len, len_mask;   // ragged batch: a length < min_len, > N or with (length & len_mask) != 0 counts as 0
 };
 struct MelArgs {
   const float* mag;        // [B][513][F]
@@ -25,6 +27,8 @@ struct MelArgs {
   float* mel;              // [B][n_mel][F]  log(clamp(basis . mag, 1e-5))   (taco_stft.py:10-16, :99-104)
   int n_mel, F;
   float* pre;              // optional [B][n_mel][F]: the pre-log sums basis . mag (saved for the backward)
+  const int* lens;         // ragged batch: device [B] sample counts (columns behind an utterance's frames are 0) or null
+  int N;                   // ragged batch: row pitch of the audio, the upper limit of a length
 };
 struct IstftArgs {
   const float* rec;        // [B][1056][Fs]
@@ -33,6 +37,7 @@ struct IstftArgs {
   float* out;              // [B][N]
   int N, F, Fs;
   float* edge;             // grad only: [B][1024] padded positions 0..511 and N+512..N+1023
+  const int* lens;         // inverse only, ragged batch: device [B] sample counts (out[b][lens[b]:] = 0) or null
 };
 struct MelBwdArgs {
   const float* g;          // [B][n_mel][F]  d mel

@@ -80,9 +80,36 @@ class Denoiser(torch.nn.Module):
                                         mag0.data_ptr() if mag0 is not None else None, B, N, ws.data_ptr(),
                                         ws.numel(), C.c_void_p(stream)))
 
-  def forward(self, audio: torch.Tensor, strength: float):
-    """denoiser.py:51-57; returns [B, 1, N] like the reference's conv_transpose1d output."""
+  def forward(self, audio: torch.Tensor, strength: float, lengths=None):
+    """denoiser.py:51-57; returns [B, 1, N] like the reference's conv_transpose1d output.
+
+    ``lengths`` (a list or an int tensor [B] of sample counts) makes the rows of ``audio`` [B, N] utterances of
+    different lengths, denoised in ONE call: utterance b comes out bit for bit as ``forward(audio[b:b+1, :lengths[b]])``
+    gives it, with zeros behind it.  Every length is a multiple of 256 in [1024, N], as for the call without lengths."""
     audio = audio.float()
     out = torch.empty_like(audio)
-    self._run(audio, self.bias_spec.reshape(-1).contiguous(), strength, out, None)
+    if lengths is None:
+      self._run(audio, self.bias_spec.reshape(-1).contiguous(), strength, out, None)
+    else:
+      lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+      self.run_ragged(audio, lengths, torch.tensor(lengths, dtype=torch.int32).to(audio.device), strength, out)
     return out[:, None, :]
+
+  def run_ragged(self, audio, lengths, lengths_dev, strength, out):
+    """One wg_stft_denoise_ragged call on fp32 ``audio`` [B, N] into ``out``; ``lengths`` is checked here on the host,
+    ``lengths_dev`` is the same as an int32 tensor on the device (the library never reads it on the host)."""
+    audio = audio.contiguous()
+    B, N = audio.shape
+    if len(lengths) != B:
+      raise _lib.WgError(f"denoiser: {len(lengths)} lengths for a batch of {B}")
+    for n in lengths:
+      if n < 1024 or n % 256 or n > N:
+        raise _lib.WgError(f"denoiser: unsupported utterance length {n} (multiple of 256, >= 1024, <= {N})")
+    nbytes = self.lib.wg_stft_workspace_bytes(self._h, B, N)
+    if nbytes == 0:
+      raise _lib.WgError(f"denoiser: unsupported audio length {N} (multiple of 256, >= 1024)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
+    stream = torch.cuda.current_stream(audio.device).cuda_stream
+    _lib.check(self.lib.wg_stft_denoise_ragged(self._h, audio.data_ptr(), lengths_dev.data_ptr(),
+                                               self.bias_spec.data_ptr(), float(strength), out.data_ptr(), None, B, N,
+                                               ws.data_ptr(), ws.numel(), C.c_void_p(stream)))

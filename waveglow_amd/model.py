@@ -334,7 +334,9 @@ class WaveGlow(nn.Module):
     if frames is not None:
       fr = frames.to(device=spect.device, dtype=torch.int32).contiguous()
       assert fr.shape == (B,)
-      if not torch.cuda.is_current_stream_capturing():
+      if frames.device.type == "cpu":                      # checked where the values are: no device synchronise
+        assert int(frames.min()) >= 1 and int(frames.max()) <= T
+      elif not torch.cuda.is_current_stream_capturing():
         assert int(fr.min()) >= 1 and int(fr.max()) <= T
     _lib.check(eng.lib.wg_infer_ragged(eng.handle, spect.data_ptr(), fr.data_ptr() if fr is not None else None,
                                        z_init.data_ptr(), ze, len(z_early), float(sigma), audio.data_ptr(), B, T, io,

@@ -12,6 +12,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import pcm
 from .audio import is_overamp
 from .checkpoint import CheckpointWaveglow
 from .denoiser import Denoiser
@@ -51,6 +52,18 @@ class InferenceResult:
   timepoint: datetime.datetime
 
 
+@dataclass
+class PcmResult:
+  """One utterance of ``Synthesizer.infer_batch_pcm``: the samples that go into the wav file."""
+  pcm: np.ndarray               # int16, 256 * T samples: convert_wav(normalize_wav(denoised audio), int16)
+  sampling_rate: int
+  was_overamplified: bool       # of the raw audio, as InferenceResult.was_overamplified
+  peak: float                   # max |x| of the denoised audio, the value the normalisation divided by
+  inference_duration_s: float
+  denoising_duration_s: float
+  timepoint: datetime.datetime
+
+
 def load_model(hparams, state_dict: Optional[dict], device: torch.device) -> WaveGlow:
   """src/waveglow/train.py:48-55 (without the silent CPU fallback of try_copy_to: the kernels need the GPU)."""
   model = WaveGlow(hparams).to(device)
@@ -70,6 +83,7 @@ class Synthesizer:
     model = WaveGlow.remove_weightnorm(model).eval()
     self.device, self.hparams, self.model = device, hparams, model
     self.denoiser = Denoiser(waveglow=model, hparams=hparams, mode="zeros", device=device).to(device)
+    self._pinned = None          # host staging buffer of infer_batch_pcm, grown on demand
 
   def infer(self, mel: torch.Tensor, *, sigma: float = 1.0, denoiser_strength: float = 0.0005,
             seed: int = 0) -> InferenceResult:
@@ -97,14 +111,12 @@ class Synthesizer:
                            inference_duration_s=end - start, denoising_duration_s=denoising_duration,
                            was_overamplified=over, timepoint=timepoint)
 
-  def infer_batch(self, mels, *, sigma: float = 1.0, denoiser_strength: float = 0.0005, seed: int = 0):
-    """Several mel-spectrograms ``[1 or -, n_mel, T_i]`` of different lengths in ONE ragged launch sequence (the
-    reference's commented-out ``--batch-size``, inference_v2.py:64).  Every utterance gets the audio that ``infer`` on
-    it alone would return with the same seed: its noise is drawn exactly as that call draws it (seed reset, then the
-    three tensors in the reference's order and shapes, model.py:234-271), and the kernels treat the padding behind an
-    utterance as the end of the sequence (``wg_infer_ragged``).  Returns one InferenceResult per utterance; the
-    durations are the batch's, divided evenly."""
-    timepoint = datetime.datetime.now()
+  def _infer_batch_device(self, mels, sigma, denoiser_strength, seed):
+    """The device work of a ragged batch, enqueued without a synchronise: noise drawn per utterance exactly as ``infer``
+    draws it (seed reset, then the three tensors in the reference's order and shapes, model.py:234-271), one
+    ``wg_infer_ragged`` sequence and, for a strength above 0, one ragged denoiser call.  Returns the raw fp32 audio
+    [B, 256 Tmax], the denoised audio (the raw tensor itself at strength 0), the frame counts, the sample counts as an
+    int32 tensor on the device and three events: before the flow, behind it, behind the denoiser."""
     mels = [m.squeeze(0) if m.dim() == 3 else m for m in mels]
     B = len(mels)
     lens = [int(m.shape[1]) for m in mels]
@@ -116,6 +128,7 @@ class Synthesizer:
     z_init = torch.zeros((B, model.n_remaining_channels, Tm * 256 // ng), dtype=dtype, device=dev)
     early = [k for k in reversed(range(model.n_flows)) if k % model.n_early_every == 0 and k > 0]
     z_early = [torch.zeros((B, model.n_early_size, Tm * 256 // ng), dtype=dtype, device=dev) for _ in early]
+    samples_dev = torch.tensor([256 * t for t in lens], dtype=torch.int32).to(dev)
     for b, m in enumerate(mels):
       L = lens[b] * 256 // ng
       mel[b, :, :lens[b]] = m.to(dev)
@@ -123,23 +136,59 @@ class Synthesizer:
       z_init[b, :, :L] = torch.empty((1, model.n_remaining_channels, L), dtype=dtype, device=dev).normal_()[0]
       for j in range(len(early)):
         z_early[j][b, :, :L] = torch.empty((1, model.n_early_size, L), dtype=dtype, device=dev).normal_()[0]
-    start = time.perf_counter()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    stream = torch.cuda.current_stream(dev)
     with torch.no_grad():
-      audio = model.infer_with_noise(mel, z_init, z_early, sigma, frames=torch.tensor(lens, dtype=torch.int32))
-      torch.cuda.synchronize(dev)
-      end = time.perf_counter()
-      t0 = time.perf_counter()
-      outs = []
-      for b in range(B):
-        a = audio[b:b + 1, :256 * lens[b]]
-        d = self.denoiser(a.contiguous(), strength=denoiser_strength) if denoiser_strength > 0 else a
-        outs.append((a, d))
-      torch.cuda.synchronize(dev)
-      den = time.perf_counter() - t0 if denoiser_strength > 0 else 0
+      ev[0].record(stream)
+      audio = model.infer_with_noise(mel, z_init, z_early, sigma, frames=torch.tensor(lens, dtype=torch.int32)).float().contiguous()
+      ev[1].record(stream)
+      den = audio
+      if denoiser_strength > 0:
+        den = torch.empty_like(audio)
+        self.denoiser.run_ragged(audio, [256 * t for t in lens], samples_dev, denoiser_strength, den)
+      ev[2].record(stream)
+    return audio, den, lens, samples_dev, ev
+
+  def infer_batch(self, mels, *, sigma: float = 1.0, denoiser_strength: float = 0.0005, seed: int = 0):
+    """Several mel-spectrograms ``[1 or -, n_mel, T_i]`` of different lengths in ONE ragged launch sequence (the
+    reference's commented-out ``--batch-size``, inference_v2.py:64).  Every utterance gets the audio that ``infer`` on
+    it alone would return with the same seed: its noise is drawn exactly as that call draws it, and the kernels treat the
+    padding behind an utterance as the end of the sequence (``wg_infer_ragged``, ``wg_stft_denoise_ragged``).  Returns
+    one InferenceResult per utterance; the durations are the batch's on the device, divided evenly."""
+    timepoint = datetime.datetime.now()
+    audio, den, lens, _, ev = self._infer_batch_device(mels, sigma, denoiser_strength, seed)
+    B = len(lens)
+    audio_np = audio.cpu().numpy()
+    den_np = den.cpu().numpy() if den is not audio else audio_np
+    inf_s = ev[0].elapsed_time(ev[1]) / 1e3
+    den_s = ev[1].elapsed_time(ev[2]) / 1e3 if denoiser_strength > 0 else 0
     res = []
-    for a, d in outs:
-      a_np, d_np = a.squeeze().float().cpu().numpy(), d.squeeze().float().cpu().numpy()
+    for b in range(B):
+      a_np, d_np = audio_np[b, :256 * lens[b]].copy(), den_np[b, :256 * lens[b]].copy()
       res.append(InferenceResult(wav=a_np, wav_denoised=d_np, sampling_rate=self.hparams.sampling_rate,
-                                 inference_duration_s=(end - start) / B, denoising_duration_s=den / B,
+                                 inference_duration_s=inf_s / B, denoising_duration_s=den_s / B,
                                  was_overamplified=bool(is_overamp(a_np)), timepoint=timepoint))
     return res
+
+  def infer_batch_pcm(self, mels, *, sigma: float = 1.0, denoiser_strength: float = 0.0005, seed: int = 0):
+    """``infer_batch`` finished to int16 on the device (``wg_wav_finish``): behind the noise draws the batch is one
+    launch sequence, and ONE copy (the int16 samples and the statistics, through a pinned buffer) and one synchronise
+    bring it to the host.  Returns one PcmResult per utterance; ``pcm`` equals
+    ``convert_wav(normalize_wav(r.wav_denoised), np.int16)`` of the corresponding ``infer_batch`` result bit for bit.
+    An utterance with NaN or infinite samples raises WgError."""
+    timepoint = datetime.datetime.now()
+    audio, den, lens, samples_dev, ev = self._infer_batch_device(mels, sigma, denoiser_strength, seed)
+    B, N = audio.shape
+    out = pcm.finish_enqueue(audio, den, samples_dev)
+    if self._pinned is None or self._pinned.numel() < out.numel():
+      self._pinned = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
+    host = self._pinned[:out.numel()]
+    host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream(self.device).synchronize()
+    samples, stats = pcm.finish_read(host, B, N)
+    inf_s = ev[0].elapsed_time(ev[1]) / 1e3
+    den_s = ev[1].elapsed_time(ev[2]) / 1e3 if denoiser_strength > 0 else 0
+    return [PcmResult(pcm=samples[b, :256 * lens[b]].copy(), sampling_rate=self.hparams.sampling_rate,
+                      was_overamplified=bool(stats[b, pcm.RAW_MIN] < -1.0 or stats[b, pcm.RAW_MAX] > 1.0),
+                      peak=float(stats[b, pcm.DEN_PEAK]), inference_duration_s=inf_s / B,
+                      denoising_duration_s=den_s / B, timepoint=timepoint) for b in range(B)]

@@ -163,6 +163,39 @@ class TacotronSTFT(torch.nn.Module):
                                     out.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     return out
 
+  def mel_spectrogram_ragged(self, wavs):
+    """``mel_spectrogram`` of several utterances of different lengths in one upload and one ``wg_stft_mel_ragged`` call.
+
+    ``wavs``: 1-D float32 CPU tensors in [-1, 1], each longer than 512 samples.  Returns ``(mel, frames)``: ``mel``
+    [B, n_mel_channels, Tmax] on the module's device, ``frames[b] = len(wavs[b]) // 256 + 1``; ``mel[b, :, :frames[b]]``
+    is bit for bit ``mel_spectrogram(wavs[b][None])[0]`` and the columns behind it are 0.  The reference's range assert
+    (taco_stft.py:95-97) runs on the host before the upload, so nothing on the device is synchronised.  No graph."""
+    if len(wavs) == 0:
+      raise _lib.WgError("mel_spectrogram_ragged: empty batch")
+    lens = []
+    for w in wavs:
+      if not isinstance(w, torch.Tensor) or w.device.type != "cpu" or w.dtype != torch.float32 or w.dim() != 1:
+        raise _lib.WgError("mel_spectrogram_ragged takes 1-D float32 CPU tensors")
+      if w.numel() <= 512:
+        raise _lib.WgError(f"mel front-end: audio of {w.numel()} samples is too short (reflect padding needs > 512)")
+      assert float(w.min()) >= FLOAT32_64_MIN_WAV and float(w.max()) <= FLOAT32_64_MAX_WAV   # taco_stft.py:95-97
+      lens.append(int(w.numel()))
+    B, N = len(wavs), max(lens)
+    host = torch.zeros(4 * (B * N + B), dtype=torch.uint8)           # padded audio, then the lengths: one upload
+    audio = host[:4 * B * N].view(torch.float32).view(B, N)
+    for b, w in enumerate(wavs):
+      audio[b, :lens[b]] = w
+    host[4 * B * N:].view(torch.int32).copy_(torch.tensor(lens, dtype=torch.int32))
+    dev = host.to(self.device)
+    y, lens_dev = dev[:4 * B * N], dev[4 * B * N:]
+    out = torch.empty((B, self.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=self.device)
+    ws = torch.empty(self.lib.wg_stft_mel_workspace_bytes(self._h, B, N), dtype=torch.uint8, device=self.device)
+    stream = torch.cuda.current_stream(self.device).cuda_stream
+    _lib.check(self.lib.wg_stft_mel_ragged(self._h, self.mel_basis.data_ptr(), self.n_mel_channels, y.data_ptr(),
+                                           lens_dev.data_ptr(), out.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
+                                           C.c_void_p(stream)))
+    return out, [n // 256 + 1 for n in lens]
+
   def mel_spectrogram_differentiable(self, y: torch.Tensor) -> torch.Tensor:
     """``mel_spectrogram(y)`` with an autograd graph back to ``y`` (taco_stft.py:84-104 without the detach at :99).
 
@@ -190,6 +223,10 @@ class TacotronSTFT(torch.nn.Module):
 
   def get_mel_tensor_from_file(self, wav_path) -> torch.Tensor:
     return self.get_mel_tensor(self.get_wav_tensor_from_file(wav_path))
+
+  def get_mel_tensors_from_files(self, wav_paths):
+    """``mel_spectrogram_ragged`` of wav files (each checked like ``get_wav_tensor_from_file``): ``(mel, frames)``."""
+    return self.mel_spectrogram_ragged([self.get_wav_tensor_from_file(p) for p in wav_paths])
 
   def get_mel_tensor(self, wav_tensor: torch.Tensor) -> torch.Tensor:
     return self.mel_spectrogram(wav_tensor.unsqueeze(0)).squeeze(0)
