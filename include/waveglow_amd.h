@@ -212,6 +212,33 @@ size_t wg_wav_finish_workspace_bytes(int32_t B);
 int wg_wav_finish(const float* raw, const float* denoised, const int32_t* lens, int16_t* pcm_out, float* stats_out,
                   int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Validation metrics of mel-spectrogram pairs (src/waveglow/validation.py:211-235), no handle --------------------
+ * Ragged batches: arrays [B][C][tmax] fp32 device, frame counts int32 device [B], read by the kernels only.  A frame
+ * count outside [1, min(tmax, 4096)] counts as 0: that utterance's MFCC columns are all 0 and its metrics NaN.  fp64
+ * arithmetic without contraction, every sum in a fixed order, no atomics: a call gives the same bits every time, and an
+ * utterance of a batch the bits of its own call with B = 1 and tmax = its frame count.  Enqueue-only.
+ * wg_metrics_mfcc: mfcc_out[b][k-1][t] = fp32 of sum_{n ascending} mel[b][n][t] sqrt(2/N) cos(pi k (2n+1) / (2N)),
+ *   k = 1..n_mfcc, N = n_mel (orthonormal DCT-II over the mel axis without coefficient 0; no logarithm is taken);
+ *   0 behind an utterance's frames.  1 <= n_mfcc < n_mel <= 128, 1 <= tmax <= 4096.
+ * wg_metrics_dtw: exact dynamic time warping of feat_a[b] [K][tmax_a] against feat_b[b] [K][tmax_b], 1 <= K <= 128,
+ *   1 <= tmax <= 4096.  d(i,j) = sqrt(sum_{k ascending} (a[k][i] - b[k][j])^2); C(0,0) = d(0,0), L(0,0) = 1; otherwise
+ *   C(i,j) = d(i,j) + C(pred), L(i,j) = L(pred) + 1 with pred the first minimal of (i-1,j), (i,j-1), (i-1,j-1).
+ *   cost_out[b] = C(Ta-1, Tb-1) (fp64), frames_out[b] = L(Ta-1, Tb-1) (int32; 0 with a NaN cost for a refused count).
+ * wg_metrics_mel: the two above chained on the MFCCs of both mels, plus the padded comparison (F = max(Ta, Tb), the
+ *   shorter one's MFCCs / mel 0 behind its end).  rows_out[b] = 8 fp64:
+ *     {mcd = mean_t |fa_t - fb_t|_2, penalty = 2 - (Ta+Tb)/F, F, mcd_dtw = C/L, penalty_dtw = 2 - (Ta+Tb)/L, L,
+ *      cosine = 1 - mean_c (1 - u.v / (|u| |v|)) over the mel channels (score 1 where |u| |v| = 0), 0}.
+ * Workspace: wg_metrics_workspace_bytes (0 for arguments outside the limits) serves all three with the same sizes. */
+size_t wg_metrics_workspace_bytes(int32_t B, int32_t n_mel, int32_t n_mfcc, int32_t tmax_a, int32_t tmax_b);
+int wg_metrics_mfcc(const float* mel, const int32_t* frames, float* mfcc_out, int32_t B, int32_t n_mel, int32_t n_mfcc,
+                    int32_t tmax, void* workspace, size_t workspace_bytes, void* stream);
+int wg_metrics_dtw(const float* feat_a, const int32_t* frames_a, const float* feat_b, const int32_t* frames_b,
+                   double* cost_out, int32_t* frames_out, int32_t B, int32_t K, int32_t tmax_a, int32_t tmax_b,
+                   void* stream);
+int wg_metrics_mel(const float* mel_a, const int32_t* frames_a, const float* mel_b, const int32_t* frames_b,
+                   double* rows_out, int32_t B, int32_t n_mel, int32_t n_mfcc, int32_t tmax_a, int32_t tmax_b,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Multi-resolution STFT loss (spectral convergence + log-magnitude L1), fp32, with its backward ------------------
  * For resolution r = (n_fft, hop, win): X = STFT(x) with reflect padding by n_fft/2 and the window of `win` samples
  * centred in n_fft, M = sqrt(max(re^2 + im^2, eps)); sc_r = |M(y) - M(x)|_F / |M(y)|_F over the whole batch,

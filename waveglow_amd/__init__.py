@@ -21,6 +21,12 @@ def __getattr__(name):
   if name == "MultiResolutionSTFTLoss":
     from .stft_loss import MultiResolutionSTFTLoss
     return MultiResolutionSTFTLoss
+  if name in ("mel_metrics", "MelMetrics"):
+    from . import metrics
+    return getattr(metrics, name)
+  if name in ("validate", "ValidationEntry", "ValidationEntries"):
+    from . import validation
+    return getattr(validation, name)
   if name == "Denoiser":
     from .denoiser import Denoiser
     return Denoiser

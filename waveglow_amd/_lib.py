@@ -141,6 +141,13 @@ SIGNATURES = {
   "wg_wav_finish_workspace_bytes": (C.c_size_t, [C.c_int32]),
   "wg_wav_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_metrics_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+  "wg_metrics_mfcc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_metrics_dtw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+  "wg_metrics_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stftloss_create": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_void_p), C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stftloss_destroy": (C.c_int, [C.c_void_p]),

@@ -9,6 +9,12 @@ commented-out ``--batch-size``, inference_v2.py:64) and per-rank sharding of the
   python -m waveglow_amd.cli train TRAIN-FOLDER VAL-FOLDER CHECKPOINTS-FOLDER [--device cuda:0] [--custom-hparams ...]
          [--pre-trained-model CKPT --warm-start]                     (src/waveglow_cli/training.py:24-79)
   python -m waveglow_amd.cli continue-train TRAIN-FOLDER VAL-FOLDER CHECKPOINTS-FOLDER [...]   (training.py:82-124)
+  python -m waveglow_amd.cli validate CHECKPOINTS-FOLDER OUTPUT-FOLDER DATA-FOLDER [--sigma S] [--denoiser-strength D]
+         [--device cuda:0] [--custom-hparams ...] [--full-run] [--files NAME ...] [--custom-checkpoints IT ...]
+         [--custom-seed N] [--batch-size B]                          (src/waveglow_cli/validation.py:86-153)
+         copy synthesis of validation utterances and their metrics on the device (MCD, DTW-MCD, penalties, cosine
+         similarity): OUTPUT-FOLDER/log.txt, total.csv and one folder of mels and wavs per utterance and checkpoint;
+         no PNG plots and no structural similarity, single process only
 Under ``python -m torch.distributed.run`` the training commands run data-parallel (one process per GPU, RCCL).
 """
 from __future__ import annotations
@@ -65,6 +71,22 @@ def build_parser() -> argparse.ArgumentParser:
     if name == "train":
       t.add_argument("--pre-trained-model", type=Path, default=None)
       t.add_argument("--warm-start", action="store_true")
+  v = sub.add_parser("validate", description="Validate checkpoint(s) using the validation set or any other dataset.")
+  v.add_argument("checkpoints_dir", type=Path, metavar="CHECKPOINTS-FOLDER")
+  v.add_argument("output_dir", type=Path, metavar="OUTPUT-FOLDER")
+  v.add_argument("dataset_dir", type=Path, metavar="DATA-FOLDER")
+  v.add_argument("--sigma", type=_unit_float, default=1.0)
+  v.add_argument("--denoiser-strength", type=_unit_float, default=0.0005)
+  v.add_argument("--device", type=str, default="cuda:0")
+  v.add_argument("--custom-hparams", type=str, default=None)
+  v.add_argument("--full-run", action="store_true", help="validate all files in DATA-FOLDER")
+  v.add_argument("--files", type=str, nargs="*", metavar="UTTERANCE", default=[],
+                 help="names of utterances in DATA-FOLDER; if left unset a random utterance is chosen")
+  v.add_argument("--custom-checkpoints", type=int, nargs="*", default=[],
+                 help="validate the checkpoints of these iterations; if left unset the last one")
+  v.add_argument("--custom-seed", type=int, default=None)
+  v.add_argument("--batch-size", type=int, default=1,
+                 help="utterances per launch sequence (ragged batch; results equal one-by-one validation)")
   return p
 
 
@@ -146,10 +168,80 @@ def synthesize(ns, from_wav: bool = False) -> bool:
   return True
 
 
+def _save_validation(entry, output, val_dir: Path, iteration: int) -> None:
+  """src/waveglow_cli/validation.py:61-83 without the plots."""
+  dest = val_dir / f"it={iteration}_name={entry.basename}"
+  dest.mkdir(parents=True, exist_ok=True)
+  np.save(dest / "original.mel.npy", output.mel_orig)
+  np.save(dest / "inferred_denoised.mel.npy", output.mel_inferred_denoised)
+  float_to_wav(output.wav_orig, dest / "original.wav", sample_rate=output.orig_sr)
+  write_wav(filename=dest / "inferred_denoised.wav", rate=output.inferred_sr, data=output.wav_inferred_denoised)
+  write_wav(filename=dest / "inferred.wav", rate=output.inferred_sr, data=output.wav_inferred)
+
+
+def validate_cmd(ns) -> bool:
+  """src/waveglow_cli/validation.py:107-153."""
+  import logging
+  from functools import partial
+  from .training import get_last_checkpoint, get_pytorch_filename, load_dataset
+  from .validation import ValidationEntries, get_df, validate
+  logger = getLogger(__name__)
+  if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    logger.error("validate runs in a single process: start it without torch.distributed.run")
+    return False
+  for d in (ns.checkpoints_dir, ns.dataset_dir):
+    if not d.is_dir():
+      logger.error(f"{d} is not a directory!")
+      return False
+  data = load_dataset(ns.dataset_dir)
+  try:
+    iterations = sorted(set(ns.custom_checkpoints)) or [get_last_checkpoint(ns.checkpoints_dir)[1]]
+  except Exception as e:
+    logger.error(str(e))
+    return False
+  ns.output_dir.mkdir(parents=True, exist_ok=True)
+  val_logger = getLogger("waveglow_amd")
+  handler = logging.FileHandler(ns.output_dir / "log.txt", mode="w")
+  handler.setFormatter(logging.Formatter("[%(asctime)s] (%(levelname)s) %(message)s"))
+  old_level = val_logger.level
+  val_logger.addHandler(handler)
+  val_logger.setLevel(logging.INFO)
+  try:
+    logger.info("Validating...")
+    logger.info(f"Checkpoints: {','.join(str(x) for x in iterations)}")
+    result = ValidationEntries()
+    for iteration in iterations:
+      logger.info(f"Current checkpoint: {iteration}")
+      path = ns.checkpoints_dir / get_pytorch_filename(iteration)
+      if not path.is_file():
+        logger.error(f"Checkpoint {path} not found!")
+        return False
+      ckpt = CheckpointWaveglow.load(path, torch.device(ns.device))
+      try:
+        result.extend(validate(checkpoint=ckpt, data=data, custom_hparams=split_hparams_string(ns.custom_hparams),
+                               entry_names=set(ns.files), full_run=ns.full_run,
+                               save_callback=partial(_save_validation, val_dir=ns.output_dir, iteration=iteration),
+                               sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=ns.custom_seed,
+                               device=torch.device(ns.device), batch_size=ns.batch_size))
+      except AssertionError as e:
+        logger.error(str(e) or "validation failed an assertion")
+        return False
+    if len(result) > 0:
+      get_df(result).to_csv(ns.output_dir / "total.csv", sep="\t", header=True, index=False)
+      logger.info(f"Saved output to: {ns.output_dir.absolute()}")
+    return True
+  finally:
+    val_logger.removeHandler(handler)
+    val_logger.setLevel(old_level)
+    handler.close()
+
+
 def main(argv=None) -> int:
   ns = build_parser().parse_args(argv)
   if ns.command in ("synthesize", "synthesize-wav"):
     ok = synthesize(ns, from_wav=ns.command == "synthesize-wav")
+  elif ns.command == "validate":
+    ok = validate_cmd(ns)
   else:
     ok = train_cmd(ns, resume=ns.command == "continue-train")
   return 0 if ok else 1

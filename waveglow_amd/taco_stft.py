@@ -196,6 +196,35 @@ class TacotronSTFT(torch.nn.Module):
                                            C.c_void_p(stream)))
     return out, [n // 256 + 1 for n in lens]
 
+  def mel_spectrogram_ragged_device(self, audio: torch.Tensor, lens):
+    """``mel_spectrogram_ragged`` of audio that is on the device already (synthesised audio on its way to the metrics).
+
+    ``audio``: fp32 [B, N] on the module's device, row b holding ``lens[b]`` samples; ``lens``: B host integers in
+    (512, N].  Returns ``(mel, frames, frames_dev)``: ``mel`` [B, n_mel_channels, N // 256 + 1], ``frames[b] = lens[b] //
+    256 + 1`` as a list and as an int32 tensor on the device; ``mel[b, :, :frames[b]]`` is bit for bit
+    ``mel_spectrogram(audio[b:b+1, :lens[b]])[0]`` and the columns behind it are 0.  The device copy of ``lens`` is uploaded
+    here.  No range assert and no synchronise: the caller answers for the audio lying in [-1, 1].  No graph."""
+    if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda" or \
+        _lib.device_index(audio.device) != _lib.device_index(self.device):
+      raise _lib.WgError(f"mel_spectrogram_ragged_device: audio must be on {self.device} (no CPU fallback)")
+    if audio.dtype != torch.float32 or audio.dim() != 2:
+      raise _lib.WgError("mel_spectrogram_ragged_device takes float32 audio [B, N]")
+    B, N = audio.shape
+    lens = [int(n) for n in lens]
+    if len(lens) != B or B < 1:
+      raise _lib.WgError(f"mel_spectrogram_ragged_device: {len(lens)} lengths for a batch of {B}")
+    if any(n <= 512 or n > N for n in lens):
+      raise _lib.WgError(f"mel front-end: lengths in (512, {N}] expected (reflect padding needs > 512), got {lens}")
+    audio = audio.contiguous()
+    both = torch.tensor([lens, [n // 256 + 1 for n in lens]], dtype=torch.int32).to(audio.device)
+    out = torch.empty((B, self.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=audio.device)
+    ws = torch.empty(self.lib.wg_stft_mel_workspace_bytes(self._h, B, N), dtype=torch.uint8, device=audio.device)
+    stream = torch.cuda.current_stream(audio.device).cuda_stream
+    _lib.check(self.lib.wg_stft_mel_ragged(self._h, self.mel_basis.data_ptr(), self.n_mel_channels, audio.data_ptr(),
+                                           both[0].data_ptr(), out.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
+                                           C.c_void_p(stream)))
+    return out, [n // 256 + 1 for n in lens], both[1]
+
   def mel_spectrogram_differentiable(self, y: torch.Tensor) -> torch.Tensor:
     """``mel_spectrogram(y)`` with an autograd graph back to ``y`` (taco_stft.py:84-104 without the detach at :99).
 

@@ -1,0 +1,200 @@
+"""``validate`` with the reference's surface (src/waveglow/validation.py:23-108, :125-287): copy synthesis of validation
+utterances from their own mels, and per utterance the mel-cepstral distortion with and without DTW alignment, the
+alignment penalties and the cosine similarity between the original mel and the mel of the synthesised audio.
+
+Behind the noise draws a batch of utterances is one launch sequence on the device: the flow and the denoiser
+(``Synthesizer._infer_batch_device``), the int16 finishing (``wg_wav_finish``), the normalisation, the mel of the result
+(``TacotronSTFT.mel_spectrogram_ragged_device``) and the metrics (``wg_metrics_mel``).  Not built: the PNG plots and the
+structural similarity computed from them (``structural_similarity`` stays None).
+"""
+from __future__ import annotations
+
+import datetime
+import random
+from dataclasses import dataclass
+from logging import getLogger
+from typing import Callable, Dict, List, Optional, Set
+
+import numpy as np
+import torch
+
+from . import _lib, metrics, pcm
+from .audio import wav_to_float32
+from .checkpoint import CheckpointWaveglow
+from .synthesizer import PcmResult, Synthesizer
+from .taco_stft import TacotronSTFT
+from .training import Entry
+
+MCD_NO_OF_COEFFS_PER_FRAME = 16          # src/waveglow/globals.py
+
+
+@dataclass
+class ValidationEntry:
+  entry: Entry = None
+  inference_result: PcmResult = None     # the durations, sampling rate and over-amplification flag of the reference's field
+  seed: int = None
+  diff_duration_s: float = None
+  iteration: int = None
+  inferred_duration_s: float = None
+  timepoint: datetime.datetime = None
+  diff_frames: int = None
+  mfcc_no_coeffs: int = None
+  mfcc_dtw_mcd: float = None
+  mfcc_dtw_penalty: float = None
+  mfcc_dtw_frames: int = None
+  mcd: float = None
+  mcd_penalty: float = None
+  mcd_frames: int = None
+  structural_similarity: float = None
+  cosine_similarity: float = None
+  denoiser_strength: float = None
+  sigma: float = None
+
+
+class ValidationEntries(List[ValidationEntry]):
+  pass
+
+
+@dataclass
+class ValidationEntryOutput:
+  mel_orig: np.ndarray = None
+  orig_sr: int = None
+  wav_orig: np.ndarray = None
+  inferred_sr: int = None
+  mel_inferred_denoised: np.ndarray = None
+  wav_inferred_denoised: np.ndarray = None     # int16: convert_wav(normalize_wav(denoised audio), int16)
+  wav_inferred: np.ndarray = None              # int16: convert_wav(normalize_wav(raw audio), int16)
+
+
+def get_df(entries: ValidationEntries):
+  """The reference's table (validation.py:52-108) without the "Structual Similarity (Padded)" column."""
+  from pandas import DataFrame
+  if len(entries) == 0:
+    return DataFrame()
+  data = [{
+    "Name": e.entry.basename,
+    "Subpath": e.entry.stem,
+    "Timepoint": f"{e.timepoint:%Y/%m/%d %H:%M:%S}",
+    "Iteration": e.iteration,
+    "Seed": e.seed,
+    "Sigma": e.sigma,
+    "Denoiser strength": e.denoiser_strength,
+    "Inference duration (s)": e.inference_result.inference_duration_s,
+    "Denoising duration (s)": e.inference_result.denoising_duration_s,
+    "Overamplified?": e.inference_result.was_overamplified,
+    "Inferred wav duration (s)": e.inferred_duration_s,
+    "# Difference frames": e.diff_frames,
+    "Sampling rate (Hz)": e.inference_result.sampling_rate,
+    "# MFCC Coefficients": e.mfcc_no_coeffs,
+    "MFCC DTW MCD": e.mfcc_dtw_mcd,
+    "MFCC DTW PEN": e.mfcc_dtw_penalty,
+    "# MFCC DTW frames": e.mfcc_dtw_frames,
+    "MCD": e.mcd,
+    "PEN": e.mcd_penalty,
+    "# Frames": e.mcd_frames,
+    "Cosine Similarity (Padded)": e.cosine_similarity,
+    "Wav path": str(e.entry.wav_absolute_path),
+  } for e in entries]
+  return DataFrame(data=[list(x.values()) for x in data], columns=list(data[0].keys()))
+
+
+def select_entries(data: List[Entry], entry_names: Set[str], full_run: bool, seed: int) -> List[Entry]:
+  """validation.py:133-144: everything, the named entries (all of them must exist), or one random entry."""
+  if full_run:
+    return list(data)
+  if len(entry_names) == 0:
+    assert len(data) > 0
+    random.seed(seed)
+    return [random.choice(data)]
+  entries = [x for x in data if x.basename in entry_names]
+  if len(entries) != len(entry_names):
+    getLogger(__name__).error("Not all entry name's were found!")
+    raise AssertionError("Not all entry name's were found!")
+  return entries
+
+
+def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], sigma, denoiser_strength, seed, iteration,
+                    save_callback, out: ValidationEntries) -> None:
+  logger = getLogger(__name__)
+  dev = synth.device
+  timepoint = datetime.datetime.now()
+  B = len(chunk)
+  mel_orig, frames = taco.get_mel_tensors_from_files([e.wav_absolute_path for e in chunk])
+  if max(frames) + 1 > metrics.MAX_FRAMES:
+    raise _lib.WgError(f"validate: an utterance of {max(frames)} frames is too long for the metrics "
+                       f"(at most {metrics.MAX_FRAMES - 1})")
+  audio, den, frames, samples_dev, ev = synth._infer_batch_device([mel_orig[b, :, :frames[b]] for b in range(B)], sigma,
+                                                                 denoiser_strength, seed)
+  N = audio.shape[1]
+  fin = pcm.finish_enqueue(audio, den, samples_dev)                       # inferred_denoised.wav, as infer_batch_pcm
+  fin_raw = pcm.finish_enqueue(audio, audio, samples_dev) if den is not audio else fin      # inferred.wav
+  # normalize_wav (audio_utils.py:67-95) of the denoised audio on the device: x / peak unless the peak is 1 or 0
+  peak = fin[2 * B * N:].view(torch.float32).view(B, pcm.N_STATS)[:, pcm.DEN_PEAK:pcm.DEN_PEAK + 1]
+  normed = torch.where((peak != 1.0) & (peak != 0.0), den / peak, den)
+  samples = [256 * t for t in frames]
+  mel_inf, frames_inf, frames_inf_dev = taco.mel_spectrogram_ragged_device(normed, samples)
+  frames_dev = torch.tensor(frames, dtype=torch.int32).to(dev)
+  rows = metrics.mel_metrics_enqueue(mel_orig, frames_dev, mel_inf, frames_inf_dev, MCD_NO_OF_COEFFS_PER_FRAME)
+  # one copy for the rows, with the peak of the normalised audio beside them (what normalize_wav asserts of its result)
+  inside = torch.arange(N, device=dev)[None, :] < samples_dev[:, None]
+  rows = torch.cat([rows, torch.where(inside, normed.abs(), 0.0).amax(dim=1, keepdim=True).double()], dim=1).cpu()
+  fin_h = fin.cpu()
+  fin_raw_h = fin_raw.cpu() if fin_raw is not fin else fin_h
+  mel_orig_h, mel_inf_h = mel_orig.cpu().numpy(), mel_inf.cpu().numpy()
+  den_pcm, stats = pcm.finish_read(fin_h, B, N)
+  raw_pcm, _ = pcm.finish_read(fin_raw_h, B, N)
+  inf_s = ev[0].elapsed_time(ev[1]) / 1e3
+  den_s = ev[1].elapsed_time(ev[2]) / 1e3 if denoiser_strength > 0 else 0
+  sr = synth.hparams.sampling_rate
+  for b, (entry, m) in enumerate(zip(chunk, metrics.rows_to_metrics(rows[:, :metrics.N_ROW]))):
+    norm_peak = float(rows[b, metrics.N_ROW])
+    assert norm_peak == 1.0 or norm_peak == 0.0                                    # audio_utils.py:92-93
+    n = samples[b]
+    res = PcmResult(pcm=den_pcm[b, :n].copy(), sampling_rate=sr,
+                    was_overamplified=bool(stats[b, pcm.RAW_MIN] < -1.0 or stats[b, pcm.RAW_MAX] > 1.0),
+                    peak=float(stats[b, pcm.DEN_PEAK]), inference_duration_s=inf_s / B, denoising_duration_s=den_s / B,
+                    timepoint=timepoint)
+    val = ValidationEntry(entry=entry, inference_result=res, seed=seed, iteration=iteration, timepoint=timepoint,
+                          inferred_duration_s=n / sr, denoiser_strength=denoiser_strength, sigma=sigma,
+                          mfcc_no_coeffs=MCD_NO_OF_COEFFS_PER_FRAME, diff_frames=frames_inf[b] - frames[b],
+                          mfcc_dtw_mcd=m.mcd_dtw, mfcc_dtw_penalty=m.penalty_dtw, mfcc_dtw_frames=m.frames_dtw, mcd=m.mcd,
+                          mcd_penalty=m.penalty, mcd_frames=m.frames, cosine_similarity=m.cosine)
+    wav_orig, orig_sr = wav_to_float32(entry.wav_absolute_path)
+    output = ValidationEntryOutput(mel_orig=mel_orig_h[b, :, :frames[b]].copy(), orig_sr=orig_sr, wav_orig=wav_orig,
+                                   inferred_sr=sr, mel_inferred_denoised=mel_inf_h[b, :, :frames_inf[b]].copy(),
+                                   wav_inferred_denoised=res.pcm, wav_inferred=raw_pcm[b, :n].copy())
+    logger.info(f"Current: {entry.stem}")
+    logger.info(f"MCD DTW: {val.mfcc_dtw_mcd}")
+    logger.info(f"MCD DTW penalty: {val.mfcc_dtw_penalty}")
+    logger.info(f"MCD DTW frames: {val.mfcc_dtw_frames}")
+    logger.info(f"MCD: {val.mcd}")
+    logger.info(f"MCD penalty: {val.mcd_penalty}")
+    logger.info(f"MCD frames: {val.mcd_frames}")
+    logger.info(f"Cosine Similarity: {val.cosine_similarity}")
+    save_callback(entry, output)
+    out.append(val)
+
+
+def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: Optional[Dict[str, str]],
+             denoiser_strength: float, sigma: float, entry_names: Set[str], full_run: bool,
+             save_callback: Callable[[Entry, ValidationEntryOutput], None], seed: Optional[int], device: torch.device, *,
+             batch_size: int = 1) -> ValidationEntries:
+  """validation.py:125-287.  ``batch_size`` utterances share one launch sequence; every utterance gets the audio, the
+  mels and the metrics it gets alone (its noise is drawn as ``Synthesizer.infer`` draws it, and every kernel of the
+  sequence treats the padding behind an utterance as the end of the sequence)."""
+  logger = getLogger(__name__)
+  result = ValidationEntries()
+  if seed is None:
+    seed = random.randint(1, 9999)
+    logger.info(f"As no seed was given, using random seed: {seed}.")
+  entries = select_entries(data, set(entry_names), full_run, seed)
+  if len(entries) == 0:
+    logger.info("Nothing to synthesize!")
+    return result
+  synth = Synthesizer(checkpoint=checkpoint, custom_hparams=custom_hparams, device=device)
+  taco = TacotronSTFT(synth.hparams, synth.device)
+  bs = max(1, int(batch_size))
+  for i in range(0, len(entries), bs):
+    _validate_batch(synth, taco, entries[i:i + bs], sigma, denoiser_strength, seed, checkpoint.iteration, save_callback,
+                    result)
+  return result
