@@ -354,9 +354,11 @@ size_t wg_train_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames,
  *   there and are not replayed) and computes d spect flow by flow into an fp32 accumulator.  About 0.2x the workspace at
  *   256 channels for about one more forward pass of the WN layers.  Outputs of the forwards and every gradient except those
  *   that go through d spect (upsample weight / bias, d mel: summation order, <= 3e-5 relative) are bit-identical to flags = 0.
- *   A workspace keeps one layout from its forward to its backward: the workspace of a recompute call must be smaller than
- *   the full-save size and at least the recompute size; a call whose flags do not match the size it is given returns
- *   WG_ERR_INVALID, as does the flag at a depth where two slots already hold every flow. */
+ *   A workspace keeps one layout from its forward to its backward: where the recompute size is below the full-save size,
+ *   the workspace of a recompute call must be smaller than the full-save size and at least the recompute size, and a call
+ *   whose flags do not match the size it is given returns WG_ERR_INVALID.  At a depth where the flag saves nothing (one or
+ *   two flows: the two slots hold every flow; one layer per flow) it runs all the same, on a workspace of
+ *   wg_train_workspace_bytes_ex(..., WG_TRAIN_RECOMPUTE) bytes, which is then no smaller than the full-save one. */
 #define WG_TRAIN_RECOMPUTE 1
 size_t wg_train_workspace_bytes_ex(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, int32_t flags);
 

@@ -237,6 +237,9 @@ int wg_create(const wg_config* cfg, int device_id, wg_handle** out) {
     return fail(WG_ERR_INVALID, "n_mel_channels=%d unsupported (multiple of 16, <= 80)", c.n_mel_channels);
   if (c.n_flows < 1 || c.n_early_every < 1 || c.n_early_size < 0 || c.n_early_size % 2 != 0)
     return fail(WG_ERR_INVALID, "bad flow configuration");
+  // zero-channel early outputs (the reference runs them as empty tensors) are outside the envelope: an empty tensor has no
+  // device pointer to hand over, and the flow-step kernels have never run with n_extra = n_peel = 0 at an early flow
+  if (c.n_early_size == 0) return fail(WG_ERR_INVALID, "n_early_size=0 unsupported (even, >= 2)");
   std::vector<int> ck = flow_channels(c);
   if (ck.back() < 2 || ck.back() % 2 != 0) return fail(WG_ERR_INVALID, "flow configuration leaves %d channels", ck.back());
   wg_handle* h = new wg_handle();

@@ -188,17 +188,20 @@ int setup(wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, void* wo
     x.n_slabs[1] = (int)s2;
   }
   x.w = carve(c, x.g, x.n_slabs, (char*)workspace, x.recompute);
-  // A workspace keeps one layout from its forward to its backward.  The two sizes tell the layouts apart: a recompute
-  // workspace is smaller than a full-save one, so a call whose flags do not match the size it is given is refused.
+  // A workspace keeps one layout from its forward to its backward.  Where the two sizes differ they tell the layouts apart:
+  // a recompute workspace is then smaller than a full-save one, so a call whose flags do not match the size it is given is
+  // refused.  At a depth where recomputation saves nothing (one or two flows: the two slots hold every flow and nothing is
+  // replayed; one layer per flow: the fp32 d spect accumulator outweighs the planes saved) the flag still runs, on a
+  // workspace of its own size, and only the flags say which layout a workspace has.
   const size_t full = x.recompute ? carve(c, x.g, x.n_slabs, nullptr, false).bytes : x.w.bytes;
   const size_t rec = x.recompute ? x.w.bytes : carve(c, x.g, x.n_slabs, nullptr, true).bytes;
-  if (x.recompute && rec >= full)
-    return fail(WG_ERR_INVALID, "WG_TRAIN_RECOMPUTE saves no memory at this depth (two flow slots hold every layer)");
-  if (workspace) {
+  if (workspace && rec < full) {
     if (x.recompute && workspace_bytes >= full)
       return fail(WG_ERR_INVALID, "WG_TRAIN_RECOMPUTE with a full-save training workspace: flags and workspace size do not match");
-    if (!x.recompute && workspace_bytes < full && rec < full && workspace_bytes >= rec)
+    if (!x.recompute && workspace_bytes < full && workspace_bytes >= rec)
       return fail(WG_ERR_INVALID, "training workspace of the WG_TRAIN_RECOMPUTE size without the flag: flags and workspace size do not match");
+  }
+  if (workspace) {
     if (x.w.bytes > workspace_bytes) return fail(WG_ERR_WORKSPACE, "training workspace too small");
   }
   if ((size_t)x.g.R * 128 >= (1ull << 32)) return fail(WG_ERR_INVALID, "plane too large for 32-bit offsets");

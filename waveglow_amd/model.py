@@ -82,6 +82,10 @@ class _Engine:
     self.mel_width = (hp.n_mel_channels + 15) // 16 * 16
     if not 1 <= hp.n_mel_channels <= 80:
       raise _lib.WgError(f"n_mel_channels={hp.n_mel_channels} unsupported (1..80)")
+    # zero-channel early outputs: the reference runs them as empty tensors; here they are outside the envelope (an empty
+    # tensor has no device pointer to hand to the library) and refused before anything is launched, as wg_create does
+    if hp.n_early_size == 0:
+      raise _lib.WgError("n_early_size=0 unsupported (even, >= 2)")
     cfg = _lib.WgConfig(self.mel_width, hp.n_flows, hp.n_group, hp.n_early_every, hp.n_early_size,
                         hp.n_layers, self.width, hp.kernel_size, 1024, 256)
     handle = C.c_void_p()
