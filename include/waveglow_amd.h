@@ -212,6 +212,22 @@ size_t wg_wav_finish_workspace_bytes(int32_t B);
 int wg_wav_finish(const float* raw, const float* denoised, const int32_t* lens, int16_t* pcm_out, float* stats_out,
                   int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Training segments out of a device-resident wav pool (src/waveglow/dataloader.py:45-54, audio_utils.py:141-150
+ * get_wav_tensor_segment, :36-64 convert_wav), no handle ----------------------------------------------------------------
+ * pool: the samples of n_utt utterances back to back on the device, int16 (WG_PCM_I16) or fp32 (WG_PCM_F32), pool_elems
+ * of them; offsets device [n_utt + 1] int64, ascending, offsets[n_utt] == pool_elems; picks device [B][2] int32:
+ * utterance index, start sample.  For row b with u = picks[b][0], s = picks[b][1], len = offsets[u+1] - offsets[u]:
+ *   audio_out[b][i] = conv(pool[offsets[u] + s + i]) where s + i < len, 0 elsewhere (the zero padding a short utterance
+ *   gets); conv is (float)x * (1.0f / 32768.0f) for int16 -- a power of two, so bit for bit what convert_wav computes in
+ *   fp64 and rounds -- and the identity for fp32.
+ * A pick outside the pool (u outside [0, n_utt), s < 0, s > max(len - segment_length, 0)) gives an all-zero row and, if
+ * status_out (device [1], may be null) is given, sets status_out[0] = 1; otherwise status_out is left alone.  Nothing
+ * outside [0, pool_elems) is read whatever the picks hold.  One launch, no workspace.  Enqueue-only. */
+typedef enum wg_pcm_dtype { WG_PCM_I16 = 0, WG_PCM_F32 = 1 } wg_pcm_dtype;
+int wg_data_gather(const void* pool, int32_t pool_dtype, int64_t pool_elems, const int64_t* offsets, int32_t n_utt,
+                   const int32_t* picks, float* audio_out, int32_t* status_out, int32_t B, int32_t segment_length,
+                   void* stream);
+
 /* ---- Validation metrics of mel-spectrogram pairs (src/waveglow/validation.py:211-235), no handle --------------------
  * Ragged batches: arrays [B][C][tmax] fp32 device, frame counts int32 device [B], read by the kernels only.  A frame
  * count outside [1, min(tmax, 4096)] counts as 0: that utterance's MFCC columns are all 0 and its metrics NaN.  fp64

@@ -13,7 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WAVEGLOW_AMD_LIB", os.path.join(_HERE, "csrc", "libwaveglow_amd.so"))
 
 WG_F32, WG_F16 = 0, 1
-WG_TRAIN_RECOMPUTE = 1          # flag of the wg_train_*_flags entry points (include/waveglow_amd.h)
+WG_PCM_I16, WG_PCM_F32 = 0, 1   # pool_dtype of wg_data_gather
+WG_TRAIN_RECOMPUTE = 1         # flag of the wg_train_*_flags entry points (include/waveglow_amd.h)
 
 
 class WgConfig(C.Structure):
@@ -141,6 +142,8 @@ SIGNATURES = {
   "wg_wav_finish_workspace_bytes": (C.c_size_t, [C.c_int32]),
   "wg_wav_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_data_gather": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
   "wg_metrics_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
   "wg_metrics_mfcc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_size_t, C.c_void_p]),

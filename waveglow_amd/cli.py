@@ -7,8 +7,9 @@ commented-out ``--batch-size``, inference_v2.py:64) and per-rank sharding of the
   python -m waveglow_amd.cli synthesize-wav CHECKPOINT FOLDER [same flags]   wav -> mel (HIP front-end) -> wav
          (src/waveglow_cli/inference_wav.py:74-130; copy synthesis)
   python -m waveglow_amd.cli train TRAIN-FOLDER VAL-FOLDER CHECKPOINTS-FOLDER [--device cuda:0] [--custom-hparams ...]
-         [--pre-trained-model CKPT --warm-start]                     (src/waveglow_cli/training.py:24-79)
+         [--pre-trained-model CKPT --warm-start] [--device-dataset]  (src/waveglow_cli/training.py:24-79)
   python -m waveglow_amd.cli continue-train TRAIN-FOLDER VAL-FOLDER CHECKPOINTS-FOLDER [...]   (training.py:82-124)
+         --device-dataset: all wavs stay on the device and every batch is built there (waveglow_amd/device_data.py)
   python -m waveglow_amd.cli validate CHECKPOINTS-FOLDER OUTPUT-FOLDER DATA-FOLDER [--sigma S] [--denoiser-strength D]
          [--device cuda:0] [--custom-hparams ...] [--full-run] [--files NAME ...] [--custom-checkpoints IT ...]
          [--custom-seed N] [--batch-size B]                          (src/waveglow_cli/validation.py:86-153)
@@ -68,6 +69,8 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("checkpoints_dir", type=Path, metavar="CHECKPOINTS-FOLDER")
     t.add_argument("--device", type=str, default="cuda:0")
     t.add_argument("--custom-hparams", type=str, default=None)
+    t.add_argument("--device-dataset", action="store_true",
+                   help="keep all wavs on the device and build every batch there (same batches; cache_wavs is ignored)")
     if name == "train":
       t.add_argument("--pre-trained-model", type=Path, default=None)
       t.add_argument("--warm-start", action="store_true")
@@ -108,7 +111,7 @@ def train_cmd(ns, resume: bool) -> bool:
     warm = CheckpointWaveglow.load(ns.pre_trained_model, device)
   train(custom_hparams=split_hparams_string(ns.custom_hparams), logdir=None, trainset=load_dataset(ns.train_folder),
         valset=load_dataset(ns.val_folder), save_checkpoint_dir=ns.checkpoints_dir, checkpoint=checkpoint,
-        warm_model=warm, device=device)
+        warm_model=warm, device=device, device_dataset=ns.device_dataset)
   if world > 1:
     torch.distributed.destroy_process_group()
   return True

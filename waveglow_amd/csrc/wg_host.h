@@ -137,6 +137,12 @@ hipEvent_t wg_internal_sync_event(wg_handle* h);                    // next even
 hipEvent_t wg_internal_mark_event(wg_handle* h, int slot);          // event `slot` of the mark pool
 hipError_t wg_internal_upload(wg_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s);   // pinned H2D copy
 
+namespace wg {
+// data.hip: the one launch of wg_data_gather (arguments as in include/waveglow_amd.h, checked by data_api.cpp)
+hipError_t launch_data_gather(const void* pool, bool is_i16, int64_t pool_elems, const int64_t* offsets, int n_utt,
+                              const int* picks, float* out, int* status, int B, int N, hipStream_t s);
+}  // namespace wg
+
 // W_k^-1 of the finalised handle on the device (fp32 of the fp64 inverse, the matrix wg_infer uses), null before wg_finalize
 inline const float* wg_internal_winv(const wg_handle* h, int k) {
   if (!h || !h->finalized || k < 0 || k >= (int)h->flows.size()) return nullptr;

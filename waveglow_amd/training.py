@@ -192,22 +192,27 @@ def load_optimizer(model_parameters, hparams: HParams, state_dict: Optional[dict
 
 
 def validate_model(model, criterion, val_loader) -> float:
-  """Average validation loss (utils.py:330-357); runs the no-grad forward of the library."""
+  """Average validation loss (utils.py:330-357); runs the no-grad forward of the library.  ``val_loader`` is the
+  ``DataLoader`` of ``prepare_valloader`` or a ``DeviceBatchLoader``."""
   model.eval()
   losses = []
   with torch.no_grad():
     for batch in val_loader:
       x, y = parse_batch(batch)
       losses.append(float(criterion(model(x), y)))
+  if hasattr(val_loader, "check_status"):
+    val_loader.check_status(sync=True)
   model.train()
   return float(np.mean(losses)) if losses else float("nan")
 
 
 def train(custom_hparams: Optional[Dict[str, str]], logdir: Optional[Path], trainset: List[Entry], valset: List[Entry],
           save_checkpoint_dir: Path, checkpoint: Optional[CheckpointWaveglow], warm_model: Optional[CheckpointWaveglow],
-          device: torch.device, max_iterations: Optional[int] = None) -> List[float]:
+          device: torch.device, max_iterations: Optional[int] = None, device_dataset: bool = False) -> List[float]:
   """train.py:93-238.  ``max_iterations`` (not in the reference) stops after that many optimiser steps.
-  Returns the training losses of the executed steps."""
+  ``device_dataset`` (not in the reference) keeps the wavs on the device and builds every batch there
+  (waveglow_amd/device_data.py): the same batches, so the same training; ``cache_wavs`` is then ignored, as no host copy is
+  kept.  Under ``torch.distributed`` every rank pools its own shard.  Returns the training losses of the executed steps."""
   logger = getLogger(__name__)
   complete_start = time.time()
   device = torch.device(device)
@@ -238,8 +243,13 @@ def train(custom_hparams: Optional[Dict[str, str]], logdir: Optional[Path], trai
   if world > 1 and not enable_data_parallel(model):
     reducer = GradientAllReducer(model.parameters())
 
-  train_loader = prepare_trainloader(hparams, trainset, device)
-  val_loader = prepare_valloader(hparams, valset, device)
+  if device_dataset:
+    from .device_data import DeviceBatchLoader
+    train_loader = DeviceBatchLoader(trainset, hparams, device, drop_last=True)     # train first, then validation: each
+    val_loader = DeviceBatchLoader(valset, hparams, device, drop_last=False)        # constructor re-seeds `random`
+  else:
+    train_loader = prepare_trainloader(hparams, trainset, device)
+    val_loader = prepare_valloader(hparams, valset, device)
   batch_iterations = len(train_loader)
   if batch_iterations == 0:
     logger.error("Not enough training data.")
@@ -262,7 +272,9 @@ def train(custom_hparams: Optional[Dict[str, str]], logdir: Optional[Path], trai
   continue_epoch = get_continue_epoch(iteration, batch_iterations)
   for epoch in range(continue_epoch, hparams.epochs):
     next_batch_iteration = get_continue_batch_iteration(iteration, batch_iterations)
-    for batch_iteration, batch in enumerate(train_loader):
+    # the device loader draws the picks of the skipped batches of a resumed epoch and builds none of them
+    batches = train_loader.epoch(skip=next_batch_iteration) if device_dataset else enumerate(train_loader)
+    for batch_iteration, batch in batches:
       if skip_batch(batch_iteration=batch_iteration, continue_batch_iteration=next_batch_iteration):
         continue
       model.zero_grad()
@@ -290,7 +302,18 @@ def train(custom_hparams: Optional[Dict[str, str]], logdir: Optional[Path], trai
         from .train import nonfinite_message
         raise Exception(nonfinite_message(float(getattr(model, "grad_scale", 0.0))))
       optimizer.step()
+      if device_dataset:
+        # the next batch (batch 0 of the next epoch behind the last one) is drawn and enqueued before the step's host sync,
+        # so its host work overlaps the tail of the running step.  Not ahead of a validation pass, which draws from the same
+        # `random` stream first in the legacy order, and not behind the last step.
+        ends_here = (max_iterations is not None and len(losses) + 1 >= max_iterations) or \
+            (epoch + 1 == hparams.epochs and batch_iteration + 1 == batch_iterations)
+        if not ends_here and not check_save_it(epoch, iteration + 1, settings):
+          train_loader.prefetch()
+        train_loader.post_status()
       reduced_loss = loss.item()
+      if device_dataset:
+        train_loader.check_status()
       if gated and not bool(finite):
         from .train import nonfinite_message
         raise Exception(nonfinite_message(float(getattr(model, "grad_scale", 0.0))))
