@@ -2,10 +2,13 @@
 
 Follows src/waveglow/stft.py:98-198 (Prem Seetharaman's conv-STFT: Hann-windowed Fourier bases, reflect padding,
 magnitude/phase, inverse via the pseudo-inverse basis + window-sum-square normalisation) and
-src/waveglow/denoiser.py:51-57 (spectral subtraction).  PARITY UNPINNED: the reference module imports librosa
-(absent here) so no golden vectors could be generated from it; ``pad_center`` / ``tiny`` / ``normalize(norm=None)`` are
-restated from their documented behaviour, and scipy's ``get_window('hann', n, fftbins=True)`` is the same call the
-reference makes (stft.py:125).
+src/waveglow/denoiser.py:51-57 (spectral subtraction).  Pinned to outputs of the reference's own ``STFT``,
+``TacotronSTFT`` and ``Denoiser`` classes (tests/golden/stft_ref.npz, tests/test_stft_ref_cpu.py) at a tenth of the bars
+the GPU tests hold the kernels to.  The reference module imports librosa (absent here); the fixture was made with
+functional stand-ins for ``pad_center`` / ``tiny`` / ``normalize(norm=None)``, which are restated here from their
+documented behaviour as well, and with the project's mel filter bank in place of ``librosa.filters.mel`` -- those four
+are what stays unpinned.  scipy's ``get_window('hann', n, fftbins=True)`` is the same call the reference makes
+(stft.py:125).
 """
 import numpy as np
 from scipy.signal import get_window
@@ -50,6 +53,12 @@ def inverse(re, im, inv, win_sq, filter_length=1024, hop_length=256):
   return out[:, filter_length // 2:-(filter_length // 2)]
 
 
+def bias_spectrum(bias_audio, fwd):
+  """denoiser.py:45-49: the magnitudes of frame 0 of the bias audio [1, N] -> [513]."""
+  re, im = transform(np.asarray(bias_audio, dtype=np.float64), fwd)
+  return np.sqrt(re ** 2 + im ** 2)[0, :, 0]
+
+
 def denoise(audio, bias_mag, strength, fwd, inv, win_sq):
   """denoiser.py:51-57: magnitude minus strength * bias magnitude (first frame of the bias audio), clamped at 0,
   original phase, inverse STFT."""
@@ -62,7 +71,8 @@ def denoise(audio, bias_mag, strength, fwd, inv, win_sq):
 
 def mel_spectrogram(audio: np.ndarray, mel_basis: np.ndarray, filter_length=1024, hop_length=256, win_length=1024):
   """TacotronSTFT.mel_spectrogram (src/waveglow/taco_stft.py:84-104) in fp64: log(clamp(mel_basis @ |STFT(audio)|, 1e-5)).
-  audio [B, N] -> [B, n_mel, N // hop + 1].  Parity unpinned against the reference (librosa absent), see header."""
+  audio [B, N] -> [B, n_mel, N // hop + 1].  Pinned to the reference's outputs for a given ``mel_basis`` (see header); the
+  basis' values are the caller's."""
   fwd, _, _ = bases(filter_length, hop_length, win_length)
   re, im = transform(np.asarray(audio, dtype=np.float64), fwd, filter_length, hop_length)
   mel = np.einsum("mk,bkf->bmf", mel_basis.astype(np.float64), np.sqrt(re ** 2 + im ** 2))

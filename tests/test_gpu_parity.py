@@ -461,7 +461,8 @@ def test_synthesizer_and_cli_end_to_end(tmp_path):
 
 def test_denoiser_stft_vs_numpy_oracle():
   """The HIP denoiser (exact-fp32 MFMA conv-STFT) against oracle/stft_oracle.py (numpy fp64 restatement of
-  stft.py / denoiser.py; parity unpinned against the reference itself: its STFT module needs librosa)."""
+  stft.py / denoiser.py, itself pinned to outputs of the reference's STFT and Denoiser classes by
+  tests/test_stft_ref_cpu.py; the kernels against those outputs: tests/test_gpu_stft_ref.py)."""
   import ctypes as C
   import numpy as np
   from oracle import stft_oracle as S
@@ -669,7 +670,8 @@ def test_synthesizer_against_oracle_composition(tmp_path, strength):
   seed -> the three device draws of WaveGlow.infer (model.py:234-244, :260-271; replayed here after the same
   init_global_seeds) -> oracle infer_ref -> bias spectrum of infer(zeros[1,80,88], sigma 0) (denoiser.py:29-49) ->
   oracle spectral subtraction (denoiser.py:51-57).  The flow leg is pinned to the reference (torch_oracle); the
-  denoiser leg is pinned only to oracle/stft_oracle.py (parity unpinned vs the reference: librosa absent)."""
+  denoiser leg is pinned to oracle/stft_oracle.py, which answers to outputs of the reference's own Denoiser
+  (tests/golden/stft_ref.npz, tests/test_stft_ref_cpu.py)."""
   from oracle import stft_oracle as S
   from oracle import torch_oracle as O
   from waveglow_amd.checkpoint import CheckpointWaveglow

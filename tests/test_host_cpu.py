@@ -447,7 +447,8 @@ def test_stft_oracle_against_torch_stft():
   """oracle/stft_oracle.py (the checker of the HIP conv-STFT / denoiser / mel front-end) against torch.stft / torch.istft --
   an implementation that shares NOTHING with it (FFT, not the windowed Fourier-basis matrices that both the oracle and
   waveglow_amd.denoiser.stft_bases construct).  Same parameters as the reference's STFT (stft.py:98-132: hann, periodic,
-  n_fft 1024, hop 256, reflect padding).  The grade of f2 / f4 stays "parity unpinned" (no reference-run fixture)."""
+  n_fft 1024, hop 256, reflect padding).  What is specific to the reference (window_sumsquare, crop, clamp, bias frame,
+  compression) is pinned by its own outputs in tests/test_stft_ref_cpu.py."""
   from oracle import stft_oracle as S
   rng = np.random.default_rng(3)
   x = rng.standard_normal((2, 256 * 13)).astype(np.float64) * 0.3

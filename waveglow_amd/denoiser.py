@@ -2,9 +2,10 @@
 library (``wg_stft_*``: conv-STFT of src/waveglow/stft.py:98-198 as exact-fp32 MFMA GEMMs).
 
 The Fourier / pseudo-inverse bases are built on the host exactly like ``STFT.__init__`` (stft.py:108-132) and handed
-to the library once.  librosa's ``pad_center`` is restated (the reference imports it; librosa is absent here), so the
-parity of this post-filter is pinned only against ``oracle/stft_oracle.py`` (numpy fp64 restatement), not against
-reference outputs.  No torch/CPU fallback.
+to the library once.  librosa's ``pad_center`` is restated (the reference imports it; librosa is absent here).  The
+post-filter is pinned against ``oracle/stft_oracle.py`` (numpy fp64 restatement) and against outputs of the reference's own
+``STFT`` and ``Denoiser`` classes, run with functional stand-ins for the librosa names (tests/golden/stft_ref.npz,
+tests/test_gpu_stft_ref.py; ``stft_bases`` row by row in tests/test_stft_ref_cpu.py).  No torch/CPU fallback.
 """
 from __future__ import annotations
 

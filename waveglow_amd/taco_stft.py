@@ -2,8 +2,10 @@
 (``wg_stft_mel``: conv-STFT magnitudes on exact-fp32 MFMA, mel projection + log compression).
 
 ``librosa.filters.mel`` (taco_stft.py:66-73) is restated below (Slaney scale, Slaney area normalisation -- librosa's
-defaults ``htk=False, norm='slaney'``); librosa is absent here, so this front-end is pinned only against
-``oracle/stft_oracle.py`` (numpy fp64 restatement), not against reference outputs: **parity unpinned**.
+defaults ``htk=False, norm='slaney'``); librosa is absent here.  The front-end is pinned against
+``oracle/stft_oracle.py`` (numpy fp64 restatement) and against outputs of the reference's own
+``TacotronSTFT.mel_spectrogram`` (tests/golden/stft_ref.npz, tests/test_gpu_stft_ref.py) -- made with THIS filter bank in
+place of ``librosa.filters.mel``, so everything is pinned except the filter bank's values.
 
 ``TacotronSTFT.mel_spectrogram_differentiable`` is the same front-end with an autograd graph back to the audio (the
 reference detaches at taco_stft.py:99): ``wg_stft_mel_forward_saved`` keeps the spectrum, and ``wg_stft_mel_backward``
