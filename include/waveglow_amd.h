@@ -178,7 +178,8 @@ int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* 
 /* The same for a batch of utterances of DIFFERENT lengths (taco_stft.py:84-103 per utterance): `lens` is a device array
  * of B sample counts, each in (512, n_samples]; n_samples is the row pitch of audio.  mel_out is
  * [B][n_mel][n_samples/256 + 1]: columns below lens[b]/256 + 1 are bit for bit those of the uniform call on that
- * utterance alone, the others are 0.  A length outside the limits is treated as 0 (row all zero).  No gradient variant.
+ * utterance alone, the others are 0.  A length outside the limits is treated as 0 (row all zero).  The gradient
+ * variant is wg_stft_mel_forward_saved_ragged / wg_stft_mel_backward_ragged below.
  * Workspace as in the uniform call.  Enqueue-only. */
 int wg_stft_mel_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
                        float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
@@ -198,6 +199,20 @@ int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel,
                               int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
 int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
                          int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for a batch of utterances of DIFFERENT lengths: `lens` as in wg_stft_mel_ragged (device [B], each in
+ * (512, n_samples], anything else counts as 0; read by the kernels only), n_samples the row pitch, the workspace that of
+ * wg_stft_mel_grad_workspace_bytes(B, n_samples).
+ * wg_stft_mel_forward_saved_ragged: mel_out bit for bit that of wg_stft_mel_ragged (0 at and behind column lens[b]/256
+ *   + 1); keeps the state of the backward.
+ * wg_stft_mel_backward_ragged: g_mel at and behind an utterance's frame count is not read; audio_grad_out[b][:lens[b]]
+ *   is bit for bit the dense backward of that utterance alone (reflect padding folded about its own sample lens[b] - 1),
+ *   audio_grad_out[b][lens[b]:] = 0.  Pass the lens of the forward.  A null lens is an argument error. */
+int wg_stft_mel_forward_saved_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio,
+                                     const int32_t* lens, float* mel_out, int32_t B, int32_t n_samples, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int wg_stft_mel_backward_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel,
+                                const int32_t* lens, float* audio_grad_out, int32_t B, int32_t n_samples,
+                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- PCM finishing of a synthesised batch (src/waveglow/audio_utils.py:36-95, :132-138), no handle -----------------
  * raw, denoised [B][n_samples] fp32 device (they may be the same array), lens device [B] sample counts (clamped to
@@ -269,6 +284,16 @@ int wg_metrics_mel(const float* mel_a, const int32_t* frames_a, const float* mel
  * wg_stftloss_backward: g_out3 [3] fp32 DEVICE = d loss / d out3 -> audio_grad_out [B][n_samples] = d loss / d audio
  *   (no gradient under the clamp, sign(0) = 0).  Reads the workspace of a forward_saved call with the same factors, B
  *   and n_samples and leaves its saved state intact, so it may run more than once.
+ * wg_stftloss_*_ragged: the same for utterances of DIFFERENT lengths inside the dense [B][n_samples] arrays.  `lens` is a
+ *   device array of B sample counts, read by the kernels only.  Utterance b is transformed as its own crop
+ *   x[b][:lens[b]] (reflect padding about its own last sample, F_b = lens[b] / hop + 1 frames); the norms of sc_r run
+ *   over the frames f < F_b of every utterance and mag_r divides by K sum_b F_b, formed on the device: the loss of the
+ *   cropped utterances with their frames concatenated.  audio_grad_out[b][lens[b]:] = 0.  A length outside
+ *   (max n_fft / 2, n_samples] counts as 0: that utterance contributes nothing, gets a zero gradient row, and nothing is
+ *   indexed with it; if every length counts as 0, out3 and the gradient are zeros.  The workspace is the dense one for
+ *   (B, n_samples); the backward takes the lens of its forward.  With every length equal to n_samples the results are
+ *   bit for bit those of the dense entry points.  A null lens is an argument error, reported (like bad sizes) before the
+ *   refusal of a planning handle.
  * Sums are reduced in a fixed order (no floating-point atomics): results are bit-reproducible.  Enqueue-only; argument
  * checks run before any device work. */
 typedef struct wg_stftloss wg_stftloss;
@@ -284,6 +309,15 @@ int wg_stftloss_forward_saved(wg_stftloss* h, const float* audio, const float* t
                               size_t workspace_bytes, void* stream);
 int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, float factor_mag, float* audio_grad_out,
                          int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
+int wg_stftloss_forward_ragged(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens,
+                               float factor_sc, float factor_mag, float* out3, int32_t B, int32_t n_samples,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int wg_stftloss_forward_saved_ragged(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens,
+                                     float factor_sc, float factor_mag, float* out3, int32_t B, int32_t n_samples,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int wg_stftloss_backward_ragged(wg_stftloss* h, const float* g_out3, const int32_t* lens, float factor_sc,
+                                float factor_mag, float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* ---- Training direction: WaveGlow.forward under autograd and loss.backward() ---------------------------------------
  * (src/waveglow/model.py:178-221, train.py:190-199).  Weights change every optimiser step, so they are NOT taken from

@@ -10,14 +10,20 @@ shape and mode; shapes B x N: 16 x 221 184 (the audio of configs[1]) and 32 x 16
      test of the vocoder cycle runs it.  Not in the default modes: its first forward + backward at 16 x 221 184 did
      not finish within 7 minutes on the MI355X; give it --shapes 32x16128 and few steps
 
-  python tools/bench_mel_grads.py [--shapes 16x221184,32x16128] [--steps 20] [--warmup 3] [--modes pfbt]
+  r  mel_spectrogram_differentiable(y, lengths) forward only  } added by --lengths: B utterances spread evenly from
+  l  the same, forward + backward                             } 200/864 of the row pitch to all of it, in whole frames
+     of 256 samples (16 x 221 184: 200 ... 864 frames); shapes whose N is no multiple of 256 skip them
 
-Each line also gives the GEMM work of one direction (2 x 1056 x 1024 x B x F flops on the padded 1056-row basis) and
-its rate over the measured time of the forward / backward part.
+  python tools/bench_mel_grads.py [--shapes 16x221184,32x16128] [--steps 20] [--warmup 3] [--modes pfbt] [--lengths]
+
+The modes of a shape run interleaved, step by step, in one process.  Each line gives the mean of the forward and of the
+backward part (hipEvent milliseconds) with median, p10 and p90 over the steps after the warm-up, the GEMM work of one
+direction (2 x 1056 x 1024 x B x F flops on the padded 1056-row basis) and its rate over the mean time.
 """
 import argparse
 import json
 import os
+import statistics
 import sys
 
 import torch
@@ -40,31 +46,64 @@ def mel_unfold(y, fwd, basis):
   return torch.log(torch.clamp(torch.matmul(basis, mag), min=1e-5))
 
 
-def run_mode(taco, consts, y, g, mode, steps, warmup):
+def spread_lengths(B, N):
+  """B lengths in whole frames of 256 samples, evenly from 200/864 of the pitch to the pitch; None if N % 256."""
+  if N % 256 or B < 2:
+    return None
+  T = N // 256
+  lo = round(T * 200 / 864)
+  return [256 * round(lo + (T - lo) * b / (B - 1)) for b in range(B)]
+
+
+def run_once(taco, consts, y, g, mode, lens, ev):
+  """One iteration of one mode: (forward ms, backward ms)."""
+  torch.cuda.synchronize()
+  ev[0].record()
+  if mode == "p":
+    with torch.no_grad():
+      taco.mel_spectrogram_differentiable(y)
+    ev[1].record()
+  else:
+    yg = y.detach().requires_grad_(True)
+    fn = {"t": lambda t: mel_unfold(t, *consts), "c": lambda t: mel_ref64(t, *consts),
+          "r": lambda t: taco.mel_spectrogram_differentiable(t, lens),
+          "l": lambda t: taco.mel_spectrogram_differentiable(t, lens)}.get(mode, taco.mel_spectrogram_differentiable)
+    mel = fn(yg)
+    ev[1].record()
+    if mode not in "fr":
+      mel.backward(g)
+    del mel
+  ev[2].record()
+  torch.cuda.synchronize()
+  return ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+
+
+def spread(v):
+  s = sorted(v)
+  pct = lambda q: s[min(len(s) - 1, max(0, round(q * (len(s) - 1))))]
+  return {"median": statistics.median(v), "p10": pct(0.1), "p90": pct(0.9)}
+
+
+def run_modes(taco, consts, y, g, modes, lens, steps, warmup):
+  """All modes interleaved, step by step: one result per mode."""
   ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-  t_f = t_b = 0.0
+  times = {m: ([], []) for m in modes}
   for it in range(warmup + steps):
-    torch.cuda.synchronize()
-    ev[0].record()
-    if mode == "p":
-      with torch.no_grad():
-        taco.mel_spectrogram_differentiable(y)
-      ev[1].record()
-    else:
-      yg = y.detach().requires_grad_(True)
-      fn = {"t": lambda t: mel_unfold(t, *consts), "c": lambda t: mel_ref64(t, *consts)}.get(
-          mode, taco.mel_spectrogram_differentiable)
-      mel = fn(yg)
-      ev[1].record()
-      if mode != "f":
-        mel.backward(g)
-      del mel
-    ev[2].record()
-    torch.cuda.synchronize()
-    if it >= warmup:
-      t_f += ev[0].elapsed_time(ev[1])
-      t_b += ev[1].elapsed_time(ev[2])
-  return {"mode": mode, "ms_forward": t_f / steps, "ms_backward": t_b / steps, "ms_fwd_plus_bwd": (t_f + t_b) / steps}
+    for m in modes:
+      tf, tb = run_once(taco, consts, y, g, m, lens, ev)
+      if it >= warmup:
+        times[m][0].append(tf)
+        times[m][1].append(tb)
+    if it % 5 == 0:
+      print(json.dumps({"step": it, "of": warmup + steps}), flush=True)
+  out = []
+  for m in modes:
+    tf, tb = times[m]
+    both = [a + b for a, b in zip(tf, tb)]
+    out.append({"mode": m, "ms_forward": sum(tf) / steps, "ms_backward": sum(tb) / steps,
+                "ms_fwd_plus_bwd": sum(both) / steps, "forward": spread(tf), "backward": spread(tb),
+                "fwd_plus_bwd": spread(both)})
+  return out
 
 
 def main():
@@ -73,6 +112,7 @@ def main():
   ap.add_argument("--steps", type=int, default=20)
   ap.add_argument("--warmup", type=int, default=3)
   ap.add_argument("--modes", default="pfbt")
+  ap.add_argument("--lengths", action="store_true", help="add the modes r and l: per-utterance lengths")
   a = ap.parse_args()
   dev = "cuda:0"
   taco = TacotronSTFT(TSTFTHParams(), dev)
@@ -86,10 +126,14 @@ def main():
     g = torch.randn(B, 80, F, device=dev, generator=gen) / (B * 80 * F)
     gflop = 2.0 * 1056 * 1024 * B * F / 1e9
     ws = int(taco.lib.wg_stft_mel_grad_workspace_bytes(taco._h, B, N))
-    for mode in a.modes:
-      print(json.dumps({"starting": mode, "batch": B, "n_samples": N}), flush=True)
-      out = run_mode(taco, consts, y, g, mode, a.steps, a.warmup)
+    lens = spread_lengths(B, N) if a.lengths else None
+    modes = a.modes + ("rl" if lens is not None else "")
+    print(json.dumps({"starting": modes, "batch": B, "n_samples": N}), flush=True)
+    for out in run_modes(taco, consts, y, g, modes, lens, a.steps, a.warmup):
+      mode = out["mode"]
       out.update(batch=B, n_samples=N, frames=F, gemm_gflop=gflop, workspace_bytes=ws)
+      if mode in "rl":
+        out.update(lengths=lens, samples_of_dense=sum(lens) / (B * N))
       if mode in "pfb":
         out["fwd_tflops"] = gflop / out["ms_forward"]
       if mode == "b":

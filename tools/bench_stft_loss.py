@@ -1,6 +1,6 @@
 """Timing of ``MultiResolutionSTFTLoss`` (HIP forward and backward).  One JSON line per shape and leg; shapes B x N:
 16 x 221 184 (the audio of configs[1]) and 32 x 16 128 by default.  All legs of a shape run interleaved, step by step,
-in one process; times are hipEvent milliseconds, mean / median / min over the steps after the warm-up.
+in one process; times are hipEvent milliseconds, mean / median / min / p10 / p90 over the steps after the warm-up.
 
   all      the default three resolutions: forward without a graph, forward with saved state, backward
   r<i>     the same for a module with resolution i alone
@@ -8,9 +8,12 @@ in one process; times are hipEvent milliseconds, mean / median / min over the st
            backward under autograd
   vocoder  WaveGlow.infer_differentiable forward + backward (d mel) at --vocoder-batch x --vocoder-frames, the step this
            loss is attached to
+  --lengths  beside every library leg, the same module called with ``lengths=``: B utterances spread evenly from
+           200/864 of the row pitch to all of it, in whole frames of 256 samples (16 x 221 184: 200 ... 864 frames),
+           reported as leg "<name>.lengths" with the sum of the lengths; shapes whose N is no multiple of 256 skip it
 
   python tools/bench_stft_loss.py [--shapes 16x221184,32x16128] [--steps 20] [--warmup 3] [--legs all,r0,r1,r2]
-      [--no-vocoder] [--no-torch]
+      [--no-vocoder] [--no-torch] [--lengths]
 
 GEMM work per line: ``gflop_window`` counts the products the kernels execute (only the taps under the window),
 ``gflop_full`` the full n_fft x (n_fft + 2) basis; the rates are over the measured time.
@@ -58,7 +61,18 @@ class Timer:
 
   def stats(self, key, warmup):
     v = self.t[key][warmup:]
-    return {"mean": sum(v) / len(v), "median": statistics.median(v), "min": min(v)}
+    s = sorted(v)
+    pct = lambda q: s[min(len(s) - 1, max(0, round(q * (len(s) - 1))))]
+    return {"mean": sum(v) / len(v), "median": statistics.median(v), "min": min(v), "p10": pct(0.1), "p90": pct(0.9)}
+
+
+def spread_lengths(B, N):
+  """B lengths in whole frames of 256 samples, evenly from 200/864 of the pitch to the pitch; None if N % 256."""
+  if N % 256 or B < 2:
+    return None
+  T = N // 256
+  lo = round(T * 200 / 864)
+  return [256 * round(lo + (T - lo) * b / (B - 1)) for b in range(B)]
 
 
 def gflops(res, B, N):
@@ -101,6 +115,7 @@ def main():
   ap.add_argument("--legs", default="all,r0,r1,r2", help="which library modules to time")
   ap.add_argument("--no-vocoder", action="store_true")
   ap.add_argument("--no-torch", action="store_true")
+  ap.add_argument("--lengths", action="store_true", help="also time every library leg with per-utterance lengths")
   ap.add_argument("--vocoder-batch", type=int, default=32)
   ap.add_argument("--vocoder-frames", type=int, default=63)
   a = ap.parse_args()
@@ -126,6 +141,7 @@ def main():
         torch_fn = lambda t: loss_unfold(t, y, DEFAULT_RES, 1e-7, 1.0, 1.0, dtype=torch.float32)[2]
         torch_name = "pad + unfold + matmul"
     tm = Timer()
+    lens = spread_lengths(B, N) if a.lengths else None
     for _ in range(a.warmup + a.steps):
       for key, crit in mods.items():
         with torch.no_grad():
@@ -134,6 +150,13 @@ def main():
         loss = tm.run(key + ".forward_saved", lambda: crit(xg, y))
         tm.run(key + ".backward", loss.backward)
         del loss, xg
+        if lens is not None:
+          with torch.no_grad():
+            tm.run(key + ".lengths.forward", lambda: crit(x, y, lens))
+          xg = x.detach().requires_grad_(True)
+          loss = tm.run(key + ".lengths.forward_saved", lambda: crit(xg, y, lens))
+          tm.run(key + ".lengths.backward", loss.backward)
+          del loss, xg
       if torch_fn is not None:
         xg = x.detach().requires_grad_(True)
         loss = tm.run("torch.forward", lambda: torch_fn(xg))
@@ -152,6 +175,12 @@ def main():
         "gflop_window": {"forward_two_signals": 2 * gf, "backward": gb}, "gflop_full_one_signal": full,
         "tflops_window": {"forward_saved": 2 * gf / s["median"], "backward": gb / b["median"]},
         "tflops_full_basis": {"forward_saved": 2 * full / s["median"], "backward": full / b["median"]}}), flush=True)
+      if lens is not None:
+        f, s, b = (tm.stats(f"{key}.lengths.{leg}", a.warmup) for leg in ("forward", "forward_saved", "backward"))
+        print(json.dumps({
+          "leg": key + ".lengths", "batch": B, "n_samples": N, "resolutions": res, "lengths": lens,
+          "samples_of_dense": sum(lens) / (B * N), "ms_forward": f, "ms_forward_saved": s, "ms_backward": b,
+          "ms_fwd_saved_plus_bwd_median": s["median"] + b["median"]}), flush=True)
     if torch_fn is not None:
       f, b = tm.stats("torch.forward", a.warmup), tm.stats("torch.backward", a.warmup)
       print(json.dumps({"leg": "torch", "what": torch_name, "batch": B, "n_samples": N, "ms_forward": f,

@@ -139,6 +139,10 @@ SIGNATURES = {
                                           C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stft_mel_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_mel_forward_saved_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_mel_backward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_wav_finish_workspace_bytes": (C.c_size_t, [C.c_int32]),
   "wg_wav_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -161,6 +165,12 @@ SIGNATURES = {
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stftloss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stftloss_forward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stftloss_forward_saved_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                                 C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stftloss_backward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_debug_set_stamp_buffer": (C.c_int, [C.c_void_p, C.c_void_p]),
   "wg_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
   "wg_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),

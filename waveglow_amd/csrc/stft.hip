@@ -6,6 +6,8 @@
 // Mel gradients (TacotronSTFT.mel_spectrogram_differentiable): mel_kernel also keeps the pre-log sums, mel_bwd_kernel
 // turns d mel into d (re, im) in the inverse's [B][1056][Fs] layout, istft_kernel<true> is the transposed conv-STFT
 // with the forward basis, and reflect_fold_kernel adds the reflect-padded edges back onto the audio gradient.
+// With per-utterance lengths (wg_stft_mel_*_ragged) the three take the utterance's own frames and samples: d (re, im)
+// behind its frames stays zero, the interior is stored up to its length, the edges fold about its own last sample.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -102,7 +104,8 @@ __global__ void __launch_bounds__(512) stft_kernel(const StftArgs a) {
 
 // kGrad = false: inverse STFT (stft.py:165-198).  kGrad = true: the same 4-tap polyphase GEMM with the forward basis
 // is the transposed conv-STFT, g ypad[256 q + r] = sum_j sum_c fwd[c][r + 256 j] gX[c][q - j]; its epilogue stores the
-// interior (audio positions 0..N-1) straight to out and the reflect-padded edges to a.edge.
+// interior (audio positions 0..N-1) straight to out and the reflect-padded edges to a.edge; in a ragged batch N is the
+// utterance's own length (513 or more, else 0) and out is 0 behind it.
 template <bool kGrad>
 __global__ void __launch_bounds__(512) istft_kernel(const IstftArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
@@ -110,10 +113,11 @@ __global__ void __launch_bounds__(512) istft_kernel(const IstftArgs a) {
   const int q0 = blockIdx.x * 32, b = blockIdx.y;
   const int col = lane & 31, kk = lane >> 5;
   int N = a.N, F = a.F;                                   // this utterance's samples and frames; a.N is the row pitch
-  if (!kGrad && a.lens) {
-    N = ragged_len(a.lens, b, a.N, kFL, kHop - 1);
+  if (a.lens) {
+    N = kGrad ? ragged_len(a.lens, b, a.N, kFL / 2 + 1, 0) : ragged_len(a.lens, b, a.N, kFL, kHop - 1);
     F = ragged_frames(N);
-    if (q0 * kHop - kFL / 2 >= N) {                       // tile wholly behind the utterance: zeros, no GEMM
+    // tile wholly behind the utterance (and, for the gradient, behind its right padding): zeros, no GEMM
+    if (q0 * kHop - kFL / 2 >= N + (kGrad ? kFL / 2 : 0)) {
 #pragma unroll
       for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -146,9 +150,12 @@ __global__ void __launch_bounds__(512) istft_kernel(const IstftArgs a) {
       const int o = n - kFL / 2;
       if (kGrad) {
         const float v = acc[4 * g + e];
-        if (o >= 0 && o < a.N) a.out[(size_t)b * a.N + o] = v;
+        if (o >= 0 && o < N) a.out[(size_t)b * a.N + o] = v;
         else if (o < 0) a.edge[(size_t)b * kFL + n] = v;                      // n in [0, 512)
-        else if (o < a.N + kFL / 2) a.edge[(size_t)b * kFL + kFL / 2 + (o - a.N)] = v;
+        else {
+          if (o < N + kFL / 2) a.edge[(size_t)b * kFL + kFL / 2 + (o - N)] = v;
+          if (o < a.N) a.out[(size_t)b * a.N + o] = 0.0f;                     // ragged batch: behind the utterance
+        }
         continue;
       }
       if (o < 0 || o >= a.N) continue;
@@ -216,9 +223,14 @@ __global__ void __launch_bounds__(256) mel_bwd_kernel(const MelBwdArgs a) {
   const int fl = threadIdx.x & 63, b = blockIdx.y;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int f = blockIdx.x * 64 + fl;
+  int F = a.F;                                            // this utterance's frames; a.F is the row pitch
+  if (a.lens) {
+    F = ragged_frames(ragged_len(a.lens, b, a.N, kFL / 2 + 1, 0));
+    if ((int)blockIdx.x * 64 >= F) return;                // block wholly behind the utterance: gX stays zero
+  }
   for (int m = wave; m < a.n_mel; m += 4) {
     float v = 0.0f;
-    if (f < a.F) {
+    if (f < F) {
       const size_t i = ((size_t)b * a.n_mel + m) * a.F + f;
       const float A = a.pre[i];
       v = A >= 1e-5f ? a.g[i] / A : 0.0f;
@@ -226,7 +238,7 @@ __global__ void __launch_bounds__(256) mel_bwd_kernel(const MelBwdArgs a) {
     sg[m][fl] = v;
   }
   __syncthreads();
-  if (f >= a.F) return;
+  if (f >= F) return;
   const float* mp = a.mag + (size_t)b * kCut * a.F + f;
   const float* rp = a.rec + (size_t)b * kRows * a.Fs + 3 + f;
   float* gp = a.gX + (size_t)b * kRows * a.Fs + 3 + f;
@@ -243,11 +255,17 @@ __global__ void __launch_bounds__(256) mel_bwd_kernel(const MelBwdArgs a) {
 
 // g y[s] += g ypad[512 - s] (1 <= s <= 512) + g ypad[2(N-1) - s + 512] (N-513 <= s <= N-2): the reflect padding of
 // stft.py:141-147 folded back.  One thread per audio position, so overlapping edges of a short utterance do not race.
-// grid (B), 256 threads; runs after istft_kernel<true> in stream order.
-__global__ void __launch_bounds__(256) reflect_fold_kernel(const float* edge, float* gy, int N) {
+// grid (B), 256 threads; runs after istft_kernel<true> in stream order.  Ragged batch: N is the utterance's own length
+// inside the row pitch, and an utterance that counts as 0 has nothing to fold.
+__global__ void __launch_bounds__(256) reflect_fold_kernel(const float* edge, float* gy, int pitch, const int* lens) {
   const int b = blockIdx.x;
   const float* e = edge + (size_t)b * kFL;
-  float* y = gy + (size_t)b * N;
+  float* y = gy + (size_t)b * pitch;
+  int N = pitch;
+  if (lens) {
+    N = ragged_len(lens, b, pitch, kFL / 2 + 1, 0);
+    if (!N) return;
+  }
   constexpr int kHalf = kFL / 2;
   for (int t = threadIdx.x; t < 2 * (kHalf + 1); t += 256) {
     const int s = t <= kHalf ? t : N - 2 * (kHalf + 1) + t;      // [0, 512] then [N-513, N-1]
@@ -269,7 +287,7 @@ hipError_t launch_stft_grad(const IstftArgs& a, int B, hipStream_t s) {
   hipLaunchKernelGGL(istft_kernel<true>, dim3((a.F + 3 + 31) / 32, B), dim3(512), 0, s, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(reflect_fold_kernel, dim3(B), dim3(256), 0, s, a.edge, a.out, a.N);
+  hipLaunchKernelGGL(reflect_fold_kernel, dim3(B), dim3(256), 0, s, a.edge, a.out, a.N, a.lens);
   return hipGetLastError();
 }
 

@@ -177,34 +177,65 @@ static int mel_grad_check(wg_stft* h, const float* mel_basis, int32_t n_mel, con
   return WG_OK;
 }
 
-int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out,
-                              int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+// lens == nullptr: every row has n_samples samples.  Otherwise lens is a device array read by the kernels only.
+static int mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
+                             float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                             void* stream) {
   const int rc = mel_grad_check(h, mel_basis, n_mel, audio, mel_out, B, n_samples, workspace, workspace_bytes);
   if (rc != WG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const MelGradLayout L = mel_grad_layout(B, n_samples);
   float* ws = (float*)workspace;
   HIP_TRY(hipMemsetAsync(ws + L.rec, 0, (L.gX - L.rec) * 4, s));  // zero lead/tail columns and pad rows of rec
-  StftArgs a{audio, h->d_fwdA, nullptr, 0.0f, ws + L.rec, nullptr, n_samples, L.F, L.Fs, ws + L.mag};
+  StftArgs a{audio, h->d_fwdA, nullptr, 0.0f, ws + L.rec, nullptr, n_samples, L.F, L.Fs, ws + L.mag,
+             lens, kFL / 2 + 1, 0};
   HIP_TRY(launch_stft(a, B, s));
-  MelArgs m{ws + L.mag, mel_basis, mel_out, n_mel, L.F, ws + L.pre};
+  MelArgs m{ws + L.mag, mel_basis, mel_out, n_mel, L.F, ws + L.pre, lens, n_samples};
   HIP_TRY(launch_mel(m, B, s));
   return WG_OK;
 }
 
-int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
-                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+static int mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, const int32_t* lens,
+                        float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                        void* stream) {
   const int rc = mel_grad_check(h, mel_basis, n_mel, g_mel, audio_grad_out, B, n_samples, workspace, workspace_bytes);
   if (rc != WG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const MelGradLayout L = mel_grad_layout(B, n_samples);
   float* ws = (float*)workspace;
   HIP_TRY(hipMemsetAsync(ws + L.gX, 0, (L.mag - L.gX) * 4, s));   // gX pads and uncovered edge positions are zero
-  MelBwdArgs m{g_mel, ws + L.pre, ws + L.mag, ws + L.rec, mel_basis, ws + L.gX, n_mel, L.F, L.Fs};
+  MelBwdArgs m{g_mel, ws + L.pre, ws + L.mag, ws + L.rec, mel_basis, ws + L.gX, n_mel, L.F, L.Fs, lens, n_samples};
   HIP_TRY(launch_mel_bwd(m, B, s));
-  IstftArgs t{ws + L.gX, h->d_fwdT, nullptr, audio_grad_out, n_samples, L.F, L.Fs, ws + L.edge};
+  IstftArgs t{ws + L.gX, h->d_fwdT, nullptr, audio_grad_out, n_samples, L.F, L.Fs, ws + L.edge, lens};
   HIP_TRY(launch_stft_grad(t, B, s));
   return WG_OK;
+}
+
+int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out,
+                              int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+  return mel_forward_saved(h, mel_basis, n_mel, audio, nullptr, mel_out, B, n_samples, workspace, workspace_bytes,
+                           stream);
+}
+
+int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
+                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+  return mel_backward(h, mel_basis, n_mel, g_mel, nullptr, audio_grad_out, B, n_samples, workspace, workspace_bytes,
+                      stream);
+}
+
+int wg_stft_mel_forward_saved_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio,
+                                     const int32_t* lens, float* mel_out, int32_t B, int32_t n_samples, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (!lens) return fail(WG_ERR_INVALID, "null argument");
+  return mel_forward_saved(h, mel_basis, n_mel, audio, lens, mel_out, B, n_samples, workspace, workspace_bytes, stream);
+}
+
+int wg_stft_mel_backward_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel,
+                                const int32_t* lens, float* audio_grad_out, int32_t B, int32_t n_samples,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (!lens) return fail(WG_ERR_INVALID, "null argument");
+  return mel_backward(h, mel_basis, n_mel, g_mel, lens, audio_grad_out, B, n_samples, workspace, workspace_bytes,
+                      stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,11 @@
 // then a gather sums, for every audio sample, the frame contributions of its (up to three, reflect padding) padded
 // positions in ascending frame order.  Sums are reduced per thread and per workgroup in fp64 and combined by one
 // fixed-order final kernel: no floating-point atomics anywhere.
+//
+// Ragged batches (wg_stftloss_*_ragged): a device array lens gives utterance b its own N_b = lens[b] samples and
+// F_b = N_b / hop + 1 frames inside the dense [B][n_samples] layout.  Reflections use N_b, frames f >= F_b add nothing
+// and store nothing, a workgroup wholly behind its utterance does no GEMM, and the term count K sum_b F_b is formed on
+// the device.  With lens == nullptr every kernel takes a uniform branch to the dense geometry.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,7 +50,18 @@ struct GemmArgs {
   double inv_cnt;        // kBwd: 1 / (B K F)
   float* G;              // kBwd: [B][F][Wp] frame gradients over the window taps
   int Wp;
+  const int* lens;       // ragged batch: device [B] sample counts (N, F, Fp are then the pitches) or null
+  int min_len;           // ragged batch: a length < min_len or > N counts as 0
+  const double* cnt;     // kBwd, ragged batch: K sum_b F_b of this resolution, written by sl_final_kernel
 };
+
+// Sample count of utterance b in a ragged batch, as ragged_len of stft.hip: a length outside [min_len, pitch] counts as
+// 0, the utterance then contributes nothing and nothing is indexed with it.
+__device__ __forceinline__ int ragged_len(const int* lens, int b, int pitch, int min_len) {
+  const int n = lens[b];
+  return (n < min_len || n > pitch) ? 0 : n;
+}
+__device__ __forceinline__ int ragged_frames(int n, int hop) { return n ? n / hop + 1 : 0; }
 
 // re^2 + im^2 with one rounding per operation, in the forward and in the backward alike, so both see the same clamp
 __device__ __forceinline__ float power(float re, float im) {
@@ -66,7 +82,8 @@ constexpr int kStB = kBN * (kKC / 2) / 256;   // backward: staged bins per threa
 
 // forward operand of chunk kc: taps lpad + 64 kc .. + 63 of 64 frames, read along the audio (reflect padding as index
 // arithmetic); element i = tid + 256 it is frame i >> 6, tap i & 63
-__device__ __forceinline__ void fetch_fwd(const GemmArgs& a, int kc, int f0, int b, int tid, float (&pv)[kStF]) {
+__device__ __forceinline__ void fetch_fwd(const GemmArgs& a, int kc, int f0, int b, int N, int F, int tid,
+                                          float (&pv)[kStF]) {
   const float* x = a.audio + (size_t)b * a.N;
   const int k0 = a.lpad + kc * kKC, half = a.n_fft / 2;
 #pragma unroll
@@ -74,10 +91,10 @@ __device__ __forceinline__ void fetch_fwd(const GemmArgs& a, int kc, int f0, int
     const int i = tid + 256 * it;
     const int f = f0 + (i >> 6), k = k0 + (i & 63);
     float v = 0.0f;
-    if (f < a.F && k < a.n_fft) {
+    if (f < F && k < a.n_fft) {
       int s = f * a.hop + k - half;
       if (s < 0) s = -s;
-      if (s >= a.N) s = 2 * (a.N - 1) - s;
+      if (s >= N) s = 2 * (N - 1) - s;
       v = x[s];
     }
     pv[it] = v;
@@ -86,7 +103,7 @@ __device__ __forceinline__ void fetch_fwd(const GemmArgs& a, int kc, int f0, int
 
 // backward operand of chunk kc: (re, im) and M(y) of bins 32 kc .. + 31 at 64 frames, read along the frames; element
 // i = tid + 256 it is frame i & 63, bin 32 kc + (i >> 6).  Zeros (no gradient) outside the transform.
-__device__ __forceinline__ void fetch_bwd(const GemmArgs& a, int kc, int f0, int b, int tid, float (&pv)[kStF],
+__device__ __forceinline__ void fetch_bwd(const GemmArgs& a, int kc, int f0, int b, int F, int tid, float (&pv)[kStF],
                                           float (&pm)[kStB], float& pm2) {
   const int half = a.n_fft / 2;
   const float* myb = a.my + (size_t)b * (half + 1) * a.Fp;
@@ -95,7 +112,7 @@ __device__ __forceinline__ void fetch_bwd(const GemmArgs& a, int kc, int f0, int
     const int i = tid + 256 * it;
     const int f = f0 + (i & 63), p = kc * (kKC / 2) + (i >> 6);
     float re = 0.0f, im = 0.0f, my = 0.0f;
-    if (f < a.F && p < half) {
+    if (f < F && p < half) {
       const float* xr = a.xraw + ((size_t)b * a.n_fft + 2 * p) * a.Fp + f;
       re = xr[0];
       im = xr[a.Fp];
@@ -145,12 +162,25 @@ __global__ void __launch_bounds__(256, 2) sl_gemm_kernel(const GemmArgs a) {
   const int col = lane & 31, kk = lane >> 5;
   const int half = a.n_fft / 2;
 
+  int N = a.N, F = a.F;                                     // this utterance's samples and frames; a.N / a.F are the pitches
+  if (a.lens) {
+    N = ragged_len(a.lens, b, a.N, a.min_len);
+    F = ragged_frames(N, a.hop);
+    if (f0 >= F) {                                          // workgroup wholly behind the utterance: no GEMM
+      if (MODE == kFwdX || MODE == kFwdXSave) {             // the final kernel adds every partial
+        const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        if (tid < 3) a.part[blk * 3 + tid] = 0.0;
+      }
+      return;
+    }
+  }
+
   float cs = 0.0f, cm = 0.0f;
   if (MODE == kBwd) {
     const double S0 = a.sums[0], S1 = a.sums[1];
     const float gsc = (a.g[0] + a.fsc * a.g[2]) * a.inv_res, gmag = (a.g[1] + a.fmag * a.g[2]) * a.inv_res;
     cs = S0 > 0.0 ? (float)((double)gsc / (sqrt(S0) * sqrt(S1))) : 0.0f;
-    cm = (float)((double)gmag * a.inv_cnt);
+    cm = (float)((double)gmag * (a.cnt ? 1.0 / a.cnt[0] : a.inv_cnt));   // a running workgroup has cnt >= K
   }
 
   // wave w takes tiles m0 + w + 4 t < m1; a tile past the end repeats the last one (computed, never stored)
@@ -172,8 +202,8 @@ __global__ void __launch_bounds__(256, 2) sl_gemm_kernel(const GemmArgs a) {
   // after them, so its latency hides behind the MFMAs.
   float pv[kStF], pm[kStB], pm2 = 0.0f;
   const int nkc = a.KS / 32;
-  if (MODE != kBwd) fetch_fwd(a, 0, f0, b, tid, pv);
-  else fetch_bwd(a, 0, f0, b, tid, pv, pm, pm2);
+  if (MODE != kBwd) fetch_fwd(a, 0, f0, b, N, F, tid, pv);
+  else fetch_bwd(a, 0, f0, b, F, tid, pv, pm, pm2);
   for (int kc = 0; kc < nkc; ++kc) {
     __syncthreads();
     if (MODE != kBwd) {
@@ -205,8 +235,8 @@ __global__ void __launch_bounds__(256, 2) sl_gemm_kernel(const GemmArgs a) {
     }
     __syncthreads();
     if (kc + 1 < nkc) {
-      if (MODE != kBwd) fetch_fwd(a, kc + 1, f0, b, tid, pv);
-      else fetch_bwd(a, kc + 1, f0, b, tid, pv, pm, pm2);
+      if (MODE != kBwd) fetch_fwd(a, kc + 1, f0, b, N, F, tid, pv);
+      else fetch_bwd(a, kc + 1, f0, b, F, tid, pv, pm, pm2);
     }
     mma_chunk<TW, MODE == kBwd>(acc, bt, a.A + (size_t)kc * 32 * 64 + lane, toff, col, kk);
   }
@@ -222,7 +252,7 @@ __global__ void __launch_bounds__(256, 2) sl_gemm_kernel(const GemmArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int f = f0 + n * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-          if (f < a.F) a.G[((size_t)b * a.F + f) * a.Wp + mt * 32 + col] = acc[t][n][r];
+          if (f < F) a.G[((size_t)b * a.F + f) * a.Wp + mt * 32 + col] = acc[t][n][r];
         }
     }
     return;
@@ -237,7 +267,7 @@ __global__ void __launch_bounds__(256, 2) sl_gemm_kernel(const GemmArgs a) {
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
       const int f = f0 + n * 32 + col;
-      if (f >= a.F) continue;
+      if (f >= F) continue;
 #pragma unroll
       for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -293,6 +323,8 @@ struct GatherArgs {
   const float* G;     // [B][F][Wp]
   float* gx;          // [B][N]
   int n_fft, hop, win, lpad, N, F, Wp, accumulate;
+  const int* lens;    // ragged batch: device [B] sample counts (N and F are then the pitches) or null
+  int min_len;
 };
 
 // d loss / d x[s]: the padded positions that hold x[s] (its own, and up to two reflected ones), each the sum over the
@@ -302,19 +334,27 @@ __global__ void __launch_bounds__(256) sl_gather_kernel(const GatherArgs a) {
   if (s >= a.N) return;
   const float* Gb = a.G + (size_t)b * a.F * a.Wp;
   const int h = a.n_fft / 2;
+  int N = a.N, F = a.F;                                     // this utterance's samples and frames
+  if (a.lens) {
+    N = ragged_len(a.lens, b, a.N, a.min_len);
+    F = ragged_frames(N, a.hop);
+  }
   auto at = [&](int p) -> float {
     const int u = p - a.lpad;                               // tap offset of frame f: u - f hop in [0, win)
     if (u < 0) return 0.0f;
     int fhi = u / a.hop;
-    if (fhi > a.F - 1) fhi = a.F - 1;
+    if (fhi > F - 1) fhi = F - 1;
     const int flo = u - a.win + 1 <= 0 ? 0 : (u - a.win + a.hop) / a.hop;
     float v = 0.0f;
     for (int f = flo; f <= fhi; ++f) v += Gb[(size_t)f * a.Wp + (u - f * a.hop)];
     return v;
   };
-  float v = at(s + h);
-  if (s >= 1 && s <= h) v += at(h - s);
-  if (s >= a.N - 1 - h && s <= a.N - 2) v += at(2 * (a.N - 1) - s + h);
+  float v = 0.0f;
+  if (s < N) {                                              // behind the utterance: 0
+    v = at(s + h);
+    if (s >= 1 && s <= h) v += at(h - s);
+    if (s >= N - 1 - h && s <= N - 2) v += at(2 * (N - 1) - s + h);
+  }
   float* o = a.gx + (size_t)b * a.N + s;
   *o = a.accumulate ? *o + v : v;
 }
@@ -325,8 +365,11 @@ struct FinalArgs {
   double cnt[kMaxRes];
   int n_res;
   float fsc, fmag;
-  double* sums;     // [n_res][2]
+  double* sums;     // [n_res][2], then from sums + 2 kMaxRes the term counts [n_res] of a ragged batch
   float* out;       // sc, mag, fsc sc + fmag mag
+  const int* lens;  // ragged batch: device [B] sample counts, or null (cnt is then the host's B K F)
+  int B, N, min_len;
+  int hop[kMaxRes], K[kMaxRes];
 };
 
 __global__ void __launch_bounds__(256) sl_final_kernel(const FinalArgs a) {
@@ -345,11 +388,35 @@ __global__ void __launch_bounds__(256) sl_final_kernel(const FinalArgs a) {
         for (int q = 0; q < 3; ++q) sh[256 * q + tid] += sh[256 * q + tid + w];
       __syncthreads();
     }
+    if (!a.lens) {
+      if (tid == 0) {
+        a.sums[2 * r] = sh[0];
+        a.sums[2 * r + 1] = sh[256];
+        sc += sqrt(sh[0]) / sqrt(sh[256]);
+        mag += sh[512] / a.cnt[r];
+      }
+      continue;
+    }
+    // ragged batch: the term count K sum_b F_b, exact integers in fp64 whatever the order
+    const double S0 = sh[0], S1 = sh[256], S2 = sh[512];
+    double nf = 0.0;
+    for (int b = tid; b < a.B; b += 256) nf += (double)ragged_frames(ragged_len(a.lens, b, a.N, a.min_len), a.hop[r]);
+    __syncthreads();
+    sh[tid] = nf;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (tid < w) sh[tid] += sh[tid + w];
+      __syncthreads();
+    }
     if (tid == 0) {
-      a.sums[2 * r] = sh[0];
-      a.sums[2 * r + 1] = sh[256];
-      sc += sqrt(sh[0]) / sqrt(sh[256]);
-      mag += sh[512] / a.cnt[r];
+      const double cnt = (double)a.K[r] * sh[0];
+      a.sums[2 * r] = S0;
+      a.sums[2 * r + 1] = S1;
+      a.sums[2 * kMaxRes + r] = cnt;
+      if (cnt > 0.0) {                                      // no valid utterance: both terms are 0, not NaN
+        sc += sqrt(S0) / sqrt(S1);
+        mag += S2 / cnt;
+      }
     }
   }
   if (tid == 0) {
@@ -508,15 +575,34 @@ size_t wg_stftloss_workspace_bytes(const wg_stftloss* h, int32_t B, int32_t n_sa
   return L.total * 4;
 }
 
-static int loss_forward(wg_stftloss* h, const float* audio, const float* target, float factor_sc, float factor_mag,
-                        float* out3, int32_t B, int32_t N, void* workspace, size_t workspace_bytes, void* stream,
-                        bool saved) {
-  if (!h || !audio || !target || !out3 || !workspace) return wg::fail(WG_ERR_INVALID, "null argument");
-  if (h->device < 0) return wg::fail(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
-  Layout L;
+// shortest length a ragged batch may hold: every resolution reflects about the utterance's own end
+static int ragged_min_len(const wg_stftloss* h) {
+  int n = 0;
+  for (int i = 0; i < h->n_res; ++i) n = h->res[i].n_fft > n ? h->res[i].n_fft : n;
+  return n / 2 + 1;
+}
+
+// Argument checks shared by the forward and the backward.  The ragged entry points (ragged = true, lens a device array
+// that only kernels read) report a null lens and bad sizes before the planning-handle refusal, the dense ones keep
+// their order.
+static int loss_check(const wg_stftloss* h, bool any_null, bool ragged, const int32_t* lens, int32_t B, int32_t N,
+                      bool saved, size_t workspace_bytes, Layout& L) {
+  if (!h || any_null || (ragged && !lens)) return wg::fail(WG_ERR_INVALID, "null argument");
+  if (!ragged && h->device < 0)
+    return wg::fail(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
   if (!layout(h, B, N, saved, L) || B > 65535)
     return wg::fail(WG_ERR_INVALID, "stft loss: bad B, or n_samples <= max n_fft / 2");
   if (workspace_bytes < L.total * 4) return wg::fail(WG_ERR_WORKSPACE, "stft loss workspace too small");
+  if (h->device < 0) return wg::fail(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
+  return WG_OK;
+}
+
+static int loss_forward(wg_stftloss* h, const float* audio, const float* target, bool ragged, const int32_t* lens,
+                        float factor_sc, float factor_mag, float* out3, int32_t B, int32_t N, void* workspace,
+                        size_t workspace_bytes, void* stream, bool saved) {
+  Layout L;
+  const int rc = loss_check(h, !audio || !target || !out3 || !workspace, ragged, lens, B, N, saved, workspace_bytes, L);
+  if (rc != WG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   FinalArgs fa{};
@@ -525,6 +611,10 @@ static int loss_forward(wg_stftloss* h, const float* audio, const float* target,
   fa.fmag = factor_mag;
   fa.sums = (double*)(ws + L.sums);
   fa.out = out3;
+  fa.lens = lens;
+  fa.B = B;
+  fa.N = N;
+  fa.min_len = ragged_min_len(h);
   for (int i = 0; i < h->n_res; ++i) {
     const Res& r = h->res[i];
     GemmArgs a{};
@@ -542,6 +632,8 @@ static int loss_forward(wg_stftloss* h, const float* audio, const float* target,
     a.my = ws + L.my[i];
     a.xraw = saved ? ws + L.xraw[i] : nullptr;
     a.part = (double*)(ws + L.part[i]);
+    a.lens = lens;
+    a.min_len = fa.min_len;
     const dim3 grid(L.nbx[i], L.nby[i], B);
     a.audio = target;
     hipLaunchKernelGGL((sl_gemm_kernel<kFwdY, kTW>), grid, dim3(256), 0, s, a);
@@ -553,6 +645,8 @@ static int loss_forward(wg_stftloss* h, const float* audio, const float* target,
     fa.part[i] = a.part;
     fa.nblk[i] = L.nbx[i] * L.nby[i] * B;
     fa.cnt[i] = (double)B * (r.n_fft / 2 + 1) * L.F[i];
+    fa.hop[i] = r.hop;
+    fa.K[i] = r.n_fft / 2 + 1;
   }
   hipLaunchKernelGGL(sl_final_kernel, dim3(1), dim3(256), 0, s, fa);
   HIP_TRY(hipGetLastError());
@@ -562,25 +656,37 @@ static int loss_forward(wg_stftloss* h, const float* audio, const float* target,
 int wg_stftloss_forward(wg_stftloss* h, const float* audio, const float* target, float factor_sc, float factor_mag,
                         float* out3, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
                         void* stream) {
-  return loss_forward(h, audio, target, factor_sc, factor_mag, out3, B, n_samples, workspace, workspace_bytes, stream,
-                      false);
+  return loss_forward(h, audio, target, false, nullptr, factor_sc, factor_mag, out3, B, n_samples, workspace,
+                      workspace_bytes, stream, false);
 }
 
 int wg_stftloss_forward_saved(wg_stftloss* h, const float* audio, const float* target, float factor_sc,
                               float factor_mag, float* out3, int32_t B, int32_t n_samples, void* workspace,
                               size_t workspace_bytes, void* stream) {
-  return loss_forward(h, audio, target, factor_sc, factor_mag, out3, B, n_samples, workspace, workspace_bytes, stream,
-                      true);
+  return loss_forward(h, audio, target, false, nullptr, factor_sc, factor_mag, out3, B, n_samples, workspace,
+                      workspace_bytes, stream, true);
 }
 
-int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, float factor_mag, float* audio_grad_out,
-                         int32_t B, int32_t N, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h || !g_out3 || !audio_grad_out || !workspace) return wg::fail(WG_ERR_INVALID, "null argument");
-  if (h->device < 0) return wg::fail(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
+int wg_stftloss_forward_ragged(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens,
+                               float factor_sc, float factor_mag, float* out3, int32_t B, int32_t n_samples,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  return loss_forward(h, audio, target, true, lens, factor_sc, factor_mag, out3, B, n_samples, workspace,
+                      workspace_bytes, stream, false);
+}
+
+int wg_stftloss_forward_saved_ragged(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens,
+                                     float factor_sc, float factor_mag, float* out3, int32_t B, int32_t n_samples,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  return loss_forward(h, audio, target, true, lens, factor_sc, factor_mag, out3, B, n_samples, workspace,
+                      workspace_bytes, stream, true);
+}
+
+static int loss_backward(wg_stftloss* h, const float* g_out3, bool ragged, const int32_t* lens, float factor_sc,
+                         float factor_mag, float* audio_grad_out, int32_t B, int32_t N, void* workspace,
+                         size_t workspace_bytes, void* stream) {
   Layout L;
-  if (!layout(h, B, N, true, L) || B > 65535)
-    return wg::fail(WG_ERR_INVALID, "stft loss: bad B, or n_samples <= max n_fft / 2");
-  if (workspace_bytes < L.total * 4) return wg::fail(WG_ERR_WORKSPACE, "stft loss workspace too small");
+  const int rc = loss_check(h, !g_out3 || !audio_grad_out || !workspace, ragged, lens, B, N, true, workspace_bytes, L);
+  if (rc != WG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   for (int i = 0; i < h->n_res; ++i) {
@@ -607,6 +713,9 @@ int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, f
     a.inv_cnt = 1.0 / ((double)B * (r.n_fft / 2 + 1) * L.F[i]);
     a.G = ws + L.G;
     a.Wp = r.MTb * 32;
+    a.lens = lens;
+    a.min_len = ragged_min_len(h);
+    a.cnt = lens ? (const double*)(ws + L.sums) + 2 * kMaxRes + i : nullptr;
     const dim3 grid(L.nbx[i], a.nby, B);
     switch (((r.MTb + a.nby - 1) / a.nby + 3) / 4) {          // tiles per wave of the fullest workgroup
       case 1: hipLaunchKernelGGL((sl_gemm_kernel<kBwd, 1>), grid, dim3(256), 0, s, a); break;
@@ -615,11 +724,24 @@ int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, f
       default: hipLaunchKernelGGL((sl_gemm_kernel<kBwd, 4>), grid, dim3(256), 0, s, a); break;
     }
     HIP_TRY(hipGetLastError());
-    GatherArgs ga{a.G, audio_grad_out, r.n_fft, r.hop, r.win, r.lpad, N, L.F[i], a.Wp, i > 0};
+    GatherArgs ga{a.G, audio_grad_out, r.n_fft, r.hop, r.win, r.lpad, N, L.F[i], a.Wp, i > 0, lens, a.min_len};
     hipLaunchKernelGGL(sl_gather_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, ga);
     HIP_TRY(hipGetLastError());
   }
   return WG_OK;
+}
+
+int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, float factor_mag, float* audio_grad_out,
+                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+  return loss_backward(h, g_out3, false, nullptr, factor_sc, factor_mag, audio_grad_out, B, n_samples, workspace,
+                       workspace_bytes, stream);
+}
+
+int wg_stftloss_backward_ragged(wg_stftloss* h, const float* g_out3, const int32_t* lens, float factor_sc,
+                                float factor_mag, float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  return loss_backward(h, g_out3, true, lens, factor_sc, factor_mag, audio_grad_out, B, n_samples, workspace,
+                       workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -36,8 +36,8 @@ struct IstftArgs {
   const float* win_sq;     // [1024]
   float* out;              // [B][N]
   int N, F, Fs;
-  float* edge;             // grad only: [B][1024] padded positions 0..511 and N+512..N+1023
-  const int* lens;         // inverse only, ragged batch: device [B] sample counts (out[b][lens[b]:] = 0) or null
+  float* edge;             // grad only: [B][1024] padded positions 0..511 and N+512..N+1023 (N the utterance's own)
+  const int* lens;         // ragged batch: device [B] sample counts (out[b][lens[b]:] = 0) or null
 };
 struct MelBwdArgs {
   const float* g;          // [B][n_mel][F]  d mel
@@ -47,6 +47,9 @@ struct MelBwdArgs {
   const float* basis;      // [n_mel][513]
   float* gX;               // [B][1056][Fs]  d (re, im); pad rows / columns zero
   int n_mel, F, Fs;
+  const int* lens;         // ragged batch: device [B] sample counts (g and pre behind an utterance's frames are unread,
+                           // gX stays zero there) or null
+  int N;                   // ragged batch: row pitch of the audio, the upper limit of a length
 };
 
 hipError_t launch_stft(const StftArgs& a, int B, hipStream_t s);

@@ -10,6 +10,11 @@ pad_mode="reflect")``), ``M = sqrt(max(re^2 + im^2, eps))``,
   mag_r = mean |log M(y) - log M(x)|            (over all B K F elements)
 
 and ``loss = factor_sc * mean_r sc_r + factor_mag * mean_r mag_r``.  No torch / CPU fallback.
+
+With ``lengths`` (a padded batch of utterances of different lengths) utterance ``b`` is transformed as its own crop
+``x[b, :lengths[b]]``: reflect padding about its own last sample, ``F_b = lengths[b] // hop + 1`` frames; the norms run
+over the frames of all crops and the mean divides by ``K * sum_b F_b``.  That is the loss of the cropped utterances with
+their frames concatenated; the samples behind an utterance's end are never read and get a zero gradient.
 """
 from __future__ import annotations
 
@@ -51,16 +56,40 @@ def check_geometry(fft_sizes, hop_sizes, win_lengths):
       raise _lib.WgError(f"win_length must be in [1, n_fft], got {w} for n_fft {n}")
 
 
+def check_lengths(lengths, B: int, N: int, min_exclusive: int):
+  """``lengths`` of a padded batch [B, N] as a list of B ints, each in (min_exclusive, N]; anything else raises WgError
+  naming the offending value.  ``lengths``: a list, tuple or CPU tensor of integers.  Pure host code."""
+  if isinstance(lengths, torch.Tensor):
+    if lengths.device.type != "cpu":
+      raise _lib.WgError("lengths must be host integers (a list, a tuple or a CPU tensor)")
+    if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+      raise _lib.WgError(f"lengths must be a 1-D integer tensor, got {lengths.dtype} of shape {tuple(lengths.shape)}")
+    lengths = lengths.tolist()
+  elif not isinstance(lengths, (list, tuple)):
+    raise _lib.WgError(f"lengths must be a list, a tuple or a CPU tensor, got {type(lengths).__name__}")
+  if len(lengths) != B:
+    raise _lib.WgError(f"{len(lengths)} lengths for a batch of {B}")
+  out = []
+  for b, n in enumerate(lengths):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+      raise _lib.WgError(f"lengths[{b}] = {n!r} is not an integer")
+    if not min_exclusive < n <= N:
+      raise _lib.WgError(f"lengths[{b}] = {n} is outside ({min_exclusive}, {N}] (reflect padding needs > "
+                         f"{min_exclusive} samples, the batch holds {N})")
+    out.append(int(n))
+  return out
+
+
 class _LossFn(torch.autograd.Function):
-  """Inputs: the module, prediction and target [B, N].  Output: the device vector (sc, mag, loss).  The forward keeps
-  the library's workspace on ctx; the backward writes only to that workspace's scratch part, so a second backward under
-  retain_graph gives the same bits."""
+  """Inputs: the module, prediction and target [B, N], and the device copy of the lengths or None.  Output: the device
+  vector (sc, mag, loss).  The forward keeps the library's workspace and the lengths on ctx; the backward writes only to
+  that workspace's scratch part, so a second backward under retain_graph gives the same bits."""
 
   @staticmethod
-  def forward(ctx, crit, x, y):
+  def forward(ctx, crit, x, y, lens):
     B, N = x.shape
-    out, ws = crit._run(x, y, saved=True)
-    ctx.crit, ctx.ws, ctx.dims = crit, ws, (B, N)
+    out, ws = crit._run(x, y, saved=True, lens=lens)
+    ctx.crit, ctx.ws, ctx.dims, ctx.lens = crit, ws, (B, N), lens
     return out
 
   @staticmethod
@@ -70,14 +99,24 @@ class _LossFn(torch.autograd.Function):
     g = g_out.to(torch.float32).contiguous()
     gx = torch.empty((B, N), dtype=torch.float32, device=ws.device)
     stream = torch.cuda.current_stream(ws.device).cuda_stream
-    _lib.check(crit.lib.wg_stftloss_backward(crit._h, g.data_ptr(), crit.factor_sc, crit.factor_mag, gx.data_ptr(), B, N,
-                                             ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    return None, gx, None
+    if ctx.lens is None:
+      _lib.check(crit.lib.wg_stftloss_backward(crit._h, g.data_ptr(), crit.factor_sc, crit.factor_mag, gx.data_ptr(), B,
+                                               N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    else:
+      _lib.check(crit.lib.wg_stftloss_backward_ragged(crit._h, g.data_ptr(), ctx.lens.data_ptr(), crit.factor_sc,
+                                                      crit.factor_mag, gx.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
+                                                      C.c_void_p(stream)))
+    return None, gx, None, None
 
 
 class MultiResolutionSTFTLoss(torch.nn.Module):
-  """``crit(audio, target)`` -> 0-dim fp32 loss on the device with a graph back to ``audio``; ``crit.terms(audio,
-  target)`` -> ``(sc, mag)``.
+  """``crit(audio, target, lengths=None)`` -> 0-dim fp32 loss on the device with a graph back to ``audio``;
+  ``crit.terms(audio, target, lengths=None)`` -> ``(sc, mag)``.
+
+  ``lengths``: B host integers (list, tuple or CPU tensor), the sample count of every utterance of a padded batch, each
+  in ``(max(fft_sizes) / 2, N]`` (checked on the host by ``check_lengths``, WgError otherwise); they go up in one small
+  copy per call.  The loss is then that of the crops ``audio[b, :lengths[b]]`` with their frames concatenated (see the
+  module docstring), ``audio.grad[b, lengths[b]:]`` is 0, and ``lengths=[N] * B`` gives the bits of ``lengths=None``.
 
   ``audio``, ``target``: fp32 ``[B, N]`` on the module's device, same shape, ``N > max(fft_sizes) / 2``; anything else
   raises WgError.  Only ``audio`` gets a gradient (a ``target`` that requires grad raises WgError); the clamp at ``eps``
@@ -141,8 +180,16 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
     if x.shape[0] < 1 or x.shape[1] <= need:
       raise _lib.WgError(f"audio of {x.shape[1]} samples is too short (reflect padding needs > {need})")
 
-  def _run(self, x, y, saved):
-    """One library call on contiguous fp32 [B, N]: (out3, workspace)."""
+  def _lens(self, lengths, x):
+    """The checked lengths as an int32 tensor on x's device (one small copy), or None."""
+    if lengths is None:
+      return None
+    B, N = x.shape
+    lens = check_lengths(lengths, B, N, max(n for n, _, _ in self.resolutions) // 2)
+    return torch.tensor(lens, dtype=torch.int32).to(x.device)
+
+  def _run(self, x, y, saved, lens=None):
+    """One library call on contiguous fp32 [B, N]: (out3, workspace).  lens: int32 [B] on the device, or None."""
     x, y = x.detach().contiguous(), y.detach().contiguous()
     B, N = x.shape
     nbytes = self.lib.wg_stftloss_workspace_bytes(self._h, B, N, 1 if saved else 0)
@@ -151,21 +198,27 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
     out = torch.empty(3, dtype=torch.float32, device=x.device)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    fn = self.lib.wg_stftloss_forward_saved if saved else self.lib.wg_stftloss_forward
-    _lib.check(fn(self._h, x.data_ptr(), y.data_ptr(), self.factor_sc, self.factor_mag, out.data_ptr(), B, N,
-                  ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    if lens is None:
+      fn = self.lib.wg_stftloss_forward_saved if saved else self.lib.wg_stftloss_forward
+      _lib.check(fn(self._h, x.data_ptr(), y.data_ptr(), self.factor_sc, self.factor_mag, out.data_ptr(), B, N,
+                    ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    else:
+      fn = self.lib.wg_stftloss_forward_saved_ragged if saved else self.lib.wg_stftloss_forward_ragged
+      _lib.check(fn(self._h, x.data_ptr(), y.data_ptr(), lens.data_ptr(), self.factor_sc, self.factor_mag,
+                    out.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     return out, ws
 
-  def _out3(self, audio, target):
+  def _out3(self, audio, target, lengths=None):
     self._check(audio, target)
+    lens = self._lens(lengths, audio)
     if torch.is_grad_enabled() and audio.requires_grad:
-      return _LossFn.apply(self, audio, target)
-    return self._run(audio, target, saved=False)[0]
+      return _LossFn.apply(self, audio, target, lens)
+    return self._run(audio, target, saved=False, lens=lens)[0]
 
-  def terms(self, audio: torch.Tensor, target: torch.Tensor):
+  def terms(self, audio: torch.Tensor, target: torch.Tensor, lengths=None):
     """(sc, mag): the spectral-convergence and log-magnitude terms, each averaged over the resolutions."""
-    out = self._out3(audio, target)
+    out = self._out3(audio, target, lengths)
     return out[0], out[1]
 
-  def forward(self, audio: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    return self._out3(audio, target)[2]
+  def forward(self, audio: torch.Tensor, target: torch.Tensor, lengths=None) -> torch.Tensor:
+    return self._out3(audio, target, lengths)[2]

@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from .audio import wav_to_float32
 from .denoiser import stft_bases
+from .stft_loss import check_lengths
 
 FLOAT32_64_MIN_WAV, FLOAT32_64_MAX_WAV = -1.0, 1.0   # audio_utils.py
 
@@ -82,12 +83,13 @@ def dynamic_range_decompression(x, C_=1):
 
 
 class _MelFn(torch.autograd.Function):
-  """Inputs: the TacotronSTFT module and the audio [B, N].  The forward keeps the library's workspace (spectrum,
-  magnitudes, pre-log sums) on ctx; the backward writes its d (re, im) to a separate part of that workspace, so the
-  saved state survives and a second backward under retain_graph gives the same gradient."""
+  """Inputs: the TacotronSTFT module, the audio [B, N] and the device copy of the lengths (int32 [B]) or None.  The
+  forward keeps the library's workspace (spectrum, magnitudes, pre-log sums) and the lengths on ctx; the backward writes
+  its d (re, im) to a separate part of that workspace, so the saved state survives and a second backward under
+  retain_graph gives the same gradient."""
 
   @staticmethod
-  def forward(ctx, taco, y):
+  def forward(ctx, taco, y, lens):
     y = y.contiguous()
     B, N = y.shape
     lib = taco.lib
@@ -97,9 +99,14 @@ class _MelFn(torch.autograd.Function):
     mel = torch.empty((B, taco.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=y.device)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
     stream = torch.cuda.current_stream(y.device).cuda_stream
-    _lib.check(lib.wg_stft_mel_forward_saved(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, y.data_ptr(),
-                                             mel.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    ctx.taco, ctx.ws, ctx.dims = taco, ws, (B, N)
+    if lens is None:
+      _lib.check(lib.wg_stft_mel_forward_saved(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, y.data_ptr(),
+                                               mel.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    else:
+      _lib.check(lib.wg_stft_mel_forward_saved_ragged(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels,
+                                                      y.data_ptr(), lens.data_ptr(), mel.data_ptr(), B, N,
+                                                      ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    ctx.taco, ctx.ws, ctx.dims, ctx.lens = taco, ws, (B, N), lens
     return mel
 
   @staticmethod
@@ -109,9 +116,14 @@ class _MelFn(torch.autograd.Function):
     g = g_mel.to(torch.float32).contiguous()
     gy = torch.empty((B, N), dtype=torch.float32, device=ws.device)
     stream = torch.cuda.current_stream(ws.device).cuda_stream
-    _lib.check(taco.lib.wg_stft_mel_backward(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, g.data_ptr(),
-                                             gy.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    return None, gy
+    if ctx.lens is None:
+      _lib.check(taco.lib.wg_stft_mel_backward(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, g.data_ptr(),
+                                               gy.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    else:
+      _lib.check(taco.lib.wg_stft_mel_backward_ragged(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels,
+                                                      g.data_ptr(), ctx.lens.data_ptr(), gy.data_ptr(), B, N,
+                                                      ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    return None, gy, None
 
 
 class TacotronSTFT(torch.nn.Module):
@@ -227,8 +239,14 @@ class TacotronSTFT(torch.nn.Module):
                                            C.c_void_p(stream)))
     return out, [n // 256 + 1 for n in lens], both[1]
 
-  def mel_spectrogram_differentiable(self, y: torch.Tensor) -> torch.Tensor:
+  def mel_spectrogram_differentiable(self, y: torch.Tensor, lengths=None) -> torch.Tensor:
     """``mel_spectrogram(y)`` with an autograd graph back to ``y`` (taco_stft.py:84-104 without the detach at :99).
+
+    ``lengths``: B host integers in (512, N] (list, tuple or CPU tensor; WgError otherwise), the sample counts of a padded
+    batch.  The result is then what ``mel_spectrogram_ragged_device(y, lengths)`` returns as ``mel``, bit for bit: row b
+    is the mel of the crop ``y[b, :lengths[b]]`` in its first ``lengths[b] // 256 + 1`` columns and 0 behind them.  Its
+    backward ignores the gradient of those zero columns, gives ``y.grad[b, :lengths[b]]`` the bits of the crop's own
+    backward (reflect padding about its own last sample) and ``y.grad[b, lengths[b]:] = 0``.
 
     ``y`` [B, N] fp32 on the module's device, any N > 512 -> [B, n_mel_channels, N // 256 + 1], bit-identical to
     ``mel_spectrogram``.  No range assert and no host synchronisation: generated audio may leave [-1, 1].  With grad
@@ -241,8 +259,13 @@ class TacotronSTFT(torch.nn.Module):
       raise _lib.WgError(f"mel_spectrogram_differentiable takes float32 audio, got {y.dtype}")
     if y.dim() != 2:
       raise _lib.WgError(f"mel_spectrogram_differentiable takes audio [B, N], got shape {tuple(y.shape)}")
+    if lengths is not None:
+      lens = check_lengths(lengths, y.shape[0], y.shape[1], 512)
+      if torch.is_grad_enabled() and y.requires_grad:
+        return _MelFn.apply(self, y, torch.tensor(lens, dtype=torch.int32).to(y.device))
+      return self.mel_spectrogram_ragged_device(y.detach(), lens)[0]
     if torch.is_grad_enabled() and y.requires_grad:
-      return _MelFn.apply(self, y)
+      return _MelFn.apply(self, y, None)
     return self._mel(y.detach().contiguous())
 
   def get_wav_tensor_from_file(self, wav_path) -> torch.Tensor:
