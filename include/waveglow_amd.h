@@ -270,6 +270,55 @@ int wg_metrics_mel(const float* mel_a, const int32_t* frames_a, const float* mel
                    double* rows_out, int32_t B, int32_t n_mel, int32_t n_mfcc, int32_t tmax_a, int32_t tmax_b,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Pitch metrics of audio pairs: a YIN F0 tracker and the F0 / voicing errors of two tracks, no handle ------------
+ * The reference has no counterpart.  The tracker restates steps 1-5 of de Cheveigne & Kawahara, "YIN, a fundamental
+ * frequency estimator for speech and music", JASA 111(4), 2002: difference function (eq. 6), cumulative mean normalised
+ * difference (eq. 8), absolute threshold (step 4), parabolic interpolation (step 5).  Step 6, an energy gate, centred
+ * frames and any smoothing of the track are not built.
+ * Parameters: sampling_rate sr, frame_length W in [16, 2048], hop_length H >= 1, 2 <= tau_min < tau_max <= 1024,
+ * 0 < threshold < 1; a caller with a frequency range passes tau_max = ceil(sr / fmin), tau_min = max(2, floor(sr / fmax)).
+ * Anything else is WG_ERR_INVALID.
+ * Frames: audio [B][N] fp32 device, lens int32 device [B], read by the kernels only; a length outside [0, N] counts as
+ *   0 frames.  Utterance b has F_b = (len_b - W - tau_max) / H + 1 frames if len_b >= W + tau_max, else 0 (wg_pitch_frames
+ *   gives this count for a length).  Frame t starts at s = t H and reads x[s .. s + W + tau_max - 1]: no padding, no
+ *   centring, nothing behind len_b is ever read.
+ * Per frame, in fp64 on the fp32 samples, no contraction:
+ *   d(tau) = sum_{j = 0 .. W-1 ascending} (x[s+j] - x[s+j+tau])^2, tau = 0 .. tau_max, as written (no autocorrelation
+ *     identity);
+ *   d'(0) = 1, d'(tau) = d(tau) tau / sum_{k=1..tau} d(k), and 1 where that sum is 0;
+ *   pick: the smallest tau in [tau_min, tau_max] with d'(tau) < threshold, then tau += 1 while tau + 1 <= tau_max and
+ *     d'(tau+1) < d'(tau).  No such lag: f0 = 0 (unvoiced), aperiodicity = min d' over [tau_min, tau_max].  Otherwise
+ *     aperiodicity = d'(tau) and, where tau - 1 >= 1 and tau + 1 <= tau_max, with a, b, c = d'(tau-1), d'(tau), d'(tau+1)
+ *     and den = a - 2b + c: shift = (a - c) / (2 den) if den > 0 and |shift| <= 1, else 0; f0 = sr / (tau + shift).
+ *   d(tau) is the plain ascending sum; the running sum of d is a scan of fixed shape (it depends on tau_max alone), so a
+ *   frame's values depend on its samples and the parameters only: a call gives the same bits every time, an utterance of
+ *   a batch the bits of its own call with B = 1 and N = len_b, and audio scaled by a power of two the same tracks.
+ * wg_pitch_yin: f0_out, aperiodicity_out [B][fmax] fp64, 0 behind an utterance's frames; frames_out int32 [B].
+ *   1 <= B <= 65535, N >= 1, fmax >= max(1, F(N)).
+ * wg_pitch_compare: tracks f0_a [B][fmax_a], f0_b [B][fmax_b] with frame counts (a count outside [0, fmax] counts as 0)
+ *   -> rows_out[b] = 8 fp64 over the F = min(Fa, Fb) first frames, a frame being voiced where f0 > 0:
+ *     {F0_RMSE_CENTS = sqrt(mean over the both-voiced frames of (1200 log2(f0_b / f0_a))^2), F0_RMSE_HZ = the same of
+ *      f0_b - f0_a, GPE = share of the both-voiced frames with |f0_b / f0_a - 1| > 0.2, VUV_ERROR = share of the F frames
+ *      voiced on exactly one side, FRAMES = F, VOICED_A, VOICED_B, VOICED_BOTH = counts among the F frames}.
+ *   The first three are NaN when no frame is voiced on both sides, the first four when F = 0.  A thread sums its frames
+ *   ascending, the partial sums are joined by a fixed tree.
+ * wg_pitch_metrics: wg_pitch_yin of audio_a [B][n_a] and of audio_b [B][n_b], then wg_pitch_compare of the two tracks,
+ *   bit for bit those three calls.  Workspace: wg_pitch_workspace_bytes (0 for arguments outside the limits).
+ * Enqueue-only. */
+typedef struct wg_pitch_params {
+  double sampling_rate, threshold;
+  int32_t frame_length, hop_length, tau_min, tau_max;
+} wg_pitch_params;
+int32_t wg_pitch_frames(const wg_pitch_params* params, int32_t n_samples);   /* F(n_samples), or an error code (< 0) */
+size_t wg_pitch_workspace_bytes(const wg_pitch_params* params, int32_t B, int32_t n_a, int32_t n_b);
+int wg_pitch_yin(const float* audio, const int32_t* lens, const wg_pitch_params* params, double* f0_out,
+                 double* aperiodicity_out, int32_t* frames_out, int32_t B, int32_t N, int32_t fmax, void* stream);
+int wg_pitch_compare(const double* f0_a, const int32_t* frames_a, const double* f0_b, const int32_t* frames_b,
+                     double* rows_out, int32_t B, int32_t fmax_a, int32_t fmax_b, void* stream);
+int wg_pitch_metrics(const float* audio_a, const int32_t* lens_a, int32_t n_a, const float* audio_b, const int32_t* lens_b,
+                     int32_t n_b, const wg_pitch_params* params, double* rows_out, int32_t B, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ---- Multi-resolution STFT loss (spectral convergence + log-magnitude L1), fp32, with its backward ------------------
  * For resolution r = (n_fft, hop, win): X = STFT(x) with reflect padding by n_fft/2 and the window of `win` samples
  * centred in n_fft, M = sqrt(max(re^2 + im^2, eps)); sc_r = |M(y) - M(x)|_F / |M(y)|_F over the whole batch,

@@ -21,7 +21,7 @@ def __getattr__(name):
   if name == "MultiResolutionSTFTLoss":
     from .stft_loss import MultiResolutionSTFTLoss
     return MultiResolutionSTFTLoss
-  if name in ("mel_metrics", "MelMetrics"):
+  if name in ("mel_metrics", "MelMetrics", "pitch_metrics", "PitchMetrics", "yin_f0"):
     from . import metrics
     return getattr(metrics, name)
   if name in ("validate", "ValidationEntry", "ValidationEntries"):

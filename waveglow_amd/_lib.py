@@ -44,6 +44,12 @@ class WgTrainGrads(C.Structure):
     ("layer_stride", C.c_int64), ("flow_stride", C.c_int64)]
 
 
+class WgPitchParams(C.Structure):
+  """wg_pitch_params (include/waveglow_amd.h)."""
+  _fields_ = [("sampling_rate", C.c_double), ("threshold", C.c_double)] + [(n, C.c_int32) for n in (
+    "frame_length", "hop_length", "tau_min", "tau_max")]
+
+
 class WgError(RuntimeError):
   pass
 
@@ -155,6 +161,14 @@ SIGNATURES = {
                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
   "wg_metrics_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_pitch_frames": (C.c_int32, [C.POINTER(WgPitchParams), C.c_int32]),
+  "wg_pitch_workspace_bytes": (C.c_size_t, [C.POINTER(WgPitchParams), C.c_int32, C.c_int32, C.c_int32]),
+  "wg_pitch_yin": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(WgPitchParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+  "wg_pitch_compare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_void_p]),
+  "wg_pitch_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                 C.POINTER(WgPitchParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stftloss_create": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_void_p), C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stftloss_destroy": (C.c_int, [C.c_void_p]),

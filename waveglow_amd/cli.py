@@ -12,10 +12,11 @@ commented-out ``--batch-size``, inference_v2.py:64) and per-rank sharding of the
          --device-dataset: all wavs stay on the device and every batch is built there (waveglow_amd/device_data.py)
   python -m waveglow_amd.cli validate CHECKPOINTS-FOLDER OUTPUT-FOLDER DATA-FOLDER [--sigma S] [--denoiser-strength D]
          [--device cuda:0] [--custom-hparams ...] [--full-run] [--files NAME ...] [--custom-checkpoints IT ...]
-         [--custom-seed N] [--batch-size B]                          (src/waveglow_cli/validation.py:86-153)
+         [--custom-seed N] [--batch-size B] [--pitch-metrics]        (src/waveglow_cli/validation.py:86-153)
          copy synthesis of validation utterances and their metrics on the device (MCD, DTW-MCD, penalties, cosine
          similarity): OUTPUT-FOLDER/log.txt, total.csv and one folder of mels and wavs per utterance and checkpoint;
-         no PNG plots and no structural similarity, single process only
+         no PNG plots and no structural similarity, single process only.  --pitch-metrics adds the F0 RMSE, the gross
+         pitch error and the voicing decision error between the original and the synthesis (a YIN tracker on the device)
 Under ``python -m torch.distributed.run`` the training commands run data-parallel (one process per GPU, RCCL).
 """
 from __future__ import annotations
@@ -90,6 +91,9 @@ def build_parser() -> argparse.ArgumentParser:
   v.add_argument("--custom-seed", type=int, default=None)
   v.add_argument("--batch-size", type=int, default=1,
                  help="utterances per launch sequence (ragged batch; results equal one-by-one validation)")
+  v.add_argument("--pitch-metrics", action="store_true",
+                 help="also track F0 of the original and the synthesis (YIN) and report F0 RMSE, gross pitch error and "
+                      "voicing decision error in seven more columns")
   return p
 
 
@@ -225,7 +229,8 @@ def validate_cmd(ns) -> bool:
                                entry_names=set(ns.files), full_run=ns.full_run,
                                save_callback=partial(_save_validation, val_dir=ns.output_dir, iteration=iteration),
                                sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=ns.custom_seed,
-                               device=torch.device(ns.device), batch_size=ns.batch_size))
+                               device=torch.device(ns.device), batch_size=ns.batch_size,
+                               pitch_metrics=ns.pitch_metrics))
       except AssertionError as e:
         logger.error(str(e) or "validation failed an assertion")
         return False

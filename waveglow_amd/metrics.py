@@ -1,4 +1,4 @@
-"""Validation metrics of mel-spectrogram pairs on the device (``wg_metrics_*``): MFCCs, mel-cepstral distortion with and
+"""Validation metrics on the device.  Of mel-spectrogram pairs (``wg_metrics_*``): MFCCs, mel-cepstral distortion with and
 without exact dynamic time warping, the alignment penalties and the per-channel cosine similarity -- what the reference's
 ``validate`` computes per utterance on the host with ``mel_cepstral_distance.get_metrics_mels(n_mfcc=16, take_log=False)``
 and ``cosine_dist_mels`` (src/waveglow/validation.py:211-235, utils.py:510-523).
@@ -7,6 +7,11 @@ Ragged batches in the project's usual form: fp32 tensors ``[B, C, Tmax]`` on one
 Everything is enqueued on the current stream; only ``mel_metrics`` copies to the host.  The definitions are stated in
 include/waveglow_amd.h and DESIGN.md section 7; parity with the ``mel_cepstral_distance`` package itself is unpinned (the
 package is absent), and the alignment here is exact where that package's ``fastdtw`` is approximate.  No CPU fallback.
+
+Of audio pairs (``wg_pitch_*``, the second half of this file): a YIN F0 tracker (steps 1-5 of de Cheveigne & Kawahara 2002)
+over fp32 audio ``[B, N]`` with per-utterance sample counts, and the F0 RMSE, gross pitch error and voicing decision error of
+two tracks.  The reference has no counterpart; parity with any external tracker (librosa's ``yin`` / ``pyin`` and others,
+all absent) is unpinned, the numpy restatement tests/_pitch_oracle.py is the yardstick.
 """
 from __future__ import annotations
 
@@ -23,6 +28,10 @@ MAX_FEATURES = 128      # mel channels / feature rows
 N_ROW = 8               # fp64 values per utterance of the fused call
 MCD, PENALTY, FRAMES, MCD_DTW, PENALTY_DTW, FRAMES_DTW, COSINE = range(7)
 
+PITCH_MIN_FRAME, PITCH_MAX_FRAME = 16, 2048      # frame_length (include/waveglow_amd.h: wg_pitch_*)
+PITCH_MAX_TAU = 1024                             # largest lag
+F0_RMSE_CENTS, F0_RMSE_HZ, GPE, VUV_ERROR, PITCH_FRAMES, VOICED_A, VOICED_B, VOICED_BOTH = range(8)
+
 Frames = Union[None, Sequence[int], torch.Tensor]
 
 
@@ -35,6 +44,18 @@ class MelMetrics:
   penalty_dtw: float      # 2 - (Ta + Tb) / frames_dtw
   frames_dtw: int         # length of the optimal warping path
   cosine: float           # 1 - mean over the mel channels of the cosine distance, zero-padded in time
+
+
+@dataclass
+class PitchMetrics:
+  f0_rmse_cents: float    # over the frames voiced on both sides; NaN without one
+  f0_rmse_hz: float
+  gross_pitch_error: float   # share of the both-voiced frames more than 20 % apart
+  vuv_error: float        # share of the frames voiced on exactly one side; NaN without a frame
+  frames: int             # min(Fa, Fb)
+  voiced_a: int
+  voiced_b: int
+  voiced_both: int
 
 
 def _features(name: str, x, device=None) -> torch.Tensor:
@@ -151,3 +172,148 @@ def mel_metrics(mel_a: torch.Tensor, frames_a: Frames, mel_b: torch.Tensor, fram
   host.copy_(rows, non_blocking=True)
   torch.cuda.current_stream(rows.device).synchronize()
   return rows_to_metrics(host)
+
+
+# ------------------------------------------------------------------------------------------------------ pitch metrics
+def pitch_params(sampling_rate=22050, frame_length: int = 1024, hop_length: int = 256, fmin: float = 60.0,
+                 fmax: float = 600.0, threshold: float = 0.1) -> _lib.WgPitchParams:
+  """The tracker's parameters with the lags derived from the frequency range, tau_max = ceil(sr / fmin) and tau_min =
+  max(2, floor(sr / fmax)); WgError outside the limits of include/waveglow_amd.h (wg_pitch_*).  Needs no GPU."""
+  import math
+  try:
+    sr, W, H, lo, hi, th = float(sampling_rate), int(frame_length), int(hop_length), float(fmin), float(fmax), \
+        float(threshold)
+  except (TypeError, ValueError) as e:
+    raise _lib.WgError(f"pitch: numeric parameters expected ({e})")
+  if W != frame_length or H != hop_length:
+    raise _lib.WgError(f"pitch: integer frame_length and hop_length expected, got {frame_length}, {hop_length}")
+  if not (math.isfinite(sr) and math.isfinite(lo) and math.isfinite(hi) and 0 < sr < 1e9 and 0 < lo < hi):
+    raise _lib.WgError(f"pitch: 0 < fmin < fmax and a sampling rate in (0, 1e9) expected, got {fmin}, {fmax}, {sampling_rate}")
+  if not PITCH_MIN_FRAME <= W <= PITCH_MAX_FRAME:
+    raise _lib.WgError(f"pitch: frame_length in [{PITCH_MIN_FRAME}, {PITCH_MAX_FRAME}] expected, got {W}")
+  if H < 1 or H >= 2 ** 31:
+    raise _lib.WgError(f"pitch: hop_length >= 1 expected, got {H}")
+  tau_max, tau_min = math.ceil(sr / lo), max(2, math.floor(sr / hi))
+  if not 2 <= tau_min < tau_max <= PITCH_MAX_TAU:
+    raise _lib.WgError(f"pitch: 2 <= tau_min < tau_max <= {PITCH_MAX_TAU} expected, got lags {tau_min} .. {tau_max} from "
+                       f"fmin {fmin}, fmax {fmax} at {sampling_rate} Hz")
+  if not 0 < th < 1:
+    raise _lib.WgError(f"pitch: threshold in (0, 1) expected, got {threshold}")
+  return _lib.WgPitchParams(sr, th, W, H, tau_min, tau_max)
+
+
+def pitch_frames(n_samples: int, p: _lib.WgPitchParams) -> int:
+  """F(n_samples): (n - W - tau_max) // H + 1, or 0 for fewer than W + tau_max samples."""
+  need = p.frame_length + p.tau_max
+  return (n_samples - need) // p.hop_length + 1 if n_samples >= need else 0
+
+
+def _audio(name: str, x, device=None) -> torch.Tensor:
+  if not isinstance(x, torch.Tensor):
+    raise _lib.WgError(f"{name} takes a tensor, got {type(x).__name__}")
+  if x.dtype != torch.float32:
+    raise _lib.WgError(f"{name} takes float32, got {x.dtype}")
+  if x.dim() != 2 or x.shape[0] < 1 or x.shape[0] > 65535 or x.shape[1] < 1 or x.shape[1] >= 2 ** 31:
+    raise _lib.WgError(f"{name} takes [B, N] with 1 <= B <= 65535 and N >= 1, got shape {tuple(x.shape)}")
+  if x.device.type != "cuda":
+    raise _lib.WgError(f"{name}: the pitch metrics run on the GPU library only (no CPU fallback)")
+  if device is not None and x.device != device:
+    raise _lib.WgError(f"{name}: both sides must be on one GPU, got {x.device} and {device}")
+  return x.contiguous()
+
+
+def _lengths(name: str, lengths: Frames, x: torch.Tensor) -> torch.Tensor:
+  """int32 [B] on x's device.  A host list is range-checked here; a device tensor is never read on the host (the kernels
+  treat a length outside [0, N] as 0 frames)."""
+  B, N = x.shape
+  if lengths is None:
+    lengths = [N] * B
+  if isinstance(lengths, torch.Tensor) and lengths.device.type == "cuda":
+    if lengths.device != x.device or lengths.dtype != torch.int32 or lengths.dim() != 1 or lengths.numel() != B:
+      raise _lib.WgError(f"{name}: lengths on the device must be int32 [{B}] on {x.device}")
+    return lengths.contiguous()
+  host = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+  if len(host) != B:
+    raise _lib.WgError(f"{name}: {len(host)} lengths for a batch of {B}")
+  if any(n < 0 or n > N for n in host):
+    raise _lib.WgError(f"{name}: lengths in [0, {N}] expected, got {host}")
+  return torch.tensor(host, dtype=torch.int32).to(x.device)
+
+
+def yin_f0(audio: torch.Tensor, lengths: Frames = None, *, sampling_rate=22050, frame_length: int = 1024,
+           hop_length: int = 256, fmin: float = 60.0, fmax: float = 600.0,
+           threshold: float = 0.1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+  """YIN tracks (steps 1-5, include/waveglow_amd.h: wg_pitch_yin) of fp32 audio [B, N] on one GPU: ``(f0, aperiodicity,
+  frames)``, fp64 [B, Fmax] twice and int32 [B], on the device.  Fmax = max(1, F(N)); utterance b has ``frames[b]`` =
+  F(lengths[b]) frames, 0 behind them; an unvoiced frame has f0 = 0.  Nothing behind an utterance's length is read."""
+  p = pitch_params(sampling_rate, frame_length, hop_length, fmin, fmax, threshold)
+  x = _audio("yin_f0: audio", audio)
+  ln = _lengths("yin_f0", lengths, x)
+  B, N = x.shape
+  F = max(1, pitch_frames(N, p))
+  f0 = torch.empty((B, F), dtype=torch.float64, device=x.device)
+  ap = torch.empty((B, F), dtype=torch.float64, device=x.device)
+  frames = torch.empty(B, dtype=torch.int32, device=x.device)
+  with torch.cuda.device(x.device):
+    _lib.check(_lib.load().wg_pitch_yin(x.data_ptr(), ln.data_ptr(), C.byref(p), f0.data_ptr(), ap.data_ptr(),
+                                        frames.data_ptr(), B, N, F, _stream(x)))
+  return f0, ap, frames
+
+
+def pitch_compare(f0_a: torch.Tensor, frames_a: torch.Tensor, f0_b: torch.Tensor, frames_b: torch.Tensor) -> torch.Tensor:
+  """Rows fp64 [B, 8] (wg_pitch_compare) of two track sets as ``yin_f0`` returns them: fp64 [B, F] and int32 [B] on one
+  GPU."""
+  for name, f0, fr in (("f0_a", f0_a, frames_a), ("f0_b", f0_b, frames_b)):
+    if not isinstance(f0, torch.Tensor) or f0.device.type != "cuda" or not isinstance(fr, torch.Tensor):
+      raise _lib.WgError(f"pitch_compare: {name}: the pitch metrics run on the GPU library only (no CPU fallback)")
+    if f0.dtype != torch.float64 or f0.dim() != 2 or f0.shape[0] < 1 or f0.shape[0] > 65535 or f0.shape[1] < 1:
+      raise _lib.WgError(f"pitch_compare: {name} takes float64 [B, F], got {f0.dtype} {tuple(f0.shape)}")
+    if fr.device != f0_a.device or f0.device != f0_a.device or fr.dtype != torch.int32 or fr.dim() != 1 or \
+        fr.numel() != f0_a.shape[0] or f0.shape[0] != f0_a.shape[0]:
+      raise _lib.WgError(f"pitch_compare: {name} and its frame counts must be [B, F] and int32 [B] on {f0_a.device}")
+  a, b = f0_a.contiguous(), f0_b.contiguous()
+  rows = torch.empty((a.shape[0], N_ROW), dtype=torch.float64, device=a.device)
+  with torch.cuda.device(a.device):
+    _lib.check(_lib.load().wg_pitch_compare(a.data_ptr(), frames_a.contiguous().data_ptr(), b.data_ptr(),
+                                            frames_b.contiguous().data_ptr(), rows.data_ptr(), a.shape[0], a.shape[1],
+                                            b.shape[1], _stream(a)))
+  return rows
+
+
+def pitch_metrics_enqueue(audio_a: torch.Tensor, lengths_a: Frames, audio_b: torch.Tensor, lengths_b: Frames, *,
+                          sampling_rate=22050, frame_length: int = 1024, hop_length: int = 256, fmin: float = 60.0,
+                          fmax: float = 600.0, threshold: float = 0.1) -> torch.Tensor:
+  """The pitch metrics of the pairs (audio_a[b], audio_b[b]), a the original and b the synthesised audio, aligned frame
+  by frame, in one launch sequence without a synchronise: fp64 [B, 8] on the device, columns F0_RMSE_CENTS, F0_RMSE_HZ,
+  GPE, VUV_ERROR, PITCH_FRAMES, VOICED_A, VOICED_B, VOICED_BOTH (wg_pitch_metrics)."""
+  p = pitch_params(sampling_rate, frame_length, hop_length, fmin, fmax, threshold)
+  a = _audio("pitch_metrics: audio_a", audio_a)
+  b = _audio("pitch_metrics: audio_b", audio_b, a.device)
+  if a.shape[0] != b.shape[0]:
+    raise _lib.WgError(f"pitch_metrics: batch sizes differ, {tuple(a.shape)} against {tuple(b.shape)}")
+  la, lb = _lengths("pitch_metrics: lengths_a", lengths_a, a), _lengths("pitch_metrics: lengths_b", lengths_b, b)
+  B = a.shape[0]
+  lib = _lib.load()
+  rows = torch.empty((B, N_ROW), dtype=torch.float64, device=a.device)
+  ws = torch.empty(lib.wg_pitch_workspace_bytes(C.byref(p), B, a.shape[1], b.shape[1]), dtype=torch.uint8, device=a.device)
+  with torch.cuda.device(a.device):
+    _lib.check(lib.wg_pitch_metrics(a.data_ptr(), la.data_ptr(), a.shape[1], b.data_ptr(), lb.data_ptr(), b.shape[1],
+                                    C.byref(p), rows.data_ptr(), B, ws.data_ptr(), ws.numel(), _stream(a)))
+  return rows
+
+
+def rows_to_pitch_metrics(rows) -> List[PitchMetrics]:
+  """Host copy of ``pitch_metrics_enqueue``'s rows -> one PitchMetrics per pair."""
+  return [PitchMetrics(f0_rmse_cents=r[F0_RMSE_CENTS], f0_rmse_hz=r[F0_RMSE_HZ], gross_pitch_error=r[GPE],
+                       vuv_error=r[VUV_ERROR], frames=int(r[PITCH_FRAMES]), voiced_a=int(r[VOICED_A]),
+                       voiced_b=int(r[VOICED_B]), voiced_both=int(r[VOICED_BOTH])) for r in rows.tolist()]
+
+
+def pitch_metrics(audio_a: torch.Tensor, lengths_a: Frames, audio_b: torch.Tensor, lengths_b: Frames,
+                  **params) -> List[PitchMetrics]:
+  """``pitch_metrics_enqueue`` + one copy to the host + one stream synchronise."""
+  rows = pitch_metrics_enqueue(audio_a, lengths_a, audio_b, lengths_b, **params)
+  host = torch.empty(rows.shape, dtype=rows.dtype, pin_memory=True)
+  host.copy_(rows, non_blocking=True)
+  torch.cuda.current_stream(rows.device).synchronize()
+  return rows_to_pitch_metrics(host)

@@ -184,6 +184,13 @@ class TacotronSTFT(torch.nn.Module):
     [B, n_mel_channels, Tmax] on the module's device, ``frames[b] = len(wavs[b]) // 256 + 1``; ``mel[b, :, :frames[b]]``
     is bit for bit ``mel_spectrogram(wavs[b][None])[0]`` and the columns behind it are 0.  The reference's range assert
     (taco_stft.py:95-97) runs on the host before the upload, so nothing on the device is synchronised.  No graph."""
+    mel, frames, _, _ = self.mel_spectrogram_ragged_keep(wavs)
+    return mel, frames
+
+  def mel_spectrogram_ragged_keep(self, wavs):
+    """``mel_spectrogram_ragged`` that also returns what it uploaded: ``(mel, frames, audio, lens)`` with ``audio`` fp32
+    [B, N] (zero behind an utterance) and ``lens`` int32 [B] on the module's device, for callers that go on working with
+    the waveforms there (the pitch metrics of ``validate``)."""
     if len(wavs) == 0:
       raise _lib.WgError("mel_spectrogram_ragged: empty batch")
     lens = []
@@ -208,7 +215,7 @@ class TacotronSTFT(torch.nn.Module):
     _lib.check(self.lib.wg_stft_mel_ragged(self._h, self.mel_basis.data_ptr(), self.n_mel_channels, y.data_ptr(),
                                            lens_dev.data_ptr(), out.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
                                            C.c_void_p(stream)))
-    return out, [n // 256 + 1 for n in lens]
+    return out, [n // 256 + 1 for n in lens], y.view(torch.float32).view(B, N), lens_dev.view(torch.int32)
 
   def mel_spectrogram_ragged_device(self, audio: torch.Tensor, lens):
     """``mel_spectrogram_ragged`` of audio that is on the device already (synthesised audio on its way to the metrics).
@@ -281,6 +288,10 @@ class TacotronSTFT(torch.nn.Module):
   def get_mel_tensors_from_files(self, wav_paths):
     """``mel_spectrogram_ragged`` of wav files (each checked like ``get_wav_tensor_from_file``): ``(mel, frames)``."""
     return self.mel_spectrogram_ragged([self.get_wav_tensor_from_file(p) for p in wav_paths])
+
+  def get_mel_and_wav_tensors_from_files(self, wav_paths):
+    """``mel_spectrogram_ragged_keep`` of wav files, each read once: ``(mel, frames, audio, lens)``."""
+    return self.mel_spectrogram_ragged_keep([self.get_wav_tensor_from_file(p) for p in wav_paths])
 
   def get_mel_tensor(self, wav_tensor: torch.Tensor) -> torch.Tensor:
     return self.mel_spectrogram(wav_tensor.unsqueeze(0)).squeeze(0)

@@ -4,8 +4,9 @@ alignment penalties and the cosine similarity between the original mel and the m
 
 Behind the noise draws a batch of utterances is one launch sequence on the device: the flow and the denoiser
 (``Synthesizer._infer_batch_device``), the int16 finishing (``wg_wav_finish``), the normalisation, the mel of the result
-(``TacotronSTFT.mel_spectrogram_ragged_device``) and the metrics (``wg_metrics_mel``).  Not built: the PNG plots and the
-structural similarity computed from them (``structural_similarity`` stays None).
+(``TacotronSTFT.mel_spectrogram_ragged_device``), the metrics (``wg_metrics_mel``) and, with ``pitch_metrics``, the F0 and
+voicing errors between the original wavs, kept on the device, and that audio (``wg_pitch_metrics``).  Not built: the PNG
+plots and the structural similarity computed from them (``structural_similarity`` stays None).
 """
 from __future__ import annotations
 
@@ -49,6 +50,14 @@ class ValidationEntry:
   cosine_similarity: float = None
   denoiser_strength: float = None
   sigma: float = None
+  # validate(pitch_metrics=True) only (waveglow_amd/metrics.py: PitchMetrics); None otherwise
+  f0_rmse_cents: float = None
+  f0_rmse_hz: float = None
+  gross_pitch_error: float = None
+  vuv_error: float = None
+  pitch_frames: int = None
+  voiced_frames_orig: int = None
+  voiced_frames_inferred: int = None
 
 
 class ValidationEntries(List[ValidationEntry]):
@@ -67,10 +76,12 @@ class ValidationEntryOutput:
 
 
 def get_df(entries: ValidationEntries):
-  """The reference's table (validation.py:52-108) without the "Structual Similarity (Padded)" column."""
+  """The reference's table (validation.py:52-108) without the "Structual Similarity (Padded)" column.  Entries validated
+  with the pitch metrics get seven more columns behind "Cosine Similarity (Padded)"."""
   from pandas import DataFrame
   if len(entries) == 0:
     return DataFrame()
+  with_pitch = any(e.pitch_frames is not None for e in entries)
   data = [{
     "Name": e.entry.basename,
     "Subpath": e.entry.stem,
@@ -93,6 +104,15 @@ def get_df(entries: ValidationEntries):
     "PEN": e.mcd_penalty,
     "# Frames": e.mcd_frames,
     "Cosine Similarity (Padded)": e.cosine_similarity,
+    **({
+      "F0 RMSE (cents)": e.f0_rmse_cents,
+      "F0 RMSE (Hz)": e.f0_rmse_hz,
+      "Gross pitch error": e.gross_pitch_error,
+      "V/UV error": e.vuv_error,
+      "# Pitch frames": e.pitch_frames,
+      "# Voiced frames original": e.voiced_frames_orig,
+      "# Voiced frames inferred": e.voiced_frames_inferred,
+    } if with_pitch else {}),
     "Wav path": str(e.entry.wav_absolute_path),
   } for e in entries]
   return DataFrame(data=[list(x.values()) for x in data], columns=list(data[0].keys()))
@@ -114,12 +134,16 @@ def select_entries(data: List[Entry], entry_names: Set[str], full_run: bool, see
 
 
 def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], sigma, denoiser_strength, seed, iteration,
-                    save_callback, out: ValidationEntries) -> None:
+                    save_callback, out: ValidationEntries, pitch_metrics: bool = False) -> None:
   logger = getLogger(__name__)
   dev = synth.device
   timepoint = datetime.datetime.now()
   B = len(chunk)
-  mel_orig, frames = taco.get_mel_tensors_from_files([e.wav_absolute_path for e in chunk])
+  if pitch_metrics:                                                       # the wavs stay on the device: read once
+    mel_orig, frames, wav_orig_dev, n_orig_dev = taco.get_mel_and_wav_tensors_from_files(
+      [e.wav_absolute_path for e in chunk])
+  else:
+    mel_orig, frames = taco.get_mel_tensors_from_files([e.wav_absolute_path for e in chunk])
   if max(frames) + 1 > metrics.MAX_FRAMES:
     raise _lib.WgError(f"validate: an utterance of {max(frames)} frames is too long for the metrics "
                        f"(at most {metrics.MAX_FRAMES - 1})")
@@ -137,7 +161,14 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
   rows = metrics.mel_metrics_enqueue(mel_orig, frames_dev, mel_inf, frames_inf_dev, MCD_NO_OF_COEFFS_PER_FRAME)
   # one copy for the rows, with the peak of the normalised audio beside them (what normalize_wav asserts of its result)
   inside = torch.arange(N, device=dev)[None, :] < samples_dev[:, None]
-  rows = torch.cat([rows, torch.where(inside, normed.abs(), 0.0).amax(dim=1, keepdim=True).double()], dim=1).cpu()
+  parts = [rows, torch.where(inside, normed.abs(), 0.0).amax(dim=1, keepdim=True).double()]
+  if pitch_metrics:
+    # d' is a ratio: the tracks do not depend on the level of either side (bit for bit under a power of two, to rounding
+    # otherwise), so the original as loaded is compared with the peak-normalised synthesis
+    parts.append(metrics.pitch_metrics_enqueue(wav_orig_dev, n_orig_dev, normed, samples_dev,
+                                               sampling_rate=synth.hparams.sampling_rate))
+  rows = torch.cat(parts, dim=1).cpu()
+  pitch = metrics.rows_to_pitch_metrics(rows[:, metrics.N_ROW + 1:]) if pitch_metrics else None
   fin_h = fin.cpu()
   fin_raw_h = fin_raw.cpu() if fin_raw is not fin else fin_h
   mel_orig_h, mel_inf_h = mel_orig.cpu().numpy(), mel_inf.cpu().numpy()
@@ -159,6 +190,11 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
                           mfcc_no_coeffs=MCD_NO_OF_COEFFS_PER_FRAME, diff_frames=frames_inf[b] - frames[b],
                           mfcc_dtw_mcd=m.mcd_dtw, mfcc_dtw_penalty=m.penalty_dtw, mfcc_dtw_frames=m.frames_dtw, mcd=m.mcd,
                           mcd_penalty=m.penalty, mcd_frames=m.frames, cosine_similarity=m.cosine)
+    if pitch:
+      pm = pitch[b]
+      val.f0_rmse_cents, val.f0_rmse_hz, val.gross_pitch_error, val.vuv_error = \
+          pm.f0_rmse_cents, pm.f0_rmse_hz, pm.gross_pitch_error, pm.vuv_error
+      val.pitch_frames, val.voiced_frames_orig, val.voiced_frames_inferred = pm.frames, pm.voiced_a, pm.voiced_b
     wav_orig, orig_sr = wav_to_float32(entry.wav_absolute_path)
     output = ValidationEntryOutput(mel_orig=mel_orig_h[b, :, :frames[b]].copy(), orig_sr=orig_sr, wav_orig=wav_orig,
                                    inferred_sr=sr, mel_inferred_denoised=mel_inf_h[b, :, :frames_inf[b]].copy(),
@@ -171,6 +207,13 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
     logger.info(f"MCD penalty: {val.mcd_penalty}")
     logger.info(f"MCD frames: {val.mcd_frames}")
     logger.info(f"Cosine Similarity: {val.cosine_similarity}")
+    if pitch:
+      logger.info(f"F0 RMSE (cents): {val.f0_rmse_cents}")
+      logger.info(f"F0 RMSE (Hz): {val.f0_rmse_hz}")
+      logger.info(f"Gross pitch error: {val.gross_pitch_error}")
+      logger.info(f"V/UV error: {val.vuv_error}")
+      logger.info(f"Pitch frames: {val.pitch_frames} (voiced: original {val.voiced_frames_orig}, "
+                  f"inferred {val.voiced_frames_inferred})")
     save_callback(entry, output)
     out.append(val)
 
@@ -178,10 +221,12 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
 def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: Optional[Dict[str, str]],
              denoiser_strength: float, sigma: float, entry_names: Set[str], full_run: bool,
              save_callback: Callable[[Entry, ValidationEntryOutput], None], seed: Optional[int], device: torch.device, *,
-             batch_size: int = 1) -> ValidationEntries:
+             batch_size: int = 1, pitch_metrics: bool = False) -> ValidationEntries:
   """validation.py:125-287.  ``batch_size`` utterances share one launch sequence; every utterance gets the audio, the
   mels and the metrics it gets alone (its noise is drawn as ``Synthesizer.infer`` draws it, and every kernel of the
-  sequence treats the padding behind an utterance as the end of the sequence)."""
+  sequence treats the padding behind an utterance as the end of the sequence).  ``pitch_metrics`` adds the F0 and
+  voicing errors between the original wav and the synthesis (``metrics.pitch_metrics_enqueue`` with its defaults at the
+  model's sampling rate); without it nothing of them is launched and their fields stay None."""
   logger = getLogger(__name__)
   result = ValidationEntries()
   if seed is None:
@@ -196,5 +241,5 @@ def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: 
   bs = max(1, int(batch_size))
   for i in range(0, len(entries), bs):
     _validate_batch(synth, taco, entries[i:i + bs], sigma, denoiser_strength, seed, checkpoint.iteration, save_callback,
-                    result)
+                    result, pitch_metrics)
   return result
