@@ -319,6 +319,38 @@ int wg_pitch_metrics(const float* audio_a, const int32_t* lens_a, int32_t n_a, c
                      int32_t n_b, const wg_pitch_params* params, double* rows_out, int32_t B, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- Resampling by a rational ratio: wav data of any sampling rate in, any rate out, no handle ------------------------
+ * The reference has no counterpart.  The definition is scipy.signal.resample_poly(x, up, down) with its defaults
+ * (window ('kaiser', 5.0), padtype 'constant') in closed form.  With up / down reduced, M = max(up, down), half = 10 M and
+ * h = up * firwin(2 half + 1, 1 / M, window=('kaiser', 5.0)) in fp64:
+ *   out_len(len) = ceil(len up / down)
+ *   y[n] = sum over m ascending, 0 <= m < len with 0 <= half + n down - m up <= 2 half, of x[m] h[half + n down - m up].
+ * Limits: 1 <= up, down <= 1024, gcd(up, down) = 1, 0 <= half <= 10240, B >= 1, 1 <= n_in <= 2^26, out_len(n_in) < 2^31;
+ * anything else is WG_ERR_INVALID before any launch.  All index arithmetic (n down, m up) is 64-bit.
+ * in: [B][n_in] device, fp32 (WG_PCM_F32) or int16 (WG_PCM_I16; converted as (float)x * (1.0f / 32768.0f), as in
+ *   wg_data_gather).  lens: int32 device [B], read by the kernel only; a length outside [0, n_in] counts as 0.  Nothing at
+ *   or behind in[b][lens[b]] is read (it may hold NaN).
+ * taps: the caller's h as a polyphase table on the device, fp64 [up][K] with K = ceil((2 half + 1) / up) and every row
+ *   reversed: taps[p][j] = h[p + (K - 1 - j) up], 0 where that index exceeds 2 half.  One output's taps are one row, read
+ *   in ascending j, which is ascending m.  The library does not compute h: a caller with another filter passes its own.
+ * out: [B][n_out] fp32, out_len(n_in) <= n_out <= 2^31 - 1 - 1024; row b holds out_len(lens[b]) samples and zeros behind them up to n_out.
+ * Arithmetic: each product is an fp32 sample widened to fp64 times an fp64 tap, the sum is fp64 in ascending m over the
+ *   terms of the definition only and is rounded to fp32 once; no contraction, no atomics.  A call gives the same bits
+ *   every time, and every row of a batch the bits of its own call with B = 1 and n_in = lens[b]; the tile
+ *   (wg_resample_plan) and the kernel variant do not enter the arithmetic.
+ * flags: WG_RESAMPLE_CLIP clamps the fp32 result to [-1, 1] as y < -1 ? -1 : (y > 1 ? 1 : y) (a NaN stays a NaN): a
+ *   band-limited copy of full-scale audio overshoots 1.
+ * up == down == 1 copies (or converts int16) and zero-fills behind the length: the bits of the input.
+ * wg_resample_plan: the argument checks of wg_resample alone, and (each pointer may be null) out_len(n_in), K, the number
+ *   of consecutive outputs one workgroup computes and whether the workgroups of this ratio stage their samples in LDS (1)
+ *   or read them through the cache (0: down / up above about 7, and the copy).  No workspace is needed.  One launch.
+ *   Enqueue-only. */
+#define WG_RESAMPLE_CLIP 1
+int wg_resample_plan(int32_t up, int32_t down, int32_t half, int32_t n_in, int32_t* out_len, int32_t* taps_per_phase,
+                     int32_t* tile, int32_t* staged);
+int wg_resample(const void* in, int32_t in_dtype, const int32_t* lens, float* out, const double* taps, int32_t up,
+                int32_t down, int32_t half, int32_t flags, int32_t B, int32_t n_in, int32_t n_out, void* stream);
+
 /* ---- Multi-resolution STFT loss (spectral convergence + log-magnitude L1), fp32, with its backward ------------------
  * For resolution r = (n_fft, hop, win): X = STFT(x) with reflect padding by n_fft/2 and the window of `win` samples
  * centred in n_fft, M = sqrt(max(re^2 + im^2, eps)); sc_r = |M(y) - M(x)|_F / |M(y)|_F over the whole batch,

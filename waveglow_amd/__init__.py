@@ -24,6 +24,10 @@ def __getattr__(name):
   if name in ("mel_metrics", "MelMetrics", "pitch_metrics", "PitchMetrics", "yin_f0"):
     from . import metrics
     return getattr(metrics, name)
+  if name in ("resample_enqueue", "resample_plan", "out_len"):
+    # `waveglow_amd.resample` is the submodule (as `waveglow_amd.metrics` is); its function is `resample.resample`
+    from . import resample
+    return getattr(resample, name)
   if name in ("validate", "ValidationEntry", "ValidationEntries"):
     from . import validation
     return getattr(validation, name)

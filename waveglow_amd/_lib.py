@@ -14,7 +14,8 @@ LIB_PATH = os.environ.get("WAVEGLOW_AMD_LIB", os.path.join(_HERE, "csrc", "libwa
 
 WG_F32, WG_F16 = 0, 1
 WG_PCM_I16, WG_PCM_F32 = 0, 1   # pool_dtype of wg_data_gather
-WG_TRAIN_RECOMPUTE = 1         # flag of the wg_train_*_flags entry points (include/waveglow_amd.h)
+WG_RESAMPLE_CLIP = 1           # flag of wg_resample
+WG_TRAIN_RECOMPUTE = 1        # flag of the wg_train_*_flags entry points (include/waveglow_amd.h)
 
 
 class WgConfig(C.Structure):
@@ -169,6 +170,10 @@ SIGNATURES = {
                                  C.c_int32, C.c_void_p]),
   "wg_pitch_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                  C.POINTER(WgPitchParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_resample_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+  "wg_resample": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
   "wg_stftloss_create": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_void_p), C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stftloss_destroy": (C.c_int, [C.c_void_p]),

@@ -3,9 +3,11 @@
 commented-out ``--batch-size``, inference_v2.py:64) and per-rank sharding of the file list under torch.distributed.run.
 
   python -m waveglow_amd.cli synthesize CHECKPOINT FOLDER [--sigma S] [--denoiser-strength D] [--device cuda:0]
-         [--custom-hparams a=1,b=2] [--custom-seed N] [-out DIR] [-o]
+         [--custom-hparams a=1,b=2] [--custom-seed N] [-out DIR] [-o] [--batch-size B] [--output-sampling-rate R]
+         --output-sampling-rate: the synthesis is resampled to R Hz on the device (waveglow_amd/resample.py)
   python -m waveglow_amd.cli synthesize-wav CHECKPOINT FOLDER [same flags]   wav -> mel (HIP front-end) -> wav
-         (src/waveglow_cli/inference_wav.py:74-130; copy synthesis)
+         (src/waveglow_cli/inference_wav.py:74-130; copy synthesis)  [--resample-inputs]: wavs of any sampling rate
+         (also on validate, train and continue-train): resampled to the model's rate on the device
   python -m waveglow_amd.cli train TRAIN-FOLDER VAL-FOLDER CHECKPOINTS-FOLDER [--device cuda:0] [--custom-hparams ...]
          [--pre-trained-model CKPT --warm-start] [--device-dataset]  (src/waveglow_cli/training.py:24-79)
   python -m waveglow_amd.cli continue-train TRAIN-FOLDER VAL-FOLDER CHECKPOINTS-FOLDER [...]   (training.py:82-124)
@@ -63,6 +65,11 @@ def build_parser() -> argparse.ArgumentParser:
     s.add_argument("-o", "--overwrite", action="store_true")
     s.add_argument("--batch-size", type=int, default=1,
                    help="utterances per launch sequence (ragged batch; results equal one-by-one synthesis)")
+    s.add_argument("--output-sampling-rate", type=int, default=None, metavar="R",
+                   help="resample the synthesis to R Hz on the device before it is normalised and written")
+    if name == "synthesize-wav":
+      s.add_argument("--resample-inputs", action="store_true",
+                     help="resample wav files at other sampling rates to the model's on the device instead of refusing them")
   for name, desc in (("train", "Start training of a new model."), ("continue-train", "Continue training from the last checkpoint.")):
     t = sub.add_parser(name, description=desc)
     t.add_argument("train_folder", type=Path, metavar="TRAIN-FOLDER")
@@ -72,6 +79,8 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--custom-hparams", type=str, default=None)
     t.add_argument("--device-dataset", action="store_true",
                    help="keep all wavs on the device and build every batch there (same batches; cache_wavs is ignored)")
+    t.add_argument("--resample-inputs", action="store_true",
+                   help="resample wav files at other sampling rates to the model's on the device instead of refusing them")
     if name == "train":
       t.add_argument("--pre-trained-model", type=Path, default=None)
       t.add_argument("--warm-start", action="store_true")
@@ -94,6 +103,9 @@ def build_parser() -> argparse.ArgumentParser:
   v.add_argument("--pitch-metrics", action="store_true",
                  help="also track F0 of the original and the synthesis (YIN) and report F0 RMSE, gross pitch error and "
                       "voicing decision error in seven more columns")
+  v.add_argument("--resample-inputs", action="store_true",
+                 help="resample wav files at other sampling rates to the model's on the device instead of refusing them; "
+                      "original.wav is still written as loaded")
   return p
 
 
@@ -115,7 +127,7 @@ def train_cmd(ns, resume: bool) -> bool:
     warm = CheckpointWaveglow.load(ns.pre_trained_model, device)
   train(custom_hparams=split_hparams_string(ns.custom_hparams), logdir=None, trainset=load_dataset(ns.train_folder),
         valset=load_dataset(ns.val_folder), save_checkpoint_dir=ns.checkpoints_dir, checkpoint=checkpoint,
-        warm_model=warm, device=device, device_dataset=ns.device_dataset)
+        warm_model=warm, device=device, device_dataset=ns.device_dataset, resample_inputs=ns.resample_inputs)
   if world > 1:
     torch.distributed.destroy_process_group()
   return True
@@ -142,7 +154,7 @@ def synthesize(ns, from_wav: bool = False) -> bool:
   taco_stft = None
   if from_wav:
     from .taco_stft import TacotronSTFT
-    taco_stft = TacotronSTFT(synth.hparams, device)                   # inference_wav.py:110
+    taco_stft = TacotronSTFT(synth.hparams, device, resample_inputs=ns.resample_inputs)   # inference_wav.py:110
   todo = []
   for mel_path in mel_files:
     wav_path = out_dir / mel_path.relative_to(ns.folder).parent / f"{mel_path.stem}.wav"
@@ -152,7 +164,7 @@ def synthesize(ns, from_wav: bool = False) -> bool:
   bs = max(1, ns.batch_size)
   for i in range(0, len(todo), bs):
     chunk = todo[i:i + bs]
-    if len(chunk) == 1:                                               # the reference-shaped path, one utterance
+    if len(chunk) == 1 and ns.output_sampling_rate is None:           # the reference-shaped path, one utterance
       mel_path, wav_path = chunk[0]
       if from_wav:
         mel = taco_stft.get_mel_tensor_from_file(mel_path).unsqueeze(0)
@@ -168,7 +180,9 @@ def synthesize(ns, from_wav: bool = False) -> bool:
       mels = [mel[b, :, :frames[b]] for b in range(len(chunk))]
     else:
       mels = [torch.FloatTensor(np.load(p)) for p, _ in chunk]
-    results = synth.infer_batch_pcm(mels, sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=seed)
+    results = synth.infer_batch_pcm(mels, sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=seed,
+                                    **({} if ns.output_sampling_rate is None else
+                                       {"output_sampling_rate": ns.output_sampling_rate}))
     for (_, wav_path), res in zip(chunk, results):
       wav_path.parent.mkdir(parents=True, exist_ok=True)
       write_wav(filename=wav_path, rate=res.sampling_rate, data=res.pcm)
@@ -230,7 +244,7 @@ def validate_cmd(ns) -> bool:
                                save_callback=partial(_save_validation, val_dir=ns.output_dir, iteration=iteration),
                                sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=ns.custom_seed,
                                device=torch.device(ns.device), batch_size=ns.batch_size,
-                               pitch_metrics=ns.pitch_metrics))
+                               pitch_metrics=ns.pitch_metrics, resample_inputs=ns.resample_inputs))
       except AssertionError as e:
         logger.error(str(e) or "validation failed an assertion")
         return False

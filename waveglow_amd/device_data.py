@@ -70,17 +70,24 @@ class DeviceWavPool:
   ``TacotronSTFT.get_wav_tensor_from_file`` checks it.  If every file is int16 the pool keeps the raw int16 samples
   (``wg_data_gather`` scales them by 1 / 32768, which is what ``convert_wav`` gives); otherwise it keeps fp32 after
   ``convert_wav``, and the reference's [-1, 1] assert (taco_stft.py:95-97) is applied here, once, on the host.  A file
-  without samples is allowed: its rows come out as zeros."""
+  without samples is allowed: its rows come out as zeros.
 
-  def __init__(self, entries: Sequence, hparams, device):
+  ``resample_inputs`` (not in the reference): files at other rates are resampled to ``hparams.sampling_rate`` on the device
+  while the pool is built (waveglow_amd/resample.py, clipped to [-1, 1]), ``RESAMPLE_FILES`` files of one rate per launch.
+  Such a pool is fp32, and ``lengths`` are the resampled lengths."""
+
+  RESAMPLE_FILES = 64      # files per upload and wg_resample launch while a resampled pool is built
+
+  def __init__(self, entries: Sequence, hparams, device, resample_inputs: bool = False):
     from scipy.io.wavfile import read
     self.device = torch.device(device)
     if self.device.type != "cuda":
       raise _lib.WgError("the device wav pool lives on the GPU only")
-    wavs = []
+    wavs, rates = [], []
     for e in entries:
       sampling_rate, wav = read(e.wav_absolute_path)
-      if sampling_rate != hparams.sampling_rate:
+      rates.append(int(sampling_rate))
+      if sampling_rate != hparams.sampling_rate and not resample_inputs:
         raise ValueError(f"{e.wav_absolute_path}: The sampling rate of the file ({sampling_rate}Hz) doesn't match the "
                          f"target sampling rate ({hparams.sampling_rate}Hz)!")
       if wav.ndim != 1:
@@ -88,6 +95,9 @@ class DeviceWavPool:
       wavs.append(wav)
     if len(wavs) == 0:
       raise _lib.WgError("the device wav pool needs at least one file")
+    if any(r != hparams.sampling_rate for r in rates):
+      self._build_resampled(entries, wavs, rates, int(hparams.sampling_rate))
+      return
     self.is_int16 = all(w.dtype == np.int16 for w in wavs)
     if not self.is_int16:
       wavs = [np.ascontiguousarray(convert_wav(w, np.float32), dtype=np.float32) for w in wavs]
@@ -104,10 +114,56 @@ class DeviceWavPool:
       host = np.zeros(1, dtype=host.dtype)        # a pointer to hand over; pool_elems stays 0 and nothing is read
     self.pool = torch.from_numpy(host).to(self.device)
     self.offsets = torch.from_numpy(offsets).to(self.device)
+    self._log()
+
+  def _log(self) -> None:
     self.dtype_code = _lib.WG_PCM_I16 if self.is_int16 else _lib.WG_PCM_F32
     getLogger(__name__).info(f"Device wav pool: {self.n_utt} files, {self.elems} samples, "
                              f"{self.pool.numel() * self.pool.element_size()} bytes "
                              f"({'int16' if self.is_int16 else 'float32'}) on {self.device}")
+
+  def _build_resampled(self, entries, wavs, rates, target: int) -> None:
+    """The pool of files of which at least one is not at ``target`` Hz: fp32.  Files at ``target`` are converted and
+    range-checked on the host as above and uploaded; the others go up as read (int16 stays int16) in batches of at most
+    ``RESAMPLE_FILES`` files of one rate, padded to the longest of the batch, and each batch is one ``wg_resample`` launch
+    whose rows are then copied to their places in the pool.  The lengths follow from the file lengths on the host."""
+    from .resample import out_len, resample, resample_plan
+    self.is_int16 = False
+    lens = []
+    for w, r in zip(wavs, rates):
+      up, down, _, _ = resample_plan(r, target)
+      lens.append(out_len(int(w.shape[0]), up, down))
+    self.lengths = lens
+    offsets = np.zeros(len(wavs) + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    self.n_utt = len(wavs)
+    self.elems = int(offsets[-1])
+    self.pool = torch.zeros(max(self.elems, 1), dtype=torch.float32, device=self.device)
+    self.offsets = torch.from_numpy(offsets).to(self.device)
+    by_rate = {}
+    for i, r in enumerate(rates):
+      by_rate.setdefault(r, []).append(i)
+    for r, idx in by_rate.items():
+      for lo in range(0, len(idx), self.RESAMPLE_FILES):
+        chunk = [i for i in idx[lo:lo + self.RESAMPLE_FILES] if wavs[i].shape[0] > 0]
+        if not chunk:
+          continue
+        part = [wavs[i] for i in chunk]
+        if r == target or not all(w.dtype == np.int16 for w in part):
+          part = [np.ascontiguousarray(convert_wav(w, np.float32), dtype=np.float32) for w in part]
+          for i, w in zip(chunk, part):
+            assert float(w.min()) >= FLOAT32_64_MIN_WAV and float(w.max()) <= FLOAT32_64_MAX_WAV, \
+                entries[i].wav_absolute_path
+        n = [int(w.shape[0]) for w in part]
+        host = np.zeros((len(part), max(n)), dtype=part[0].dtype)
+        for k, w in enumerate(part):
+          host[k, :n[k]] = w
+        dev = torch.from_numpy(host).to(self.device)
+        if r != target:
+          dev, _ = resample(dev, n, r, target, clip=True)
+        for k, i in enumerate(chunk):
+          self.pool[int(offsets[i]):int(offsets[i + 1])].copy_(dev[k, :lens[i]])
+    self._log()
 
   def gather(self, picks_dev: torch.Tensor, segment_length: int, status: torch.Tensor = None) -> torch.Tensor:
     """Enqueue ``wg_data_gather`` on the current stream: ``picks_dev`` int32 [B, 2] on the pool's device ->
@@ -138,15 +194,15 @@ class DeviceBatchLoader:
   with the device: ``post_status()`` enqueues the copy of the bad-pick flag behind the work queued so far and
   ``check_status()`` reads it once the caller has synchronised (``train()`` does both around its ``loss.item()``)."""
 
-  def __init__(self, entries: Sequence, hparams, device, drop_last: bool):
+  def __init__(self, entries: Sequence, hparams, device, drop_last: bool, resample_inputs: bool = False):
     self.device = torch.device(device)
     self.hparams = hparams
     self.drop_last = bool(drop_last)
     self.batch_size = int(hparams.batch_size)
     self.segment_length = int(hparams.segment_length)
     data = shuffled(entries, hparams.seed)
-    self.taco_stft = TacotronSTFT(hparams, self.device)
-    self.pool = DeviceWavPool(data, hparams, self.device) if data else None
+    self.taco_stft = TacotronSTFT(hparams, self.device, resample_inputs=resample_inputs)
+    self.pool = DeviceWavPool(data, hparams, self.device, resample_inputs=resample_inputs) if data else None
     self.lengths = self.pool.lengths if self.pool is not None else []
     self._n = batch_count(len(self.lengths), self.batch_size, self.drop_last)
     self.status = torch.zeros(1, dtype=torch.int32, device=self.device)

@@ -170,12 +170,22 @@ class Synthesizer:
                                  was_overamplified=bool(is_overamp(a_np)), timepoint=timepoint))
     return res
 
-  def infer_batch_pcm(self, mels, *, sigma: float = 1.0, denoiser_strength: float = 0.0005, seed: int = 0):
+  def infer_batch_pcm(self, mels, *, sigma: float = 1.0, denoiser_strength: float = 0.0005, seed: int = 0,
+                      output_sampling_rate: Optional[int] = None):
     """``infer_batch`` finished to int16 on the device (``wg_wav_finish``): behind the noise draws the batch is one
     launch sequence, and ONE copy (the int16 samples and the statistics, through a pinned buffer) and one synchronise
     bring it to the host.  Returns one PcmResult per utterance; ``pcm`` equals
     ``convert_wav(normalize_wav(r.wav_denoised), np.int16)`` of the corresponding ``infer_batch`` result bit for bit.
-    An utterance with NaN or infinite samples raises WgError."""
+    An utterance with NaN or infinite samples raises WgError.
+
+    ``output_sampling_rate`` (not in the reference): the denoised audio is resampled to that rate on the device
+    (waveglow_amd/resample.py, not clipped) between the denoiser and ``wg_wav_finish``, so the peak normalisation and the
+    int16 conversion run on the resampled signal: ``pcm`` has ``out_len(256 T)`` samples and equals
+    ``convert_wav(normalize_wav(x), np.int16)`` of ``x = resample(wav_denoised)``, ``sampling_rate`` is the output rate and
+    ``peak`` the resampled signal's; ``was_overamplified`` stays the statement about the raw audio at the model's rate.
+    Still one host copy and one synchronise.  Without it nothing changes and nothing more is launched."""
+    if output_sampling_rate is not None:
+      return self._infer_batch_pcm_resampled(mels, sigma, denoiser_strength, seed, output_sampling_rate)
     timepoint = datetime.datetime.now()
     audio, den, lens, samples_dev, ev = self._infer_batch_device(mels, sigma, denoiser_strength, seed)
     B, N = audio.shape
@@ -190,5 +200,42 @@ class Synthesizer:
     den_s = ev[1].elapsed_time(ev[2]) / 1e3 if denoiser_strength > 0 else 0
     return [PcmResult(pcm=samples[b, :256 * lens[b]].copy(), sampling_rate=self.hparams.sampling_rate,
                       was_overamplified=bool(stats[b, pcm.RAW_MIN] < -1.0 or stats[b, pcm.RAW_MAX] > 1.0),
+                      peak=float(stats[b, pcm.DEN_PEAK]), inference_duration_s=inf_s / B,
+                      denoising_duration_s=den_s / B, timepoint=timepoint) for b in range(B)]
+
+  def _infer_batch_pcm_resampled(self, mels, sigma, denoiser_strength, seed, rate):
+    """``infer_batch_pcm`` with an output rate.  ``wg_wav_finish`` runs on the resampled denoised audio (samples, peak);
+    the raw audio at the model's rate only gives its extrema under the length mask, for ``was_overamplified``, and they
+    ride behind the finished buffer in the one copy: [int16 samples | statistics of the resampled | raw min, max, flag]."""
+    from . import _lib
+    from .resample import out_len, resample_enqueue, resample_plan
+    timepoint = datetime.datetime.now()
+    up, down, _, _ = resample_plan(self.hparams.sampling_rate, rate)        # refuses the rate before any device work
+    audio, den, lens, samples_dev, ev = self._infer_batch_device(mels, sigma, denoiser_strength, seed)
+    B, N = audio.shape
+    lens_r = [out_len(256 * t, up, down) for t in lens]
+    Nr = (out_len(N, up, down) + 7) // 8 * 8                                 # wg_wav_finish: rows of a multiple of 8
+    res = resample_enqueue(den, samples_dev, self.hparams.sampling_rate, rate, pitch=Nr)
+    lens_r_dev = torch.tensor(lens_r, dtype=torch.int32).to(self.device)
+    fin = pcm.finish_enqueue(res, res, lens_r_dev)
+    inside = torch.arange(N, device=self.device)[None, :] < samples_dev[:, None]
+    raw = torch.stack([torch.where(inside, audio, float("inf")).amin(dim=1),
+                       torch.where(inside, audio, float("-inf")).amax(dim=1),
+                       (inside & ~torch.isfinite(audio)).any(dim=1).float()], dim=1)        # fp32 [B, 3]
+    out = torch.cat([fin, raw.contiguous().view(torch.uint8).view(-1)])
+    if self._pinned is None or self._pinned.numel() < out.numel():
+      self._pinned = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
+    host = self._pinned[:out.numel()]
+    host.copy_(out, non_blocking=True)
+    torch.cuda.current_stream(self.device).synchronize()
+    samples, stats = pcm.finish_read(host[:fin.numel()], B, Nr)
+    raw = host[fin.numel():].numpy().view(np.float32).reshape(B, 3)
+    bad = np.nonzero(raw[:, 2])[0]
+    if bad.size:
+      raise _lib.WgError(f"utterance {int(bad[0])} of the batch has NaN or infinite samples: it cannot be written as PCM")
+    inf_s = ev[0].elapsed_time(ev[1]) / 1e3
+    den_s = ev[1].elapsed_time(ev[2]) / 1e3 if denoiser_strength > 0 else 0
+    return [PcmResult(pcm=samples[b, :lens_r[b]].copy(), sampling_rate=int(rate),
+                      was_overamplified=bool(raw[b, 0] < -1.0 or raw[b, 1] > 1.0),
                       peak=float(stats[b, pcm.DEN_PEAK]), inference_duration_s=inf_s / B,
                       denoising_duration_s=den_s / B, timepoint=timepoint) for b in range(B)]

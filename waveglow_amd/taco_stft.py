@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .audio import wav_to_float32
+from .audio import convert_wav, wav_to_float32
 from .denoiser import stft_bases
 from .stft_loss import check_lengths
 
@@ -41,6 +41,18 @@ class TSTFTHParams(STFTHParams):
   sampling_rate: int = 22050
   mel_fmin: float = 0.0
   mel_fmax: float = 8000.0
+
+
+def read_wav_raw(path):
+  """(samples as stored -- int16 stays int16 --, sampling rate) of a PCM wav file."""
+  from scipy.io.wavfile import read
+  sampling_rate, wav = read(path)
+  return wav, sampling_rate
+
+
+def _float32_tensor(wav: np.ndarray) -> torch.Tensor:
+  """what ``get_wav_tensor_from_file`` hands out for samples as stored: ``convert_wav`` to float32, on the host"""
+  return torch.from_numpy(np.ascontiguousarray(convert_wav(wav, np.float32), dtype=np.float32))
 
 
 def _hz_to_mel(f):
@@ -127,11 +139,14 @@ class _MelFn(torch.autograd.Function):
 
 
 class TacotronSTFT(torch.nn.Module):
-  def __init__(self, hparams, device):
+  def __init__(self, hparams, device, resample_inputs: bool = False):
+    """``resample_inputs`` (not in the reference): a wav file whose rate differs from ``hparams.sampling_rate`` is
+    resampled to it on the device (waveglow_amd/resample.py, clipped to [-1, 1]) instead of being refused."""
     super().__init__()
     device = torch.device(device)
     if device.type != "cuda":
       raise _lib.WgError("the mel front-end runs on the GPU library only")
+    self.resample_inputs = bool(resample_inputs)
     self.n_mel_channels = hparams.n_mel_channels
     self.sampling_rate = hparams.sampling_rate
     self.device = device
@@ -276,22 +291,87 @@ class TacotronSTFT(torch.nn.Module):
     return self._mel(y.detach().contiguous())
 
   def get_wav_tensor_from_file(self, wav_path) -> torch.Tensor:
-    wav, sampling_rate = wav_to_float32(wav_path)
+    wav, sampling_rate = wav_to_float32(wav_path) if not self.resample_inputs else read_wav_raw(wav_path)
     if sampling_rate != self.sampling_rate:
-      raise ValueError(f"{wav_path}: The sampling rate of the file ({sampling_rate}Hz) doesn't match the target "
-                       f"sampling rate ({self.sampling_rate}Hz)!")
-    return torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+      if not self.resample_inputs:
+        raise ValueError(f"{wav_path}: The sampling rate of the file ({sampling_rate}Hz) doesn't match the target "
+                         f"sampling rate ({self.sampling_rate}Hz)!")
+      # one upload (int16 stays int16), one launch, one copy back: this path hands out a CPU tensor, as the reference's
+      from .resample import resample
+      if wav.ndim != 1:
+        raise ValueError(f"{wav_path}: only mono files can be resampled")
+      if wav.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.float32)
+      if wav.dtype != np.int16:
+        wav = np.ascontiguousarray(convert_wav(wav, np.float32), dtype=np.float32)
+      out, lens = resample(torch.from_numpy(wav[None]).to(self.device), None, sampling_rate, self.sampling_rate, clip=True)
+      return out[0, :lens[0]].cpu()
+    return _float32_tensor(wav)
 
   def get_mel_tensor_from_file(self, wav_path) -> torch.Tensor:
     return self.get_mel_tensor(self.get_wav_tensor_from_file(wav_path))
 
   def get_mel_tensors_from_files(self, wav_paths):
-    """``mel_spectrogram_ragged`` of wav files (each checked like ``get_wav_tensor_from_file``): ``(mel, frames)``."""
-    return self.mel_spectrogram_ragged([self.get_wav_tensor_from_file(p) for p in wav_paths])
+    """``mel_spectrogram_ragged`` of wav files (each checked like ``get_wav_tensor_from_file``): ``(mel, frames)``.  With
+    ``resample_inputs`` files of other rates are resampled on the device first (``_resampled_from_files``)."""
+    mel, frames, _, _ = self.get_mel_and_wav_tensors_from_files(wav_paths)
+    return mel, frames
 
   def get_mel_and_wav_tensors_from_files(self, wav_paths):
-    """``mel_spectrogram_ragged_keep`` of wav files, each read once: ``(mel, frames, audio, lens)``."""
+    """``mel_spectrogram_ragged_keep`` of wav files, each read once: ``(mel, frames, audio, lens)``.  With
+    ``resample_inputs`` and a file of another rate, ``audio`` / ``lens`` are the resampled ones."""
+    if self.resample_inputs:
+      files = [read_wav_raw(p) for p in wav_paths]
+      if all(sr == self.sampling_rate for _, sr in files):                  # today's way, on the arrays just read
+        return self.mel_spectrogram_ragged_keep([_float32_tensor(w) for w, _ in files])
+      for p, (w, sr) in zip(wav_paths, files):
+        if w.ndim != 1:
+          raise ValueError(f"{p}: only mono files can be resampled or batched with resampled ones")
+      audio, lens = self._resampled_from_files(files)
+      mel, frames, _ = self.mel_spectrogram_ragged_device(audio, lens)
+      return mel, frames, audio, torch.tensor(lens, dtype=torch.int32).to(self.device)
     return self.mel_spectrogram_ragged_keep([self.get_wav_tensor_from_file(p) for p in wav_paths])
+
+  def _resampled_from_files(self, files):
+    """``files``: ``(samples, rate)`` of mono files as ``read_wav_raw`` gives them, at least one at a rate other than the model's.
+    Returns ``(audio, lens)``: fp32 [B, N] on the module's device in the order of the files, row b holding ``lens[b]``
+    samples at the model's rate in [-1, 1], and the host list of the lengths (each above 512, WgError otherwise).  The
+    files go up as read, one upload and one ``wg_resample`` call (``clip=True``) per distinct rate; files at the model's
+    rate are converted and range-checked on the host as ``mel_spectrogram_ragged_keep`` does it and only copied.  Nothing
+    comes back to the host and nothing synchronises."""
+    from .resample import resample
+    B = len(files)
+    groups = {}
+    for i, (_, sr) in enumerate(files):
+      groups.setdefault(int(sr), []).append(i)
+    lens, parts = [0] * B, []
+    for sr, idx in groups.items():
+      wavs = [files[i][0] for i in idx]
+      n = [int(w.shape[0]) for w in wavs]
+      if sr == self.sampling_rate or not all(w.dtype == np.int16 for w in wavs):
+        wavs = [np.ascontiguousarray(convert_wav(w, np.float32), dtype=np.float32) for w in wavs]
+        for w in wavs:
+          if w.size:
+            assert float(w.min()) >= FLOAT32_64_MIN_WAV and float(w.max()) <= FLOAT32_64_MAX_WAV   # taco_stft.py:95-97
+      host = np.zeros((len(idx), max(max(n), 1)), dtype=wavs[0].dtype)
+      for k, w in enumerate(wavs):
+        host[k, :n[k]] = w
+      dev = torch.from_numpy(host).to(self.device)
+      if sr != self.sampling_rate:
+        dev, n = resample(dev, n, sr, self.sampling_rate, clip=True)
+      for k, i in enumerate(idx):
+        lens[i] = n[k]
+      parts.append((idx, dev))
+    for n in lens:
+      if n <= 512:
+        raise _lib.WgError(f"mel front-end: audio of {n} samples is too short (reflect padding needs > 512)")
+    if len(parts) == 1:                                    # one rate: the resampled batch is in file order already
+      return parts[0][1][:, :max(lens)].contiguous(), lens
+    audio = torch.zeros((B, max(lens)), dtype=torch.float32, device=self.device)
+    for idx, dev in parts:
+      w = min(dev.shape[1], audio.shape[1])
+      audio[:, :w].index_copy_(0, torch.tensor(idx, dtype=torch.int64).to(self.device), dev[:, :w])
+    return audio, lens
 
   def get_mel_tensor(self, wav_tensor: torch.Tensor) -> torch.Tensor:
     return self.mel_spectrogram(wav_tensor.unsqueeze(0)).squeeze(0)

@@ -135,9 +135,9 @@ def get_last_checkpoint(checkpoint_dir: Path) -> Tuple[Path, int]:
 class MelLoader(Dataset):
   """Random training segment of every wav + its mel spectrogram, both on the device (dataloader.py:16-57)."""
 
-  def __init__(self, entries: List[Entry], hparams: HParams, device: torch.device):
+  def __init__(self, entries: List[Entry], hparams: HParams, device: torch.device, resample_inputs: bool = False):
     self.device = torch.device(device)
-    self.taco_stft = TacotronSTFT(hparams, self.device)
+    self.taco_stft = TacotronSTFT(hparams, self.device, resample_inputs=resample_inputs)
     self.hparams = hparams
     data = list(entries)
     random.seed(hparams.seed)
@@ -162,13 +162,13 @@ def parse_batch(batch):
   return (mel, audio), (mel, audio)
 
 
-def prepare_trainloader(hparams: HParams, trainset: List[Entry], device) -> DataLoader:
-  return DataLoader(MelLoader(trainset, hparams, device), num_workers=0, shuffle=False, sampler=None,
+def prepare_trainloader(hparams: HParams, trainset: List[Entry], device, resample_inputs: bool = False) -> DataLoader:
+  return DataLoader(MelLoader(trainset, hparams, device, resample_inputs), num_workers=0, shuffle=False, sampler=None,
                     batch_size=hparams.batch_size, pin_memory=False, drop_last=True)
 
 
-def prepare_valloader(hparams: HParams, valset: List[Entry], device) -> DataLoader:
-  return DataLoader(MelLoader(valset, hparams, device), num_workers=0, shuffle=False, sampler=None,
+def prepare_valloader(hparams: HParams, valset: List[Entry], device, resample_inputs: bool = False) -> DataLoader:
+  return DataLoader(MelLoader(valset, hparams, device, resample_inputs), num_workers=0, shuffle=False, sampler=None,
                     batch_size=hparams.batch_size, pin_memory=False)
 
 
@@ -208,11 +208,13 @@ def validate_model(model, criterion, val_loader) -> float:
 
 def train(custom_hparams: Optional[Dict[str, str]], logdir: Optional[Path], trainset: List[Entry], valset: List[Entry],
           save_checkpoint_dir: Path, checkpoint: Optional[CheckpointWaveglow], warm_model: Optional[CheckpointWaveglow],
-          device: torch.device, max_iterations: Optional[int] = None, device_dataset: bool = False) -> List[float]:
+          device: torch.device, max_iterations: Optional[int] = None, device_dataset: bool = False,
+          resample_inputs: bool = False) -> List[float]:
   """train.py:93-238.  ``max_iterations`` (not in the reference) stops after that many optimiser steps.
   ``device_dataset`` (not in the reference) keeps the wavs on the device and builds every batch there
   (waveglow_amd/device_data.py): the same batches, so the same training; ``cache_wavs`` is then ignored, as no host copy is
-  kept.  Under ``torch.distributed`` every rank pools its own shard.  Returns the training losses of the executed steps."""
+  kept.  Under ``torch.distributed`` every rank pools its own shard.  ``resample_inputs`` (not in the reference) goes to both
+  loaders: wav files at other rates are resampled to ``hparams.sampling_rate`` on the device instead of being refused.  Returns the training losses of the executed steps."""
   logger = getLogger(__name__)
   complete_start = time.time()
   device = torch.device(device)
@@ -245,11 +247,12 @@ def train(custom_hparams: Optional[Dict[str, str]], logdir: Optional[Path], trai
 
   if device_dataset:
     from .device_data import DeviceBatchLoader
-    train_loader = DeviceBatchLoader(trainset, hparams, device, drop_last=True)     # train first, then validation: each
-    val_loader = DeviceBatchLoader(valset, hparams, device, drop_last=False)        # constructor re-seeds `random`
+    train_loader = DeviceBatchLoader(trainset, hparams, device, drop_last=True, resample_inputs=resample_inputs)    # train first, then validation: each
+    val_loader = DeviceBatchLoader(valset, hparams, device, drop_last=False, resample_inputs=resample_inputs)     # constructor re-seeds `random`
   else:
-    train_loader = prepare_trainloader(hparams, trainset, device)
-    val_loader = prepare_valloader(hparams, valset, device)
+    opt_in = {"resample_inputs": True} if resample_inputs else {}       # off: the calls are the ones they were
+    train_loader = prepare_trainloader(hparams, trainset, device, **opt_in)
+    val_loader = prepare_valloader(hparams, valset, device, **opt_in)
   batch_iterations = len(train_loader)
   if batch_iterations == 0:
     logger.error("Not enough training data.")

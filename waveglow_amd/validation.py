@@ -221,12 +221,14 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
 def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: Optional[Dict[str, str]],
              denoiser_strength: float, sigma: float, entry_names: Set[str], full_run: bool,
              save_callback: Callable[[Entry, ValidationEntryOutput], None], seed: Optional[int], device: torch.device, *,
-             batch_size: int = 1, pitch_metrics: bool = False) -> ValidationEntries:
+             batch_size: int = 1, pitch_metrics: bool = False, resample_inputs: bool = False) -> ValidationEntries:
   """validation.py:125-287.  ``batch_size`` utterances share one launch sequence; every utterance gets the audio, the
   mels and the metrics it gets alone (its noise is drawn as ``Synthesizer.infer`` draws it, and every kernel of the
   sequence treats the padding behind an utterance as the end of the sequence).  ``pitch_metrics`` adds the F0 and
   voicing errors between the original wav and the synthesis (``metrics.pitch_metrics_enqueue`` with its defaults at the
-  model's sampling rate); without it nothing of them is launched and their fields stay None."""
+  model's sampling rate); without it nothing of them is launched and their fields stay None.  ``resample_inputs``: wavs at
+  other rates are resampled to the model's on the device (``TacotronSTFT(..., resample_inputs=True)``) and the metrics
+  compare the resampled original with the synthesis; ``wav_orig`` / ``orig_sr`` of the output stay the file's own."""
   logger = getLogger(__name__)
   result = ValidationEntries()
   if seed is None:
@@ -237,7 +239,7 @@ def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: 
     logger.info("Nothing to synthesize!")
     return result
   synth = Synthesizer(checkpoint=checkpoint, custom_hparams=custom_hparams, device=device)
-  taco = TacotronSTFT(synth.hparams, synth.device)
+  taco = TacotronSTFT(synth.hparams, synth.device, resample_inputs=resample_inputs)
   bs = max(1, int(batch_size))
   for i in range(0, len(entries), bs):
     _validate_batch(synth, taco, entries[i:i + bs], sigma, denoiser_strength, seed, checkpoint.iteration, save_callback,
