@@ -80,7 +80,10 @@ const char* wg_expected_tensor_name(const wg_handle* h, int32_t i);
 int wg_finalize(wg_handle* h);
 
 /* Bytes of device workspace wg_infer / wg_forward need for batch B and n_frames mel frames
- * (forward: audio_len samples per utterance, a multiple of n_group). 0 on invalid arguments. */
+ * (forward: audio_len samples per utterance, a multiple of n_group). 0 on invalid arguments and for a batch
+ * outside the accepted size range, which the calls refuse with WG_ERR_INVALID before they look at the workspace:
+ *   B * (F + 8) <= 1 048 448   (F = n_frames, forward: ceil(audio_len / 256); F + 16 / F + 32 at 9 / 10 layers)
+ * -- one 64-channel activation plane stays below 4 GiB. wg_last_error() says which. */
 size_t wg_infer_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames);
 size_t wg_forward_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len);
 

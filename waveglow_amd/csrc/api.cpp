@@ -109,6 +109,19 @@ Workspace carve(const wg_handle* h, const RowGeom& g, char* base) {
   return w;
 }
 
+// The one size check of the inference and no-grad-forward calls and of their workspace queries (kMaxRowsPerPhase,
+// wg_host.h): made before the workspace-size check, so that a caller learns the limit without first allocating a
+// workspace of tens of GB for a call that would be refused anyway.
+static int check_envelope(const wg_config& c, int B, int L) {
+  const int64_t rows = rows_per_phase(c, B, L), F = (L + kPhases - 1) / kPhases, guard = rows / B - F;
+  if (rows > kMaxRowsPerPhase)
+    return fail(WG_ERR_INVALID,
+                "batch too large: %d utterances x (%lld + %lld guard) frames = %lld rows per phase, the limit is B * (T + %lld) <= "
+                "%lld (one 64-channel activation plane must stay below 4 GiB)",
+                B, (long long)F, (long long)guard, (long long)rows, (long long)guard, (long long)kMaxRowsPerPhase);
+  return WG_OK;
+}
+
 const HostTensor* find(const wg_handle* h, const std::string& name) {
   auto it = h->tensors.find(name);
   return it == h->tensors.end() ? nullptr : &it->second;
@@ -624,14 +637,22 @@ int wg_finalize(wg_handle* h) {
 }
 
 size_t wg_infer_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames) {
-  if (!h || B < 1 || n_frames < 1) return 0;
+  if (!h || B < 1 || n_frames < 1) {
+    fail(WG_ERR_INVALID, "bad B/n_frames");
+    return 0;
+  }
   const int L = n_frames * h->cfg.upsample_stride / h->cfg.n_group;
+  if (check_envelope(h->cfg, B, L) != WG_OK) return 0;   // the call would refuse it: wg_last_error names the limit
   RowGeom g = make_geom(h->cfg, B, L, n_frames);
   return carve(h, g, nullptr).bytes;
 }
 
 size_t wg_forward_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len) {
-  if (!h || B < 1 || n_frames < 1 || audio_len < h->cfg.n_group || audio_len % h->cfg.n_group) return 0;
+  if (!h || B < 1 || n_frames < 1 || audio_len < h->cfg.n_group || audio_len % h->cfg.n_group) {
+    fail(WG_ERR_INVALID, "bad B/n_frames, or audio_len is not a positive multiple of n_group");
+    return 0;
+  }
+  if (check_envelope(h->cfg, B, audio_len / h->cfg.n_group) != WG_OK) return 0;
   RowGeom g = make_geom(h->cfg, B, audio_len / h->cfg.n_group, n_frames);
   return carve(h, g, nullptr).bytes;
 }
@@ -714,12 +735,13 @@ int wg_infer_ragged(wg_handle* h, const void* mel, const int32_t* frames, const 
   const int n_early = n_early_flows(c);
   if (n_z_early != n_early || (n_early && !z_early)) return fail(WG_ERR_INVALID, "expected %d early-noise tensors", n_early);
   const int L = n_frames * c.upsample_stride / c.n_group;
-  if ((int64_t)B * L * 8 >= (1ll << 31)) return fail(WG_ERR_INVALID, "batch too large for 32-bit row indexing");
+  // size range first, workspace size second.  (The [B*L][8] state, indexed with 32-bit rows in flow_kernel, needs no check
+  // of its own: B * L * 8 <= 256 * B * T < 2^28 inside the envelope, the plane limit always binds first.)
+  if (int rc = check_envelope(c, B, L)) return rc;
   RowGeom g = make_geom(c, B, L, n_frames);
   g.frames = (const int*)frames;
   Workspace w = carve(h, g, (char*)workspace);
   if (w.bytes > workspace_bytes) return fail(WG_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.bytes);
-  if ((size_t)g.R * 128 >= (1ull << 32)) return fail(WG_ERR_INVALID, "plane too large for 32-bit offsets");
   hipStream_t s = (hipStream_t)stream;
   const int C = c.n_channels;
   {
@@ -821,11 +843,10 @@ int wg_forward(wg_handle* h, const void* mel, const void* audio, float* z, float
   if ((int64_t)(n_frames - 1) * c.upsample_stride + c.upsample_kernel < audio_len)
     return fail(WG_ERR_INVALID, "upsampled mel (%d frames) shorter than audio (%d)", n_frames, audio_len);
   const int L = audio_len / c.n_group;
-  if ((int64_t)B * L * 8 >= (1ll << 31)) return fail(WG_ERR_INVALID, "batch too large for 32-bit row indexing");
+  if (int rc = check_envelope(c, B, L)) return rc;   // as in wg_infer_ragged: the one size check, before the workspace's
   RowGeom g = make_geom(c, B, L, n_frames);
   Workspace w = carve(h, g, (char*)workspace);
   if (w.bytes > workspace_bytes) return fail(WG_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.bytes);
-  if ((size_t)g.R * 128 >= (1ull << 32)) return fail(WG_ERR_INVALID, "plane too large for 32-bit offsets");
   hipStream_t s = (hipStream_t)stream;
   const int C = c.n_channels;
   for (int k = 0; k < c.n_flows; ++k) log_det_W[k] = (float)((double)B * L * h->flows[k].logdet);   // model.py:63

@@ -65,6 +65,20 @@ inline RowGeom make_geom(const wg_config& c, int B, int L, int T) {
   return g;
 }
 
+// The accepted size range of wg_infer / wg_infer_ragged / wg_forward (DESIGN.md sections 2 and 8).  A 64-channel chunk
+// plane holds R * 128 bytes, and the first layer of every WN keeps a byte offset into the a0 plane in an unsigned 32-bit
+// register (wn_layer_kernel A0G), so R * 128 < 2^32: with R = 32 Rp + 32 and Rp a multiple of 128 that is
+// Rp <= 2^20 - 128, i.e. B * Fp <= 1 048 448 rows per phase block.  Every other 32-bit quantity of the two directions
+// (B * L * 8 state elements, B * L rows of flow_kernel, mel rows, tile counts) stays far below its type's range inside
+// this limit, so this is the only size check.  Evaluated in 64 bits, before make_geom's int arithmetic.
+constexpr int64_t kMaxRowsPerPhase = (1ll << 20) - 128;
+inline int64_t rows_per_phase(const wg_config& c, int64_t B, int64_t L) {
+  const int64_t max_dil = 1ll << (c.n_layers - 1);
+  int64_t Gf = (kPhases - 1 + max_dil) / kPhases;
+  if (Gf < 4) Gf = 4;
+  return B * ((L + kPhases - 1) / kPhases + 2 * Gf);
+}
+
 struct HostTensor {
   std::vector<int64_t> shape;
   std::vector<float> data;

@@ -169,6 +169,19 @@ class _Engine:
       return spect
     return torch.nn.functional.pad(spect, (0, 0, 0, self.mel_width - self.n_mel))
 
+  def workspace_bytes(self, kind: str, B: int, T: int, S: int = 0) -> int:
+    """The library's workspace size of an inference ("infer": B x T mel frames) or no-grad forward ("fwd": S samples per
+    utterance) call.  The library answers 0 for a call it would refuse -- a batch outside the size range
+    ``B * (T + 8) <= 1 048 448`` (``T + 16`` / ``T + 32`` at 9 / 10 layers) or bad arguments -- and that is raised here, with
+    the library's message, before anything is allocated for the call."""
+    if kind == "infer":
+      n = int(self.lib.wg_infer_workspace_bytes(self.handle, int(B), int(T)))
+    else:
+      n = int(self.lib.wg_forward_workspace_bytes(self.handle, int(B), int(T), int(S)))
+    if n == 0:
+      raise _lib.WgError(self.lib.wg_last_error().decode())
+    return n
+
   def workspace(self, kind: str, nbytes: int, key: Tuple[int, int, int]) -> torch.Tensor:
     """One cached workspace (the last shape's).  A captured hipGraph bakes its workspace's device pointer in, so
     ``_infer_graphed`` keeps its own reference in the graph's cache entry: evicting here never frees memory that a
@@ -321,6 +334,7 @@ class WaveGlow(nn.Module):
       return self._infer_graphed(spect, z_init, z_early, sigma, frames)
     eng = self._get_engine(spect.device)
     io = self._io_dtype(spect)
+    nbytes = eng.workspace_bytes("infer", spect.shape[0], spect.shape[2])    # raises outside the size range, before any allocation
     spect = eng.pad_mel_input(spect).contiguous()
     B, M, T = spect.shape
     L = T * 256 // self.n_group
@@ -330,7 +344,6 @@ class WaveGlow(nn.Module):
     for z in z_early:
       assert z.shape == (B, self.n_early_size, L) and z.dtype == spect.dtype and z.device == spect.device
     audio = torch.empty((B, T * 256), dtype=spect.dtype, device=spect.device)
-    nbytes = eng.lib.wg_infer_workspace_bytes(eng.handle, B, T)
     ws = eng.workspace("infer", nbytes, (B, T, 0))
     ze = (C.c_void_p * max(1, len(z_early)))(*[z.data_ptr() for z in z_early])
     stream = torch.cuda.current_stream(spect.device).cuda_stream
@@ -425,6 +438,7 @@ class WaveGlow(nn.Module):
     eng = self._get_engine(spect.device)
     io = self._io_dtype(spect)
     assert audio.dtype == spect.dtype and audio.device == spect.device
+    nbytes = eng.workspace_bytes("fwd", spect.shape[0], spect.shape[2], audio.shape[1] - audio.shape[1] % self.n_group)
     spect, audio = eng.pad_mel_input(spect).contiguous(), audio.contiguous()
     B, M, F_ = spect.shape
     S = audio.shape[1]
@@ -436,7 +450,6 @@ class WaveGlow(nn.Module):
     z = torch.empty((B, self.n_group, L), dtype=torch.float32, device=spect.device)
     log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=spect.device) for c in self.flow_channels()]
     log_det = (C.c_float * self.n_flows)()
-    nbytes = eng.lib.wg_forward_workspace_bytes(eng.handle, B, F_, S)
     ws = eng.workspace("fwd", nbytes, (B, F_, S))
     ls = (C.c_void_p * self.n_flows)(*[t.data_ptr() for t in log_s])
     stream = torch.cuda.current_stream(spect.device).cuda_stream
