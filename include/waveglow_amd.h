@@ -408,9 +408,9 @@ int wg_stftloss_backward_ragged(wg_stftloss* h, const float* g_out3, const int32
  * the handle: the caller passes device buffers.  Every fp16 matrix below is given as [rows][K] in "(pos,pos)" order
  * -- rows and K columns permuted inside 32-blocks so that position 16h+4g+i holds channel 8g+4h+i -- and then laid out
  * in MFMA-fragment order [K/64][rows/32][4][64 lanes][8]: lane (r = lane&31, h = lane>>5), element j of sub-step s,
- * block b, K-step t = Mat[32b + pos(r)][64t + 32h + 8s + j]  (waveglow_amd/train.py: differentiable torch ops build
- * the (pos,pos) matrices, so weight norm and the folds below are differentiated by the caller's autograd; one gather
- * per matrix type produces the fragment order).  Gradients come back as plain [rows][K] (pos,pos) fp32.
+ * block b, K-step t = Mat[32b + pos(r)][64t + 32h + 8s + j]  (wg_train_prepare fills the struct from the module's own
+ * parameter tensors: weight norm, the folds below and every layout in one pass per tensor on the device).
+ * Gradients come back in natural channel order (wg_train_grads).
  * C = n_channels, M8 = 8*n_mel_channels, fl = flow*n_layers + layer, K1 = 3C + M8, h_k / c_k per flow.
  * Needs only wg_create (no wg_set_tensor / wg_finalize). */
 typedef struct wg_train_weights {
@@ -443,10 +443,10 @@ typedef struct wg_train_weights {
   const float* const* bstart;    /* [C] */
   const float* const* out_init;  /* [8]   W_end.(sum_i b_skip_i) + b_end, zero padded */
   const float* const* w1x1;      /* [c_k][c_k] fp32 row-major (model.py:64) */
-  /* Optional (null: not packed, not read): the upsample transposed for the mel input gradient (wg_train_backward_ex with
+  /* Optional (null: not packed, not read): the upsample transposed for the mel input gradient (wg_train_backward with
    * g_mel), fp16 [32 p][4 j][M8/64 t][NB][4 s][64 lanes][8] with NB = ceil(n_mel/32): lane (r, h), element e of sub-step
    * s = W_up[i = 32 blk + r][o][8p + g + 256j] for the spectrogram channel (o, g) = 8o + g at d spect plane position
-   * 64t + 32h + 8s + e (zero for i >= n_mel).  wg_train_pack / wg_train_prepare fill it when it is non-null. */
+   * 64t + 32h + 8s + e (zero for i >= n_mel).  wg_train_prepare fills it when it is non-null. */
   const void* wupt;
   /* Optional (null: not filled, not read): n_flows pointers to [c_k][c_k] fp32 row-major W_k^-1 of the 1x1 matrices.
    * wg_train_prepare fills them when the member is non-null: an fp64 Gauss-Jordan elimination with partial pivoting on the
@@ -456,15 +456,15 @@ typedef struct wg_train_weights {
   const float* const* winv;
 } wg_train_weights;
 
-/* Gradients: fp32 device buffers in NATURAL channel order, w.r.t. the matrices of wg_train_plain (dw1, dw2, dwes, dwup)
- * and the natural-order bias vectors; dwes is w.r.t. the effective end x skip matrix [8][C]. */
+/* Gradients: fp32 device buffers in NATURAL channel order, w.r.t. the stacked natural-order matrices (dw1, dw2, dwes,
+ * dwup) and the natural-order bias vectors; wg_train_param_grads turns them into one gradient per parameter. */
 typedef struct wg_train_grads {
-  float* dw1;          /* [FL][2C][K1] */
+  float* dw1;          /* [FL][2C][K1]   in_layers[i].weight as K = tap*C + c_in (tap-major), then the layer's cond_layer rows [M8] */
   float* db1;          /* [FL][2C] */
-  float* dw2;          /* [FL][C][C]   (last layer of each flow: untouched) */
+  float* dw2;          /* [FL][C][C]     res rows of res_skip_layers[i] (last layer of each flow: untouched) */
   float* db2;          /* [FL][C] */
-  float* dwes;         /* [FL][8][C] */
-  float* dwup;         /* [32][M8][512] */
+  float* dwes;         /* [FL][8][C]     the effective end x skip matrix W_end . W_skip_i, zero padded to 8 rows */
+  float* dwup;         /* [32][M8][512]  upsample per phase p: row (o,g), K = [tap j][128]: W_up[i][o][8p+g+256j] */
   float* dbup;         /* [M8] */
   float* const* dstart;      /* n_flows pointers: [5][C]: rows j < 4 = d Wstart[:, j] (zero for j >= h_k), row 4 = d bstart */
   float* const* dout_init;   /* [8] */
@@ -479,9 +479,7 @@ typedef struct wg_train_grads {
   int64_t flow_stride;
 } wg_train_grads;
 
-size_t wg_train_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len);
-
-/* Flags of the flag-taking training entry points (the forms without flags are flags = 0).
+/* Flag of the training entry points below (flags = 0: every activation is kept).
  * WG_TRAIN_RECOMPUTE: activation recomputation.  The workspace keeps the layer planes (X / T / S / A / d pre) of two flow
  *   slots (flow k in slot k & 1) instead of every flow, plus every flow's fp32 state as before; the backward replays each
  *   flow's forward into its slot just before that flow's data-gradient chain (the last two flows the forward ran are still
@@ -492,29 +490,16 @@ size_t wg_train_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames,
  *   the workspace of a recompute call must be smaller than the full-save size and at least the recompute size, and a call
  *   whose flags do not match the size it is given returns WG_ERR_INVALID.  At a depth where the flag saves nothing (one or
  *   two flows: the two slots hold every flow; one layer per flow) it runs all the same, on a workspace of
- *   wg_train_workspace_bytes_ex(..., WG_TRAIN_RECOMPUTE) bytes, which is then no smaller than the full-save one. */
+ *   wg_train_workspace_bytes(..., WG_TRAIN_RECOMPUTE) bytes, which is then no smaller than the full-save one. */
 #define WG_TRAIN_RECOMPUTE 1
-size_t wg_train_workspace_bytes_ex(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, int32_t flags);
 
-/* The stacked weight matrices in NATURAL channel order, fp32, as the caller's autograd packing produces them every step
- * (waveglow_amd/train.py: pack_weights; reference modules: WN.in_layers / cond_layer / res_skip_layers / end,
- * model.py:85-113, upsample model.py:145-150). */
-typedef struct wg_train_plain {
-  const float* w1;     /* [FL][2C][K1]   in_layers[i].weight as K = tap*C + c_in (tap-major), then the layer's cond_layer rows [M8] */
-  const float* w2;     /* [FL][C][C]     res rows of res_skip_layers[i] (unused for the last layer of a flow) */
-  const float* wes;    /* [FL][8][C]     W_end . W_skip_i, zero padded to 8 rows */
-  const float* wup;    /* [32][M8][512]  upsample per phase: row (o,g), K = [tap j][128]: W_up[i][o][8p+g+256j] */
-} wg_train_plain;
+/* Bytes of device workspace the four calls below need for batch B, n_frames mel frames and audio_len samples per
+ * utterance (a multiple of n_group, at most what n_frames upsample to; the synthesis calls: 256 * n_frames), with the
+ * flags of those calls.  0 on invalid arguments or unknown flags; wg_last_error() says which. */
+size_t wg_train_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, int32_t flags);
 
-/* Fills the fp16 fragment tensors a1, a1c, a2, es, wat, wbt, wct, wup of *out (device buffers of the sizes documented on
- * wg_train_weights; its other members are not touched) from the natural-order matrices: the permutations, transposes,
- * gate pre-scales and fragment orders above in one pass per tensor.  Not differentiable -- the gradients come back in
- * natural order (wg_train_grads).  Enqueue-only. */
-int wg_train_pack(wg_handle* h, const wg_train_plain* in, const wg_train_weights* out, void* stream);
-
-/* ---- Training plumbing on the device (round 3): the module's OWN parameter tensors in, one gradient per parameter out.
- * Replaces wg_train_plain / wg_train_pack plus the caller-side autograd ops around them (weight norm, stacking, the
- * W_end x W_skip fold and their backward): reference modules WN.start / in_layers / cond_layer / res_skip_layers
+/* ---- Training plumbing on the device: the module's OWN parameter tensors in, one gradient per parameter out.  Weight
+ * norm, stacking, the W_end x W_skip fold and their backward run here, not in the caller's autograd: reference modules WN.start / in_layers / cond_layer / res_skip_layers
  * (torch weight_norm: w = g v / ||v||, model.py:85-113), WN.end (model.py:90-92), Invertible1x1Conv.conv
  * (model.py:29-43), WaveGlow.upsample (model.py:145-150).
  * The parameters come in the library's canonical order: wg_train_param_count / _name (the state_dict key of the
@@ -541,104 +526,80 @@ int32_t wg_wn_waves(int32_t n_channels);
 
 /* Forward with saved activations.  mel [B][n_mel][n_frames] fp32, audio [B][audio_len] fp32 (audio_len % 8 == 0),
  * z [B][8][L] fp32 out, log_s[k] [B][h_k][L] fp32 out.  `fresh` != 0: the workspace has not been used with this
- * geometry before (it is cleared: guard rows must read as zero).  The workspace must stay untouched until
- * wg_train_backward has run.  Enqueue-only.  At large batch the call (and wg_train_backward) also enqueues on two
- * streams the handle owns: they are forked from `stream` inside the call and joined back into it before it returns,
- * so the caller sees ordinary stream order.  Environment: WG_TRAIN_SERIAL=1 keeps every launch on `stream`
- * (timing single kernels); WG_TRAIN_HALVES=1|2 never / always runs the forward as two half-batch chains. */
+ * geometry before (it is cleared: guard rows must read as zero).  The workspace (wg_train_workspace_bytes with the same
+ * flags) must stay untouched until wg_train_backward has run.  flags: 0 or WG_TRAIN_RECOMPUTE (only the last two flows'
+ * layer planes stay in the workspace).  Enqueue-only.  At large batch the call also enqueues on streams the handle owns:
+ * they are forked from `stream` inside the call and joined back into it before it returns, so the caller sees ordinary
+ * stream order.  Environment: WG_TRAIN_SERIAL=1 keeps every launch on `stream` (timing single kernels);
+ * WG_TRAIN_HALVES=1|2 never / always runs the forward as two half-batch chains. */
 int wg_train_forward(wg_handle* h, const wg_train_weights* w, const void* mel, const void* audio, float* z,
                      float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
-                     void* workspace, size_t workspace_bytes, void* stream);
-/* wg_train_forward with flags (WG_TRAIN_RECOMPUTE, workspace of wg_train_workspace_bytes_ex with the same flags). */
-int wg_train_forward_flags(wg_handle* h, const wg_train_weights* w, const void* mel, const void* audio, float* z,
-                           float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
-                           void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
+                     void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
 
-/* Backward of the last wg_train_forward on this workspace.  g_z [B][8][L] (or null), g_log_s[k] [B][h_k][L]
- * (null entries = zero) are the gradients of the returned tensors; `scale` multiplies them on entry (fp16 gradient
- * planes) and is divided out of every result.  Enqueue-only. */
-int wg_train_backward(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_z,
-                      const float* const* g_log_s, float scale, const void* audio, int32_t B, int32_t n_frames,
-                      int32_t audio_len, void* workspace, size_t workspace_bytes, void* stream);
-
-/* The same backward pass cut at flow boundaries: processes flows flow_hi, flow_hi-1, ..., flow_lo (0 <= flow_lo <=
- * flow_hi < n_flows); calls must come in descending, contiguous order starting at n_flows-1, and the call with
- * flow_lo == 0 also produces the upsample gradients.  After a call returns, the gradient slices of its flows
- * (dw1[fl], db1[fl], dw2[fl], db2[fl], dwes[fl] for fl in [flow_lo*n_layers, (flow_hi+1)*n_layers), dstart / dout_init /
- * dw1x1 of those flows) are final on `stream` -- a data-parallel caller can start their all-reduce while the earlier
- * flows are still being computed (waveglow_amd/train.py). */
-int wg_train_backward_flows(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_z,
-                            const float* const* g_log_s, float scale, const void* audio, int32_t B, int32_t n_frames,
-                            int32_t audio_len, void* workspace, size_t workspace_bytes, int32_t flow_hi,
-                            int32_t flow_lo, void* stream);
-
-/* The backward pass with input gradients and an optional weight-gradient part.  WaveGlow.forward is plain autograd in the
- * reference (src/waveglow/model.py:178-221): after loss.backward() the inputs hold mel.grad and audio.grad as well.
- *   grads   null: no parameter gradient is computed at all (a frozen model used as a likelihood loss): no weight-gradient
- *           launch, slab reduction, start / 1x1 partial or upsample-gradient job runs, and the d spect GEMM only for g_mel.
- *           Otherwise exactly wg_train_backward_flows.
+/* Backward of the last wg_train_forward on this workspace, with the flags of that forward: loss.backward() of the
+ * reference's plain autograd (src/waveglow/model.py:178-221), after which the parameters and the inputs hold gradients.
+ * g_z [B][8][L] (or null), g_log_s[k] [B][h_k][L] (null entries = zero) are the gradients of the returned tensors;
+ * `scale` (> 0) multiplies them on entry (fp16 gradient planes) and is divided out of every result.
+ *   grads   the packed parameter gradients, or null: no parameter gradient is computed at all (a frozen model used as a
+ *           likelihood loss): no weight-gradient launch, slab reduction, start / 1x1 partial or upsample-gradient job
+ *           runs, and the d spect GEMM only for g_mel.
  *   g_mel   null, or fp32 [B][n_mel][n_frames]: d loss / d mel through the upsample and squeeze (model.py:186-193); frames
  *           whose spectrogram columns were trimmed to audio_len (model.py:188-189) get 0.  Needs w->wupt.
  *   g_audio null, or fp32 [B][audio_len]: d loss / d audio through the unfold and flow 0's 1x1 conv (model.py:195, :64).
- * Both are written entirely (no accumulation) and are final on `stream` after the call with flow_lo == 0; the flow range
- * works as for wg_train_backward_flows (flow_hi = n_flows-1, flow_lo = 0: the whole pass).  Enqueue-only. */
-int wg_train_backward_ex(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_z,
-                         const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
-                         int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
-                         int32_t flow_hi, int32_t flow_lo, void* stream);
-/* wg_train_backward_ex with the flags of the forward it belongs to.  With WG_TRAIN_RECOMPUTE every call of a flow range
- * replays the flows of its range; the call with flow_lo == 0 finishes d spect (upsample gradients, g_mel). */
-int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_z,
-                               const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
-                               int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
-                               int32_t flow_hi, int32_t flow_lo, int32_t flags, void* stream);
+ *   flow_hi, flow_lo   the pass cut at flow boundaries: the call processes flows flow_hi, flow_hi-1, ..., flow_lo
+ *           (0 <= flow_lo <= flow_hi < n_flows); calls must come in descending, contiguous order starting at n_flows-1.
+ *           flow_hi = n_flows - 1, flow_lo = 0, flags = 0 is the whole plain pass.  After a call returns, the gradient
+ *           slices of its flows (dw1[fl], db1[fl], dw2[fl], db2[fl], dwes[fl] for fl in [flow_lo*n_layers,
+ *           (flow_hi+1)*n_layers), dstart / dout_init / dw1x1 of those flows) are final on `stream` -- a data-parallel
+ *           caller can start their all-reduce while the earlier flows are still being computed (waveglow_amd/train.py).
+ *           The call with flow_lo == 0 also produces the upsample gradients, and g_mel / g_audio, both written entirely
+ *           (no accumulation), are final on `stream` after it.
+ *   flags   WG_TRAIN_RECOMPUTE: every call of a flow range replays the flows of its range; the call with flow_lo == 0
+ *           finishes d spect (upsample gradients, g_mel).
+ * Enqueue-only.  Like the forward, the call forks streams the handle owns from `stream` (the weight-gradient launches
+ * and their reductions run on two low-priority ones) and joins them back before it returns; WG_TRAIN_SERIAL=1 keeps
+ * everything on `stream`. */
+int wg_train_backward(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_z,
+                      const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
+                      int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
+                      int32_t flow_hi, int32_t flow_lo, int32_t flags, void* stream);
 
 /* Differentiable synthesis: WaveGlow.infer with injected noise (src/waveglow/model.py:223-273) with saved state, and its
- * backward w.r.t. mel and the noise (and, through wg_train_infer_backward_params, the weights).  Both run on the training workspace of the same
- * geometry, wg_train_workspace_bytes(h, B, n_frames, 256 * n_frames) (infer's trim to 256 T samples is forward's crop to
+ * backward w.r.t. mel, the noise and the weights.  Both run on the training workspace of the same geometry,
+ * wg_train_workspace_bytes(h, B, n_frames, 256 * n_frames, flags) (infer's trim to 256 T samples is forward's crop to
  * audio_len), and on the wg_train_weights of wg_train_prepare (with wupt for g_mel).  The inverse 1x1 matrices are
  * w->winv when it is given; otherwise those wg_infer uses: the handle must then be finalised with the same weights
  * (WG_ERR_STATE otherwise).
  *
  * Forward: mel [B][n_mel][n_frames] fp32, z_init [B][c_last][L] fp32, z_early[i] [B][n_early_size][L] fp32 in descending
- * flow order (as wg_infer), audio [B][256 n_frames] fp32 out; L = 32 n_frames.  `fresh` as for wg_train_forward.  The
- * workspace must stay untouched until wg_train_infer_backward has run.  Enqueue-only. */
+ * flow order (as wg_infer), audio [B][256 n_frames] fp32 out; L = 32 n_frames.  `fresh`, flags (WG_TRAIN_RECOMPUTE: flows
+ * 1 and 0 stay in the two slots) and the streams as for wg_train_forward.  The workspace must stay untouched until
+ * wg_train_infer_backward has run.  Enqueue-only. */
 int wg_train_infer_forward(wg_handle* h, const wg_train_weights* w, const void* mel, const void* z_init,
                            const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
-                           int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, void* stream);
-/* wg_train_infer_forward with flags (WG_TRAIN_RECOMPUTE: workspace of wg_train_workspace_bytes_ex with the same flags). */
-int wg_train_infer_forward_flags(wg_handle* h, const wg_train_weights* w, const void* mel, const void* z_init,
-                                 const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
-                                 int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
-                                 void* stream);
+                           int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
+                           void* stream);
 
-/* Backward of the last wg_train_infer_forward on this workspace.  g_audio [B][256 n_frames] fp32 is the gradient of the
- * returned audio; `scale` multiplies it on entry (fp16 gradient planes) and is divided out of every result.  Outputs,
- * each optional (null: not computed) and written entirely (no accumulation): g_mel [B][n_mel][n_frames],
- * g_z_init [B][c_last][L], g_z_early[i] [B][n_early_size][L] (g_z_early itself or any entry may be null).  Runs on
- * `stream` alone.  Enqueue-only. */
-int wg_train_infer_backward(wg_handle* h, const wg_train_weights* w, const float* g_audio, float scale, float sigma,
-                            float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
-                            int32_t n_frames, void* workspace, size_t workspace_bytes, void* stream);
-/* wg_train_infer_backward with the flags of its forward (WG_TRAIN_RECOMPUTE: flows 2.. are replayed; still one stream). */
-int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* w, const float* g_audio, float scale, float sigma,
-                                  float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
-                                  int32_t n_frames, void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
-
-/* wg_train_infer_backward_flags plus the gradients of the weights through synthesis (the vocoder trained on a loss on its
- * own output).  grads null: exactly wg_train_infer_backward_flags, launch by launch.  Otherwise the packed gradients of
- * wg_train_grads are filled as wg_train_backward fills them -- dw1 | db1 | dw2 | db2 | dwes per layer, dstart, dout_init per
- * flow, the upsample tail -- and dw1x1[k] = - sum over rows of (W_k^-T d w) (x) w for the inverse 1x1 step w = W_k^-1 u
- * (an [8][8] record, rows / columns >= c_k zero; this direction has no logdet term); wg_train_param_grads turns them into
- * one gradient per parameter.  Every entry is written except dw2 / db2 of the last layer of each flow.  The d spect GEMM
- * runs when g_mel or grads is given.  The forward must have run on the same wg_train_weights; with a moving model that
- * means one prepared with winv.  Flows in ascending order.  With grads the weight-gradient launches and their reductions
- * run on two low-priority streams the handle owns, forked from `stream` inside the call and joined back into it before it
- * returns, as in wg_train_backward (WG_TRAIN_SERIAL=1: everything on `stream`; same results bit for bit).  Enqueue-only. */
-int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads, const float* g_audio,
-                                   float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
-                                   int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace, size_t workspace_bytes,
-                                   int32_t flags, void* stream);
+/* Backward of the last wg_train_infer_forward on this workspace, with the flags of that forward (WG_TRAIN_RECOMPUTE:
+ * flows 2.. are replayed).  g_audio [B][256 n_frames] fp32 is the gradient of the returned audio; `scale` (> 0)
+ * multiplies it on entry (fp16 gradient planes) and is divided out of every result.  Flows in ascending order.
+ * Outputs, each optional (null: not computed) and written entirely (no accumulation): g_mel [B][n_mel][n_frames],
+ * g_z_init [B][c_last][L], g_z_early[i] [B][n_early_size][L] (g_z_early itself or any entry may be null).
+ *   grads   null: the data gradients alone, on `stream` alone.  Otherwise also the gradients of the weights through
+ *           synthesis (the vocoder trained on a loss on its own output): the packed gradients of wg_train_grads are filled
+ *           as wg_train_backward fills them -- dw1 | db1 | dw2 | db2 | dwes per layer, dstart, dout_init per flow, the
+ *           upsample tail -- and dw1x1[k] = - sum over rows of (W_k^-T d w) (x) w for the inverse 1x1 step w = W_k^-1 u
+ *           (an [8][8] record, rows / columns >= c_k zero; this direction has no logdet term); wg_train_param_grads turns
+ *           them into one gradient per parameter.  Every entry is written except dw2 / db2 of the last layer of each
+ *           flow.  The forward must have run on the same wg_train_weights; with a moving model that means one prepared
+ *           with winv.  The weight-gradient launches and their reductions run on two low-priority streams the handle
+ *           owns, forked from `stream` inside the call and joined back into it before it returns, as in
+ *           wg_train_backward (WG_TRAIN_SERIAL=1: everything on `stream`; same results bit for bit).
+ * The d spect GEMM runs when g_mel or grads is given.  Enqueue-only. */
+int wg_train_infer_backward(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads,
+                            const float* g_audio, float scale, float sigma, float* g_mel, float* g_z_init,
+                            float* const* g_z_early, int32_t n_z_early, int32_t B, int32_t n_frames,
+                            void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
 
 /* Diagnostic builds only (-DWG_STAMPS): device buffer of n_tiles*8 uint64 that the WN-layer kernel fills with
  * s_memtime stamps at its phase boundaries (last launch wins).  A no-op pointer in the shipped library. */

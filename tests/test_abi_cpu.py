@@ -30,6 +30,29 @@ def test_header_symbols_all_exported_and_bound(lib):
     assert hasattr(lib, s), s
     assert s in _lib.SIGNATURES, f"{s} declared in the header but not bound in _lib.SIGNATURES"
   assert sorted(_lib.SIGNATURES) == syms
+  # one entry point per call: no suffixed variant of a name, and the natural-order packing entry is gone everywhere
+  assert not [s for s in syms if re.search(r"_(ex|flags|flows|params)$", s)]
+  text = open(os.path.join(ROOT, "include", "waveglow_amd.h")).read()
+  for gone in ("wg_train_" + n for n in ("pack", "plain")):
+    assert gone not in text and gone not in _lib.SIGNATURES and not hasattr(lib, gone), gone
+
+
+def _struct_listing(name):
+  """Member names of the ctypes Structure `name` as the condensed binding in INTEGRATION.md lists them."""
+  text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+  code = "\n".join(re.findall(r"```python\n(.*?)```", text, flags=re.S))
+  assert code.count(f"class {name}(C.Structure)") == 1, name
+  # the _fields_ statement: from its first line to the next class statement or blank line
+  m = re.search(rf"class {name}\(C\.Structure\).*?(_fields_ = .*?)\n(?:class |\s*\n)", code, flags=re.S)
+  assert m, name
+  return re.findall(r'"(\w+)"', re.sub(r"#[^\n]*", "", m.group(1)))
+
+
+@pytest.mark.parametrize("name", ["WgTrainWeights", "WgTrainGrads"])
+def test_integration_guide_lists_the_structs_as_bound(name):
+  """The struct a reader binds from INTEGRATION.md has every member of the library's struct, in order: one that is short
+  of the tail members makes wg_train_prepare and the backward read past its end."""
+  assert _struct_listing(name) == [n for n, _ in getattr(_lib, name)._fields_]
 
 
 def test_create_validates_configuration(lib):
@@ -78,13 +101,23 @@ def test_train_entry_points_validate_arguments_without_a_gpu():
   cfg = _lib.WgConfig(80, 12, 8, 4, 2, 8, 256, 3, 1024, 256)
   h = C.c_void_p()
   assert lib.wg_create(C.byref(cfg), 0, C.byref(h)) == 0
-  assert lib.wg_train_workspace_bytes(h, 32, 63, 16000) > 10 * 2 ** 30          # saved activations of configs[3]
-  assert lib.wg_train_workspace_bytes(h, 32, 63, 16001) == 0                      # not a multiple of n_group
-  assert lib.wg_train_workspace_bytes(h, 32, 10, 16000) == 0                      # upsampled mel shorter than audio
+  assert lib.wg_train_workspace_bytes(h, 32, 63, 16000, 0) > 10 * 2 ** 30       # saved activations of configs[3]
+  assert lib.wg_train_workspace_bytes(h, 32, 63, 16001, 0) == 0                   # not a multiple of n_group
+  assert lib.wg_train_workspace_bytes(h, 32, 10, 16000, 0) == 0                   # upsampled mel shorter than audio
   w = _lib.WgTrainWeights()
   dummy = (C.c_char * 64)()
   ls = (C.c_void_p * 12)(*[C.addressof(dummy)] * 12)
   rc = lib.wg_train_forward(h, C.byref(w), C.addressof(dummy), C.addressof(dummy), C.addressof(dummy), ls, 1, 8, 2048, 0,
-                            C.addressof(dummy), 1 << 40, None)
+                            C.addressof(dummy), 1 << 40, 0, None)
   assert rc == -1 and b"null member" in lib.wg_last_error()
+  # the backward's own checks, before any geometry: the loss scale, then (grads may be null) the required pointers
+  d = C.addressof(dummy)
+  g = _lib.WgTrainGrads()
+  for grads in (C.byref(g), None):
+    assert lib.wg_train_backward(h, C.byref(w), grads, d, ls, C.c_float(0.0), d, None, None, 1, 8, 2048, d, 1 << 40, 11, 0, 0,
+                                 None) == -1
+    assert b"scale" in lib.wg_last_error()
+    assert lib.wg_train_backward(h, C.byref(w), grads, d, ls, C.c_float(1.0), None, None, None, 1, 8, 2048, d, 1 << 40, 11, 0,
+                                 0, None) == -1
+    assert b"null argument" in lib.wg_last_error()
   lib.wg_destroy(h)

@@ -201,7 +201,7 @@ def test_infer_differentiable_equal_and_refusals():
 
 
 def test_flow_ranges_under_data_parallel_single_rank():
-  """Data-parallel mode cuts the backward into one call per flow (wg_train_backward_ex_flags with flow_hi = flow_lo):
+  """Data-parallel mode cuts the backward into one call per flow (wg_train_backward with flow_hi = flow_lo):
   each call replays its own flow, the call of flow 0 finishes d spect.  Equal to the single-call recompute backward."""
   import torch.distributed as dist
   from waveglow_amd.train import enable_data_parallel

@@ -132,7 +132,7 @@ def test_train_step_both_layer_tile_widths(force_bn, monkeypatch):
                                     (dict(n_channels=64, n_layers=8, n_flows=4, n_early_every=2), 4)])
 def test_train_step_half_batch_chains(over, B, monkeypatch):
   """Large batches run as two half-batch chains on two streams, with the weight-gradient launches on a third (train_api.cpp:
-  setup, wg_train_backward_flows); small test shapes would never choose that, so it is forced here.  The same step with
+  setup, wg_train_backward with a flow range); small test shapes would never choose that, so it is forced here.  The same step with
   everything serialised on one stream must give bit-identical outputs and gradients (the streams only reorder launches
   that do not depend on each other -- any difference is a missing dependency), and both match the oracle."""
   from oracle import torch_oracle as O
@@ -297,7 +297,7 @@ def test_train_step_other_widths(channels):
 
 
 def test_backward_with_fused_per_flow_allreduce_single_rank():
-  """Data-parallel mode of the autograd node: backward cut at flow boundaries (wg_train_backward_flows) with one RCCL
+  """Data-parallel mode of the autograd node: backward cut at flow boundaries (wg_train_backward with a flow range) with one RCCL
   all-reduce per flow queued behind it.  In a one-rank group the result must equal the single-call backward."""
   import socket
   import torch.distributed as dist

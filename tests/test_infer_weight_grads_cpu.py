@@ -114,10 +114,27 @@ def _header_decl(name):
   return m.group(1).strip(), [a.strip() for a in m.group(2).split(",")]
 
 
+_KINDS = {C.c_float: "float", C.c_int32: "int32_t", C.c_size_t: "size_t"}      # (c_int32 is c_int where int has 32 bits)
+
+
+@pytest.mark.parametrize("name", ["wg_train_workspace_bytes", "wg_train_forward", "wg_train_backward", "wg_train_infer_forward",
+                                  "wg_train_infer_backward"])
+def test_header_and_binding_agree_argument_by_argument(name):
+  """Return type and every argument of the five training calls: pointer / float / int32_t / size_t in the header is the same
+  kind, at the same place, in _lib.SIGNATURES -- a binding left at another arity or order does not pass."""
+  ret, args = _header_decl(name)
+  res, argtypes = _lib.SIGNATURES[name]
+  assert (ret, res) in (("int", C.c_int), ("size_t", C.c_size_t))
+  assert ["ptr" if "*" in a else a.split()[0] for a in args] == [_KINDS.get(t, "ptr") for t in argtypes]
+  want_len = {"wg_train_workspace_bytes": 5, "wg_train_forward": 14, "wg_train_backward": 18, "wg_train_infer_forward": 15,
+              "wg_train_infer_backward": 16}[name]
+  assert len(args) == want_len
+
+
 def test_abi_of_the_new_entry_points():
   build.build_library()
   lib = _lib.load()
-  ret, args = _header_decl("wg_train_infer_backward_params")
+  ret, args = _header_decl("wg_train_infer_backward")
   assert ret == "int"
   kinds = []
   for a in args:
@@ -128,13 +145,10 @@ def test_abi_of_the_new_entry_points():
   want = ["ptr", "ptr", "ptr", "ptr", "float", "float", "ptr", "ptr", "ptr", "int32_t", "int32_t", "int32_t", "ptr", "size_t",
           "int32_t", "ptr"]
   assert kinds == want
-  res, argtypes = _lib.SIGNATURES["wg_train_infer_backward_params"]
-  assert res is C.c_int and hasattr(lib, "wg_train_infer_backward_params")
+  res, argtypes = _lib.SIGNATURES["wg_train_infer_backward"]
+  assert res is C.c_int and hasattr(lib, "wg_train_infer_backward")
   ctk = {C.c_float: "float", C.c_int32: "int32_t", C.c_size_t: "size_t"}
   assert [ctk.get(t, "ptr") for t in argtypes] == want
-  # the flag form's arguments with the gradient block inserted after the weights
-  _, flag_args = _lib.SIGNATURES["wg_train_infer_backward_flags"]
-  assert argtypes[:2] == flag_args[:2] and argtypes[3:] == flag_args[2:]
   # wg_train_weights: winv appended, every earlier member where it was
   names = [n for n, _ in _lib.WgTrainWeights._fields_]
   assert names[-1] == "winv" and names[-2] == "wupt" and names.index("w1x1") == 14
@@ -152,9 +166,9 @@ def test_abi_of_the_new_entry_points():
   dummy = (C.c_char * 64)()
   d = C.addressof(dummy)
   w = _lib.WgTrainWeights()
-  assert lib.wg_train_infer_backward_params(h, C.byref(w), None, None, 1.0, 1.0, None, None, None, 0, 1, 8, d, 64, 0, None) == -1
+  assert lib.wg_train_infer_backward(h, C.byref(w), None, None, 1.0, 1.0, None, None, None, 0, 1, 8, d, 64, 0, None) == -1
   assert b"null argument" in lib.wg_last_error()
-  assert lib.wg_train_infer_backward_params(h, C.byref(w), None, d, 0.0, 1.0, None, None, None, 0, 1, 8, d, 64, 0, None) == -1
+  assert lib.wg_train_infer_backward(h, C.byref(w), None, d, 0.0, 1.0, None, None, None, 0, 1, 8, d, 64, 0, None) == -1
   assert b"scale" in lib.wg_last_error()
   # wg_train_prepare: a winv array with a null entry is refused
   nulls = (C.c_void_p * 12)()

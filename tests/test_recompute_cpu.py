@@ -23,14 +23,14 @@ def handle():
 
 def test_workspace_bytes_of_both_modes(handle):
   lib, h = handle
-  full = lib.wg_train_workspace_bytes_ex(h, 32, 63, 16000, 0)
-  rec = lib.wg_train_workspace_bytes_ex(h, 32, 63, 16000, RC)
-  assert full == lib.wg_train_workspace_bytes(h, 32, 63, 16000) > 20 * 2 ** 30
+  full = lib.wg_train_workspace_bytes(h, 32, 63, 16000, 0)
+  rec = lib.wg_train_workspace_bytes(h, 32, 63, 16000, RC)
+  assert full > 20 * 2 ** 30
   assert 0 < rec <= 0.25 * full                                     # 0.20 at 256 channels
   # whole utterances: 16 x 10 s (861 frames) -- about 135 GB of saved planes without recomputation
-  assert lib.wg_train_workspace_bytes_ex(h, 16, 861, 861 * 256, RC) < 0.25 * lib.wg_train_workspace_bytes_ex(h, 16, 861, 861 * 256, 0)
-  assert lib.wg_train_workspace_bytes_ex(h, 32, 63, 16000, 2) == 0 and b"flags" in lib.wg_last_error()
-  assert lib.wg_train_workspace_bytes_ex(h, 32, 63, 16001, RC) == 0
+  assert lib.wg_train_workspace_bytes(h, 16, 861, 861 * 256, RC) < 0.25 * lib.wg_train_workspace_bytes(h, 16, 861, 861 * 256, 0)
+  assert lib.wg_train_workspace_bytes(h, 32, 63, 16000, 2) == 0 and b"flags" in lib.wg_last_error()
+  assert lib.wg_train_workspace_bytes(h, 32, 63, 16001, RC) == 0
 
 
 def test_recompute_refused_where_two_slots_hold_every_flow():
@@ -41,18 +41,18 @@ def test_recompute_refused_where_two_slots_hold_every_flow():
   h = C.c_void_p()
   assert lib.wg_create(C.byref(_lib.WgConfig(80, 2, 8, 1, 2, 2, 128, 3, 1024, 256)), 0, C.byref(h)) == 0
   try:
-    full = lib.wg_train_workspace_bytes_ex(h, 2, 7, 1792, 0)
-    rec = lib.wg_train_workspace_bytes_ex(h, 2, 7, 1792, RC)
+    full = lib.wg_train_workspace_bytes(h, 2, 7, 1792, 0)
+    rec = lib.wg_train_workspace_bytes(h, 2, 7, 1792, RC)
     assert 0 < full <= rec
     w = _lib.WgTrainWeights()
     buf = (C.c_char * 64)()
     p = C.addressof(buf)
     ls = (C.c_void_p * 2)(p, p)
     for nbytes, flags in ((rec, RC), (full, 0), (rec, 0)):
-      assert lib.wg_train_forward_flags(h, C.byref(w), p, p, p, ls, 2, 7, 1792, 0, p, nbytes, flags, None) == -1
+      assert lib.wg_train_forward(h, C.byref(w), p, p, p, ls, 2, 7, 1792, 0, p, nbytes, flags, None) == -1
       assert b"null member" in lib.wg_last_error(), (nbytes, flags)
     if rec > full:
-      assert lib.wg_train_forward_flags(h, C.byref(w), p, p, p, ls, 2, 7, 1792, 0, p, full, RC, None) == -4   # too small
+      assert lib.wg_train_forward(h, C.byref(w), p, p, p, ls, 2, 7, 1792, 0, p, full, RC, None) == -4   # too small
   finally:
     lib.wg_destroy(h)
 
@@ -62,8 +62,8 @@ def test_flags_must_match_the_workspace_size(handle):
   of the other mode's size with WG_ERR_INVALID (-1); with matching sizes the call gets as far as its weight checks."""
   lib, h = handle
   B, T, S = 2, 8, 2048
-  full = lib.wg_train_workspace_bytes_ex(h, B, T, S, 0)
-  rec = lib.wg_train_workspace_bytes_ex(h, B, T, S, RC)
+  full = lib.wg_train_workspace_bytes(h, B, T, S, 0)
+  rec = lib.wg_train_workspace_bytes(h, B, T, S, RC)
   assert 0 < rec < full
   w = _lib.WgTrainWeights()
   buf = (C.c_char * 64)()
@@ -71,19 +71,19 @@ def test_flags_must_match_the_workspace_size(handle):
   ls = (C.c_void_p * 12)(*[p] * 12)
 
   def fwd(nbytes, flags):
-    return lib.wg_train_forward_flags(h, C.byref(w), p, p, p, ls, B, T, S, 0, p, nbytes, flags, None)
+    return lib.wg_train_forward(h, C.byref(w), p, p, p, ls, B, T, S, 0, p, nbytes, flags, None)
 
   def bwd(nbytes, flags):
-    return lib.wg_train_backward_ex_flags(h, C.byref(w), None, p, ls, C.c_float(1.0), p, None, None, B, T, S, p, nbytes,
-                                          11, 0, flags, None)
+    return lib.wg_train_backward(h, C.byref(w), None, p, ls, C.c_float(1.0), p, None, None, B, T, S, p, nbytes, 11, 0, flags,
+                                 None)
 
   def ifwd(nbytes, flags):
     ze = (C.c_void_p * 2)(p, p)
-    return lib.wg_train_infer_forward_flags(h, C.byref(w), p, p, ze, 2, C.c_float(1.0), p, B, T, 0, p, nbytes, flags, None)
+    return lib.wg_train_infer_forward(h, C.byref(w), p, p, ze, 2, C.c_float(1.0), p, B, T, 0, p, nbytes, flags, None)
 
   def ibwd(nbytes, flags):
-    return lib.wg_train_infer_backward_flags(h, C.byref(w), p, C.c_float(1.0), C.c_float(1.0), None, None, None, 2, B, T,
-                                             p, nbytes, flags, None)
+    return lib.wg_train_infer_backward(h, C.byref(w), None, p, C.c_float(1.0), C.c_float(1.0), None, None, None, 2, B, T, p,
+                                       nbytes, flags, None)
 
   for call in (fwd, bwd, ifwd, ibwd):
     assert call(full, RC) == -1 and b"do not match" in lib.wg_last_error(), call.__name__

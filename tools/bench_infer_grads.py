@@ -159,7 +159,7 @@ def main():
   ze = [torch.randn(B, hp.n_early_size, L, device="cuda:0", generator=gen) for _ in range(n_early)]
   wav = (torch.rand(B, 256 * T - 128, generator=torch.Generator().manual_seed(3)) * 0.6 - 0.3).cuda()   # 16000 at T = 63
   eng = model._get_engine(mel.device, need_weights=bool(a.modes))      # --modes "": the frozen engine stays unfinalised
-  ws = int(eng.lib.wg_train_workspace_bytes(eng.handle, B, T, 256 * T))
+  ws = int(eng.lib.wg_train_workspace_bytes(eng.handle, B, T, 256 * T, 0))
   print(json.dumps({"workspace_bytes": ws, "bytes_per_output_sample": ws / (B * 256 * T), "batch": B, "frames": T}), flush=True)
   for r in range(a.rounds):
     for mode in a.modes:

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("WAVEGLOW_AMD_LIB", os.path.join(_HERE, "csrc", "libwa
 WG_F32, WG_F16 = 0, 1
 WG_PCM_I16, WG_PCM_F32 = 0, 1   # pool_dtype of wg_data_gather
 WG_RESAMPLE_CLIP = 1           # flag of wg_resample
-WG_TRAIN_RECOMPUTE = 1        # flag of the wg_train_*_flags entry points (include/waveglow_amd.h)
+WG_TRAIN_RECOMPUTE = 1        # flag of the wg_train_* entry points that take flags (include/waveglow_amd.h)
 
 
 class WgConfig(C.Structure):
@@ -31,11 +31,6 @@ class WgTrainWeights(C.Structure):
   _fields_ = [(n, C.c_void_p) for n in (
     "a1", "a1c", "b1", "a2", "b2", "es", "wat", "wbt", "wct", "wup", "bup", "wstart", "bstart", "out_init", "w1x1", "wupt",
     "winv")]
-
-
-class WgTrainPlain(C.Structure):
-  """wg_train_plain: the natural-order fp32 matrices wg_train_pack reads."""
-  _fields_ = [(n, C.c_void_p) for n in ("w1", "w2", "wes", "wup")]
 
 
 class WgTrainGrads(C.Structure):
@@ -82,10 +77,8 @@ SIGNATURES = {
   "wg_loss_dev": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32,
                             C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_macs_per_group_step": (C.c_double, [C.c_void_p]),
-  "wg_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
-  "wg_train_workspace_bytes_ex": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+  "wg_train_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
   "wg_wn_waves": (C.c_int32, [C.c_int32]),
-  "wg_train_pack": (C.c_int, [C.c_void_p, C.POINTER(WgTrainPlain), C.POINTER(WgTrainWeights), C.c_void_p]),
   "wg_train_param_count": (C.c_int32, [C.c_void_p, C.c_int32]),
   "wg_train_param_name": (C.c_char_p, [C.c_void_p, C.c_int32, C.c_int32]),
   "wg_train_param_numel": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -96,39 +89,18 @@ SIGNATURES = {
                                      C.c_size_t, C.c_void_p, C.c_void_p]),
   "wg_train_forward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                 C.c_size_t, C.c_void_p]),
-  "wg_train_forward_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                       C.c_size_t, C.c_int32, C.c_void_p]),
+                                 C.c_size_t, C.c_int32, C.c_void_p]),
   "wg_train_backward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
-                                  C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                  C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_train_backward_flows": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
-                                        C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p]),
-  "wg_train_backward_ex": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
-                                     C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                     C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p]),
-  "wg_train_backward_ex_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
-                                           C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
-                                           C.c_int32, C.c_void_p]),
+                                  C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_void_p]),
   "wg_train_infer_forward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p,
-                                       C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_train_infer_backward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_float, C.c_float,
-                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_train_infer_forward_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p,
-                                             C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.c_void_p, C.c_int32,
-                                             C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
-  "wg_train_infer_backward_flags": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_float, C.c_float,
-                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32,
-                                              C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
-  "wg_train_infer_backward_params": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
-                                               C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
-                                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
-                                               C.c_void_p]),
+                                       C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.c_void_p, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+  "wg_train_infer_backward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
+                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
+                                        C.c_void_p]),
   "wg_stft_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stft_destroy": (C.c_int, [C.c_void_p]),
   "wg_stft_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -233,7 +233,7 @@ hipEvent_t wg_internal_sync_event(wg_handle* h) {
 
 extern "C" {
 
-const char* wg_version(void) { return "waveglow_amd 0.1 (gfx950)"; }
+const char* wg_version(void) { return "waveglow_amd 0.2 (gfx950)"; }
 const char* wg_last_error(void) { return g_err.c_str(); }
 
 int wg_create(const wg_config* cfg, int device_id, wg_handle** out) {

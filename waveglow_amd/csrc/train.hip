@@ -846,7 +846,7 @@ hipError_t launch_wgrad(const WgradJob* jobs, int n_jobs, const RowGeom& g, cons
 }
 
 // =============================================================================================
-// Weight packing (wg_train_pack): natural-order fp32 matrices -> the fp16 MFMA-fragment tensors of wg_train_weights,
+// Weight packing (wg_train_prepare): natural-order fp32 matrices -> the fp16 MFMA-fragment tensors of wg_train_weights,
 // one pass per tensor, one thread per 16-byte output piece (8 consecutive K positions of one row).  Position order is
 // a permutation inside 32-blocks (wg_common.h: pos_to_chan): positions p0 .. p0+7 of a block (p0 = 0, 8, 16, 24) are
 // natural channels n0 .. n0+3 and n0+8 .. n0+11 with n0 = 16*((p0>>3)&1) + 4*(p0>>4) -- two runs of four.
@@ -855,8 +855,8 @@ namespace {
 __device__ __forceinline__ int nat0_of(int p0) { return 16 * ((p0 >> 3) & 1) + 4 * (p0 >> 4); }   // p0 in {0, 8, 16, 24}
 }  // namespace
 
-// Element accessors of the stacked natural-order matrices.  native = 0: they exist in memory (wg_train_plain).  native = 1
-// (wg_train_prepare): read from the module's own tensors with the weight-norm row scale applied on the fly --
+// Element accessors of the stacked natural-order matrices.  The matrices never exist in memory: every element is read from
+// the module's own tensors (PrepArgs::tab) with the weight-norm row scale applied on the fly --
 //   W1[fl][m][n]: n < 3C: in_layers[fl].weight[m][c = n % C][tap = n / C] (native [2C][C][3]); else cond_layer row
 //   (fl % nl) * 2C + m, column n - 3C;   W2[fl][r][c]: res rows of res_skip_layers[fl] (zero in a flow's last layer).
 // An fp32 product that is about to be rounded to fp16 must be ROUNDED TO fp32 FIRST (what torch's weight norm followed by
@@ -871,7 +871,6 @@ struct PackSrc {
   const PackArgs& a;
   __device__ __forceinline__ float w1(int fl, int m, int n) const {
     const int C = a.C;
-    if (!a.native) return a.w1[((size_t)fl * 2 * C + m) * (3 * C + a.M8) + n];
     const PrepArgs& p = a.prep;
     if (n < 3 * C) {
       const int tap = n / C, c = n - tap * C;
@@ -882,14 +881,12 @@ struct PackSrc {
   }
   __device__ __forceinline__ float w2(int fl, int r, int c) const {
     const int C = a.C;
-    if (!a.native) return a.w2[((size_t)fl * C + r) * C + c];
     const PrepArgs& p = a.prep;
     if (fl % p.nl == p.nl - 1) return 0.0f;
     return f32_rounded(((const float*)p.tab[prep_slot(p, SEC_RS_V, fl)])[(size_t)r * C + c] * p.s_rs[(size_t)fl * 2 * C + r]);
   }
   // Wup[p][row = 8 o + g][col = 128 j + i] = upsample.weight[i][o][256 j + 8 p + g], zero for i >= M
   __device__ __forceinline__ float wup(int ph, int row, int col) const {
-    if (!a.native) return a.wup[((size_t)ph * a.M8 + row) * 512 + col];
     const int M = a.M8 / 8, j = col >> 7, i = col & 127, o = row >> 3, g = row & 7;
     if (i >= M) return 0.0f;
     return ((const float*)a.prep.tab[prep_slot(a.prep, SEC_UP_W, 0)])[((size_t)i * M + o) * 1024 + 256 * j + 8 * ph + g];

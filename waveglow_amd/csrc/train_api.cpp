@@ -275,6 +275,14 @@ int fwd_block_n(const Ctx& x) {
   return BNw;
 }
 
+// stream of the forward's second chain (the caller's stream `s` is the first): see setup
+int second_chain_stream(wg_handle* h, const Ctx& x, hipStream_t s, hipStream_t& sB) {
+  sB = s;
+  if (x.halves == 2 && !x.serial && !(sB = wg_internal_aux_stream(h, 0)))
+    return fail(WG_ERR_HIP, "cannot create the second chain's stream");
+  return WG_OK;
+}
+
 // mel planes, then upsample (ConvTranspose1d 1024/256, model.py:145-150, :186-189) + squeeze (:191-193): one matrix per
 // phase -> the SP planes every layer's conditioning K-segment reads
 int spect_planes(const Ctx& x, const wg_train_weights* wt, const void* mel, hipStream_t s) {
@@ -404,8 +412,8 @@ size_t grad_ofs(const wg_train_grads* gr, int nl, int fl, size_t dense) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// What the two backward drivers share (wg_train_backward_ex_flags: training direction, flows descending;
-// wg_train_infer_backward_params: synthesis direction, flows ascending): the plan of one call, the WN data-gradient chain
+// What the two backward drivers share (wg_train_backward: training direction, flows descending;
+// wg_train_infer_backward: synthesis direction, flows ascending): the plan of one call, the WN data-gradient chain
 // of one flow (wn_flow_backward) and the d spect tail behind the last flow (dspect_finish).
 //
 // Streams of one backward call.  The caller's stream `s` carries chain 0 (d acts / gate derivative and d x of the first
@@ -757,43 +765,7 @@ extern "C" {
 
 int32_t wg_wn_waves(int32_t n_channels) { return wn_waves(n_channels); }
 
-int wg_train_pack(wg_handle* h, const wg_train_plain* in, const wg_train_weights* out, void* stream) {
-  if (!h || !in || !out) return fail(WG_ERR_INVALID, "null argument");
-  if (!in->w1 || !in->w2 || !in->wes || !in->wup || !out->a1 || !out->a1c || !out->a2 || !out->es || !out->wat ||
-      !out->wbt || !out->wct || !out->wup)
-    return fail(WG_ERR_INVALID, "wg_train_pack: null tensor");
-  const wg_config& c = h->cfg;
-  hipStream_t s = (hipStream_t)stream;
-  const int C = c.n_channels, M8 = c.n_mel_channels * 8, FL = c.n_flows * c.n_layers, NW = wn_waves(C);
-  if (NW <= 0 || M8 % 64) return fail(WG_ERR_INVALID, "wg_train_pack: unsupported channel counts");
-  const size_t K1 = 3 * (size_t)C + M8;
-  PackArgs a;
-  memset(&a, 0, sizeof a);
-  a.C = C; a.M8 = M8; a.FL = FL; a.NW = NW;
-  a.w1 = in->w1; a.w2 = in->w2; a.wes = in->wes; a.wup = in->wup;
-  auto run = [&](int kind, const void* dst, const void* dst2, size_t elements) -> hipError_t {
-    a.kind = kind;
-    a.dst = (_Float16*)const_cast<void*>(dst);
-    a.dst2 = (_Float16*)const_cast<void*>(dst2);
-    a.n_pieces = elements / 8;
-    return launch_pack(a, s);
-  };
-  TR_TRY(run(PACK_A1, out->a1, out->a1c, (size_t)FL * 2 * C * K1));
-  TR_TRY(run(PACK_A2, out->a2, nullptr, (size_t)FL * C * C));
-  TR_TRY(run(PACK_ES, out->es, nullptr, (size_t)FL * 16 * C));
-  TR_TRY(run(PACK_WAT, out->wat, nullptr, (size_t)FL * C * (C + 64)));
-  TR_TRY(run(PACK_WBT, out->wbt, nullptr, (size_t)FL * C * 6 * C));
-  TR_TRY(run(PACK_WCT, out->wct, nullptr, (size_t)M8 * FL * 2 * C));
-  TR_TRY(run(PACK_WUP, out->wup, nullptr, (size_t)32 * M8 * 512));
-  if (out->wupt) TR_TRY(run(PACK_WUPT, out->wupt, nullptr, (size_t)32 * 4 * M8 * wupt_blocks(M8) * 32));
-  return WG_OK;
-}
-
-size_t wg_train_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len) {
-  return wg_train_workspace_bytes_ex(h, B, n_frames, audio_len, 0);
-}
-
-size_t wg_train_workspace_bytes_ex(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, int32_t flags) {
+size_t wg_train_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, int32_t flags) {
   Ctx x;
   if (setup(const_cast<wg_handle*>(h), B, n_frames, audio_len, nullptr, 0, flags, x) != WG_OK) return 0;
   return x.w.bytes;
@@ -801,14 +773,7 @@ size_t wg_train_workspace_bytes_ex(const wg_handle* h, int32_t B, int32_t n_fram
 
 int wg_train_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* audio, float* z,
                      float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
-                     void* workspace, size_t workspace_bytes, void* stream) {
-  return wg_train_forward_flags(h, wt, mel, audio, z, log_s, B, n_frames, audio_len, fresh, workspace, workspace_bytes, 0,
-                                stream);
-}
-
-int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* audio, float* z,
-                           float* const* log_s, int32_t B, int32_t n_frames, int32_t audio_len, int32_t fresh,
-                           void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
+                     void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
   if (!wt || !mel || !audio || !z || !log_s || !workspace) return fail(WG_ERR_INVALID, "null argument");
   Ctx x;
   int rc = setup(h, B, n_frames, audio_len, workspace, workspace_bytes, flags, x);
@@ -819,12 +784,8 @@ int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void*
   TrainWs& w = x.w;
   hipStream_t s = (hipStream_t)stream;
   const int C = x.C;
-  // second chain (the caller's stream is the first): see setup
-  hipStream_t sB = s;
-  if (x.halves == 2 && !x.serial) {
-    sB = wg_internal_aux_stream(h, 0);
-    if (!sB) return fail(WG_ERR_HIP, "cannot create the second chain's stream");
-  }
+  hipStream_t sB;
+  if ((rc = second_chain_stream(h, x, s, sB))) return rc;
   const int BNw = fwd_block_n(x);
 
   if (fresh) TR_TRY(hipMemsetAsync(workspace, 0, w.zero_bytes, s));
@@ -876,36 +837,9 @@ int wg_train_forward_flags(wg_handle* h, const wg_train_weights* wt, const void*
 }
 
 int wg_train_backward(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_z,
-                      const float* const* g_log_s, float scale, const void* audio, int32_t B, int32_t n_frames,
-                      int32_t audio_len, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h) return fail(WG_ERR_INVALID, "null handle");
-  const wg_config* c = &h->cfg;
-  if (!gr) return fail(WG_ERR_INVALID, "null argument");
-  return wg_train_backward_ex(h, wt, gr, g_z, g_log_s, scale, audio, nullptr, nullptr, B, n_frames, audio_len, workspace,
-                              workspace_bytes, c->n_flows - 1, 0, stream);
-}
-
-int wg_train_backward_flows(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_z,
-                            const float* const* g_log_s, float scale, const void* audio, int32_t B, int32_t n_frames,
-                            int32_t audio_len, void* workspace, size_t workspace_bytes, int32_t flow_hi, int32_t flow_lo,
-                            void* stream) {
-  if (!gr) return fail(WG_ERR_INVALID, "null argument");
-  return wg_train_backward_ex(h, wt, gr, g_z, g_log_s, scale, audio, nullptr, nullptr, B, n_frames, audio_len, workspace,
-                              workspace_bytes, flow_hi, flow_lo, stream);
-}
-
-int wg_train_backward_ex(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_z,
-                         const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
-                         int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
-                         int32_t flow_hi, int32_t flow_lo, void* stream) {
-  return wg_train_backward_ex_flags(h, wt, gr, g_z, g_log_s, scale, audio, g_mel, g_audio, B, n_frames, audio_len, workspace,
-                                    workspace_bytes, flow_hi, flow_lo, 0, stream);
-}
-
-int wg_train_backward_ex_flags(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_z,
-                               const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
-                               int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
-                               int32_t flow_hi, int32_t flow_lo, int32_t flags, void* stream) {
+                      const float* const* g_log_s, float scale, const void* audio, float* g_mel, float* g_audio,
+                      int32_t B, int32_t n_frames, int32_t audio_len, void* workspace, size_t workspace_bytes,
+                      int32_t flow_hi, int32_t flow_lo, int32_t flags, void* stream) {
   if (!wt || !audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
   if (!(scale > 0.f)) return fail(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
@@ -1040,15 +974,8 @@ void infer_next(const Ctx& x, const wg_train_weights* wt, int j, FlowArgs& f) {
 
 int wg_train_infer_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* z_init,
                            const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
-                           int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, void* stream) {
-  return wg_train_infer_forward_flags(h, wt, mel, z_init, z_early, n_z_early, sigma, audio, B, n_frames, fresh, workspace,
-                                      workspace_bytes, 0, stream);
-}
-
-int wg_train_infer_forward_flags(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* z_init,
-                                 const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
-                                 int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
-                                 void* stream) {
+                           int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
+                           void* stream) {
   if (!wt || !mel || !z_init || !audio || !workspace || (n_z_early > 0 && !z_early))
     return fail(WG_ERR_INVALID, "null argument");
   Ctx x;
@@ -1059,11 +986,8 @@ int wg_train_infer_forward_flags(wg_handle* h, const wg_train_weights* wt, const
     if (!z_early[i]) return fail(WG_ERR_INVALID, "null early-noise tensor");
   const wg_config& c = *x.c;
   hipStream_t s = (hipStream_t)stream;
-  hipStream_t sB = s;
-  if (x.halves == 2 && !x.serial) {
-    sB = wg_internal_aux_stream(h, 0);
-    if (!sB) return fail(WG_ERR_HIP, "cannot create the second chain's stream");
-  }
+  hipStream_t sB;
+  if ((rc = second_chain_stream(h, x, s, sB))) return rc;
   const int BNw = fwd_block_n(x);
   if (fresh) TR_TRY(hipMemsetAsync(workspace, 0, x.w.zero_bytes, s));
   if ((rc = spect_planes(x, wt, mel, s))) return rc;
@@ -1113,24 +1037,10 @@ int wg_train_infer_forward_flags(wg_handle* h, const wg_train_weights* wt, const
   return WG_OK;
 }
 
-int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const float* g_audio, float scale, float sigma,
-                            float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
-                            int32_t n_frames, void* workspace, size_t workspace_bytes, void* stream) {
-  return wg_train_infer_backward_flags(h, wt, g_audio, scale, sigma, g_mel, g_z_init, g_z_early, n_z_early, B, n_frames,
-                                       workspace, workspace_bytes, 0, stream);
-}
-
-int wg_train_infer_backward_flags(wg_handle* h, const wg_train_weights* wt, const float* g_audio, float scale, float sigma,
-                                  float* g_mel, float* g_z_init, float* const* g_z_early, int32_t n_z_early, int32_t B,
-                                  int32_t n_frames, void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
-  return wg_train_infer_backward_params(h, wt, nullptr, g_audio, scale, sigma, g_mel, g_z_init, g_z_early, n_z_early, B,
-                                        n_frames, workspace, workspace_bytes, flags, stream);
-}
-
-int wg_train_infer_backward_params(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_audio,
-                                   float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
-                                   int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace, size_t workspace_bytes,
-                                   int32_t flags, void* stream) {
+int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_audio,
+                            float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
+                            int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace, size_t workspace_bytes,
+                            int32_t flags, void* stream) {
   if (!wt || !g_audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
   if (!(scale > 0.f)) return fail(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
@@ -1402,7 +1312,6 @@ int wg_train_prepare(wg_handle* h, const void* const* params, int32_t weight_nor
   PackArgs a;
   memset(&a, 0, sizeof a);
   a.C = C; a.M8 = M8; a.FL = FL; a.NW = NW;
-  a.native = 1;
   a.prep = pa;
   a.wes = pa.wes;
   auto run = [&](int kind, const void* dst, const void* dst2, size_t elements) -> hipError_t {

@@ -223,9 +223,8 @@ __host__ __device__ inline int wupt_blocks(int M8) { return (M8 / 8 + 31) / 32; 
 struct PackArgs {
   int kind;
   int C, M8, FL, NW;
-  const float *w1, *w2, *wes, *wup;   // natural-order sources (include/waveglow_amd.h: wg_train_plain)
-  int native;                         // 1: w1 / w2 / wup are read from the module's own tensors instead (prep.tab, weight-norm
-  PrepArgs prep;                      //    scales applied on the fly): wg_train_prepare; wes is prep.wes either way
+  const float* wes;                   // [FL][8][C] W_end . W_skip_i in natural order (prep.wes)
+  PrepArgs prep;                      // the module's own tensors (prep.tab) and the weight-norm row scales applied on the fly
   _Float16 *dst, *dst2;               // PACK_A1: a1 (tap K-steps) and a1c (conditioning K-steps)
   size_t n_pieces;                    // 16-byte output pieces
 };

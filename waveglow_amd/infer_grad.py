@@ -13,9 +13,8 @@ synthesises): the backward then also runs the training direction's weight-gradie
   order, with the training kernels' saved activations and the state that enters every inverse step; the inverse 1x1
   matrices are the fp64-computed ones ``infer`` uses (the engine is finalised with the current weights);
 * ``wg_train_infer_backward``: ascending flow order, two row kernels per flow around the training direction's WN
-  data-gradient chain, then the d spect GEMM and the transposed upsample for ``d mel``;
-* ``wg_train_infer_backward_params``: the same plus the packed weight gradients (``GradBuffers``), among them
-  ``d W_k = - sum (W_k^-T d w) (x) w`` of every inverse 1x1 step.
+  data-gradient chain, then the d spect GEMM and the transposed upsample for ``d mel``; with ``grads`` also the packed
+  weight gradients (``GradBuffers``), among them ``d W_k = - sum (W_k^-T d w) (x) w`` of every inverse 1x1 step.
 
 The binding uses ``_TrainFn``'s plumbing (waveglow_amd/train.py): ``_Weights`` from ``wg_train_prepare``, one training
 workspace per outstanding graph (``request_workspace``), the fp16 loss scale and ``model.grad_finite``
@@ -61,9 +60,9 @@ class _InferFn(torch.autograd.Function):
     ws = slot["ws"]
     audio = torch.empty((B, S), dtype=torch.float32, device=mel.device)
     ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
-    _lib.check(lib.wg_train_infer_forward_flags(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
-                                                float(sigma), _ptr(audio), B, T, 1 if fresh else 0, _ptr(ws), ws.numel(),
-                                                flags, C.c_void_p(stream)))
+    _lib.check(lib.wg_train_infer_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
+                                          float(sigma), _ptr(audio), B, T, 1 if fresh else 0, _ptr(ws), ws.numel(), flags,
+                                          C.c_void_p(stream)))
     ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.guard = model, wts, ws, (B, M, T), _SlotGuard(slot)
     ctx.flags, ctx.wgrads = flags, wgrads
     ctx.sigma, ctx.n_early, ctx.n_params = float(sigma), n_early, len(params)
@@ -108,17 +107,11 @@ class _InferFn(torch.autograd.Function):
     gstruct, _keep = bufs.struct() if want_params else (None, None)
     views = None
     try:
-      if ctx.wgrads:
-        _lib.check(lib.wg_train_infer_backward_params(eng.handle, C.byref(ctx.wts.struct),
-                                                      C.byref(gstruct) if want_params else None, _ptr(ga),
-                                                      C.c_float(ctx.scale), C.c_float(ctx.sigma),
-                                                      _ptr(g_mel) if want_mel else None, _ptr(g_zi) if want_zi else None, ze,
-                                                      ne, B, T, _ptr(ctx.ws), ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
-      else:
-        _lib.check(lib.wg_train_infer_backward_flags(eng.handle, C.byref(ctx.wts.struct), _ptr(ga), C.c_float(ctx.scale),
-                                                     C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
-                                                     _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws),
-                                                     ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
+      _lib.check(lib.wg_train_infer_backward(eng.handle, C.byref(ctx.wts.struct),
+                                             C.byref(gstruct) if want_params else None, _ptr(ga), C.c_float(ctx.scale),
+                                             C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
+                                             _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws), ctx.ws.numel(),
+                                             ctx.flags, C.c_void_p(stream)))
       if want_params:      # (no logdet term in this direction)
         views = param_grad_views(eng, ctx.wts, gstruct, ctx.shapes, stream)
     finally:

@@ -464,7 +464,7 @@ class WaveGlow(nn.Module):
   def gradient_workspace_bytes(self, batch_size: int, n_frames: int, audio_len: Optional[int] = None,
                                recompute: Optional[bool] = None) -> int:
     """Bytes of the saved state that one outstanding training-direction forward (or ``infer_differentiable`` call) holds
-    until its ``backward()``: the library's own figure (``wg_train_workspace_bytes_ex``), for sizing batches.
+    until its ``backward()``: the library's own figure (``wg_train_workspace_bytes``), for sizing batches.
     ``audio_len`` None: ``256 * n_frames`` (the geometry of ``infer_differentiable``); it is cropped to a multiple of
     n_group as ``forward`` crops the audio.  ``recompute`` None: ``self.recompute_activations``."""
     dev = next(self.parameters()).device
@@ -475,7 +475,7 @@ class WaveGlow(nn.Module):
     if recompute is None:
       recompute = bool(self.recompute_activations)
     flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
-    n = int(eng.lib.wg_train_workspace_bytes_ex(eng.handle, int(batch_size), int(n_frames), int(audio_len), flags))
+    n = int(eng.lib.wg_train_workspace_bytes(eng.handle, int(batch_size), int(n_frames), int(audio_len), flags))
     if n == 0:
       raise _lib.WgError(eng.lib.wg_last_error().decode())
     return n

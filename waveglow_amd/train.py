@@ -343,7 +343,7 @@ def enable_data_parallel(model, group=None, force: bool = False) -> bool:
 def request_workspace(eng, B: int, n_frames: int, audio_len: int, flags: int) -> Tuple[dict, bool]:
   """(slot, fresh) of ``_Engine.train_workspace`` for one forward of either direction: the saved state of its graph, of the
   library's own size for the geometry and the wg_train ``flags``.  The caller hands the slot to a ``_SlotGuard``."""
-  nbytes = eng.lib.wg_train_workspace_bytes_ex(eng.handle, B, n_frames, audio_len, flags)
+  nbytes = eng.lib.wg_train_workspace_bytes(eng.handle, B, n_frames, audio_len, flags)
   if nbytes == 0:
     raise _lib.WgError(eng.lib.wg_last_error().decode())
   return eng.train_workspace(nbytes, (B, n_frames, audio_len), flags)
@@ -467,7 +467,7 @@ class _TrainFn(torch.autograd.Function):
   canonical order (``canonical_params``); outputs (z, log_s...).  backward() returns what ``ctx.needs_input_grad`` asks for: d mel / d audio (written by the library
   into tensors of their own), and one gradient per parameter, each a view of ONE flat buffer the library fills --
   or, when no parameter needs one (a frozen model used as a loss), no parameter gradient at all: the library then runs
-  the data-gradient chain alone (include/waveglow_amd.h: wg_train_backward_ex)."""
+  the data-gradient chain alone (include/waveglow_amd.h: wg_train_backward)."""
 
   @staticmethod
   def forward(ctx, model, mel, audio, scale, wn, flags, *params):
@@ -486,8 +486,8 @@ class _TrainFn(torch.autograd.Function):
     slot, fresh = request_workspace(eng, B, F_, S, flags)                    # held until this graph's backward has run
     ws = slot["ws"]
     ls = (C.c_void_p * len(log_s))(*[t.data_ptr() for t in log_s])
-    _lib.check(lib.wg_train_forward_flags(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(audio), _ptr(z), ls, B, F_, S,
-                                          1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
+    _lib.check(lib.wg_train_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(audio), _ptr(z), ls, B, F_, S,
+                                    1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
     ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.audio, ctx.guard = model, wts, ws, (B, F_, S), audio, _SlotGuard(slot)
     ctx.flags = flags
     ctx.scale = float(scale) if scale else float(2.0 ** round(math.log2(z.numel())))
@@ -523,18 +523,18 @@ class _TrainFn(torch.autograd.Function):
     # input gradients stay local (as under torch DDP); only parameter gradients are averaged over the ranks
     group = _ddp_group(model) if want_params else None
     if group is None:
-      _lib.check(lib.wg_train_backward_ex_flags(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
-                                                _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(),
-                                                nf - 1, 0, ctx.flags, C.c_void_p(stream)))
+      _lib.check(lib.wg_train_backward(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
+                                       _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(), nf - 1, 0,
+                                       ctx.flags, C.c_void_p(stream)))
     else:
       # Data parallel: the backward pass is cut at flow boundaries and every flow's gradients -- ONE contiguous region
       # of the flat buffer -- are all-reduced right behind it (flow_backward_schedule).  What follows (weight-norm
       # backward, the fold's chain rule: wg_train_param_grads) is linear in these gradients, so averaging here equals
       # averaging the parameter gradients (the logdet term of the 1x1 weights is identical on every rank).
       def run_flow(k):
-        _lib.check(lib.wg_train_backward_ex_flags(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr,
-                                                  C.c_float(ctx.scale), _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S,
-                                                  _ptr(ctx.ws), ctx.ws.numel(), k, k, ctx.flags, C.c_void_p(stream)))
+        _lib.check(lib.wg_train_backward(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
+                                         _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(), k, k,
+                                         ctx.flags, C.c_void_p(stream)))
       flow_backward_schedule(nf, run_flow, bufs, group)
     ctx.guard.release()
     try:
