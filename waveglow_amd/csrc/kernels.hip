@@ -95,7 +95,8 @@ __device__ __forceinline__ void gload16(half8& dst, const void* sbase, unsigned 
 // (The next tile's A fragments are NOT prefetched under the epilogue: between such an inline-asm load and its
 // wait lies a long stretch of compiler-scheduled code, and hipcc moved the still-in-flight destination registers
 // there -- wrong results.  They are loaded at the tile top: ~1 L2 latency exposed per tile.)
-constexpr int kTilesPerWG = 2;        // tiles per workgroup (template TPW), fully unrolled; 1 for small workloads
+constexpr int kTilesPerWG = 2;        // tiles per workgroup (template TPW), fully unrolled; 1 for small workloads;
+                                      // the unrolled group of the resident tile walk (template RESIDENT)
 // Tried and measured slower on MI355X, kept out of the source: staging B tiles global -> VGPR -> ds_write instead
 // of LDS-DMA (K loop 59.3k vs 57.6k cycles per tile); offsetting the VMEM slots of the two waves of a SIMD
 // (two copies of the loop made hipcc spill).
@@ -162,7 +163,8 @@ template <int N> __device__ __forceinline__ void wait_vm() {
 // removed).  Two rings Q[parity of the step][quarter]; the quarter consumed in sub-step g of step ks is reloaded with the
 // fragment of step ks + 2.  Every fragment a step needs was issued more than a step earlier, so the step's only wait is
 // the counted one in front of its barrier.  The steps are written out for nK = NKX + 5 (80 mel channels).
-template <int C, int NW, int BN, bool HAS_RES, int TPW, int CX, int MODE = 0, int NTAPS = 3, bool HAS_COND = true, bool DEEP = false, bool M16 = false>
+template <int C, int NW, int BN, bool HAS_RES, int TPW, int CX, int MODE = 0, int NTAPS = 3, bool HAS_COND = true, bool DEEP = false, bool M16 = false,
+          bool RESIDENT = false>
 __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) {
   constexpr bool TR = MODE == 1;         // training forward
   constexpr bool PLAIN = MODE >= 2;      // backward dgrad GEMMs
@@ -196,6 +198,7 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
   // against in_layers[0] o start packed as [tap][8] along K (api.cpp wA1fx).  8 -> 6 K-steps for that launch.
   constexpr bool A0G = MODE == 0 && CX == 1 && NTAPS == 1;
   static_assert(!DEEP || (MODE == 0 && DEFER && HAS_COND && MT <= NT && NG <= NT && ((NKX >= 4 && NKX % 2 == 0) || NKX == 1)), "deep prefetch variant");
+  static_assert(!RESIDENT || (MODE == 0 && TPW == kTilesPerWG && !DEEP), "resident tile walk");
   static_assert(MODE == 0 || (TPW == 1 && CX == ((MODE == 2 || MODE == 4) ? 2 : 1) * (C / 64)) || (MODE == 3 && CX == 1), "training variants");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -332,7 +335,10 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
   // take tiles start+idx, start+idx+step, ... so tiles that run at the same time are neighbours.
   // A workgroup processes kTilesPerWG tiles in a FULLY UNROLLED loop: the next tile's first B tile (LDS-DMA) is
   // issued under the current tile's gate / GEMM2 / epilogue, and the workgroup launch cost is paid once per
-  // kTilesPerWG tiles.  (A real persistent loop makes hipcc spill 100+ VGPRs around the back edge.)
+  // kTilesPerWG tiles.  RESIDENT wraps that unrolled group in a NOT unrolled loop over the workgroup's whole share of the
+  // run (below): no spill in any instantiation of the inference kernel.  (A persistent loop whose body is ONE tile, with
+  // the prefetch state carried in registers, makes hipcc spill 100+ VGPRs around the back edge; and the outer loop applied
+  // to a training variant -- <512, 8, 64, true, 1, 8, 1> -- spills 4: hence a template flag, inference only.)
   int tile, tile_end;
   const int tile_step = gridDim.x >> 3;        // grid is a multiple of 8
   int run_start, run_quarter = 0;              // this XCD's run of tiles; a quarter of it (0: run not divisible by 4)
@@ -376,10 +382,15 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
   }
   __syncthreads();
 
+  // RESIDENT: the unrolled group of TPW tiles is itself the body of a NOT unrolled loop, so the workgroup walks its whole
+  // share of the XCD's run (see launch_wn_tttt) and the seam prefetch also crosses the back edge: it is an LDS-DMA, and the
+  // tile top waits vmcnt(0) in front of its barrier, so no register is in flight across the back edge.
+#pragma clang loop unroll(disable)
+  do {
 #pragma unroll
   for (int it = 0; it < TPW; ++it, tile += tile_step) {
     if (tile >= tile_end) break;
-    if (it > 0) set_lane_ids();
+    if (RESIDENT || it > 0) set_lane_ids();
     const int tile_m = tile_of(tile);
     const int p = tile_m / a.tiles_per_phase;         // phase of every column of this tile
     const int jt = tile_m - p * a.tiles_per_phase;
@@ -1291,10 +1302,12 @@ __global__ void __launch_bounds__(NW * 64) wn_layer_kernel(const WnLayerArgs a) 
     }   // !PLAIN
     __builtin_amdgcn_sched_barrier(0);   // keep the next tile's prologue (128 accumulator inits) out of this epilogue
   }
+  } while (RESIDENT && tile < tile_end);
 }
 
-template <int C, int BN, bool HAS_RES, int TPW, int CX, int MODE = 0, int NTAPS = 3, bool HAS_COND = true, bool DEEP = false>
-static hipError_t launch_wn_tttt(const WnLayerArgs& a, hipStream_t s) {
+// RESIDENT (resident_wgs > 0 workgroups per XCD label): see launch_wn_tt
+template <int C, int BN, bool HAS_RES, int TPW, int CX, int MODE = 0, int NTAPS = 3, bool HAS_COND = true, bool DEEP = false, bool RESIDENT = false>
+static hipError_t launch_wn_tttt(const WnLayerArgs& a, hipStream_t s, int resident_wgs = 0) {
   constexpr int NW = WnCfg<C>::NW;
   constexpr bool M16 = wn_frag16(C, BN) && MODE == 0 && !DEEP;   // the host packs GEMM-1 weights for it (api.cpp)
   if (M16 != (a.frag16 != 0)) return hipErrorInvalidValue;
@@ -1306,19 +1319,21 @@ static hipError_t launch_wn_tttt(const WnLayerArgs& a, hipStream_t s) {
   if (hipGetDevice(&cur_dev) != hipSuccess || cur_dev < 0 || cur_dev >= 64) cur_dev = 0;
   bool& attr_done = attr_done_dev[cur_dev];
   if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)wn_layer_kernel<C, NW, BN, HAS_RES, TPW, CX, MODE, NTAPS, HAS_COND, DEEP, M16>,
+    hipError_t e = hipFuncSetAttribute((const void*)wn_layer_kernel<C, NW, BN, HAS_RES, TPW, CX, MODE, NTAPS, HAS_COND, DEEP, M16, RESIDENT>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return e;
     attr_done = true;
   }
   // TPW tiles per workgroup: per XCD label ceil(tiles_on_label / TPW) blocks
-  const int per_label = ((a.n_tiles + 7) / 8 + TPW - 1) / TPW;
+  // (resident walk: resident_wgs blocks per label, each walking tiles start + idx, + resident_wgs, ... to the end of the run)
+  if (RESIDENT != (resident_wgs > 0)) return hipErrorInvalidValue;
+  const int per_label = RESIDENT ? resident_wgs : ((a.n_tiles + 7) / 8 + TPW - 1) / TPW;
   const int grid = 8 * per_label;
-  hipLaunchKernelGGL((wn_layer_kernel<C, NW, BN, HAS_RES, TPW, CX, MODE, NTAPS, HAS_COND, DEEP, M16>), dim3(grid), dim3(NW * 64), smem, s, a);
+  hipLaunchKernelGGL((wn_layer_kernel<C, NW, BN, HAS_RES, TPW, CX, MODE, NTAPS, HAS_COND, DEEP, M16, RESIDENT>), dim3(grid), dim3(NW * 64), smem, s, a);
   return hipGetLastError();
 }
-template <int C, int BN, bool HAS_RES, int TPW>
-static hipError_t launch_wn_ttt(const WnLayerArgs& a, hipStream_t s) {
+template <int C, int BN, bool HAS_RES, int TPW, bool RESIDENT = false>
+static hipError_t launch_wn_ttt(const WnLayerArgs& a, hipStream_t s, int resident_wgs = 0) {
   // small workloads (one tile per workgroup, 64 columns) at 256 channels / 80 mel channels: two-step-deep weight prefetch.
   // WG_DISABLE_DEEP=1 (read per launch, tests only) takes the one-step ring instead: the two must agree bit for bit.
   if constexpr (C == 256 && BN == 64 && TPW == 1) {
@@ -1329,14 +1344,43 @@ static hipError_t launch_wn_ttt(const WnLayerArgs& a, hipStream_t s) {
     }
   }
   // first layer with the start fold: the three taps of the a0 plane in one gathered K-step (A0G; wA1 is packed for it)
-  if (a.a0_fold) return a.x_chunks_per_tap == 1 ? launch_wn_tttt<C, BN, HAS_RES, TPW, 1, 0, 1>(a, s) : hipErrorInvalidValue;
-  return launch_wn_tttt<C, BN, HAS_RES, TPW, C / 64>(a, s);
+  if (a.a0_fold)
+    return a.x_chunks_per_tap == 1 ? launch_wn_tttt<C, BN, HAS_RES, TPW, 1, 0, 1, true, false, RESIDENT>(a, s, resident_wgs) : hipErrorInvalidValue;
+  return launch_wn_tttt<C, BN, HAS_RES, TPW, C / 64, 0, 3, true, false, RESIDENT>(a, s, resident_wgs);
 }
 template <int C, int BN, bool HAS_RES>
 static hipError_t launch_wn_tt(const WnLayerArgs& a, hipStream_t s) {
-  // two tiles per workgroup amortise the launch and prefetch across the tile seam, but need >= 2 tiles per CU -- and must not
-  // cost a round: 1120 tiles on 256 CUs are 5 rounds of single tiles but 3 rounds of pairs = 6 tile times (batch 5 x 80x864)
   const int ncu = a.n_cu > 0 ? a.n_cu : 1;
+  // Resident tile walk where a CU has at least two tiles to walk: at most one workgroup per CU, each walking its share of its
+  // XCD label's run tile by tile, so the workgroup start (dispatch, bias / end x skip staging, a cold first B tile) is paid
+  // once per CU and launch instead of once per pair, and every tile seam has the B-tile prefetch.  The workgroups do not
+  // communicate: nothing depends on their being co-resident or on the block -> XCD mapping (speed only, as above).
+  // WG_RESIDENT (read per launch, tests only): 0 = the launches below; N > 0 = the resident launch with 8 ceil(N / 8)
+  // workgroups whatever the size.  The two must agree bit for bit.
+  {
+    const char* e = getenv("WG_RESIDENT");
+    const int forced = e && *e ? atoi(e) : -1;
+    const int per_label_tiles = (a.n_tiles + 7) / 8;
+    int wgs = 0;
+    if (forced > 0) wgs = (forced + 7) / 8;
+    // Not with a sparse tail: the walk is static, so n_tiles mod CUs workgroups run the last tile-round alone after every CU
+    // has run all the full ones, where the dispatcher spreads today's pairs over that tail.  Measured at 6 x 80x864 (1312
+    // tiles on 256 CUs = 5.125 rounds): +2.4 %, outside both spreads; the next sparsest tail measured, 0.375 of a round,
+    // gains.  The quarter lies between the two.  (Too wide at many rounds: at 13 x 80x864, 11.125 rounds, the walk would
+    // gain 1.3 % -- DESIGN.md section 8.)
+    // By default only where the walk was measured against today's launches: 256 channels on 128-column tiles.  Every other
+    // width keeps today's launch -- in particular 64-column tiles at 256 channels, which api.cpp run_wn picks for 514 .. 768
+    // narrow tiles on 256 CUs (2 .. 3 tiles per CU) and which run the two-step-deep prefetch kernel (DEEP, single tiles):
+    // the walk has no DEEP form and would trade that kernel's ~10 % of a launch for its own 1 - 1.5 %.
+    else if (forced < 0 && C == 256 && BN == 128 && a.n_tiles >= 2 * ncu && !(a.n_tiles % ncu > 0 && 4 * (a.n_tiles % ncu) < ncu)) {
+      const int by_tiles = (per_label_tiles + kTilesPerWG - 1) / kTilesPerWG, by_cus = (ncu + 7) / 8;
+      wgs = by_tiles < by_cus ? by_tiles : by_cus;
+    }
+    if (wgs > 0) return launch_wn_ttt<C, BN, HAS_RES, kTilesPerWG, true>(a, s, wgs);
+  }
+  // Below two tiles per CU (and under WG_RESIDENT=0): workgroups that end after one or two tiles.  Two tiles per workgroup
+  // amortise the launch and prefetch across the tile seam, but need >= 2 tiles per CU -- and must not cost a round: 1120 tiles
+  // on 256 CUs are 5 rounds of single tiles but 3 rounds of pairs = 6 tile times (batch 5 x 80x864)
   const int rounds1 = (a.n_tiles + ncu - 1) / ncu;
   const int rounds2 = ((a.n_tiles + kTilesPerWG - 1) / kTilesPerWG + ncu - 1) / ncu * kTilesPerWG;
   if (a.n_tiles >= 2 * kTilesPerWG * ncu && rounds2 <= rounds1) return launch_wn_ttt<C, BN, HAS_RES, kTilesPerWG>(a, s);
