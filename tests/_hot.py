@@ -111,7 +111,8 @@ class Prec:
   which fault is planted, and an optional trace of the pre-activations and ``log_s``.
   Faults: "winv_t" (W^T for W^-1 in synthesis), "logdet_grad" (W for W^-T in the logdet gradient), "no_logdet" (the logdet
   term dropped from the loss), "clamp4" (the tanh argument clamped to +-4: a clamp on a instead of on the exponent),
-  "clamp_b4" (the same clamp on the sigmoid's argument)."""
+  "clamp_b4" (the same clamp on the sigmoid's argument), ("leak", k, i) (a batch leak: in layer i of flow k the right-hand
+  padding of utterance b holds the first ``d`` columns of utterance b + 1; the last utterance keeps its zeros)."""
 
   def __init__(self, r16=False, gscale=None, fault=None, trace=None, dither=None):
     self.r16, self.gscale, self.fault, self.trace, self.dither = r16, gscale, fault, trace, dither
@@ -154,6 +155,14 @@ def compose(leaves):
   return dense
 
 
+def _leaky_pad(x, d):
+  """[B, C, L] -> [B, C, L + 2 d]: zeros on the left; on the right the first ``d`` columns of the NEXT utterance (what a
+  tap that runs over missing guard rows would read), zeros behind them and behind the last utterance."""
+  n = min(d, x.size(2))
+  nxt = torch.cat([x[1:, :, :n], x.new_zeros(1, x.size(1), n)], 0)
+  return torch.cat([x.new_zeros(x.size(0), x.size(1), d), x, nxt, x.new_zeros(x.size(0), x.size(1), d - n)], 2)
+
+
 def _wn(w, k, a0, spect, cfg, P):
   """WN.forward (model.py:115-138) -> [b ; log_s]."""
   C, p = cfg.n_channels, f"WN.{k}."
@@ -162,7 +171,10 @@ def _wn(w, k, a0, spect, cfg, P):
   output = 0
   for i in range(cfg.n_layers):
     d = 2 ** i
-    a = F.conv1d(x, P.weight(w[p + f"in_layers.{i}.weight"]), w[p + f"in_layers.{i}.bias"], dilation=d, padding=d)
+    if P.fault == ("leak", k, i):
+      a = F.conv1d(_leaky_pad(x, d), P.weight(w[p + f"in_layers.{i}.weight"]), w[p + f"in_layers.{i}.bias"], dilation=d)
+    else:
+      a = F.conv1d(x, P.weight(w[p + f"in_layers.{i}.weight"]), w[p + f"in_layers.{i}.bias"], dilation=d, padding=d)
     a = P.gplane(a + cond[:, 2 * C * i:2 * C * (i + 1)])
     if P.trace is not None:
       P.trace.setdefault("a", []).append(a[:, :C].detach())
