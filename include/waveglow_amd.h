@@ -322,6 +322,48 @@ int wg_pitch_metrics(const float* audio_a, const int32_t* lens_a, int32_t n_a, c
                      int32_t n_b, const wg_pitch_params* params, double* rows_out, int32_t B, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- Intelligibility metrics of audio pairs: STOI and ESTOI of 10 kHz audio, no handle --------------------------------
+ * The reference has no counterpart.  Short-time objective intelligibility (Taal, Hendriks, Heusdens and Jensen, IEEE TASL
+ * 19(7), 2011) and its extended form (Jensen and Taal, IEEE/ACM TASLP 24(11), 2016) as pystoi.stoi(x, y, 10000, extended)
+ * computes them, restated; parity with pystoi itself is unpinned.  x is the clean signal, y the
+ * processed one; the metric is not symmetric.
+ * Constants: fs = 10000, frame W = 256, hop H = 128, NFFT = 512, 15 one-third-octave bands from 150 Hz, segments of N = 30
+ *   frames, BETA = -15 dB, dynamic range 40 dB, EPS = 2^-52, window w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257), i = 0 .. 255.
+ * 1. n = min(len_x, len_y), both cropped to n; all arithmetic from here is fp64 on the fp32 samples.
+ * 2. Frame starts range(0, n - W, H): F0 = ceil((n - 256) / 128) frames for n > 256, else 0 (exclusive end: 256 + 128 k
+ *    samples have k frames).
+ * 3. e[t] = 20 log10(||w x_t||_2 + EPS) on the clean signal; frame t is kept where max(e) - 40 - e[t] < 0.  The K kept
+ *    frames of x and the same frames of y, windowed, are overlap-added at hop 128 into x_s, y_s of (K - 1) 128 + 256
+ *    samples.
+ * 4. x_s, y_s are framed again the same way (F = K - 1 frames for K >= 2, else 0), windowed with w again, zero-padded to
+ *    512; band b sums the power at bins lo[b] .. hi[b] - 1, X[b, t] = sqrt(band sum), Y alike.  With f = k fs / 512,
+ *    lo[b] = argmin_k (f - 150 2^((2b-1)/6))^2, hi[b] = argmin_k (f - 150 2^((2b+1)/6))^2: bins 7 .. 218 at 10 kHz.
+ * 5. J = F - 29 segments m = 30 .. F over X[:, m-30:m], Y[:, m-30:m].
+ *    STOI: per band row alpha = ||x|| / (||y|| + EPS), y' = min(alpha y, x (1 + 10^(15/20))); both rows mean-removed and
+ *      divided by (their norm + EPS); d = sum x y' / (15 J) over all bands and segments.
+ *    ESTOI: both blocks row-normalised (mean removed, divided by norm + EPS), then column-normalised the same way;
+ *      d = sum over the segments of (sum x y / 30) / J.
+ * 6. F < 30 (no segment) gives NaN for both values, the counts still reported.  Silence gives exactly 0.0 twice.
+ * x, y: [B][pitch] fp32 device, 10 kHz.  len_x, len_y: int32 device [B], read by the kernels only; a length outside
+ *   [0, pitch] counts as 0.  Nothing at or behind a row's common length n is read (it may hold NaN).
+ * params: device pointers to the caller's tables: window fp64 [256]; bands int32 [15][2] = (lo, hi) (the kernels compute
+ *   bins 7 .. 218 only and clamp the table to them); cossin fp64 [512][2] = (cos, sin)(2 pi k / 512), aligned to 16 bytes.
+ *   The kernels call no device cos or sin.
+ * rows_out: fp64 [B][8] = {STOI, ESTOI, F0, K, J, 0, 0, 0}.
+ * Arithmetic: every sum is fp64 in a fixed order that depends on the utterance alone, without atomics; products may be
+ *   fused into the sums.  A call gives the same bits every time and every utterance of a batch the bits of its own call
+ *   with B = 1, whatever the pitch.
+ * Limits: 1 <= B <= 65535, 1 <= pitch <= 2^21; anything else is WG_ERR_INVALID before any launch.  Workspace:
+ *   wg_stoi_workspace_bytes(B, pitch) (0 for a refused geometry).  Five launches on `stream`.  Enqueue-only. */
+typedef struct wg_stoi_params {
+  const double* window;
+  const int32_t* bands;
+  const double* cossin;
+} wg_stoi_params;
+size_t wg_stoi_workspace_bytes(int32_t B, int32_t n_max);
+int wg_stoi(const float* x, const int32_t* len_x, const float* y, const int32_t* len_y, int32_t B, int32_t pitch,
+            const wg_stoi_params* params, double* rows_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Resampling by a rational ratio: wav data of any sampling rate in, any rate out, no handle ------------------------
  * The reference has no counterpart.  The definition is scipy.signal.resample_poly(x, up, down) with its defaults
  * (window ('kaiser', 5.0), padtype 'constant') in closed form.  With up / down reduced, M = max(up, down), half = 10 M and

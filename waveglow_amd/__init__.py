@@ -21,7 +21,8 @@ def __getattr__(name):
   if name == "MultiResolutionSTFTLoss":
     from .stft_loss import MultiResolutionSTFTLoss
     return MultiResolutionSTFTLoss
-  if name in ("mel_metrics", "MelMetrics", "pitch_metrics", "PitchMetrics", "yin_f0"):
+  if name in ("mel_metrics", "MelMetrics", "pitch_metrics", "PitchMetrics", "yin_f0", "intelligibility_metrics",
+              "IntelligibilityMetrics", "stoi"):
     from . import metrics
     return getattr(metrics, name)
   if name in ("resample_enqueue", "resample_plan", "out_len"):

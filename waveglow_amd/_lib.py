@@ -46,6 +46,11 @@ class WgPitchParams(C.Structure):
     "frame_length", "hop_length", "tau_min", "tau_max")]
 
 
+class WgStoiParams(C.Structure):
+  """wg_stoi_params (include/waveglow_amd.h): device pointers to the window, the band table and the cos/sin table."""
+  _fields_ = [(n, C.c_void_p) for n in ("window", "bands", "cossin")]
+
+
 class WgError(RuntimeError):
   pass
 
@@ -142,6 +147,9 @@ SIGNATURES = {
                                  C.c_int32, C.c_void_p]),
   "wg_pitch_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                  C.POINTER(WgPitchParams), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stoi_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+  "wg_stoi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(WgStoiParams),
+                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_resample_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
   "wg_resample": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -14,11 +14,13 @@ commented-out ``--batch-size``, inference_v2.py:64) and per-rank sharding of the
          --device-dataset: all wavs stay on the device and every batch is built there (waveglow_amd/device_data.py)
   python -m waveglow_amd.cli validate CHECKPOINTS-FOLDER OUTPUT-FOLDER DATA-FOLDER [--sigma S] [--denoiser-strength D]
          [--device cuda:0] [--custom-hparams ...] [--full-run] [--files NAME ...] [--custom-checkpoints IT ...]
-         [--custom-seed N] [--batch-size B] [--pitch-metrics]        (src/waveglow_cli/validation.py:86-153)
+         [--custom-seed N] [--batch-size B] [--pitch-metrics] [--intelligibility-metrics]
+         (src/waveglow_cli/validation.py:86-153)
          copy synthesis of validation utterances and their metrics on the device (MCD, DTW-MCD, penalties, cosine
          similarity): OUTPUT-FOLDER/log.txt, total.csv and one folder of mels and wavs per utterance and checkpoint;
          no PNG plots and no structural similarity, single process only.  --pitch-metrics adds the F0 RMSE, the gross
-         pitch error and the voicing decision error between the original and the synthesis (a YIN tracker on the device)
+         pitch error and the voicing decision error between the original and the synthesis (a YIN tracker on the device);
+         --intelligibility-metrics adds STOI and ESTOI of the two, resampled to 10 kHz on the device
 Under ``python -m torch.distributed.run`` the training commands run data-parallel (one process per GPU, RCCL).
 """
 from __future__ import annotations
@@ -103,6 +105,9 @@ def build_parser() -> argparse.ArgumentParser:
   v.add_argument("--pitch-metrics", action="store_true",
                  help="also track F0 of the original and the synthesis (YIN) and report F0 RMSE, gross pitch error and "
                       "voicing decision error in seven more columns")
+  v.add_argument("--intelligibility-metrics", action="store_true",
+                 help="also compute the short-time objective intelligibility of the synthesis against the original at "
+                      "10 kHz (STOI and ESTOI) in four more columns")
   v.add_argument("--resample-inputs", action="store_true",
                  help="resample wav files at other sampling rates to the model's on the device instead of refusing them; "
                       "original.wav is still written as loaded")
@@ -244,7 +249,8 @@ def validate_cmd(ns) -> bool:
                                save_callback=partial(_save_validation, val_dir=ns.output_dir, iteration=iteration),
                                sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=ns.custom_seed,
                                device=torch.device(ns.device), batch_size=ns.batch_size,
-                               pitch_metrics=ns.pitch_metrics, resample_inputs=ns.resample_inputs))
+                               pitch_metrics=ns.pitch_metrics, resample_inputs=ns.resample_inputs,
+                               intelligibility_metrics=ns.intelligibility_metrics))
       except AssertionError as e:
         logger.error(str(e) or "validation failed an assertion")
         return False

@@ -12,6 +12,11 @@ Of audio pairs (``wg_pitch_*``, the second half of this file): a YIN F0 tracker 
 over fp32 audio ``[B, N]`` with per-utterance sample counts, and the F0 RMSE, gross pitch error and voicing decision error of
 two tracks.  The reference has no counterpart; parity with any external tracker (librosa's ``yin`` / ``pyin`` and others,
 all absent) is unpinned, the numpy restatement tests/_pitch_oracle.py is the yardstick.
+
+Of audio pairs at 10 kHz (``wg_stoi``, the last part of this file): short-time objective intelligibility (STOI, Taal et al.
+2011) and its extended form (ESTOI, Jensen and Taal 2016) of a clean and a processed signal, with the project's resampler in
+front for other rates.  The reference has no counterpart; parity with ``pystoi`` (absent) is unpinned, the numpy restatement
+tests/_stoi_oracle.py is the yardstick.
 """
 from __future__ import annotations
 
@@ -31,6 +36,13 @@ MCD, PENALTY, FRAMES, MCD_DTW, PENALTY_DTW, FRAMES_DTW, COSINE = range(7)
 PITCH_MIN_FRAME, PITCH_MAX_FRAME = 16, 2048      # frame_length (include/waveglow_amd.h: wg_pitch_*)
 PITCH_MAX_TAU = 1024                             # largest lag
 F0_RMSE_CENTS, F0_RMSE_HZ, GPE, VUV_ERROR, PITCH_FRAMES, VOICED_A, VOICED_B, VOICED_BOTH = range(8)
+
+STOI_RATE = 10000                                # Hz (include/waveglow_amd.h: wg_stoi)
+STOI_FRAME, STOI_HOP, STOI_NFFT, STOI_BANDS, STOI_SEGMENT = 256, 128, 512, 15, 30
+STOI_MAX_PITCH = 1 << 21                         # samples per row
+STOI_FRAME_TILE = 8                              # frames per workgroup of the band-spectra kernel (csrc/wg_stoi.h)
+STOI_SEGMENT_TILE = 4                            # segments per workgroup of the segment kernel
+STOI, ESTOI, STOI_FRAMES, STOI_FRAMES_KEPT, STOI_SEGMENTS = range(5)
 
 Frames = Union[None, Sequence[int], torch.Tensor]
 
@@ -56,6 +68,15 @@ class PitchMetrics:
   voiced_a: int
   voiced_b: int
   voiced_both: int
+
+
+@dataclass
+class IntelligibilityMetrics:
+  stoi: float             # NaN without a segment (fewer than 30 frames after the silent ones are removed)
+  estoi: float
+  frames: int             # F0: frames of the common length at 10 kHz
+  frames_kept: int        # K: frames within 40 dB of the loudest frame of the clean signal
+  segments: int           # J = K - 30, or 0
 
 
 def _features(name: str, x, device=None) -> torch.Tensor:
@@ -317,3 +338,131 @@ def pitch_metrics(audio_a: torch.Tensor, lengths_a: Frames, audio_b: torch.Tenso
   host.copy_(rows, non_blocking=True)
   torch.cuda.current_stream(rows.device).synchronize()
   return rows_to_pitch_metrics(host)
+
+
+# -------------------------------------------------------------------------------------------- intelligibility metrics
+_stoi_tables = {}        # device index -> (blob on that device, WgStoiParams pointing into it)
+
+
+def stoi_window():
+  """fp64 [256]: w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257), numpy's hanning(258) without its zero ends."""
+  import numpy as np
+  return np.hanning(STOI_FRAME + 2)[1:-1].copy()
+
+
+def stoi_band_table():
+  """int32 [15, 2]: (lo, hi) of the one-third-octave bands at 10 kHz; band b sums the bins lo .. hi - 1."""
+  import numpy as np
+  f = np.linspace(0, STOI_RATE, STOI_NFFT + 1)[:STOI_NFFT // 2 + 1]
+  k = np.arange(STOI_BANDS, dtype=np.float64)
+  edges = [150.0 * 2.0 ** ((2 * k - 1) / 6), 150.0 * 2.0 ** ((2 * k + 1) / 6)]
+  return np.array([[int(np.argmin((f - v) ** 2)) for v in e] for e in edges], dtype=np.int32).T.copy()
+
+
+def stoi_frames(n_samples: int) -> int:
+  """F0(n_samples): the frame starts are range(0, n - 256, 128)."""
+  return len(range(0, int(n_samples) - STOI_FRAME, STOI_HOP))
+
+
+def _stoi_params(device: torch.device) -> _lib.WgStoiParams:
+  """The tables wg_stoi reads, made on the host in fp64 and uploaded once per device: window | cos/sin | bands."""
+  import numpy as np
+  key = _lib.device_index(device)
+  hit = _stoi_tables.get(key)
+  if hit is None:
+    ang = 2.0 * np.pi * np.arange(STOI_NFFT, dtype=np.float64) / STOI_NFFT
+    cossin = np.stack([np.cos(ang), np.sin(ang)], axis=1)
+    host = np.concatenate([stoi_window().view(np.uint8), np.ascontiguousarray(cossin).view(np.uint8).ravel(),
+                           stoi_band_table().view(np.uint8).ravel()])
+    blob = torch.from_numpy(host).to(device)
+    base = blob.data_ptr()
+    off_cs = STOI_FRAME * 8
+    off_bands = off_cs + STOI_NFFT * 16
+    hit = _stoi_tables[key] = (blob, _lib.WgStoiParams(base, base + off_bands, base + off_cs))
+  return hit[1]
+
+
+def _stoi_audio(name: str, x, device=None) -> torch.Tensor:
+  x = _audio(name, x, device)
+  if x.shape[1] > STOI_MAX_PITCH:
+    raise _lib.WgError(f"{name}: rows of at most {STOI_MAX_PITCH} samples at 10 kHz expected, got {x.shape[1]}")
+  return x
+
+
+def stoi_enqueue(x10k: torch.Tensor, lengths_x: Frames, y10k: torch.Tensor, lengths_y: Frames) -> torch.Tensor:
+  """STOI and ESTOI of the pairs (x10k[b], y10k[b]), x the clean and y the processed signal, fp32 [B, N] on one GPU and
+  already at 10 kHz, cropped to the common length of a pair; one launch sequence without a synchronise: fp64 [B, 8] on the
+  device, columns STOI, ESTOI, STOI_FRAMES, STOI_FRAMES_KEPT, STOI_SEGMENTS and three zeros (wg_stoi).  Both sides share
+  one row pitch: the shorter tensor is padded on the device."""
+  x = _stoi_audio("stoi: x10k", x10k)
+  y = _stoi_audio("stoi: y10k", y10k, x.device)
+  if x.shape[0] != y.shape[0]:
+    raise _lib.WgError(f"stoi: batch sizes differ, {tuple(x.shape)} against {tuple(y.shape)}")
+  lx, ly = _lengths("stoi: lengths_x", lengths_x, x), _lengths("stoi: lengths_y", lengths_y, y)
+  B, N = x.shape[0], max(x.shape[1], y.shape[1])
+  if x.shape[1] < N:
+    x = torch.nn.functional.pad(x, (0, N - x.shape[1]))
+  if y.shape[1] < N:
+    y = torch.nn.functional.pad(y, (0, N - y.shape[1]))
+  lib = _lib.load()
+  with torch.cuda.device(x.device):
+    p = _stoi_params(x.device)
+    rows = torch.empty((B, N_ROW), dtype=torch.float64, device=x.device)
+    ws = torch.empty(lib.wg_stoi_workspace_bytes(B, N), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.wg_stoi(x.data_ptr(), lx.data_ptr(), y.data_ptr(), ly.data_ptr(), B, N, C.byref(p), rows.data_ptr(),
+                           ws.data_ptr(), ws.numel(), _stream(x)))
+  return rows
+
+
+def rows_to_intelligibility_metrics(rows) -> List[IntelligibilityMetrics]:
+  """Host copy of ``stoi_enqueue``'s rows -> one IntelligibilityMetrics per pair."""
+  return [IntelligibilityMetrics(stoi=r[STOI], estoi=r[ESTOI], frames=int(r[STOI_FRAMES]),
+                                 frames_kept=int(r[STOI_FRAMES_KEPT]), segments=int(r[STOI_SEGMENTS])) for r in rows.tolist()]
+
+
+def _read_rows(rows: torch.Tensor):
+  host = torch.empty(rows.shape, dtype=rows.dtype, pin_memory=True)
+  host.copy_(rows, non_blocking=True)
+  torch.cuda.current_stream(rows.device).synchronize()
+  return host
+
+
+def stoi(x10k: torch.Tensor, lengths_x: Frames, y10k: torch.Tensor, lengths_y: Frames) -> List[IntelligibilityMetrics]:
+  """``stoi_enqueue`` + one copy to the host + one stream synchronise."""
+  return rows_to_intelligibility_metrics(_read_rows(stoi_enqueue(x10k, lengths_x, y10k, lengths_y)))
+
+
+def intelligibility_metrics_enqueue(audio_a: torch.Tensor, lengths_a: Frames, audio_b: torch.Tensor, lengths_b: Frames,
+                                    sampling_rate=22050) -> torch.Tensor:
+  """STOI and ESTOI of the pairs (audio_a[b], audio_b[b]), a the original (clean) and b the synthesised audio, fp32 [B, N]
+  on one GPU at ``sampling_rate``: the common length of a pair is taken on the device, both sides are resampled to 10 kHz by
+  ``resample.resample_enqueue`` (scipy's default Kaiser filter, not clipped; skipped at 10 000 Hz) and go to ``wg_stoi``.
+  Nothing is read back: fp64 [B, 8] on the device as ``stoi_enqueue`` returns it.  A rate the resampler refuses raises
+  its WgError before any device work."""
+  from . import resample
+  up, down, _, _ = resample.resample_plan(sampling_rate, STOI_RATE)
+  a = _audio("intelligibility_metrics: audio_a", audio_a)
+  b = _audio("intelligibility_metrics: audio_b", audio_b, a.device)
+  if a.shape[0] != b.shape[0]:
+    raise _lib.WgError(f"intelligibility_metrics: batch sizes differ, {tuple(a.shape)} against {tuple(b.shape)}")
+  la = _lengths("intelligibility_metrics: lengths_a", lengths_a, a)
+  lb = _lengths("intelligibility_metrics: lengths_b", lengths_b, b)
+  longest = resample.out_len(max(a.shape[1], b.shape[1]), up, down)
+  if longest > STOI_MAX_PITCH:
+    raise _lib.WgError(f"intelligibility_metrics: rows of {longest} samples at 10 kHz are beyond {STOI_MAX_PITCH}")
+  with torch.cuda.device(a.device):
+    n = torch.minimum(la, lb)                      # a length outside a row stays outside: 0 frames downstream
+    n = torch.where((la < 0) | (la > a.shape[1]) | (lb < 0) | (lb > b.shape[1]), torch.zeros_like(n), n)
+    if up == down:
+      return stoi_enqueue(a, n, b, n)
+    xa = resample.resample_enqueue(a, n, sampling_rate, STOI_RATE, pitch=longest)
+    xb = resample.resample_enqueue(b, n, sampling_rate, STOI_RATE, pitch=longest)
+    n10 = (n.to(torch.int64) * up + (down - 1)).div(down, rounding_mode="floor").to(torch.int32)
+    return stoi_enqueue(xa, n10, xb, n10)
+
+
+def intelligibility_metrics(audio_a: torch.Tensor, lengths_a: Frames, audio_b: torch.Tensor, lengths_b: Frames,
+                            sampling_rate=22050) -> List[IntelligibilityMetrics]:
+  """``intelligibility_metrics_enqueue`` + one copy to the host + one stream synchronise."""
+  return rows_to_intelligibility_metrics(_read_rows(
+    intelligibility_metrics_enqueue(audio_a, lengths_a, audio_b, lengths_b, sampling_rate)))

@@ -5,7 +5,8 @@ alignment penalties and the cosine similarity between the original mel and the m
 Behind the noise draws a batch of utterances is one launch sequence on the device: the flow and the denoiser
 (``Synthesizer._infer_batch_device``), the int16 finishing (``wg_wav_finish``), the normalisation, the mel of the result
 (``TacotronSTFT.mel_spectrogram_ragged_device``), the metrics (``wg_metrics_mel``) and, with ``pitch_metrics``, the F0 and
-voicing errors between the original wavs, kept on the device, and that audio (``wg_pitch_metrics``).  Not built: the PNG
+voicing errors between the original wavs, kept on the device, and that audio (``wg_pitch_metrics``), and with
+``intelligibility_metrics`` STOI and ESTOI of the same two, both resampled to 10 kHz (``wg_resample``, ``wg_stoi``).  Not built: the PNG
 plots and the structural similarity computed from them (``structural_similarity`` stays None).
 """
 from __future__ import annotations
@@ -58,6 +59,11 @@ class ValidationEntry:
   pitch_frames: int = None
   voiced_frames_orig: int = None
   voiced_frames_inferred: int = None
+  # validate(intelligibility_metrics=True) only (waveglow_amd/metrics.py: IntelligibilityMetrics); None otherwise
+  stoi: float = None
+  estoi: float = None
+  stoi_frames: int = None
+  stoi_frames_kept: int = None
 
 
 class ValidationEntries(List[ValidationEntry]):
@@ -77,11 +83,13 @@ class ValidationEntryOutput:
 
 def get_df(entries: ValidationEntries):
   """The reference's table (validation.py:52-108) without the "Structual Similarity (Padded)" column.  Entries validated
-  with the pitch metrics get seven more columns behind "Cosine Similarity (Padded)"."""
+  with the pitch metrics get seven more columns behind "Cosine Similarity (Padded)", entries validated with the
+  intelligibility metrics four more behind those."""
   from pandas import DataFrame
   if len(entries) == 0:
     return DataFrame()
   with_pitch = any(e.pitch_frames is not None for e in entries)
+  with_stoi = any(e.stoi_frames is not None for e in entries)
   data = [{
     "Name": e.entry.basename,
     "Subpath": e.entry.stem,
@@ -113,6 +121,12 @@ def get_df(entries: ValidationEntries):
       "# Voiced frames original": e.voiced_frames_orig,
       "# Voiced frames inferred": e.voiced_frames_inferred,
     } if with_pitch else {}),
+    **({
+      "STOI": e.stoi,
+      "ESTOI": e.estoi,
+      "# STOI frames": e.stoi_frames,
+      "# STOI frames kept": e.stoi_frames_kept,
+    } if with_stoi else {}),
     "Wav path": str(e.entry.wav_absolute_path),
   } for e in entries]
   return DataFrame(data=[list(x.values()) for x in data], columns=list(data[0].keys()))
@@ -134,12 +148,13 @@ def select_entries(data: List[Entry], entry_names: Set[str], full_run: bool, see
 
 
 def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], sigma, denoiser_strength, seed, iteration,
-                    save_callback, out: ValidationEntries, pitch_metrics: bool = False) -> None:
+                    save_callback, out: ValidationEntries, pitch_metrics: bool = False,
+                    intelligibility_metrics: bool = False) -> None:
   logger = getLogger(__name__)
   dev = synth.device
   timepoint = datetime.datetime.now()
   B = len(chunk)
-  if pitch_metrics:                                                       # the wavs stay on the device: read once
+  if pitch_metrics or intelligibility_metrics:                            # the wavs stay on the device: read once
     mel_orig, frames, wav_orig_dev, n_orig_dev = taco.get_mel_and_wav_tensors_from_files(
       [e.wav_absolute_path for e in chunk])
   else:
@@ -167,8 +182,15 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
     # otherwise), so the original as loaded is compared with the peak-normalised synthesis
     parts.append(metrics.pitch_metrics_enqueue(wav_orig_dev, n_orig_dev, normed, samples_dev,
                                                sampling_rate=synth.hparams.sampling_rate))
+  if intelligibility_metrics:
+    # the clean side is the original as loaded, the processed side the peak-normalised synthesis
+    parts.append(metrics.intelligibility_metrics_enqueue(wav_orig_dev, n_orig_dev, normed, samples_dev,
+                                                         sampling_rate=synth.hparams.sampling_rate))
   rows = torch.cat(parts, dim=1).cpu()
-  pitch = metrics.rows_to_pitch_metrics(rows[:, metrics.N_ROW + 1:]) if pitch_metrics else None
+  first = metrics.N_ROW + 1
+  pitch = metrics.rows_to_pitch_metrics(rows[:, first:first + metrics.N_ROW]) if pitch_metrics else None
+  first += metrics.N_ROW if pitch_metrics else 0
+  intel = metrics.rows_to_intelligibility_metrics(rows[:, first:first + metrics.N_ROW]) if intelligibility_metrics else None
   fin_h = fin.cpu()
   fin_raw_h = fin_raw.cpu() if fin_raw is not fin else fin_h
   mel_orig_h, mel_inf_h = mel_orig.cpu().numpy(), mel_inf.cpu().numpy()
@@ -195,6 +217,9 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
       val.f0_rmse_cents, val.f0_rmse_hz, val.gross_pitch_error, val.vuv_error = \
           pm.f0_rmse_cents, pm.f0_rmse_hz, pm.gross_pitch_error, pm.vuv_error
       val.pitch_frames, val.voiced_frames_orig, val.voiced_frames_inferred = pm.frames, pm.voiced_a, pm.voiced_b
+    if intel:
+      im = intel[b]
+      val.stoi, val.estoi, val.stoi_frames, val.stoi_frames_kept = im.stoi, im.estoi, im.frames, im.frames_kept
     wav_orig, orig_sr = wav_to_float32(entry.wav_absolute_path)
     output = ValidationEntryOutput(mel_orig=mel_orig_h[b, :, :frames[b]].copy(), orig_sr=orig_sr, wav_orig=wav_orig,
                                    inferred_sr=sr, mel_inferred_denoised=mel_inf_h[b, :, :frames_inf[b]].copy(),
@@ -214,6 +239,10 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
       logger.info(f"V/UV error: {val.vuv_error}")
       logger.info(f"Pitch frames: {val.pitch_frames} (voiced: original {val.voiced_frames_orig}, "
                   f"inferred {val.voiced_frames_inferred})")
+    if intel:
+      logger.info(f"STOI: {val.stoi}")
+      logger.info(f"ESTOI: {val.estoi}")
+      logger.info(f"STOI frames: {val.stoi_frames} (kept: {val.stoi_frames_kept})")
     save_callback(entry, output)
     out.append(val)
 
@@ -221,12 +250,15 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
 def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: Optional[Dict[str, str]],
              denoiser_strength: float, sigma: float, entry_names: Set[str], full_run: bool,
              save_callback: Callable[[Entry, ValidationEntryOutput], None], seed: Optional[int], device: torch.device, *,
-             batch_size: int = 1, pitch_metrics: bool = False, resample_inputs: bool = False) -> ValidationEntries:
+             batch_size: int = 1, pitch_metrics: bool = False, resample_inputs: bool = False,
+             intelligibility_metrics: bool = False) -> ValidationEntries:
   """validation.py:125-287.  ``batch_size`` utterances share one launch sequence; every utterance gets the audio, the
   mels and the metrics it gets alone (its noise is drawn as ``Synthesizer.infer`` draws it, and every kernel of the
   sequence treats the padding behind an utterance as the end of the sequence).  ``pitch_metrics`` adds the F0 and
   voicing errors between the original wav and the synthesis (``metrics.pitch_metrics_enqueue`` with its defaults at the
-  model's sampling rate); without it nothing of them is launched and their fields stay None.  ``resample_inputs``: wavs at
+  model's sampling rate); without it nothing of them is launched and their fields stay None.  ``intelligibility_metrics``
+  adds STOI and ESTOI of the same two signals in the same way (``metrics.intelligibility_metrics_enqueue``: both resampled
+  to 10 kHz on the device; the original is the clean side).  ``resample_inputs``: wavs at
   other rates are resampled to the model's on the device (``TacotronSTFT(..., resample_inputs=True)``) and the metrics
   compare the resampled original with the synthesis; ``wav_orig`` / ``orig_sr`` of the output stay the file's own."""
   logger = getLogger(__name__)
@@ -243,5 +275,5 @@ def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: 
   bs = max(1, int(batch_size))
   for i in range(0, len(entries), bs):
     _validate_batch(synth, taco, entries[i:i + bs], sigma, denoiser_strength, seed, checkpoint.iteration, save_callback,
-                    result, pitch_metrics)
+                    result, pitch_metrics, intelligibility_metrics)
   return result
