@@ -120,6 +120,39 @@ int wg_forward(wg_handle* h, const void* mel, const void* audio, float* z, float
                float* log_det_W, int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype,
                void* workspace, size_t workspace_bytes, void* stream);
 
+/* wg_forward for a batch of utterances of DIFFERENT lengths (scoring held-out audio): `frames` is a device array of B
+ * mel-frame counts as in wg_infer_ragged; utterance b is audio[b, :256 * frames[b]] under mel[b, :, :frames[b]].
+ *   audio    [B, 256 * n_frames]      io_dtype
+ *   z, log_s as in wg_forward with L = 32 * n_frames; same size range and workspace (wg_forward_workspace_bytes at
+ *            audio_len = 256 * n_frames)
+ * Every utterance gets, bit for bit, the z and log_s of a batch-of-one wg_forward call on its own frames; z and every
+ * log_s[k] are exactly 0 behind column 32 * frames[b].  Mel and audio behind an utterance are never used (they may hold
+ * NaN).  The counts are never read on the host: one outside [1, n_frames] reads and writes nothing outside the buffers,
+ * and that utterance's z and log_s are 0.  No log_det_W: per column it is the handle's constant (see wg_nll).
+ * frames == NULL is wg_forward at audio_len = 256 * n_frames. */
+int wg_forward_ragged(wg_handle* h, const void* mel, const int32_t* frames, const void* audio, float* z,
+                      float* const* log_s, int32_t B, int32_t n_frames, int32_t io_dtype, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* Negative log-likelihood per utterance and per mel frame from the outputs of wg_forward / wg_forward_ragged:
+ * WaveGlowLoss (src/waveglow/train.py:31-45) of every utterance alone.  With L_b = 32 * frames[b] columns (L when
+ * frames == NULL, the dense batch; with counts L must be a multiple of 32), n_b = 8 * L_b samples and
+ * logdet = sum_k log|det W_k| of the handle (fp64, the value wg_forward multiplies by B * L, model.py:63):
+ *   nll_b  = (sum z^2 / (2 sigma^2) - sum_k sum log_s[k] - L_b * logdet) / n_b        sums over the utterance's columns
+ *   bits_b = (nll_b + ln(2 pi sigma^2) / 2) / ln 2                                    the constant the training loss drops
+ * so sum_b n_b nll_b / sum_b n_b over a dense batch is the batch loss of wg_loss.
+ *   z, log_s   device fp32, [B, n_group, L] and n_flows pointers to [B, h_k, L]
+ *   frames     device int32 [B] or NULL; a count outside [1, L / 32] counts as 0 columns (samples 0, NaN figures)
+ *   rows_out   device fp64 [B, 8]: nll, bits per sample, sum z^2, sum log_s, L_b * logdet, n_b, mean of z, variance of z
+ *   frame_out  device fp64 [B, ceil(L / 32)] or NULL: the three terms over columns 32q .. 32q+31 of utterance b, divided
+ *              by 256 (256 * the track sums to n_b * nll_b); NaN behind the utterance
+ *   workspace  wg_nll_workspace_bytes(h, B, L) bytes (0 for a refused geometry: 1 <= B <= 65535, 1 <= L <= 2^26)
+ * Two kernels (one more per 16 flows beyond the first 16) on `stream`; enqueue-only.  All sums are fp64 in a fixed order
+ * without atomics: a call gives the same bits every time, an utterance the bits of its own call at any pitch L. */
+size_t wg_nll_workspace_bytes(const wg_handle* h, int32_t B, int32_t L);
+int wg_nll(const wg_handle* h, const float* z, const float* const* log_s, const int32_t* frames, double sigma, int32_t B,
+           int32_t L, double* rows_out, double* frame_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* WaveGlowLoss.forward (src/waveglow/train.py:31-45) on the outputs of wg_forward:
  *   loss = (sum z^2 / (2 sigma^2) - sum_k sum log_s[k] - sum_k log_det_W[k]) / z_elems      (z_elems = B*n_group*L)
  * z, log_s[k]: device fp32 with z_elems / log_s_elems[k] elements; log_det_W: n_flows HOST floats;

@@ -25,6 +25,9 @@ def __getattr__(name):
               "IntelligibilityMetrics", "stoi"):
     from . import metrics
     return getattr(metrics, name)
+  if name in ("Likelihood", "log_likelihood", "log_likelihood_enqueue"):
+    from . import likelihood
+    return getattr(likelihood, name)
   if name in ("resample_enqueue", "resample_plan", "out_len"):
     # `waveglow_amd.resample` is the submodule (as `waveglow_amd.metrics` is); its function is `resample.resample`
     from . import resample

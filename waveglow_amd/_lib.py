@@ -77,6 +77,11 @@ SIGNATURES = {
   "wg_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                            C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                            C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_forward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_nll_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+  "wg_nll": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_int32, C.c_int32,
+                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_loss": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32,
                         C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_loss_dev": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32,

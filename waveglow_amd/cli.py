@@ -14,13 +14,15 @@ commented-out ``--batch-size``, inference_v2.py:64) and per-rank sharding of the
          --device-dataset: all wavs stay on the device and every batch is built there (waveglow_amd/device_data.py)
   python -m waveglow_amd.cli validate CHECKPOINTS-FOLDER OUTPUT-FOLDER DATA-FOLDER [--sigma S] [--denoiser-strength D]
          [--device cuda:0] [--custom-hparams ...] [--full-run] [--files NAME ...] [--custom-checkpoints IT ...]
-         [--custom-seed N] [--batch-size B] [--pitch-metrics] [--intelligibility-metrics]
+         [--custom-seed N] [--batch-size B] [--pitch-metrics] [--intelligibility-metrics] [--likelihood]
          (src/waveglow_cli/validation.py:86-153)
          copy synthesis of validation utterances and their metrics on the device (MCD, DTW-MCD, penalties, cosine
          similarity): OUTPUT-FOLDER/log.txt, total.csv and one folder of mels and wavs per utterance and checkpoint;
          no PNG plots and no structural similarity, single process only.  --pitch-metrics adds the F0 RMSE, the gross
          pitch error and the voicing decision error between the original and the synthesis (a YIN tracker on the device);
-         --intelligibility-metrics adds STOI and ESTOI of the two, resampled to 10 kHz on the device
+         --intelligibility-metrics adds STOI and ESTOI of the two, resampled to 10 kHz on the device;
+         --likelihood adds what the checkpoint assigns to the ORIGINAL wav: negative log-likelihood in nats per sample (the
+         training loss of that utterance alone, at hparams.sigma), bits per sample and the variance of z
 Under ``python -m torch.distributed.run`` the training commands run data-parallel (one process per GPU, RCCL).
 """
 from __future__ import annotations
@@ -111,6 +113,9 @@ def build_parser() -> argparse.ArgumentParser:
   v.add_argument("--resample-inputs", action="store_true",
                  help="resample wav files at other sampling rates to the model's on the device instead of refusing them; "
                       "original.wav is still written as loaded")
+  v.add_argument("--likelihood", action="store_true",
+                 help="also score the original wav under each checkpoint (no sampling): negative log-likelihood per "
+                      "sample, bits per sample and the variance of z over its whole frames, in four more columns")
   return p
 
 
@@ -250,7 +255,7 @@ def validate_cmd(ns) -> bool:
                                sigma=ns.sigma, denoiser_strength=ns.denoiser_strength, seed=ns.custom_seed,
                                device=torch.device(ns.device), batch_size=ns.batch_size,
                                pitch_metrics=ns.pitch_metrics, resample_inputs=ns.resample_inputs,
-                               intelligibility_metrics=ns.intelligibility_metrics))
+                               intelligibility_metrics=ns.intelligibility_metrics, likelihood=ns.likelihood))
       except AssertionError as e:
         logger.error(str(e) or "validation failed an assertion")
         return False

@@ -829,12 +829,13 @@ int wg_infer_ragged(wg_handle* h, const void* mel, const int32_t* frames, const 
   return WG_OK;
 }
 
-int wg_forward(wg_handle* h, const void* mel, const void* audio, float* z, float* const* log_s, float* log_det_W,
-               int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype, void* workspace,
-               size_t workspace_bytes, void* stream) {
+// The no-grad forward of both entry points.  `frames` (device, or null): per-utterance mel-frame counts of a ragged batch.
+static int forward_impl(wg_handle* h, const void* mel, const int32_t* frames, const void* audio, float* z, float* const* log_s,
+                        int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype, void* workspace,
+                        size_t workspace_bytes, void* stream) {
   if (!h) return fail(WG_ERR_INVALID, "null handle");
+  if (!mel || !audio || !z || !log_s || !workspace) return fail(WG_ERR_INVALID, "null buffer");
   if (!h->finalized) return fail(WG_ERR_STATE, "wg_finalize has not been called");
-  if (!mel || !audio || !z || !log_s || !log_det_W || !workspace) return fail(WG_ERR_INVALID, "null buffer");
   if (io_dtype != WG_F32 && io_dtype != WG_F16) return fail(WG_ERR_INVALID, "bad io_dtype");
   const wg_config& c = h->cfg;
   if (B < 1 || n_frames < 1 || audio_len < c.n_group || audio_len % c.n_group)
@@ -845,16 +846,16 @@ int wg_forward(wg_handle* h, const void* mel, const void* audio, float* z, float
   const int L = audio_len / c.n_group;
   if (int rc = check_envelope(c, B, L)) return rc;   // as in wg_infer_ragged: the one size check, before the workspace's
   RowGeom g = make_geom(c, B, L, n_frames);
+  g.frames = (const int*)frames;   // the mel pack, the WN layers and the flow steps all take the padding columns from here
   Workspace w = carve(h, g, (char*)workspace);
   if (w.bytes > workspace_bytes) return fail(WG_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, w.bytes);
   hipStream_t s = (hipStream_t)stream;
   const int C = c.n_channels;
-  for (int k = 0; k < c.n_flows; ++k) log_det_W[k] = (float)((double)B * L * h->flows[k].logdet);   // model.py:63
   HIP_TRY(launch_zero_fill(w.X0, 2 * w.x_bytes + w.a0_bytes, s));
   {
     MelPackArgs u;
     u.mel = mel;
-    u.frames = nullptr;
+    u.frames = g.frames;
     u.melT = w.melT;
     u.B = B;
     u.M = c.n_mel_channels;
@@ -914,6 +915,25 @@ int wg_forward(wg_handle* h, const void* mel, const void* audio, float* z, float
     }
   }
   return WG_OK;
+}
+
+int wg_forward(wg_handle* h, const void* mel, const void* audio, float* z, float* const* log_s, float* log_det_W,
+               int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype, void* workspace,
+               size_t workspace_bytes, void* stream) {
+  if (!log_det_W) return fail(WG_ERR_INVALID, "null buffer");
+  const int rc = forward_impl(h, mel, nullptr, audio, z, log_s, B, n_frames, audio_len, io_dtype, workspace, workspace_bytes,
+                              stream);
+  if (rc != WG_OK) return rc;
+  const int64_t L = audio_len / h->cfg.n_group;
+  for (int k = 0; k < h->cfg.n_flows; ++k) log_det_W[k] = (float)((double)B * L * h->flows[k].logdet);   // model.py:63
+  return WG_OK;
+}
+
+int wg_forward_ragged(wg_handle* h, const void* mel, const int32_t* frames, const void* audio, float* z, float* const* log_s,
+                      int32_t B, int32_t n_frames, int32_t io_dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_frames < 1 || n_frames > (INT32_MAX >> 8)) return fail(WG_ERR_INVALID, "bad B/n_frames");
+  return forward_impl(h, mel, frames, audio, z, log_s, B, n_frames, n_frames * 256, io_dtype, workspace, workspace_bytes,
+                      stream);
 }
 
 static int loss_impl(const float* z, int64_t z_elems, const float* const* log_s, const int64_t* log_s_elems, int32_t n_flows,

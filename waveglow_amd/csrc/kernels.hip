@@ -1501,7 +1501,8 @@ __global__ void __launch_bounds__(256) mel_pack_kernel(const MelPackArgs a) {
     float v = 0.0f;
     if (row >= 0) {
       const int b = row / rows_per_utt, f = row - b * rows_per_utt - 3;
-      if (f >= 0 && f < (a.frames ? a.frames[b] : a.T)) v = load_io(a.mel, ((size_t)b * a.M + i) * a.T + f, a.io_f16);
+      // (a device count above T reads no mel behind the row)
+      if (f >= 0 && f < a.T && (a.frames == nullptr || f < a.frames[b])) v = load_io(a.mel, ((size_t)b * a.M + i) * a.T + f, a.io_f16);
     }
     a.melT[idx] = (_Float16)v;
   }
@@ -1675,7 +1676,7 @@ __global__ void __launch_bounds__(FL_ROWS) flow_kernel(const FlowArgs a) {
       const int b = (int)(r32 / (unsigned)L), t = (int)(r32 - (unsigned)b * (unsigned)L);
       // ragged batch: columns behind an utterance's own length are padding -- their state is carried along (finite,
       // never read by a valid column) but they are never written into the x / a0 planes, and their audio is zero
-      const bool pad_row = a.g.frames != nullptr && t >= 32 * a.g.frames[b];
+      bool pad_row = a.g.frames != nullptr && t >= 32 * a.g.frames[b];
       float zn[kMaxGroup];
 #pragma unroll
       for (int c = 0; c < kMaxGroup; ++c) zn[c] = 0.0f;
@@ -1740,8 +1741,20 @@ __global__ void __launch_bounds__(FL_ROWS) flow_kernel(const FlowArgs a) {
         }
       } else {
         // ------------------------------------------------ forward flow (model.py:200-218)
+        // ragged batch (wg_forward_ragged): a padding column carries an all-zero state through every flow and writes 0 to
+        // z and log_s -- its audio is never loaded (it may be NaN) and the out plane of its row is never read (exp of
+        // out_init, twelve times over, need not stay finite).  A count outside [1, T] makes the whole utterance padding.
+        if (a.g.frames != nullptr && (unsigned)a.g.frames[b] - 1u >= (unsigned)a.g.T) pad_row = true;
         float z[kMaxGroup];
-        if (a.first) {
+        if (pad_row) {
+#pragma unroll
+          for (int c = 0; c < 8; ++c) z[c] = 0.0f;
+          if (!a.first) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (q < a.h_in) a.log_s_out[((size_t)b * a.h_in + q) * L + t] = 0.0f;
+          }
+        } else if (a.first) {
 #pragma unroll
           for (int c = 0; c < 8; ++c)
             z[c] = load_io(a.audio_in, (size_t)b * L * 8 + (size_t)t * 8 + c, a.io_f16);           // :195

@@ -461,6 +461,29 @@ class WaveGlow(nn.Module):
       log_s = [t.to(spect.dtype) for t in log_s]
     return z, log_s, log_det_list
 
+  def forward_ragged(self, mel: torch.Tensor, audio: torch.Tensor, frames):
+    """``(z, [log_s_k])`` of the no-grad ``forward`` for utterances of different lengths (``frames``: mel frames of each):
+    every utterance gets its batch-of-one result bit for bit, zeros behind it (waveglow_amd/likelihood.py)."""
+    from .likelihood import forward_ragged
+    return forward_ragged(self, mel, audio, frames)
+
+  def log_likelihood(self, mel: torch.Tensor, audio: torch.Tensor, frames=None, sigma: Optional[float] = None,
+                     per_frame: bool = False):
+    """Negative log-likelihood of recorded audio under the model, per utterance: a list of ``Likelihood`` tuples
+    (``nll`` in nats per sample -- ``WaveGlowLoss`` of that utterance alone --, ``bits_per_sample``, ``samples``,
+    ``z_mean``, ``z_var``, ``sum_z2``, ``sum_log_s``, ``log_det``); with ``per_frame`` a pair with the fp64 track
+    [B, n_frames] on the device.  ``frames``: mel-frame counts of a padded batch (utterance b is
+    ``audio[b, :256 * frames[b]]`` under ``mel[b, :, :frames[b]]``), None for a dense batch.  No hipGraph, no autograd;
+    see waveglow_amd/likelihood.py."""
+    from .likelihood import log_likelihood
+    return log_likelihood(self, mel, audio, frames, sigma, per_frame)
+
+  def log_likelihood_enqueue(self, mel: torch.Tensor, audio: torch.Tensor, frames=None, sigma: Optional[float] = None,
+                             per_frame: bool = False):
+    """``log_likelihood`` without the copy: fp64 rows [B, 8] on the device (waveglow_amd/likelihood.py: ``N_ROW``)."""
+    from .likelihood import log_likelihood_enqueue
+    return log_likelihood_enqueue(self, mel, audio, frames, sigma, per_frame)
+
   def gradient_workspace_bytes(self, batch_size: int, n_frames: int, audio_len: Optional[int] = None,
                                recompute: Optional[bool] = None) -> int:
     """Bytes of the saved state that one outstanding training-direction forward (or ``infer_differentiable`` call) holds

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, metrics, pcm
+from . import likelihood as ll
 from .audio import wav_to_float32
 from .checkpoint import CheckpointWaveglow
 from .synthesizer import PcmResult, Synthesizer
@@ -64,6 +65,11 @@ class ValidationEntry:
   estoi: float = None
   stoi_frames: int = None
   stoi_frames_kept: int = None
+  # validate(likelihood=True) only (waveglow_amd/likelihood.py: Likelihood of the ORIGINAL wav under the checkpoint); None otherwise
+  nll: float = None
+  bits_per_sample: float = None
+  z_variance: float = None
+  likelihood_frames: int = None
 
 
 class ValidationEntries(List[ValidationEntry]):
@@ -84,12 +90,13 @@ class ValidationEntryOutput:
 def get_df(entries: ValidationEntries):
   """The reference's table (validation.py:52-108) without the "Structual Similarity (Padded)" column.  Entries validated
   with the pitch metrics get seven more columns behind "Cosine Similarity (Padded)", entries validated with the
-  intelligibility metrics four more behind those."""
+  intelligibility metrics four more behind those, entries validated with the likelihood four more behind those."""
   from pandas import DataFrame
   if len(entries) == 0:
     return DataFrame()
   with_pitch = any(e.pitch_frames is not None for e in entries)
   with_stoi = any(e.stoi_frames is not None for e in entries)
+  with_ll = any(e.likelihood_frames is not None for e in entries)
   data = [{
     "Name": e.entry.basename,
     "Subpath": e.entry.stem,
@@ -127,6 +134,12 @@ def get_df(entries: ValidationEntries):
       "# STOI frames": e.stoi_frames,
       "# STOI frames kept": e.stoi_frames_kept,
     } if with_stoi else {}),
+    **({
+      "NLL (nats/sample)": e.nll,
+      "Bits per sample": e.bits_per_sample,
+      "z variance": e.z_variance,
+      "# Likelihood frames": e.likelihood_frames,
+    } if with_ll else {}),
     "Wav path": str(e.entry.wav_absolute_path),
   } for e in entries]
   return DataFrame(data=[list(x.values()) for x in data], columns=list(data[0].keys()))
@@ -149,12 +162,12 @@ def select_entries(data: List[Entry], entry_names: Set[str], full_run: bool, see
 
 def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], sigma, denoiser_strength, seed, iteration,
                     save_callback, out: ValidationEntries, pitch_metrics: bool = False,
-                    intelligibility_metrics: bool = False) -> None:
+                    intelligibility_metrics: bool = False, likelihood: bool = False) -> None:
   logger = getLogger(__name__)
   dev = synth.device
   timepoint = datetime.datetime.now()
   B = len(chunk)
-  if pitch_metrics or intelligibility_metrics:                            # the wavs stay on the device: read once
+  if pitch_metrics or intelligibility_metrics or likelihood:              # the wavs stay on the device: read once
     mel_orig, frames, wav_orig_dev, n_orig_dev = taco.get_mel_and_wav_tensors_from_files(
       [e.wav_absolute_path for e in chunk])
   else:
@@ -186,11 +199,17 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
     # the clean side is the original as loaded, the processed side the peak-normalised synthesis
     parts.append(metrics.intelligibility_metrics_enqueue(wav_orig_dev, n_orig_dev, normed, samples_dev,
                                                          sampling_rate=synth.hparams.sampling_rate))
+  if likelihood:
+    # the original recording under the checkpoint: no sampling, so no seed noise; whole frames only (n // 256)
+    parts.append(ll.log_likelihood_enqueue(synth.model, mel_orig, wav_orig_dev, n_orig_dev // ll.FRAME_SAMPLES,
+                                           sigma=synth.hparams.sigma))
   rows = torch.cat(parts, dim=1).cpu()
   first = metrics.N_ROW + 1
   pitch = metrics.rows_to_pitch_metrics(rows[:, first:first + metrics.N_ROW]) if pitch_metrics else None
   first += metrics.N_ROW if pitch_metrics else 0
   intel = metrics.rows_to_intelligibility_metrics(rows[:, first:first + metrics.N_ROW]) if intelligibility_metrics else None
+  first += metrics.N_ROW if intelligibility_metrics else 0
+  like = ll.rows_to_likelihoods(rows[:, first:first + ll.N_ROW]) if likelihood else None
   fin_h = fin.cpu()
   fin_raw_h = fin_raw.cpu() if fin_raw is not fin else fin_h
   mel_orig_h, mel_inf_h = mel_orig.cpu().numpy(), mel_inf.cpu().numpy()
@@ -220,6 +239,10 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
     if intel:
       im = intel[b]
       val.stoi, val.estoi, val.stoi_frames, val.stoi_frames_kept = im.stoi, im.estoi, im.frames, im.frames_kept
+    if like:
+      lk = like[b]
+      val.nll, val.bits_per_sample, val.z_variance = lk.nll, lk.bits_per_sample, lk.z_var
+      val.likelihood_frames = lk.samples // ll.FRAME_SAMPLES
     wav_orig, orig_sr = wav_to_float32(entry.wav_absolute_path)
     output = ValidationEntryOutput(mel_orig=mel_orig_h[b, :, :frames[b]].copy(), orig_sr=orig_sr, wav_orig=wav_orig,
                                    inferred_sr=sr, mel_inferred_denoised=mel_inf_h[b, :, :frames_inf[b]].copy(),
@@ -243,6 +266,11 @@ def _validate_batch(synth: Synthesizer, taco: TacotronSTFT, chunk: List[Entry], 
       logger.info(f"STOI: {val.stoi}")
       logger.info(f"ESTOI: {val.estoi}")
       logger.info(f"STOI frames: {val.stoi_frames} (kept: {val.stoi_frames_kept})")
+    if like:
+      logger.info(f"NLL (nats/sample): {val.nll}")
+      logger.info(f"Bits per sample: {val.bits_per_sample}")
+      logger.info(f"z variance: {val.z_variance}")
+      logger.info(f"Likelihood frames: {val.likelihood_frames}")
     save_callback(entry, output)
     out.append(val)
 
@@ -251,7 +279,7 @@ def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: 
              denoiser_strength: float, sigma: float, entry_names: Set[str], full_run: bool,
              save_callback: Callable[[Entry, ValidationEntryOutput], None], seed: Optional[int], device: torch.device, *,
              batch_size: int = 1, pitch_metrics: bool = False, resample_inputs: bool = False,
-             intelligibility_metrics: bool = False) -> ValidationEntries:
+             intelligibility_metrics: bool = False, likelihood: bool = False) -> ValidationEntries:
   """validation.py:125-287.  ``batch_size`` utterances share one launch sequence; every utterance gets the audio, the
   mels and the metrics it gets alone (its noise is drawn as ``Synthesizer.infer`` draws it, and every kernel of the
   sequence treats the padding behind an utterance as the end of the sequence).  ``pitch_metrics`` adds the F0 and
@@ -260,7 +288,11 @@ def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: 
   adds STOI and ESTOI of the same two signals in the same way (``metrics.intelligibility_metrics_enqueue``: both resampled
   to 10 kHz on the device; the original is the clean side).  ``resample_inputs``: wavs at
   other rates are resampled to the model's on the device (``TacotronSTFT(..., resample_inputs=True)``) and the metrics
-  compare the resampled original with the synthesis; ``wav_orig`` / ``orig_sr`` of the output stay the file's own."""
+  compare the resampled original with the synthesis; ``wav_orig`` / ``orig_sr`` of the output stay the file's own.
+  ``likelihood`` adds what the checkpoint assigns to the ORIGINAL wav (after ``resample_inputs``, the resampled one) under
+  its own mel: the negative log-likelihood in nats per sample at ``hparams.sigma`` -- comparable with the training log --,
+  bits per sample and the variance of z, over the ``n // 256`` whole frames of the file
+  (``WaveGlow.log_likelihood_enqueue``); without it nothing of it is launched and its fields stay None."""
   logger = getLogger(__name__)
   result = ValidationEntries()
   if seed is None:
@@ -275,5 +307,5 @@ def validate(checkpoint: CheckpointWaveglow, data: List[Entry], custom_hparams: 
   bs = max(1, int(batch_size))
   for i in range(0, len(entries), bs):
     _validate_batch(synth, taco, entries[i:i + bs], sigma, denoiser_strength, seed, checkpoint.iteration, save_callback,
-                    result, pitch_metrics, intelligibility_metrics)
+                    result, pitch_metrics, intelligibility_metrics, likelihood)
   return result
