@@ -274,7 +274,7 @@ int wg_wav_finish(const float* raw, const float* denoised, const int32_t* lens, 
  * A pick outside the pool (u outside [0, n_utt), s < 0, s > max(len - segment_length, 0)) gives an all-zero row and, if
  * status_out (device [1], may be null) is given, sets status_out[0] = 1; otherwise status_out is left alone.  Nothing
  * outside [0, pool_elems) is read whatever the picks hold.  One launch, no workspace.  Enqueue-only. */
-typedef enum wg_pcm_dtype { WG_PCM_I16 = 0, WG_PCM_F32 = 1 } wg_pcm_dtype;
+typedef enum wg_pcm_dtype { WG_PCM_I16 = 0, WG_PCM_F32 = 1, WG_PCM_F64 = 2 /* wg_resample_backward's d_out only */ } wg_pcm_dtype;
 int wg_data_gather(const void* pool, int32_t pool_dtype, int64_t pool_elems, const int64_t* offsets, int32_t n_utt,
                    const int32_t* picks, float* audio_out, int32_t* status_out, int32_t B, int32_t segment_length,
                    void* stream);
@@ -397,6 +397,40 @@ size_t wg_stoi_workspace_bytes(int32_t B, int32_t n_max);
 int wg_stoi(const float* x, const int32_t* len_x, const float* y, const int32_t* len_y, int32_t B, int32_t pitch,
             const wg_stoi_params* params, double* rows_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- STOI and ESTOI as a training signal: the gradient with respect to the processed signal y --------------------------
+ * The energy gate (step 3) depends on the clean signal alone, so with the gate and x held constant both values are
+ * differentiable in y; the gradient runs through the definition above, step by step.
+ * wg_stoi_forward: wg_stoi -- the same five launches, rows_out bit for bit -- that also leaves in `saved`
+ *   (wg_stoi_saved_bytes(B, pitch) bytes, aligned to 8; 0 for a refused geometry) what the backward needs:
+ *   [counts int32 [B][4] = (n, F0, K, J) | kept-frame lists int32 [B][F0max] | band spectra fp64 [B][2][15][Fmax], X then Y],
+ *   each part aligned to 256 bytes, F0max = max(1, F0(pitch)), Fmax = max(1, F0max - 1).  workspace: as wg_stoi.
+ * wg_stoi_backward: y, B, pitch, params and saved as the forward had them; g_rows fp64 [B][2] device, the upstream
+ *   gradients of STOI and ESTOI; d_y fp64 [B][pitch] = the gradient of g_rows[b][0] STOI_b + g_rows[b][1] ESTOI_b with
+ *   respect to y[b].  Exact zeros at and behind the common length n, in gated frames and behind the last frame; a row
+ *   without a segment (J = 0) is all zeros whatever g_rows[b] holds (it is not read).  Nothing at or behind n is read.
+ *   Workspace: wg_stoi_backward_workspace_bytes(B, pitch); the backward writes to it and to d_y only, so a second call on
+ *   the same saved buffer gives the same bits.  Five launches on `stream`:
+ *   the inverse of the kept-frame list; one wave per segment recomputing its 15 x 30 block from the saved X, Y and writing
+ *   the block's gradient, weights g0 / (15 J) and g1 / (30 J) folded in; per (band, t) the sum of the at most 30 blocks
+ *   that cover it, ascending in m, divided by 2 Y[band, t]; per frame the (re, im) of bins 7 .. 218 recomputed from y as
+ *   the forward computes them, d re = 2 re dP, d im = 2 im dP, and d frame[j] = w[j] sum over the bins ascending of
+ *   (cos d re + sin d im) from the caller's table; the overlap-add as a gather, one thread per sample of y.
+ * Conventions where the definition is not smooth: the gradient through a square root whose argument is exactly 0 is 0
+ *   (band sums, row and column norms, ||y|| in alpha), so silence on either side gives exactly zero gradients; at a tie
+ *   of min(alpha y, x (1 + 10^(15/20))) the gradient goes to the alpha y branch; alpha is differentiated (it depends on
+ *   y); the gate and x are constants.
+ * Arithmetic: fp64, every sum in a fixed order that depends on the utterance alone, no atomics; products may be fused
+ *   into the sums.  A call gives the same bits every time and every utterance of a batch the bits of its own call with
+ *   B = 1, whatever the pitch.  Limits and argument checks as wg_stoi.  Enqueue-only. */
+size_t wg_stoi_saved_bytes(int32_t B, int32_t pitch);
+size_t wg_stoi_backward_workspace_bytes(int32_t B, int32_t pitch);
+int wg_stoi_forward(const float* x, const int32_t* len_x, const float* y, const int32_t* len_y, int32_t B, int32_t pitch,
+                    const wg_stoi_params* params, double* rows_out, void* saved, size_t saved_bytes, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int wg_stoi_backward(const float* y, int32_t B, int32_t pitch, const wg_stoi_params* params, const double* g_rows,
+                     const void* saved, size_t saved_bytes, double* d_y, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* ---- Resampling by a rational ratio: wav data of any sampling rate in, any rate out, no handle ------------------------
  * The reference has no counterpart.  The definition is scipy.signal.resample_poly(x, up, down) with its defaults
  * (window ('kaiser', 5.0), padtype 'constant') in closed form.  With up / down reduced, M = max(up, down), half = 10 M and
@@ -428,6 +462,28 @@ int wg_resample_plan(int32_t up, int32_t down, int32_t half, int32_t n_in, int32
                      int32_t* tile, int32_t* staged);
 int wg_resample(const void* in, int32_t in_dtype, const int32_t* lens, float* out, const double* taps, int32_t up,
                 int32_t down, int32_t half, int32_t flags, int32_t B, int32_t n_in, int32_t n_out, void* stream);
+
+/* ---- The transpose of wg_resample: the gradient of a loss computed at another rate -------------------------------------
+ *   d_in[m] = sum over n ascending, 0 <= n < out_len(lens[b]) with 0 <= half + n down - m up <= 2 half, of
+ *             d_out[n] h[half + n down - m up],
+ * the gradient with respect to in[b][m] of sum_n d_out[n] out[b][n] for the unclipped wg_resample (there is no clipped
+ * variant).  up, down, half, B, n_in, n_out, lens and their limits as in wg_resample.
+ * d_out: [B][n_out] device, fp32 (WG_PCM_F32) or fp64 (WG_PCM_F64).  Nothing at or behind d_out[b][out_len(lens[b])] is
+ *   read (it may hold NaN).
+ * d_in: [B][n_in] fp32, written for m < lens[b] and exact zeros behind.
+ * taps_t: the caller's h as a second polyphase table on the device, fp64 [down][Kt] with Kt = ceil((2 half + 1) / down):
+ *   taps_t[r][i] = h[r + i down], 0 where that index exceeds 2 half.  With c = half - m up, r = c mod down (non-negative)
+ *   and n0 = (r - c) / down, input m is sum_i d_out[n0 + i] taps_t[r][i]: one input's taps are one row, read in ascending
+ *   i, which is ascending n.
+ * Arithmetic: each product is a gradient widened to fp64 times an fp64 tap, the sum is fp64 in ascending n over the terms
+ *   of the definition only and is rounded to fp32 once; no contraction, no atomics.  A call gives the same bits every
+ *   time, and every row of a batch the bits of its own call with B = 1; the tile (1024 consecutive inputs per workgroup)
+ *   and the kernel variant (the span of d_out staged in LDS, or read through the cache for up / down above about 4) do not
+ *   enter the arithmetic.
+ * up == down == 1 copies (an fp64 gradient is rounded to fp32) and zero-fills behind the length.  One launch, no
+ *   workspace.  Enqueue-only. */
+int wg_resample_backward(const void* d_out, int32_t d_out_dtype, const int32_t* lens, float* d_in, const double* taps_t,
+                         int32_t up, int32_t down, int32_t half, int32_t B, int32_t n_in, int32_t n_out, void* stream);
 
 /* ---- Multi-resolution STFT loss (spectral convergence + log-magnitude L1), fp32, with its backward ------------------
  * For resolution r = (n_fft, hop, win): X = STFT(x) with reflect padding by n_fft/2 and the window of `win` samples

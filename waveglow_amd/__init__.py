@@ -21,6 +21,9 @@ def __getattr__(name):
   if name == "MultiResolutionSTFTLoss":
     from .stft_loss import MultiResolutionSTFTLoss
     return MultiResolutionSTFTLoss
+  if name == "STOILoss":
+    from .stoi_loss import STOILoss
+    return STOILoss
   if name in ("mel_metrics", "MelMetrics", "pitch_metrics", "PitchMetrics", "yin_f0", "intelligibility_metrics",
               "IntelligibilityMetrics", "stoi"):
     from . import metrics

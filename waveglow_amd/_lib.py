@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("WAVEGLOW_AMD_LIB", os.path.join(_HERE, "csrc", "libwa
 
 WG_F32, WG_F16 = 0, 1
 WG_PCM_I16, WG_PCM_F32 = 0, 1   # pool_dtype of wg_data_gather
+WG_PCM_F64 = 2                  # d_out_dtype of wg_resample_backward only
 WG_RESAMPLE_CLIP = 1           # flag of wg_resample
 WG_TRAIN_RECOMPUTE = 1        # flag of the wg_train_* entry points that take flags (include/waveglow_amd.h)
 
@@ -155,6 +156,15 @@ SIGNATURES = {
   "wg_stoi_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
   "wg_stoi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(WgStoiParams),
                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stoi_saved_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+  "wg_stoi_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+  "wg_stoi_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                C.POINTER(WgStoiParams), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                C.c_void_p]),
+  "wg_stoi_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(WgStoiParams), C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_resample_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
   "wg_resample_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
   "wg_resample": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,

@@ -59,4 +59,23 @@ int wg_resample(const void* in, int32_t in_dtype, const int32_t* lens, float* ou
   return WG_OK;
 }
 
+int wg_resample_backward(const void* d_out, int32_t d_out_dtype, const int32_t* lens, float* d_in, const double* taps_t,
+                         int32_t up, int32_t down, int32_t half, int32_t B, int32_t n_in, int32_t n_out, void* stream) {
+  if (!d_out || !lens || !d_in || !taps_t) return fail(WG_ERR_INVALID, "null argument");
+  if (d_out_dtype != WG_PCM_F32 && d_out_dtype != WG_PCM_F64)
+    return fail(WG_ERR_INVALID, "resample backward: d_out_dtype must be WG_PCM_F32 or WG_PCM_F64");
+  if (B < 1) return fail(WG_ERR_INVALID, "resample: B >= 1 expected, got %d", B);
+  if (const char* e = geom_error(up, down, half, n_in)) return fail(WG_ERR_INVALID, "%s", e);
+  if (n_out < resample_out_len(n_in, up, down))
+    return fail(WG_ERR_INVALID, "resample: n_out %d below the %lld outputs of %d samples", n_out,
+                (long long)resample_out_len(n_in, up, down), n_in);
+  if (n_out > INT_MAX - kResampleTile)
+    return fail(WG_ERR_INVALID, "resample: n_out %d above 2^31 - 1 - %d", n_out, kResampleTile);
+  ResampleGeom g;
+  g.up = up, g.down = down, g.half = half, g.K = row_taps(up, half), g.clip = false;
+  HIP_TRY(launch_resample_backward(d_out, d_out_dtype == WG_PCM_F64, lens, d_in, taps_t, g, row_taps(down, half), B, n_in,
+                                   n_out, (hipStream_t)stream));
+  return WG_OK;
+}
+
 }  // extern "C"

@@ -50,4 +50,17 @@ hipError_t launch_stoi(const float* x, const int* len_x, const float* y, const i
                        const int* bands, const double* cossin, double* rows, const StoiGeom& g, const StoiBuffers& w,
                        hipStream_t s);
 
+// Scratch of one backward call (stoi_grad.hip), sized like the forward's parts.
+struct StoiGradBuffers {
+  int* inv;         // [B][F0max]: silence-free index of an original frame, -1 where it was gated
+  double* blocks;   // [B][Jmax][15][30]: one segment's gradient with respect to its block of Y
+  double* dband;    // [B][15][Fmax]: gradient with respect to the band sums (the squares of Y)
+  double* dframe;   // [B][Fmax][256]: gradient with respect to the silence-free signal through one of its frames
+};
+
+// `saved` holds the counts, kept and bands parts a forward left; y [B][pitch], g_rows [B][2] -> d_y [B][pitch] fp64
+hipError_t launch_stoi_backward(const float* y, const double* window, const int* bands, const double* cossin,
+                                const double* g_rows, const StoiBuffers& saved, double* d_y, const StoiGeom& g,
+                                const StoiGradBuffers& w, hipStream_t s);
+
 }  // namespace wg

@@ -16,7 +16,8 @@ all absent) is unpinned, the numpy restatement tests/_pitch_oracle.py is the yar
 Of audio pairs at 10 kHz (``wg_stoi``, the last part of this file): short-time objective intelligibility (STOI, Taal et al.
 2011) and its extended form (ESTOI, Jensen and Taal 2016) of a clean and a processed signal, with the project's resampler in
 front for other rates.  The reference has no counterpart; parity with ``pystoi`` (absent) is unpinned, the numpy restatement
-tests/_stoi_oracle.py is the yardstick.
+tests/_stoi_oracle.py is the yardstick.  ``stoi_differentiable`` gives the same two values with a graph back to the
+processed signal (``wg_stoi_forward`` / ``wg_stoi_backward``); ``waveglow_amd.STOILoss`` is the loss built on it.
 """
 from __future__ import annotations
 
@@ -466,3 +467,84 @@ def intelligibility_metrics(audio_a: torch.Tensor, lengths_a: Frames, audio_b: t
   """``intelligibility_metrics_enqueue`` + one copy to the host + one stream synchronise."""
   return rows_to_intelligibility_metrics(_read_rows(
     intelligibility_metrics_enqueue(audio_a, lengths_a, audio_b, lengths_b, sampling_rate)))
+
+
+# ------------------------------------------------------------------------------------- STOI / ESTOI with a gradient
+def stoi_saved_bytes(B: int, N: int) -> int:
+  """Bytes ``stoi_forward_saved`` keeps for the backward besides ``y10k`` itself: the counts, the kept-frame lists and the
+  band spectra of both sides (``wg_stoi_saved_bytes``; 0 for a refused geometry)."""
+  return int(_lib.load().wg_stoi_saved_bytes(int(B), int(N)))
+
+
+def stoi_forward_saved(x10k: torch.Tensor, lengths_x: Frames, y10k: torch.Tensor, lengths_y: Frames):
+  """``(rows, state)``: the rows of ``stoi_enqueue`` bit for bit (``wg_stoi_forward`` runs the same five launches) and what
+  ``stoi_backward_enqueue`` needs: the processed signal as the kernels read it and the saved buffer.  Both sides must have
+  one row pitch here.  Enqueue-only."""
+  x = _stoi_audio("stoi: x10k", x10k)
+  y = _stoi_audio("stoi: y10k", y10k, x.device)
+  if x.shape != y.shape:
+    raise _lib.WgError(f"stoi with a gradient takes both sides in one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+  lx, ly = _lengths("stoi: lengths_x", lengths_x, x), _lengths("stoi: lengths_y", lengths_y, y)
+  B, N = x.shape
+  lib = _lib.load()
+  with torch.cuda.device(x.device):
+    p = _stoi_params(x.device)
+    rows = torch.empty((B, N_ROW), dtype=torch.float64, device=x.device)
+    saved = torch.empty(lib.wg_stoi_saved_bytes(B, N), dtype=torch.uint8, device=x.device)
+    ws = torch.empty(lib.wg_stoi_workspace_bytes(B, N), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.wg_stoi_forward(x.data_ptr(), lx.data_ptr(), y.data_ptr(), ly.data_ptr(), B, N, C.byref(p),
+                                   rows.data_ptr(), saved.data_ptr(), saved.numel(), ws.data_ptr(), ws.numel(), _stream(x)))
+  return rows, (y.detach(), saved)
+
+
+def stoi_backward_enqueue(state, g_rows: torch.Tensor) -> torch.Tensor:
+  """fp64 ``[B, N]``: the gradient of ``sum_b g_rows[b, 0] STOI_b + g_rows[b, 1] ESTOI_b`` with respect to ``y10k``
+  (``wg_stoi_backward``), from the state of ``stoi_forward_saved`` and fp64 ``[B, 2]`` upstream gradients on the device.
+  Exact zeros at and behind a pair's common length and in a row without a segment.  Writes to nothing the forward left:
+  calling it twice gives the same bits.  Enqueue-only."""
+  y, saved = state
+  B, N = y.shape
+  if not isinstance(g_rows, torch.Tensor) or g_rows.device != y.device or g_rows.dtype != torch.float64 or \
+      tuple(g_rows.shape) != (B, 2):
+    raise _lib.WgError(f"stoi backward takes the upstream gradients as float64 [{B}, 2] on {y.device}")
+  g = g_rows.contiguous()
+  lib = _lib.load()
+  with torch.cuda.device(y.device):
+    p = _stoi_params(y.device)
+    d_y = torch.empty((B, N), dtype=torch.float64, device=y.device)
+    ws = torch.empty(lib.wg_stoi_backward_workspace_bytes(B, N), dtype=torch.uint8, device=y.device)
+    _lib.check(lib.wg_stoi_backward(y.data_ptr(), B, N, C.byref(p), g.data_ptr(), saved.data_ptr(), saved.numel(),
+                                    d_y.data_ptr(), ws.data_ptr(), ws.numel(), _stream(y)))
+  return d_y
+
+
+class _StoiFn(torch.autograd.Function):
+  """(x10k, lengths_x, y10k, lengths_y) -> fp64 [B, 2]; the gradient goes to y10k alone, rounded to its fp32 once."""
+
+  @staticmethod
+  def forward(ctx, x, lx, y, ly):
+    rows, ctx.state = stoi_forward_saved(x, lx, y.detach(), ly)
+    return rows[:, :2].clone()
+
+  @staticmethod
+  def backward(ctx, g):
+    return None, None, stoi_backward_enqueue(ctx.state, g.to(torch.float64)).to(torch.float32), None
+
+
+def stoi_differentiable(x10k: torch.Tensor, lengths_x: Frames, y10k: torch.Tensor, lengths_y: Frames) -> torch.Tensor:
+  """fp64 ``[B, 2]`` on the device: STOI and ESTOI of the pairs (``x10k[b]`` clean, ``y10k[b]`` processed; fp32 ``[B, N]`` at
+  10 kHz, one shape), the bits of ``stoi_enqueue``'s first two columns, with a graph back to ``y10k``.  NaN where a pair has
+  no segment (its gradient is all zeros).  The energy gate and ``x10k`` are constants: an ``x10k`` that requires grad
+  raises WgError.  The gradient follows the definition the metric uses (include/waveglow_amd.h: wg_stoi_backward, with its
+  conventions at the points that are not smooth) in fp64 and is rounded to fp32 once.  Without grad mode, or when ``y10k``
+  does not require grad, nothing is saved and no graph comes back.  Enqueue-only; no double backward."""
+  if isinstance(x10k, torch.Tensor) and x10k.requires_grad:
+    raise _lib.WgError("stoi_differentiable: only y10k gets a gradient (the gate runs on the clean side); detach x10k")
+  x = _stoi_audio("stoi: x10k", x10k)
+  y = _stoi_audio("stoi: y10k", y10k, x.device)
+  if x.shape != y.shape:
+    raise _lib.WgError(f"stoi_differentiable takes both sides in one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+  lx, ly = _lengths("stoi: lengths_x", lengths_x, x), _lengths("stoi: lengths_y", lengths_y, y)
+  if torch.is_grad_enabled() and y10k.requires_grad:
+    return _StoiFn.apply(x, lx, y10k, ly)
+  return stoi_enqueue(x, lx, y, ly)[:, :2].clone()

@@ -180,3 +180,94 @@ def resample(audio: torch.Tensor, lengths, sr_in, sr_out, *, clip: bool = False)
   lens = check_lengths(lengths, audio.shape[0], audio.shape[1])
   lens_dev = torch.tensor(lens, dtype=torch.int32).to(audio.device)
   return resample_enqueue(audio, lens_dev, sr_in, sr_out, clip=clip), [out_len(n, up, down) for n in lens]
+
+
+# ------------------------------------------------------------------------------------------------- the differentiable path
+_tables_t: Dict[Tuple[int, int, int], torch.Tensor] = {}   # (up, down, device index) -> transposed table on that device
+
+
+def polyphase_table_backward(down: int, half: int, taps: np.ndarray) -> np.ndarray:
+  """The layout ``wg_resample_backward`` reads: fp64 ``[down, Kt]``, ``Kt = ceil((2 half + 1) / down)``,
+  ``table[r, i] = taps[r + i down]``, 0 where that index exceeds ``2 half``.  Input sample ``m`` reads row
+  ``r = (half - m up) mod down`` in ascending ``i``, which is ascending ``n`` of the definition."""
+  n = 2 * half + 1
+  Kt = (n + down - 1) // down
+  padded = np.zeros(Kt * down, dtype=np.float64)
+  padded[:n] = taps
+  return np.array(padded.reshape(Kt, down).T, dtype=np.float64, order="C", copy=True)
+
+
+def _device_table_backward(up: int, down: int, half: int, taps: np.ndarray, device: torch.device) -> torch.Tensor:
+  key = (up, down, _lib.device_index(device))
+  t = _tables_t.get(key)
+  if t is None:
+    t = _tables_t[key] = torch.from_numpy(polyphase_table_backward(down, half, taps)).to(device)
+  return t
+
+
+def resample_backward_enqueue(d_out: torch.Tensor, lengths_dev: torch.Tensor, sr_in, sr_out, n_in: int) -> torch.Tensor:
+  """Enqueue ``wg_resample_backward`` on the current stream: the gradient with respect to the fp32 ``[B, n_in]`` input of
+  ``resample_enqueue(audio, lengths_dev, sr_in, sr_out)`` (not clipped) from ``d_out``, fp32 or fp64 ``[B, n_out]`` with
+  ``n_out >= out_len(n_in)``, the gradient with respect to its result.  ``lengths_dev`` are the lengths of the INPUT rows,
+  int32 ``[B]`` on the device.  Returns fp32 ``[B, n_in]``: written below a row's length, exact zeros behind; nothing of
+  ``d_out`` at or behind ``out_len(length)`` is read."""
+  if not isinstance(d_out, torch.Tensor) or d_out.device.type != "cuda":
+    raise _lib.WgError("resample backward: d_out must be on the GPU (no CPU fallback)")
+  if d_out.dtype not in (torch.float32, torch.float64):
+    raise _lib.WgError(f"resample backward takes float32 or float64 gradients, got {d_out.dtype}")
+  if d_out.dim() != 2 or d_out.shape[0] < 1:
+    raise _lib.WgError(f"resample backward takes d_out [B, n_out], got shape {tuple(d_out.shape)}")
+  if not isinstance(lengths_dev, torch.Tensor) or lengths_dev.dtype != torch.int32 or lengths_dev.device.type != "cuda" or \
+      _lib.device_index(lengths_dev.device) != _lib.device_index(d_out.device) or lengths_dev.dim() != 1 or \
+      lengths_dev.numel() != d_out.shape[0] or not lengths_dev.is_contiguous():
+    raise _lib.WgError(f"resample backward takes the lengths as a contiguous int32 tensor [{d_out.shape[0]}] on {d_out.device}")
+  up, down, half, taps = resample_plan(sr_in, sr_out)
+  B, n_out = d_out.shape
+  n_in = int(n_in)
+  if not 1 <= n_in <= MAX_SAMPLES:
+    raise _lib.WgError(f"resample backward: 1 <= n_in <= {MAX_SAMPLES} expected, got {n_in}")
+  if n_out < out_len(n_in, up, down) or n_out > MAX_PITCH:
+    raise _lib.WgError(f"resample backward: rows of {n_out} gradients do not fit {n_in} samples at {up}/{down}")
+  d_out = d_out.contiguous()
+  table = _device_table_backward(up, down, half, taps, d_out.device)
+  d_in = torch.empty((B, n_in), dtype=torch.float32, device=d_out.device)
+  stream = torch.cuda.current_stream(d_out.device).cuda_stream
+  _lib.check(_lib.load().wg_resample_backward(
+    d_out.data_ptr(), _lib.WG_PCM_F64 if d_out.dtype == torch.float64 else _lib.WG_PCM_F32, lengths_dev.data_ptr(),
+    d_in.data_ptr(), table.data_ptr(), up, down, half, B, n_in, n_out, C.c_void_p(stream)))
+  return d_in
+
+
+class _ResampleFn(torch.autograd.Function):
+  """audio [B, N] fp32 -> ``resample_enqueue`` of it; the backward is one ``wg_resample_backward`` launch and writes to
+  nothing the forward left, so a second backward under retain_graph gives the same bits."""
+
+  @staticmethod
+  def forward(ctx, audio, lens_dev, sr_in, sr_out):
+    ctx.lens, ctx.rates, ctx.n_in = lens_dev, (sr_in, sr_out), audio.shape[1]
+    return resample_enqueue(audio.detach(), lens_dev, sr_in, sr_out)
+
+  @staticmethod
+  def backward(ctx, g):
+    with torch.cuda.device(g.device):
+      return resample_backward_enqueue(g, ctx.lens, ctx.rates[0], ctx.rates[1], ctx.n_in), None, None, None
+
+
+def resample_differentiable(audio: torch.Tensor, lengths, sr_in, sr_out, *, clip: bool = False):
+  """``(out, out_lengths)`` with the bits of ``resample(audio, lengths, sr_in, sr_out, clip=False)`` and a graph back to
+  ``audio`` (fp32 ``[B, N]`` on the GPU only): ``audio.grad`` is the transposed polyphase filter of the incoming gradient
+  (``wg_resample_backward``), exactly 0 behind a row's length.  There is no clipped variant: ``clip=True`` raises WgError.
+  Without grad mode, or when ``audio`` does not require grad, this is plain ``resample``.  No double backward."""
+  if clip:
+    raise _lib.WgError("resample_differentiable: there is no clipped variant of the differentiable path")
+  _check_audio(audio, "resample_differentiable")
+  if audio.dtype != torch.float32:
+    raise _lib.WgError(f"resample_differentiable takes float32 audio, got {audio.dtype}")
+  up, down, _, _ = resample_plan(sr_in, sr_out)
+  lens = check_lengths(lengths, audio.shape[0], audio.shape[1])
+  if not (torch.is_grad_enabled() and audio.requires_grad):
+    return resample(audio, lens, sr_in, sr_out)
+  lens_dev = torch.tensor(lens, dtype=torch.int32).to(audio.device)
+  with torch.cuda.device(audio.device):
+    out = _ResampleFn.apply(audio, lens_dev, sr_in, sr_out)
+  return out, [out_len(n, up, down) for n in lens]
