@@ -732,6 +732,31 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* w, const wg_tr
                             float* const* g_z_early, int32_t n_z_early, int32_t B, int32_t n_frames,
                             void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
 
+/* wg_train_infer_forward / wg_train_infer_backward for a batch of utterances of DIFFERENT lengths: `frames` is a device
+ * array of B mel-frame counts as in wg_infer_ragged, directly after n_frames; every other argument as in the dense calls,
+ * which are these calls with frames == NULL (one implementation; same workspace, wg_train_workspace_bytes).  Utterance b is
+ * mel[b, :, :frames[b]] with z_init[b, :, :32 frames[b]] and z_early[i][b, :, :32 frames[b]], synthesised alone
+ * (src/waveglow/model.py:223-273 on that utterance; the reference has no ragged mode, its convolutions' zero padding at
+ * the end of a sequence, model.py:98-102, is what the padding columns stand for):
+ *   forward   audio[b, :256 frames[b]] has the bits of the batch-of-one call on the utterance, audio behind it is 0.
+ *   backward  g_mel, g_z_init and g_z_early[i] are 0 behind the count and have the bits of the batch-of-one call (same
+ *             scale) in front of it; every entry of `grads` is the sum over the utterances of the batch-of-one calls'
+ *             (up to accumulation order).  The backward takes the counts of its forward.
+ * Nothing behind an utterance's count is read: mel, noise and g_audio may hold NaN there.  The counts are never read on
+ * the host and nothing synchronises: a count <= 0 makes its utterance all padding (zero audio, zero gradients, nothing
+ * added to `grads`), a count above n_frames counts as n_frames; neither reads or writes outside the buffers.
+ * With counts the forward clears the workspace's planes on every call, whatever `fresh` says (the layer kernels leave
+ * padding columns unwritten, and a reused workspace may hold another batch there). */
+int wg_train_infer_forward_ragged(wg_handle* h, const wg_train_weights* w, const void* mel, const void* z_init,
+                                  const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
+                                  int32_t n_frames, const int32_t* frames, int32_t fresh, void* workspace,
+                                  size_t workspace_bytes, int32_t flags, void* stream);
+int wg_train_infer_backward_ragged(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads,
+                                   const float* g_audio, float scale, float sigma, float* g_mel, float* g_z_init,
+                                   float* const* g_z_early, int32_t n_z_early, int32_t B, int32_t n_frames,
+                                   const int32_t* frames, void* workspace, size_t workspace_bytes, int32_t flags,
+                                   void* stream);
+
 /* Diagnostic builds only (-DWG_STAMPS): device buffer of n_tiles*8 uint64 that the WN-layer kernel fills with
  * s_memtime stamps at its phase boundaries (last launch wins).  A no-op pointer in the shipped library. */
 int wg_debug_set_stamp_buffer(wg_handle* h, void* device_buffer);

@@ -44,11 +44,19 @@ __device__ __forceinline__ size_t pos_to_natural(size_t P) {
   return (P & ~(size_t)31) + 8 * ((p >> 2) & 3u) + 4 * (p >> 4) + (p & 3u);
 }
 
+// group-timestep t of utterance b (b < g.B) lies behind the utterance's own frame count (RowGeom::frames): a padding column
+// of a ragged batch.  Its inputs, state and incoming gradients are never loaded -- any of them may be NaN -- and everything
+// written for it is an exact zero.  Dense batch (frames == nullptr, uniform over the launch): never.
+__device__ __forceinline__ bool padding_column(const RowGeom& g, int b, int t) {
+  return g.frames != nullptr && t >= 32 * g.frames[b];
+}
+
 __device__ __forceinline__ bool column_valid(const RowGeom& g, int p, int rr, int& b, int& t) {
   b = rr / g.Fp;
   const int f = rr - b * g.Fp - g.Gf;
   t = 32 * f + p;
-  return b < g.B && f >= 0 && f < g.F && t < g.L;
+  if (!(b < g.B && f >= 0 && f < g.F && t < g.L)) return false;
+  return !padding_column(g, b, t);
 }
 
 }  // namespace
@@ -1024,7 +1032,8 @@ hipError_t launch_pack(const PackArgs& a, hipStream_t s) {
 }
 
 // mel [B][M][T] -> planes [2 chunks][R][64]: row (p, b, q) = mel[b][:, q] (natural channel order, zero padded to 128),
-// identical for every phase; rows of guard frames and frames >= T are zero (transposed-conv padding, model.py:145).
+// identical for every phase; rows of guard frames and frames >= T are zero (transposed-conv padding, model.py:145), and so
+// are the frames behind an utterance's own count (RowGeom::frames), which are never loaded (kernels.hip: mel_pack_kernel).
 __global__ void __launch_bounds__(256) mel_plane_kernel(const void* __restrict__ mel, int io_f16, int M, RowGeom g,
                                                         _Float16* __restrict__ melp) {
   const size_t n = (size_t)kPhases * g.Rp * 128;
@@ -1034,7 +1043,7 @@ __global__ void __launch_bounds__(256) mel_plane_kernel(const void* __restrict__
     const int rr = (int)(row % g.Rp);
     const int b = rr / g.Fp, f = rr - b * g.Fp - g.Gf;
     float v = 0.0f;
-    if (i < M && b < g.B && f >= 0 && f < g.T) {
+    if (i < M && b < g.B && f >= 0 && f < g.T && (g.frames == nullptr || f < g.frames[b])) {
       const size_t src = ((size_t)b * M + i) * g.T + f;
       v = io_f16 ? (float)((const _Float16*)mel)[src] : ((const float*)mel)[src];
     }
@@ -1125,6 +1134,7 @@ __device__ __forceinline__ void start_dgrad_rows(const _Float16* __restrict__ GX
       b = (int)(r32 / (unsigned)L);
       t = (int)(r32 - (unsigned)b * (unsigned)L);
       pr = (unsigned)kRowPad + (unsigned)(t & 31) * (unsigned)g.Rp + (unsigned)b * (unsigned)g.Fp + (unsigned)g.Gf + (unsigned)(t >> 5);
+      if (padding_column(g, b, t)) pr = 0xffffffffu;      // ragged batch: d x_0 of a padding column is not read, its sum is 0
     }
     s_prow[threadIdx.x] = pr;
   }
@@ -1302,6 +1312,17 @@ __global__ void __launch_bounds__(FB_ROWS) inv_bwd_pre_kernel(const InvBwdArgs a
   const unsigned r32 = (unsigned)row;
   const int b = (int)(r32 / (unsigned)L), t = (int)(r32 - (unsigned)b * (unsigned)L);
   const int h = a.h, c = a.c;
+  if (padding_column(a.g, b, t)) {      // ragged batch: nothing of the row is loaded, its gradients are exact zeros
+    float4* gp = (float4*)(a.GZ + row * 8);
+    gp[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+    gp[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    half8 z16;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z16[j] = (_Float16)0.0f;
+    const size_t prow = (size_t)kRowPad + (size_t)(t & 31) * a.g.Rp + (size_t)b * a.g.Fp + a.g.Gf + (t >> 5);
+    *(half8*)(a.GO + prow * 64) = z16;
+    return;
+  }
   float g[kMaxGroup], y[kMaxGroup], o[kMaxGroup];
   {
     const float4* yp = (const float4*)(a.Y + row * 8);
@@ -1371,16 +1392,19 @@ __global__ void __launch_bounds__(FB_ROWS) inv_bwd_post_kernel(const InvBwdArgs 
   int b = 0, t = 0;
   start_dgrad_rows(a.GX, a.wstart, a.C, h, a.g, row, s_prow, s_wn, b, t);
   if (row >= nrows) return;
+  const bool pad = padding_column(a.g, b, t);      // ragged batch: GZ is not loaded, every output of the row is an exact zero
   float gy[kMaxGroup];
-  {
+#pragma unroll
+  for (int j = 0; j < kMaxGroup; ++j) gy[j] = 0.0f;
+  if (!pad) {
     const float4* gp = (const float4*)(a.GZ + row * 8);
     const float4 g0 = gp[0], g1 = gp[1];
     gy[0] = g0.x; gy[1] = g0.y; gy[2] = g0.z; gy[3] = g0.w; gy[4] = g1.x; gy[5] = g1.y; gy[6] = g1.z; gy[7] = g1.w;
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    if (j < h) gy[j] += s_wn[threadIdx.x][j];
-  const float f = a.sigma / a.scale;
+    if (j < h && !pad) gy[j] += s_wn[threadIdx.x][j];
+  const float f = pad ? 0.0f : a.sigma / a.scale;
   if (a.last) {
     if (a.g_z_init) {
 #pragma unroll
@@ -1422,9 +1446,10 @@ __global__ void __launch_bounds__(FB_ROWS) inv_dw1x1_kernel(const InvDwArgs a) {
   float gv[kMaxGroup], wv[kMaxGroup];
 #pragma unroll
   for (int j = 0; j < kMaxGroup; ++j) { gv[j] = 0.0f; wv[j] = 0.0f; }
-  if (row < nrows) {
-    const unsigned r32 = (unsigned)row;
-    const int b = (int)(r32 / (unsigned)L), t = (int)(r32 - (unsigned)b * (unsigned)L);
+  const unsigned r32 = (unsigned)row;
+  const int b = (int)(r32 / (unsigned)L), t = (int)(r32 - (unsigned)b * (unsigned)L);
+  // (a padding column of a ragged batch loads nothing and adds zeros to the workgroup's sum)
+  if (row < nrows && !padding_column(a.g, b, t)) {
     float g[kMaxGroup], y[kMaxGroup], o[kMaxGroup], u[kMaxGroup];
     {
       const float4* yp = (const float4*)(a.Y + row * 8);
@@ -1597,6 +1622,10 @@ __global__ void __launch_bounds__(64 * DM_WAVES) dmel_kernel(const DmelArgs a) {
   const int rr = blockIdx.x * 32 + c;
   const int b = rr / g.Fp, f = rr - b * g.Fp - g.Gf;
   const bool col_ok = b < g.B && f >= 0;
+  // frames of this column's utterance that carry a gradient: all F, or its own count (RowGeom::frames): d spect behind it is
+  // not read and d mel behind it is written as 0
+  int flim = g.F;
+  if (col_ok && g.frames != nullptr && g.frames[b] < flim) flim = g.frames[b];
   const int mc = a.M8 / 64;
   const size_t R64 = (size_t)g.R * 64;
   const size_t a_pair = (size_t)mc * NB * 2048;          // wupt elements per (phase, tap) pair
@@ -1612,7 +1641,7 @@ __global__ void __launch_bounds__(64 * DM_WAVES) dmel_kernel(const DmelArgs a) {
   auto fetch = [&](int st, half8 (*da)[4], half8* db) {
     const int q = st / mc, t = st - q * mc;
     const int pj = w + DM_WAVES * q, p = pj >> 2, j = pj & 3;
-    const bool ok = col_ok && f + j < g.F;
+    const bool ok = col_ok && f + j < flim;
     const _Float16* bsrc = a.GSP + (size_t)t * R64 + ((size_t)kRowPad + (size_t)p * g.Rp + rr + j) * 64 + 32 * h;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -1669,7 +1698,7 @@ __global__ void __launch_bounds__(64 * DM_WAVES) dmel_kernel(const DmelArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int i = 32 * ib + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (i < a.M) a.g_mel[((size_t)b * a.M + i) * g.T + f] = acc[ib][e] * a.inv_scale;
+        if (i < a.M) a.g_mel[((size_t)b * a.M + i) * g.T + f] = f < flim ? acc[ib][e] * a.inv_scale : 0.0f;
       }
   }
   const int nz = g.T - fmax;

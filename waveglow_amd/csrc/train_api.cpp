@@ -934,15 +934,17 @@ int wg_train_backward(wg_handle* h, const wg_train_weights* wt, const wg_train_g
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-// common checks and geometry of both calls: audio_len = 256 n_frames (infer's trim, model.py:228)
-int infer_setup(wg_handle* h, const wg_train_weights* wt, int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace,
-                size_t workspace_bytes, int32_t flags, Ctx& x, const float** winv) {
+// common checks and geometry of both calls: audio_len = 256 n_frames (infer's trim, model.py:228).  frames (device, [B], or
+// null): the utterances' own frame counts -- every launch of the call takes its padding columns from x.g.frames.
+int infer_setup(wg_handle* h, const wg_train_weights* wt, int32_t n_z_early, int32_t B, int32_t n_frames, const int32_t* frames,
+                void* workspace, size_t workspace_bytes, int32_t flags, Ctx& x, const float** winv) {
   if (!h) return fail(WG_ERR_INVALID, "null handle");
   const wg_config* c = &h->cfg;
   if (n_frames < 1) return fail(WG_ERR_INVALID, "bad n_frames");
   if (c->n_flows > 64) return fail(WG_ERR_INVALID, "too many flows");
   int rc = setup(h, B, n_frames, n_frames * c->upsample_stride, workspace, workspace_bytes, flags, x);
   if (rc) return rc;
+  x.g.frames = (const int*)frames;
   if ((rc = check_weights(wt, c->n_flows))) return rc;
   if (n_z_early != n_early_flows(*c)) return fail(WG_ERR_INVALID, "wrong number of early-noise tensors");
   // W_k^-1: the per-call weights' own (wg_train_prepare inverted them on the device), else the finalised handle's
@@ -976,11 +978,19 @@ int wg_train_infer_forward(wg_handle* h, const wg_train_weights* wt, const void*
                            const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
                            int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
                            void* stream) {
+  return wg_train_infer_forward_ragged(h, wt, mel, z_init, z_early, n_z_early, sigma, audio, B, n_frames, nullptr, fresh,
+                                       workspace, workspace_bytes, flags, stream);
+}
+
+int wg_train_infer_forward_ragged(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* z_init,
+                                  const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
+                                  int32_t n_frames, const int32_t* frames, int32_t fresh, void* workspace,
+                                  size_t workspace_bytes, int32_t flags, void* stream) {
   if (!wt || !mel || !z_init || !audio || !workspace || (n_z_early > 0 && !z_early))
     return fail(WG_ERR_INVALID, "null argument");
   Ctx x;
   const float* winv[64];
-  int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, flags, x, winv);
+  int rc = infer_setup(h, wt, n_z_early, B, n_frames, frames, workspace, workspace_bytes, flags, x, winv);
   if (rc) return rc;
   for (int i = 0; i < n_z_early; ++i)
     if (!z_early[i]) return fail(WG_ERR_INVALID, "null early-noise tensor");
@@ -989,7 +999,11 @@ int wg_train_infer_forward(wg_handle* h, const wg_train_weights* wt, const void*
   hipStream_t sB;
   if ((rc = second_chain_stream(h, x, s, sB))) return rc;
   const int BNw = fwd_block_n(x);
-  if (fresh) TR_TRY(hipMemsetAsync(workspace, 0, x.w.zero_bytes, s));
+  // Ragged batch: the planes are cleared on EVERY call, not only on a fresh workspace.  The layer kernels never write a
+  // padding column (X, T, S, A in the forward; GP, GXL in the backward), and valid columns read them there -- the dilated
+  // taps near an utterance's end, the weight-gradient jobs over every row -- as the zeros of a batch-of-one call: whatever
+  // a dense call, or a call with other counts, left in a reused workspace would be read instead.
+  if (fresh || frames) TR_TRY(hipMemsetAsync(workspace, 0, x.w.zero_bytes, s));
   if ((rc = spect_planes(x, wt, mel, s))) return rc;
   auto base = [&]() {
     FlowArgs f;
@@ -1041,11 +1055,19 @@ int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const wg_t
                             float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
                             int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace, size_t workspace_bytes,
                             int32_t flags, void* stream) {
+  return wg_train_infer_backward_ragged(h, wt, gr, g_audio, scale, sigma, g_mel, g_z_init, g_z_early, n_z_early, B, n_frames,
+                                        nullptr, workspace, workspace_bytes, flags, stream);
+}
+
+int wg_train_infer_backward_ragged(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_audio,
+                                   float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
+                                   int32_t n_z_early, int32_t B, int32_t n_frames, const int32_t* frames, void* workspace,
+                                   size_t workspace_bytes, int32_t flags, void* stream) {
   if (!wt || !g_audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
   if (!(scale > 0.f)) return fail(WG_ERR_INVALID, "scale must be positive");
   Ctx x;
   const float* winv[64];
-  int rc = infer_setup(h, wt, n_z_early, B, n_frames, workspace, workspace_bytes, flags, x, winv);
+  int rc = infer_setup(h, wt, n_z_early, B, n_frames, frames, workspace, workspace_bytes, flags, x, winv);
   if (rc) return rc;
   if (g_mel && !wt->wupt) return fail(WG_ERR_INVALID, "g_mel needs wg_train_weights.wupt (packed by wg_train_prepare)");
   // gr == null: the data-gradient chain alone.  Otherwise the packed weight gradients as well, flow by flow behind the data

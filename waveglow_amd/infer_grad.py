@@ -16,6 +16,10 @@ synthesises): the backward then also runs the training direction's weight-gradie
   data-gradient chain, then the d spect GEMM and the transposed upsample for ``d mel``; with ``grads`` also the packed
   weight gradients (``GradBuffers``), among them ``d W_k = - sum (W_k^-T d w) (x) w`` of every inverse 1x1 step.
 
+Both are called through their ``_ragged`` forms, which take the per-utterance frame counts of a padded batch
+(``infer_differentiable(..., frames=)``: int32 [B] on the device, kept on ``ctx`` for the backward) and are the dense calls
+when there are none.
+
 The binding uses ``_TrainFn``'s plumbing (waveglow_amd/train.py): ``_Weights`` from ``wg_train_prepare``, one training
 workspace per outstanding graph (``request_workspace``), the fp16 loss scale and ``model.grad_finite``
 (``set_grad_finite``), ``param_grad_views``.  Its own: the stale-weights check.  There is no fallback: CPU tensors raise.
@@ -35,16 +39,17 @@ from .train import (GradBuffers, _ddp_group, _ptr, _SlotGuard, _Weights, canonic
 
 class _InferFn(torch.autograd.Function):
   """Inputs: model, sigma, loss scale (0 = automatic), weight-norm flag, wg_train flags (``WG_TRAIN_RECOMPUTE``: activation
-  recomputation, the backward runs with its forward's flags), number of early-noise tensors, the weight-gradient mode, mel,
+  recomputation, the backward runs with its forward's flags), number of early-noise tensors, the weight-gradient mode, the
+  frame counts of a ragged batch (int32 [B] on the device, or None: kept on ``ctx`` for the backward, never differentiated), mel,
   z_init, z_early..., then the module's parameters in the library's canonical order (the library reads them through
   ``wg_train_prepare``; without the weight-gradient mode they are constants: never differentiated).  Output: audio
   [B, 256 T] fp32.  backward() returns only what ``ctx.needs_input_grad`` asks for among mel, z_init, the z_early entries
   and -- in the weight-gradient mode -- the parameters, each parameter gradient a view of ONE flat buffer (as ``_TrainFn``)."""
 
-  N_META = 7      # model, sigma, scale, wn, flags, n_early, wgrads
+  N_META = 8      # model, sigma, scale, wn, flags, n_early, wgrads, frames
 
   @staticmethod
-  def forward(ctx, model, sigma, scale, wn, flags, n_early, wgrads, mel, z_init, *rest):
+  def forward(ctx, model, sigma, scale, wn, flags, n_early, wgrads, frames, mel, z_init, *rest):
     z_early, params = rest[:n_early], rest[n_early:]
     # frozen: finalised with the current weights, the W^-1 of infer.  Weight-gradient mode: the weights move every step,
     # W^-1 comes with the per-call weights and the inference engine is left alone
@@ -60,9 +65,11 @@ class _InferFn(torch.autograd.Function):
     ws = slot["ws"]
     audio = torch.empty((B, S), dtype=torch.float32, device=mel.device)
     ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
-    _lib.check(lib.wg_train_infer_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
-                                          float(sigma), _ptr(audio), B, T, 1 if fresh else 0, _ptr(ws), ws.numel(), flags,
-                                          C.c_void_p(stream)))
+    _lib.check(lib.wg_train_infer_forward_ragged(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
+                                                 float(sigma), _ptr(audio), B, T,
+                                                 _ptr(frames) if frames is not None else None, 1 if fresh else 0, _ptr(ws),
+                                                 ws.numel(), flags, C.c_void_p(stream)))
+    ctx.frames = frames
     ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.guard = model, wts, ws, (B, M, T), _SlotGuard(slot)
     ctx.flags, ctx.wgrads = flags, wgrads
     ctx.sigma, ctx.n_early, ctx.n_params = float(sigma), n_early, len(params)
@@ -107,11 +114,12 @@ class _InferFn(torch.autograd.Function):
     gstruct, _keep = bufs.struct() if want_params else (None, None)
     views = None
     try:
-      _lib.check(lib.wg_train_infer_backward(eng.handle, C.byref(ctx.wts.struct),
-                                             C.byref(gstruct) if want_params else None, _ptr(ga), C.c_float(ctx.scale),
-                                             C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
-                                             _ptr(g_zi) if want_zi else None, ze, ne, B, T, _ptr(ctx.ws), ctx.ws.numel(),
-                                             ctx.flags, C.c_void_p(stream)))
+      _lib.check(lib.wg_train_infer_backward_ragged(eng.handle, C.byref(ctx.wts.struct),
+                                                    C.byref(gstruct) if want_params else None, _ptr(ga), C.c_float(ctx.scale),
+                                                    C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
+                                                    _ptr(g_zi) if want_zi else None, ze, ne, B, T,
+                                                    _ptr(ctx.frames) if ctx.frames is not None else None,
+                                                    _ptr(ctx.ws), ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
       if want_params:      # (no logdet term in this direction)
         views = param_grad_views(eng, ctx.wts, gstruct, ctx.shapes, stream)
     finally:
@@ -124,18 +132,51 @@ class _InferFn(torch.autograd.Function):
     return (None,) * nm + (g_mel, g_zi, *g_ze, *grads)
 
 
+def _check_frames(frames, spect: torch.Tensor):
+  """The counts as a CPU int32 tensor [B], or None for a device tensor.  Host counts (list, tuple, CPU integer tensor) are
+  range-checked here, before any launch and before anything else about the call is looked at; a device tensor is only
+  checked for its type and shape -- its values are trusted and never read on the host."""
+  if spect.dim() != 3:
+    raise _lib.WgError(f"infer_differentiable: mel [B, n_mel, T] expected, got {tuple(spect.shape)}")
+  B, _, T = spect.shape
+  if isinstance(frames, torch.Tensor) and frames.device.type == "cuda":
+    if frames.device != spect.device or frames.dtype != torch.int32 or frames.dim() != 1 or frames.numel() != B:
+      raise _lib.WgError(f"infer_differentiable: frame counts on the device must be int32 [{B}] on {spect.device}")
+    return None
+  if isinstance(frames, torch.Tensor):
+    if frames.dtype.is_floating_point or frames.dtype == torch.bool or frames.dim() != 1:
+      raise _lib.WgError(f"infer_differentiable: a 1-d tensor of integer frame counts expected, got {frames.dtype} "
+                         f"{tuple(frames.shape)}")
+    frames = frames.tolist()
+  elif not isinstance(frames, (list, tuple)):
+    raise _lib.WgError("infer_differentiable: frames must be a list, a tuple or a tensor of integer frame counts")
+  if any(isinstance(n, float) or isinstance(n, bool) for n in frames):
+    raise _lib.WgError(f"infer_differentiable: integer frame counts expected, got {list(frames)}")
+  host = [int(n) for n in frames]
+  if len(host) != B:
+    raise _lib.WgError(f"infer_differentiable: {len(host)} frame counts for a batch of {B}")
+  if any(n < 1 or n > T for n in host):
+    raise _lib.WgError(f"infer_differentiable: frame counts in [1, {T}] expected, got {host}")
+  return torch.tensor(host, dtype=torch.int32)
+
+
 def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_early: List[torch.Tensor], sigma: float,
-                         grad_scale: float = 0.0, recompute: bool = False, weight_grads: bool = False) -> torch.Tensor:
+                         grad_scale: float = 0.0, recompute: bool = False, weight_grads: bool = False,
+                         frames=None) -> torch.Tensor:
   """``model.infer_with_noise(spect, z_init, z_early, sigma)`` (fp32) with an autograd graph back to ``spect``, ``z_init``
   and every ``z_early[i]`` that requires grad -- and, with ``weight_grads``, to every parameter that requires grad.
   Without grad mode, or when nothing requires grad, exactly ``infer_with_noise`` (nothing is saved).  ``recompute``:
-  activation recomputation (``WG_TRAIN_RECOMPUTE``)."""
+  activation recomputation (``WG_TRAIN_RECOMPUTE``).  ``frames``: per-utterance mel-frame counts of a ragged batch
+  (``WaveGlow.infer_differentiable``), None for a dense one."""
+  fr_host = _check_frames(frames, spect) if frames is not None else None
   ins = [spect, z_init] + list(z_early)
   for t in ins:
     if t.device.type != "cuda":
       raise _lib.WgError("waveglow_amd runs on MI355X only: there is no CPU fallback")
     if t.dtype != torch.float32:
       raise _lib.WgError("infer_differentiable takes float32 mel and noise (the training direction's kernels)")
+  # what infer_with_noise takes (it checks host counts where they are, without a synchronise)
+  fr_plain = fr_host if fr_host is not None else frames
   eng = model._get_engine(spect.device, need_weights=False)
   if eng.width != eng.n_channels or eng.mel_width != eng.n_mel or int(eng.lib.wg_wn_waves(eng.n_channels)) <= 0:
     raise _lib.WgError(f"n_channels={eng.n_channels}, n_mel_channels={eng.n_mel}: infer_differentiable runs on the training "
@@ -153,14 +194,21 @@ def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_ear
                        "(enable_data_parallel covers the training direction only): unset model.ddp_group and reduce the "
                        "parameter gradients yourself")
   if not torch.is_grad_enabled():
-    return model.infer_with_noise(spect, z_init, z_early, sigma)
+    return model.infer_with_noise(spect, z_init, z_early, sigma, frames=fr_plain)
   trainable = any(p.requires_grad for p in model.parameters())
   if trainable and not weight_grads:
     raise _lib.WgError("infer_differentiable treats the vocoder's weights as constants and gives no weight gradients: "
                        "freeze the model first (model.requires_grad_(False)) or ask for them (weight_grads=True)")
   if not trainable and not any(t.requires_grad for t in ins):
-    return model.infer_with_noise(spect, z_init, z_early, sigma)
+    return model.infer_with_noise(spect, z_init, z_early, sigma, frames=fr_plain)
   _names, tensors, wn = canonical_params(model, eng)
   ins = [t.contiguous() for t in ins]
   flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
-  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, flags, n_early, bool(weight_grads), *ins, *tensors)
+  fr_dev = None
+  if fr_host is not None:
+    fr_dev = fr_host.to(spect.device)          # one small copy, nothing synchronises
+  elif frames is not None:
+    # trusted device counts: one outside [1, T] becomes 0, which the kernels take as an utterance that is all padding
+    fr_dev = frames.contiguous()
+    fr_dev = fr_dev.masked_fill((fr_dev < 1) | (fr_dev > spect.shape[2]), 0)
+  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, flags, n_early, bool(weight_grads), fr_dev, *ins, *tensors)

@@ -400,7 +400,8 @@ class WaveGlow(nn.Module):
     return self.infer_with_noise(spect, *self._draw_noise(spect), sigma)
 
   def infer_differentiable(self, spect: torch.Tensor, sigma: float = 1.0, z_init: Optional[torch.Tensor] = None,
-                           z_early: Optional[List[torch.Tensor]] = None, *, weight_grads: bool = False) -> torch.Tensor:
+                           z_early: Optional[List[torch.Tensor]] = None, *, weight_grads: bool = False,
+                           frames=None) -> torch.Tensor:
     """``infer_with_noise(spect, z_init, z_early, sigma)`` at fp32 I/O (model.py:223-273) whose output carries an autograd
     graph back to ``spect`` and to the noise: ``loss.backward()`` fills ``spect.grad`` / ``z_init.grad`` /
     ``z_early[i].grad`` for those that require grad (waveglow_amd/infer_grad.py).  Noise that is not given is drawn as
@@ -415,11 +416,22 @@ class WaveGlow(nn.Module):
     backward pass.  Takes the training direction's widths (n_channels 64 / 128 / 256 / 512, n_mel_channels % 16 == 0).
     ``model.recompute_activations = True`` keeps the WN layer planes of two flows instead of twelve between this call and
     ``backward()``, which recomputes the others flow by flow (``gradient_workspace_bytes`` gives both sizes): the way to
-    take gradients through whole utterances."""
+    take gradients through whole utterances.
+    ``frames`` (keyword-only): mel-frame counts of a padded batch of utterances of different lengths.  Utterance ``b`` is
+    ``spect[b, :, :frames[b]]`` with ``z_init[b, :, :32 * frames[b]]`` and ``z_early[i][b, :, :32 * frames[b]]``,
+    synthesised alone: ``audio[b, :256 * frames[b]]`` has the bits of that batch-of-one call and the audio behind it is 0;
+    ``spect.grad``, ``z_init.grad`` and ``z_early[i].grad`` are 0 behind the count and have the single call's bits in
+    front of it (same loss scale); with ``weight_grads`` every parameter gradient is the sum of the single calls'.  Nothing
+    behind a count is read -- mel, noise and the incoming audio gradient may hold NaN there.  A list, tuple or CPU integer
+    tensor is checked before any launch (every count in ``[1, T]``, else ``WgError``) and uploaded in one small copy; an
+    int32 device tensor is trusted and never read on the host: a count outside ``[1, T]`` makes its utterance all padding
+    (zero audio, zero gradients).  None, or ``[T] * B``: the dense result, bit for bit.  The automatic loss scale is
+    that of the padded tensor.  Without grad mode, or when nothing requires grad, the call is
+    ``infer_with_noise(..., frames=)``, which holds a device tensor to ``[1, T]`` with an assertion of its own."""
     z_init, z_early = self._draw_noise(spect, z_init, z_early)
     from .infer_grad import infer_differentiable
     return infer_differentiable(self, spect, z_init, list(z_early), sigma, float(getattr(self, "grad_scale", 0.0)),
-                                bool(self.recompute_activations), bool(weight_grads))
+                                bool(self.recompute_activations), bool(weight_grads), frames)
 
   def forward(self, forward_input):
     """model.py:178-221: (mel [B,M,F], audio [B,S]) -> (z [B,8,L], [log_s_k], [log_det_W_k]).
