@@ -106,13 +106,37 @@ class _LogDet(torch.autograd.Function):
     return g * (W if ctx.fault else torch.inverse(W).t()), None
 
 
+class _ConvWgradLast(torch.autograd.Function):
+  """A dilated 3-tap conv with exact values and exact data and bias gradients whose WEIGHT gradient omits the term of the
+  last column (a weight-gradient kernel whose last slab stops one column short)."""
+
+  @staticmethod
+  def forward(ctx, x, w, b, d):
+    ctx.save_for_backward(x, w)
+    ctx.d = d
+    return F.conv1d(x, w, b, dilation=d, padding=d)
+
+  @staticmethod
+  def backward(ctx, g):
+    x, w = ctx.saved_tensors
+    d = ctx.d
+    short = torch.cat([g[:, :, :-1], torch.zeros_like(g[:, :, -1:])], 2)
+    return (torch.nn.grad.conv1d_input(x.shape, w, g, dilation=d, padding=d),
+            torch.nn.grad.conv1d_weight(x, w.shape, short, dilation=d, padding=d), g.sum((0, 2)), None)
+
+
 class Prec:
   """What is rounded (``r16``: fp16 operands and saved activations; ``gscale``: fp16 gradient planes at that loss scale),
   which fault is planted, and an optional trace of the pre-activations and ``log_s``.
   Faults: "winv_t" (W^T for W^-1 in synthesis), "logdet_grad" (W for W^-T in the logdet gradient), "no_logdet" (the logdet
   term dropped from the loss), "clamp4" (the tanh argument clamped to +-4: a clamp on a instead of on the exponent),
   "clamp_b4" (the same clamp on the sigmoid's argument), ("leak", k, i) (a batch leak: in layer i of flow k the right-hand
-  padding of utterance b holds the first ``d`` columns of utterance b + 1; the last utterance keeps its zeros)."""
+  padding of utterance b holds the first ``d`` columns of utterance b + 1; the last utterance keeps its zeros).
+  Column faults of layer i of flow k (``d`` = 2^i; tests/_seams.py): ("drop_col", k, i) (the in-layer's input loses the
+  utterance's last column), ("drop_tap", k, i) (the left tap of column ``d``, which reads column 0, is lost),
+  ("seam", k, i, c) (at column ``c`` the left tap reads column c - d - 1 instead of c - d: a tile that stages its halo
+  one column off), ("wgrad_last", k, i) (backward only: the gradient of ``in_layers.i.weight`` omits the last column's
+  term; values and data gradients stay exact)."""
 
   def __init__(self, r16=False, gscale=None, fault=None, trace=None, dither=None):
     self.r16, self.gscale, self.fault, self.trace, self.dither = r16, gscale, fault, trace, dither
@@ -163,6 +187,22 @@ def _leaky_pad(x, d):
   return torch.cat([x.new_zeros(x.size(0), x.size(1), d), x, nxt, x.new_zeros(x.size(0), x.size(1), d - n)], 2)
 
 
+def _left_tap_shift(x, win, d, fault):
+  """What "drop_tap" / "seam" add to the in-layer's output: zero but in one column, where the left tap's term W[..., 0] x[c - d]
+  is removed and, for "seam", the term of column c - d - 1 (zero when that is in front of the utterance) put in its place."""
+  L = x.size(2)
+  c = d if fault[0] == "drop_tap" else fault[3]
+  delta = x.new_zeros(x.size(0), win.size(0), L)
+  if not d <= c < L:
+    return delta
+  lost = x[:, :, c - d]
+  if fault[0] == "seam":
+    lost = lost - (x[:, :, c - d - 1] if c - d - 1 >= 0 else torch.zeros_like(lost))
+  onehot = torch.zeros(L, dtype=x.dtype)
+  onehot[c] = 1.0
+  return -(lost @ win[:, :, 0].t())[:, :, None] * onehot
+
+
 def _wn(w, k, a0, spect, cfg, P):
   """WN.forward (model.py:115-138) -> [b ; log_s]."""
   C, p = cfg.n_channels, f"WN.{k}."
@@ -171,10 +211,18 @@ def _wn(w, k, a0, spect, cfg, P):
   output = 0
   for i in range(cfg.n_layers):
     d = 2 ** i
-    if P.fault == ("leak", k, i):
-      a = F.conv1d(_leaky_pad(x, d), P.weight(w[p + f"in_layers.{i}.weight"]), w[p + f"in_layers.{i}.bias"], dilation=d)
+    win, b_in = P.weight(w[p + f"in_layers.{i}.weight"]), w[p + f"in_layers.{i}.bias"]
+    fault = P.fault if isinstance(P.fault, tuple) and P.fault[1:3] == (k, i) else (None,)
+    if fault[0] == "leak":
+      a = F.conv1d(_leaky_pad(x, d), win, b_in, dilation=d)
+    elif fault[0] == "drop_col":
+      a = F.conv1d(torch.cat([x[:, :, :-1], torch.zeros_like(x[:, :, -1:])], 2), win, b_in, dilation=d, padding=d)
+    elif fault[0] == "wgrad_last":
+      a = _ConvWgradLast.apply(x, win, b_in, d)
     else:
-      a = F.conv1d(x, P.weight(w[p + f"in_layers.{i}.weight"]), w[p + f"in_layers.{i}.bias"], dilation=d, padding=d)
+      a = F.conv1d(x, win, b_in, dilation=d, padding=d)
+      if fault[0] in ("drop_tap", "seam"):
+        a = a + _left_tap_shift(x, win, d, fault)
     a = P.gplane(a + cond[:, 2 * C * i:2 * C * (i + 1)])
     if P.trace is not None:
       P.trace.setdefault("a", []).append(a[:, :C].detach())
@@ -266,15 +314,16 @@ def _leaves(sd, dtype):
   return {k: v.to(dtype).clone().requires_grad_(True) for k, v in sd.items()}
 
 
-def run_train(sd, mel, wav, cfg, P=EXACT, dtype=torch.float64):
+def run_train(sd, mel, wav, cfg, P=EXACT, dtype=torch.float64, u=None):
   """Forward, loss and one backward on the state dict as given (weight-norm or dense form).  {quantity: tensor}:
-  z, log_s.k, log_det (vector), loss, p/<parameter>, d mel, d audio."""
+  z, log_s.k, log_det (vector), loss, p/<parameter>, d mel, d audio.  With ``u`` the backward is that of sum(z u), a
+  cotangent on z alone, instead of the loss's."""
   leaves = _leaves(sd, dtype)
   m, a = mel.to(dtype).clone().requires_grad_(True), wav.to(dtype).clone().requires_grad_(True)
   z, log_s, log_det = forward(compose(leaves), m, a, cfg, P)
   loss = loss_fn(z, log_s, log_det, P)
   names = list(leaves)
-  gs = torch.autograd.grad(loss, [leaves[n] for n in names] + [m, a])
+  gs = torch.autograd.grad(loss if u is None else (z * u.to(dtype)).sum(), [leaves[n] for n in names] + [m, a])
   out = {"z": z.detach(), "log_det": torch.stack([x.detach() for x in log_det]), "loss": loss.detach().reshape(1)}
   out.update({f"log_s.{k}": ls.detach() for k, ls in enumerate(log_s)})
   out.update({f"p/{n}": g for n, g in zip(names, gs[:len(names)])})
@@ -304,20 +353,21 @@ def run_infer(sd, mel, z_init, z_early, sigma, cfg, P=EXACT, dtype=torch.float64
   return out
 
 
-def emulated(direction, sd, inputs, cfg, fault=None, r=None, dither=None):
+def emulated(direction, sd, inputs, cfg, fault=None, r=None, dither=None, u=None):
   """The fp64 oracle with the documented fp16 roundings (module docstring) on ``inputs``: (mel, wav) for "fwd",
-  (mel, z_init, z_early) for "inv".  The gradient planes are rounded at the automatic loss scale.  ``dither``: _Q."""
+  (mel, z_init, z_early) for "inv".  The gradient planes are rounded at the automatic loss scale.  ``dither``: _Q.
+  ``u``: the cotangent on z of run_train."""
   if direction == "fwd":
     mel, wav = inputs
     n = wav.size(0) * (wav.size(1) // cfg.n_group) * cfg.n_group
-    return run_train(sd, mel, wav, cfg, Prec(True, grad_scale(n), fault, dither=dither))
+    return run_train(sd, mel, wav, cfg, Prec(True, grad_scale(n), fault, dither=dither), u=u)
   mel, z_init, z_early = inputs
   return run_infer(sd, mel, z_init, z_early, SIGMA, cfg, Prec(True, grad_scale(mel.size(0) * 256 * mel.size(2)), fault, dither=dither), r=r)
 
 
-def exact(direction, sd, inputs, cfg, fault=None, r=None, dtype=torch.float64):
+def exact(direction, sd, inputs, cfg, fault=None, r=None, dtype=torch.float64, u=None):
   if direction == "fwd":
-    return run_train(sd, inputs[0], inputs[1], cfg, Prec(fault=fault), dtype)
+    return run_train(sd, inputs[0], inputs[1], cfg, Prec(fault=fault), dtype, u=u)
   return run_infer(sd, inputs[0], inputs[1], inputs[2], SIGMA, cfg, Prec(fault=fault), dtype, r=r)
 
 
@@ -336,14 +386,18 @@ def make_inputs(name, direction, draw=0):
   """The batch of a case: (mel, wav) or (mel, z_init, z_early).  Draw 0 is seeded as the other fixtures seed theirs (and
   the noise comes from the global CPU RNG in the order the reference's ``infer`` draws it); draws 1, 2 shift the seeds."""
   over, B, T, _, _ = CASES[name]
-  hp = HParams(**over)
+  return make_inputs_at(HParams(**over), B, T, direction, draw)
+
+
+def make_inputs_at(hp, B, T, direction, draw=0, crop=CROP):
+  """make_inputs for any model and shape (``crop``: samples the waveform is shorter than 256 T)."""
   mel = synthetic.make_mel(B, T, hp.n_mel_channels, seed=1234 + B + T + 1000 * draw)
   if direction == "fwd":
     # a waveform with loud and quiet stretches (Gaussian samples under a log-normal envelope of 64-sample blocks, clipped
     # to +-1) instead of the other fixtures' uniform noise: speech has a high crest factor, and it is the rare loud
     # sample that drives a trained gate deep into saturation while most of the gate stays in its working range
     g = torch.Generator().manual_seed(99 + T + 1000 * draw)
-    S = 256 * T - CROP
+    S = 256 * T - crop
     env = torch.randn(B, (S + 63) // 64, generator=g).repeat_interleave(64, dim=1)[:, :S]
     return mel, (0.05 * torch.randn(B, S, generator=g) * torch.exp(0.6 * env)).clamp(-1.0, 1.0)
   z_init, z_early = K.replay_noise(hp, B, 32 * T, noise_seed(T, draw))
