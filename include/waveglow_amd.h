@@ -431,6 +431,53 @@ int wg_stoi_backward(const float* y, int32_t B, int32_t pitch, const wg_stoi_par
                      const void* saved, size_t saved_bytes, double* d_y, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- Soft-DTW: the warped distance of wg_metrics_dtw as a training signal, no handle -----------------------------------
+ * Cuturi and Blondel, "Soft-DTW: a differentiable loss function for time-series", ICML 2017; the reference has no
+ * counterpart.  Inputs as wg_metrics_dtw: feat_a [B][K][tmax_a], feat_b [B][K][tmax_b] fp32 device, frame counts int32
+ * device [B], read by the kernels only; 1 <= K <= 128, 1 <= tmax <= 4096, gamma > 0 and finite; anything else is
+ * WG_ERR_INVALID before any launch.  A count outside [1, min(tmax, 4096)] counts as 0: that utterance's value is NaN, its
+ * part of E and of both gradients all zeros (g_value[b] is not read), and no other utterance is affected.  Nothing behind
+ * a count is read (it may hold NaN).  0-based indices, Ta = frames_a[b], Tb = frames_b[b].
+ * Cost: WG_SDTW_L2: d(i,j) = sqrt(sum_{k ascending} (a[k][i] - b[k][j])^2), wg_metrics_dtw's distance bit for bit, so the
+ *   value tends to wg_metrics_dtw's cost as gamma -> 0; WG_SDTW_SQ: the same sum without the root (the paper's cost).
+ * wg_softdtw_forward: R(0,0) = d(0,0); otherwise R(i,j) = d(i,j) + softmin(R(i-1,j), R(i,j-1), R(i-1,j-1)), a cell outside
+ *   the matrix counting as +infinity, softmin(x) = m - gamma log(sum_q exp(-(x_q - m) / gamma)) with m = min x and the sum
+ *   in the order written (the quotient is taken as a product with 1 / gamma).  value_out[b] = R(Ta-1, Tb-1), fp64.
+ *   r_out: null (values only), or the accumulated-cost matrix for the backward, wg_softdtw_bytes(B, tmax_a, tmax_b) bytes
+ *   (0 outside the limits), diagonal-major and skewed:
+ *     R(i,j) of pair b at r_out[(b (tmax_a + tmax_b - 1) + (i + j)) tmax_a + i]        for i < Ta, j < Tb;
+ *   the other elements are neither written nor, by the backward, read.
+ * wg_softdtw_backward: arguments as the forward had them and its r.  E(Ta-1, Tb-1) = 1; otherwise
+ *     E(i,j) = sum over s in ((i+1,j), (i,j+1), (i+1,j+1)), in that order, of E(s) exp((R(s) - R(i,j) - d(s)) / gamma),
+ *   evaluated as ((R(s) - d(s)) - R(i,j)) times 1 / gamma, a successor outside the matrix left out by predicate (no
+ *   inf - inf is formed).  E is the expected alignment:
+ *   E(0,0) = 1, 0 <= E <= 1, every row and column sums to at least 1.
+ *   e_out: null, or fp64 [B][tmax_a][tmax_b] row-major, written whole: E inside the frames, exact zeros elsewhere.
+ *   g_a [B][K][tmax_a], g_b [B][K][tmax_b] fp32, each may be null, written whole (exact zeros behind the frames):
+ *     g_a[k][i] = fp32(g_value[b] sum_{j ascending} E(i,j) dd(i,j)/da[k][i]),
+ *     g_b[k][j] = fp32(g_value[b] sum_{i ascending} E(i,j) dd(i,j)/db[k][j]),
+ *   dd/da = (a - b) / d for L2 and 0 where d = 0 (the library's convention for a root at 0), 2 (a - b) for SQ; the sum
+ *   over j runs as 64 interleaved ascending sums (j = l, l + 64, ...) joined by a fixed tree, the sum over i as 8 such sums
+ *   (i = w, w + 8, ...) joined as ((0+1)+(2+3))+((4+5)+(6+7)): both orders depend on the utterance's counts alone.
+ *   g_value: fp64 [B] device, the upstream gradients of the values; may be null when both g_a and g_b are.
+ *   With gradients wanted and e_out null the call takes a temporary of E's size from the stream-ordered allocator
+ *   (hipMallocAsync / hipFreeAsync on `stream`); with all three outputs null it does nothing.  The backward writes to its
+ *   outputs only, so a second call on the same r gives the same bits.
+ * Launches: forward one (one workgroup per pair, one anti-diagonal per step); backward a memset of E, one wavefront launch
+ *   and one launch per gradient.  The distances are recomputed by the backward, not stored beside R.
+ * Arithmetic: fp64, every sum in a fixed order that depends on the utterance alone, no atomics.  A call gives the same
+ *   bits every time and every utterance of a batch the bits of its own call with B = 1 and tmax = its counts.
+ *   Enqueue-only. */
+#define WG_SDTW_L2 0
+#define WG_SDTW_SQ 1
+size_t wg_softdtw_bytes(int32_t B, int32_t tmax_a, int32_t tmax_b);
+int wg_softdtw_forward(const float* feat_a, const int32_t* frames_a, const float* feat_b, const int32_t* frames_b,
+                       double gamma, int32_t cost, double* value_out, double* r_out, int32_t B, int32_t K,
+                       int32_t tmax_a, int32_t tmax_b, void* stream);
+int wg_softdtw_backward(const float* feat_a, const int32_t* frames_a, const float* feat_b, const int32_t* frames_b,
+                        double gamma, int32_t cost, const double* r, const double* g_value, double* e_out, float* g_a,
+                        float* g_b, int32_t B, int32_t K, int32_t tmax_a, int32_t tmax_b, void* stream);
+
 /* ---- Resampling by a rational ratio: wav data of any sampling rate in, any rate out, no handle ------------------------
  * The reference has no counterpart.  The definition is scipy.signal.resample_poly(x, up, down) with its defaults
  * (window ('kaiser', 5.0), padtype 'constant') in closed form.  With up / down reduced, M = max(up, down), half = 10 M and

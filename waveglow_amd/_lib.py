@@ -16,7 +16,8 @@ WG_F32, WG_F16 = 0, 1
 WG_PCM_I16, WG_PCM_F32 = 0, 1   # pool_dtype of wg_data_gather
 WG_PCM_F64 = 2                  # d_out_dtype of wg_resample_backward only
 WG_RESAMPLE_CLIP = 1           # flag of wg_resample
-WG_TRAIN_RECOMPUTE = 1        # flag of the wg_train_* entry points that take flags (include/waveglow_amd.h)
+WG_SDTW_L2, WG_SDTW_SQ = 0, 1   # cost of wg_softdtw_forward / wg_softdtw_backward
+WG_TRAIN_RECOMPUTE = 1       # flag of the wg_train_* entry points that take flags (include/waveglow_amd.h)
 
 
 class WgConfig(C.Structure):
@@ -171,6 +172,12 @@ SIGNATURES = {
                                 C.c_void_p]),
   "wg_stoi_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(WgStoiParams), C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_softdtw_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+  "wg_softdtw_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+  "wg_softdtw_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_void_p]),
   "wg_resample_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
   "wg_resample_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
