@@ -581,6 +581,58 @@ int wg_stftloss_backward_ragged(wg_stftloss* h, const float* g_out3, const int32
                                 float factor_mag, float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* ---- Multi-scale mel-spectrogram loss (log-mel L1 + linear-mel L1), fp32, with its backward ---------------------------
+ * HiFi-GAN's mel L1 in the multi-scale form of DAC and BigVGAN; the reference has no counterpart.  For scale
+ * r = (n_fft, hop, win, n_mels) with the dense bank W_r [n_mels][n_fft/2 + 1]: X = STFT(x) as in the STFT loss above (the
+ * same transform), M = sqrt(re^2 + im^2) with one rounding per operation, mel = W_r M, lmel = ln(max(mel, clamp));
+ * log_r = mean |lmel(x) - lmel(y)|, lin_r = mean |mel(x) - mel(y)| over the n_mels sum_b F_b cells of the batch;
+ * log = mean_r log_r, lin = mean_r lin_r, loss = factor_log log + factor_lin lin.
+ * Gradient: sign(0) = 0; the log term passes nothing where mel(x) < clamp; a bin with re^2 + im^2 = 0 gets 0, never NaN;
+ * only the prediction gets one.
+ * wg_melloss_create: 1..8 scales; n_fft a multiple of 32 in [32, 2048], 1 <= hop, win <= n_fft,
+ *   1 <= n_mels <= n_fft/2 + 1, clamp > 0 and finite; anything else is WG_ERR_INVALID.  fwd_basis[r] is the windowed
+ *   Fourier basis [2*(n_fft/2+1)][n_fft] (real rows, then imaginary rows) and mel_basis[r] the bank [n_mels][n_fft/2+1],
+ *   HOST pointers, packed once.  The projection multiplies a row of the bank from its first to its last non-zero bin
+ *   (a row of zeros is legal) and, in the backward, a bin over the rows whose span covers it, both in ascending index
+ *   order.  device_id < 0 makes a planning handle (no device work, both bases may be null): buffer sizes only.
+ * wg_melloss_spectra_elems / wg_melloss_mels_elems: the number of floats of the two saved buffers, 0 unless
+ *   1 <= B <= 65535 and n_samples > max n_fft / 2.  With F = n_samples / hop + 1 frames and Fp = F rounded up to 64:
+ *     spectra: scale after scale, each block rounded up to 64 floats, the prediction's transform [B][n_fft][Fp] with
+ *       rows interleaved: row 0 = re of bin 0, row 1 = re of bin n_fft/2, rows 2p and 2p + 1 = (re, im) of bin p,
+ *       1 <= p < n_fft/2;
+ *     mels: scale after scale, the prediction's linear mels [B][n_mels][Fp] rounded up to 64 floats, then the target's
+ *       in the same form; behind the last scale 64 floats that hold fp64 [8], element r the cell count
+ *       n_mels sum_b F_b of scale r (the only reduced sum the backward needs).
+ *   Columns f >= F_b of either buffer are neither written nor read.  Both buffers must be 8-byte aligned.
+ * wg_melloss_forward: audio, target [B][n_samples] fp32 device -> out3 = {log, lin, loss} fp32 device.  lens: null, or a
+ *   device array of B sample counts, read by the kernels only: utterance b is then its own crop x[b][:lens[b]] (reflect
+ *   padding about its own last sample, F_b = lens[b] / hop + 1 frames), nothing behind a length is read (it may hold NaN)
+ *   and the cell count is formed on the device.  A length outside (max n_fft / 2, n_samples] counts as 0: that utterance
+ *   contributes nothing and nothing is indexed with it; if every length counts as 0, out3 is zeros.  With every length
+ *   equal to n_samples the results are bit for bit those of a null lens.  spectra and mels may be null only together:
+ *   values only, the same out3 bits, nothing saved.
+ * wg_melloss_backward: g_out3 [3] fp32 DEVICE = d loss / d out3, the lens, factors, B and n_samples of the forward and
+ *   its spectra and mels -> audio_grad_out [B][n_samples] = d loss / d audio, written whole, exact zeros behind a length.
+ *   It reads the saved buffers and writes neither, so a second call gives the same bits.
+ * Temporaries (the target's transform, per-workgroup sums, the gradient planes) come from the stream-ordered allocator
+ *   (hipMallocAsync / hipFreeAsync on `stream`).  Every loss sum is reduced in fp64 per thread, per workgroup and in one
+ *   final kernel in a fixed order, overlapping frames are summed per sample in ascending frame order, no floating-point
+ *   atomics: results are bit-reproducible.  Enqueue-only; argument checks (null arguments and sizes, then the refusal
+ *   of a planning handle with WG_ERR_STATE) run before any device work. */
+typedef struct wg_melloss wg_melloss;
+int wg_melloss_create(int32_t n_scales, const int32_t* n_fft, const int32_t* hop, const int32_t* win,
+                      const int32_t* n_mels, const float* const* fwd_basis, const float* const* mel_basis,
+                      float clamp, int32_t device_id, wg_melloss** out);
+int wg_melloss_destroy(wg_melloss* h);
+size_t wg_melloss_spectra_elems(const wg_melloss* h, int32_t B, int32_t n_samples);
+size_t wg_melloss_mels_elems(const wg_melloss* h, int32_t B, int32_t n_samples);
+int wg_melloss_forward(wg_melloss* h, const float* audio, const float* target, const int32_t* lens,
+                       float factor_log, float factor_lin, float* out3, float* spectra, float* mels,
+                       int32_t B, int32_t n_samples, void* stream);
+int wg_melloss_backward(wg_melloss* h, const float* g_out3, const int32_t* lens, float factor_log,
+                        float factor_lin, const float* spectra, const float* mels, float* audio_grad_out,
+                        int32_t B, int32_t n_samples, void* stream);
+
 /* ---- Training direction: WaveGlow.forward under autograd and loss.backward() ---------------------------------------
  * (src/waveglow/model.py:178-221, train.py:190-199).  Weights change every optimiser step, so they are NOT taken from
  * the handle: the caller passes device buffers.  Every fp16 matrix below is given as [rows][K] in "(pos,pos)" order

@@ -21,6 +21,9 @@ def __getattr__(name):
   if name == "MultiResolutionSTFTLoss":
     from .stft_loss import MultiResolutionSTFTLoss
     return MultiResolutionSTFTLoss
+  if name == "MultiScaleMelLoss":
+    from .mel_loss import MultiScaleMelLoss
+    return MultiScaleMelLoss
   if name == "STOILoss":
     from .stoi_loss import STOILoss
     return STOILoss

@@ -200,7 +200,17 @@ SIGNATURES = {
                                                  C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stftloss_backward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
                                             C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_debug_set_stamp_buffer": (C.c_int, [C.c_void_p, C.c_void_p]),
+  "wg_melloss_create": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_float, C.c_int32,
+                                 C.POINTER(C.c_void_p)]),
+  "wg_melloss_destroy": (C.c_int, [C.c_void_p]),
+  "wg_melloss_spectra_elems": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+  "wg_melloss_mels_elems": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+  "wg_melloss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+  "wg_melloss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+  "wg_debug_set_stamp_buffer":(C.c_int, [C.c_void_p, C.c_void_p]),
   "wg_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
   "wg_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
 }
