@@ -41,7 +41,9 @@ CASES = {
   # L = 413 columns per utterance (a partial last frame); the widest dilation, 128, reaches well across an utterance
   "c64_l8": (dict(n_channels=64, n_layers=8, n_flows=4, n_early_every=2), 4, 13, 24, 6),
   # L = 160 is below the dilations 256 and 512: every outer tap of the last layers lands in padding or guard rows; B is
-  # odd (the library splits even batches only: this one runs as one chain whatever WG_TRAIN_HALVES says)
+  # odd (the library splits even batches only: this one runs as one chain whatever WG_TRAIN_HALVES says).  The cases whose
+  # taps of dilation 256 and 512 reach real samples, against the fp64 oracle, are seam_l10_*, seam_l9_c128 and tile_l10_*
+  # of tests/_seams.py (576 and 1664 columns per utterance)
   "c64_l10": (dict(n_channels=64, n_layers=10, n_flows=4, n_early_every=2), 3, 5, 0, 7),
   "c256_l8": (dict(n_channels=256, n_layers=8, n_flows=4, n_early_every=2), 4, 13, 24, 6),
   # flow widths 8, 6, 4, 2 in one model (tests/_corners.py), training direction only

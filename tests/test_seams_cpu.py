@@ -13,6 +13,11 @@ weight gradient that omits the last column's term.  For each:
 The planes are polyphase, so a tile seam of the kernels lies between two FRAMES (rows 63 | 64 or 127 | 128 of a phase
 block), not at a flow column that is a multiple of 64: (b) and (c) are shown once more at a case that has such a seam
 inside an utterance, with the fault on the first column behind it and the cotangent on the two frames around it.
+
+9 and 10 layers (dilations 256 and 512, 8 and 16 guard frames): the geometry of every such case is asserted row by row,
+and (b) and (c) are shown at seam_l10_c64 for the layers of dilation 256 and 512 under the training loss / the values and
+under the "reach" cotangent -- under "edge" a lost tap of column 512 leaves every gradient exact, because that column
+carries no cotangent (test_deep_taps_need_the_reach_cotangent).
 """
 import pytest
 import torch
@@ -94,14 +99,15 @@ def test_cotangents_are_edge_local():
         per_col = S.columns("z" if d == "fwd" else "audio", u).abs().amax(dim=(0, 2))
         assert sorted(torch.nonzero(per_col).flatten().tolist()) == cols
     assert c.L == 288 and 2 ** (c.hp.n_layers - 1) < c.L
-    assert c.B * (c.T + 2 * S.GUARD) <= 64                               # one tile: these cases have no tile seam
+    assert c.guard == 4 and c.B * (c.T + 2 * c.guard) <= 64              # one tile: these cases have no tile seam
   for name in S.TILE_IDS:
     for d in H.DIRECTIONS:
       c = S.Seam(name, d)
-      row, b, f = c.tile_seam()
       per = S.columns("z" if d == "fwd" else "audio", c.cotangent("seam")).abs().amax(dim=2)
-      assert torch.nonzero(per).tolist() == [[b, j] for j in range(32 * (f - 1), 32 * (f + 1))]
-      assert row in (64, 128) and 128 >= 2 ** (c.hp.n_layers - 1)
+      assert torch.nonzero(per).tolist() == [[b, j] for b, f in c.seam_frames() for j in range(32 * f, 32 * (f + 1))]
+      if c.hp.n_layers <= 8:
+        row, b, f = c.tile_seam()
+        assert c.seam_frames() == [(b, f - 1), (b, f)] and row in (64, 128) and 128 >= 2 ** (c.hp.n_layers - 1)
 
 
 @pytest.mark.parametrize("fault", list(INVISIBLE), ids=lambda f: "-".join(str(v) for v in f))
@@ -181,4 +187,153 @@ def test_fault_at_a_tile_seam_exceeds_the_bound(direction):
   gen = torch.Generator().manual_seed(1000)
   for rep in range(3):
     miss = S.check(S.run(c, True, "seam", emulate=True, dither=gen), ref, yard, f"{name}/{direction} realisation {rep}", quiet=True)
+    assert not miss, miss[:4]
+
+
+# ---------------------------------------------------------------- 9 and 10 layers, 128 and 512 channels, a seam on frame 0
+# (b) at seam_l10_c64: every kind of fault in the layer of dilation 512 of flow 1 and of dilation 256 of flow 0.  Columns
+# 540 and 300 are ordinary interior columns behind column d, so the shifted left tap reads real columns.
+DEEP = "seam_l10_c64"
+DEEP_FAULTS = [("drop_col", 1, 9), ("drop_col", 0, 8), ("drop_tap", 1, 9), ("drop_tap", 0, 8), ("seam", 1, 9, 540),
+               ("seam", 0, 8, 300), ("wgrad_last", 1, 9), ("wgrad_last", 0, 8)]
+WHOLE_TENSOR = "RMS_TOL 1e-3 (audio), FWD_TOL 2e-3 (z, log_s), GRAD_TOL 5e-3 (gradients)"
+
+
+def _rows(c, b, frames):
+  return [S.plane_row(b, 32 * f, c.T, c.guard) for f in frames]
+
+
+def test_geometry_of_the_deep_wide_and_first_frame_cases():
+  """Where every row of interest of the new cases falls, by plane_row at the guard of the case."""
+  from _envelope import ROW_PAD, geom
+  for name in S.DEEP_IDS:
+    c = S._case(name, "fwd")
+    d = 2 ** (c.hp.n_layers - 1)
+    assert (c.B, c.L) == (1, 576) and c.guard == {9: 8, 10: 16}[c.hp.n_layers] and c.guard * 32 >= d
+    assert geom(c.B, c.T, c.hp.n_layers).Fp == c.T + 2 * c.guard <= 64          # 34 / 50 rows: one tile, no tile seam
+    # the deepest tap has real columns on both sides: column d reads column 0, column L - 1 - d reads column L - 1 ...
+    assert 0 < c.L - 1 - d and d < c.L
+    assert S.plane_row(0, d, c.T, c.guard) - S.plane_row(0, 0, c.T, c.guard) == d // 32
+    assert S.plane_row(0, 0, c.T, c.guard) == c.guard and S.plane_row(0, c.L - 1, c.T, c.guard) == c.guard + c.T - 1
+    # ... and everywhere else it reads the case's own guard rows: never a row in front of the plane's first
+    assert S.plane_row(0, 0, c.T, c.guard) - d // 32 >= 0 and S.plane_row(0, c.L - 1, c.T, c.guard) + d // 32 < c.T + 2 * c.guard
+    assert c.reach_columns() == sorted({x for dd in (64, 128, 256, 512) if dd <= d for x in (dd, c.L - 1 - dd)})
+  assert 512 // 32 == ROW_PAD                       # a tap of dilation 512 lands exactly kRowPad rows away
+  for name in S.WIDE_IDS:
+    c = S._case(name, "fwd")
+    assert c.hp.n_layers == 8 and c.guard == 4 and c.L == 288 and c.B * (c.T + 2 * c.guard) <= 64
+    assert c.reach_columns() == [64, 128, 159, 223]
+  for name in ("tile_l10_c64", "tile_l10_c256"):
+    c = S._case(name, "fwd")
+    assert c.guard == 16 and geom(c.B, c.T, 10).Fp == 84 and c.tile_seams() == [(64, 0, 48), (128, 1, 28)]
+    assert _rows(c, 0, (0, 32, 47, 48, 51)) == [16, 48, 63, 64, 67]       # the left tap of row 64 reads frame 32
+    assert _rows(c, 1, (0, 12, 27, 28, 43, 51)) == [100, 112, 127, 128, 143, 151]
+    assert c.seam_frames() == [(0, 32), (0, 47), (0, 48), (1, 12), (1, 27), (1, 28), (1, 43)]
+    for b, f in c.seam_frames():
+      assert 0 <= f < c.T                            # every frame of the cotangent is a real one of the same utterance
+  for name in S.FIRST_IDS:
+    c = S._case(name, "fwd")
+    row, b = c.first_seam()
+    assert (row, b, c.guard) == (64, 3, 4) and geom(c.B, c.T, 8).Fp == 20
+    assert _rows(c, 3, (0, 1)) == [64, 65] and _rows(c, 2, (11,)) == [55]   # rows 56 .. 63: guard rows of both utterances
+    for d in H.DIRECTIONS:
+      per = S.columns("z" if d == "fwd" else "audio", S._case(name, d).cotangent("first")).abs().amax(dim=2)
+      assert torch.nonzero(per).tolist() == [[2, j] for j in range(352, 384)] + [[3, j] for j in range(64)]
+  # positions are reported at the guard of the case: column 0 of a 10-layer utterance is row 16
+  g = torch.ones(1, 8, 576)
+  g[0, 0, 512] = 2.0
+  assert S.worst("z", g, torch.ones(1, 8, 576), 16)[1] == (0, 512, 63, 31)
+  assert S.worst("z", g, torch.ones(1, 8, 576), 8)[1] == (0, 512, 63, 24)
+
+
+def test_reach_cotangent_is_local():
+  for name in S.DEEP_IDS + S.WIDE_IDS:
+    for d in H.DIRECTIONS:
+      c = S._case(name, d)
+      per_col = S.columns("z" if d == "fwd" else "audio", c.cotangent("reach")).abs().amax(dim=(0, 2))
+      want = sorted({j for x in c.reach_columns() for j in range(max(x - 32, 0), min(x + 32, c.L))})
+      assert sorted(torch.nonzero(per_col).flatten().tolist()) == want
+      assert all(per_col[x] > 0 for x in c.reach_columns())
+
+
+def _misses(c, ref, yard, where, fault):
+  got = S.run(c, True, where, fault=fault, emulate=True)
+  miss = S.check(got, ref, yard, f"{fault} {c.name}/{c.direction}", factor=2.0 * S.BOUND_FACTOR, quiet=True, case=c)
+  e = H.errors(got, ref)
+  rel = max((err / max(den, 1e-30), q) for q, (err, den) in e.items() if q not in ("loss", "log_det"))
+  cols = [(round(r, 1), q, pos) for r, q, pos in miss if pos is not None]
+  par = [(round(r, 1), q) for r, q, pos in miss if pos is None]
+  print(f"{fault} {c.name}/{c.direction} {where}: beyond 2 x the bound: columns {cols}; {len(par)} parameter gradients, worst "
+        f"{par[:1]}; worst whole-tensor relative error {rel[0]:.2e} ({rel[1]}) beside {WHOLE_TENSOR}")
+  return cols, par
+
+
+@pytest.mark.parametrize("direction", H.DIRECTIONS)
+def test_deep_taps_need_the_reach_cotangent(direction):
+  """Under "edge" a lost or misplaced left tap of the layers of dilation 256 and 512 moves no gradient beyond the bound
+  (column d and the interior columns carry no cotangent); under "reach" it reaches a data gradient and the parameter
+  gradients of its own layer."""
+  c = S._case(DEEP, direction)
+  for where in ("edge", "reach"):
+    ref, yard = S.oracle(DEEP, direction, True, where), S.yardstick(DEEP, direction, True, where)
+    for fault in (("drop_tap", 1, 9), ("drop_tap", 0, 8), ("seam", 1, 9, 540), ("seam", 0, 8, 300)):
+      cols, par = _misses(c, ref, yard, where, fault)
+      grads = [q for _, q, _ in cols if q.startswith("d ")]
+      own = [q for _, q in par if q.startswith(f"p/WN.{fault[1]}.in_layers.{fault[2]}.")]
+      if where == "reach":
+        assert grads and own, (fault, cols, par[:4])
+      elif fault[0] == "drop_tap":
+        assert not grads and not par, (fault, cols, par[:4])
+
+
+@pytest.mark.parametrize("direction", H.DIRECTIONS)
+def test_deep_planted_faults_exceed_the_per_column_bound(direction):
+  """(b) and (c) at seam_l10_c64 under the loss (training) or the values (synthesis) and under "reach".  wgrad_last omits
+  the LAST column's term, which "reach" gives no cotangent and a values-only run no gradient: it is held under the loss
+  in the training direction and under "edge" in the synthesis direction."""
+  c = S._case(DEEP, direction)
+  plain = "loss" if direction == "fwd" else "values"
+  wgrad_where = "loss" if direction == "fwd" else "edge"
+  for where in dict.fromkeys((plain, "reach", wgrad_where)):
+    ref, yard = S.oracle(DEEP, direction, True, where), S.yardstick(DEEP, direction, True, where)
+    print(f"{DEEP}/{direction} {where} yardsticks:", {q: f"{v:.2e}" for q, v in yard.items() if not q.startswith("p/")})
+    for fault in DEEP_FAULTS:
+      wgrad = fault[0] == "wgrad_last"
+      if (wgrad and where != wgrad_where) or (not wgrad and where == "edge"):
+        continue
+      cols, par = _misses(c, ref, yard, where, fault)
+      if wgrad:
+        assert not cols                              # values and data gradients stay exact
+        key = f"p/WN.{fault[1]}.in_layers.{fault[2]}."
+        assert par and all(q.startswith(key) for _, q in par), par
+      else:
+        assert cols, f"{fault}: no column of {DEEP}/{direction} under {where} exceeds twice the per-column bound"
+    if where == "edge":
+      continue
+    gen = torch.Generator().manual_seed(1000)
+    for rep in range(3):
+      got = S.run(c, True, where, emulate=True, dither=gen)
+      miss = S.check(got, ref, yard, f"{DEEP}/{direction} {where} realisation {rep}", quiet=True, case=c)
+      print(f"{DEEP}/{direction} {where} fault-free realisation {rep}: worst ratio to the yardstick "
+            f"{max(v / yard[q] for q, v in S.statistics(got, ref).items() if yard[q] > 0):.2f}")
+      assert not miss, miss[:4]
+
+
+@pytest.mark.parametrize("direction", H.DIRECTIONS)
+def test_fault_at_a_tile_seam_under_a_16_row_tap(direction):
+  """(b) and (c) at tile_l10_c64: the left tap of dilation 512 of the first column behind row 64 (frame 48 of utterance 0)
+  reads frame 32, 16 rows in front of the seam, one column off.  seam_l10_c64 has 18 frames and no such column, so the
+  fault is planted in the case that has the seam."""
+  name = "tile_l10_c64"
+  c = S._case(name, direction)
+  row, b, f = c.tile_seam()
+  assert (row, b, f) == (64, 0, 48)
+  ref = S.oracle(name, direction, True, "seam")
+  yard = S.yardstick(name, direction, True, "seam")
+  cols, par = _misses(c, ref, yard, "seam", ("seam", 1, 9, 32 * f))
+  assert cols and any(pos[3] == 0 for _, _, pos in cols), cols
+  gen = torch.Generator().manual_seed(1000)
+  for rep in range(3):
+    miss = S.check(S.run(c, True, "seam", emulate=True, dither=gen), ref, yard, f"{name}/{direction} realisation {rep}",
+                   quiet=True, case=c)
     assert not miss, miss[:4]
