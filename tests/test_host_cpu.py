@@ -473,3 +473,13 @@ def test_stft_oracle_against_torch_stft():
   ft = np.einsum("kn,bnf->bkf", pf.reshape(1026, 1024), np.stack(
       [np.pad(x, ((0, 0), (512, 512)), mode="reflect")[:, f * 256:f * 256 + 1024] for f in range(14)], axis=2))
   assert np.abs(ft[:, :513] - X.real.numpy()).max() < 1e-4 and np.abs(ft[:, 513:] - X.imag.numpy()).max() < 1e-4
+
+
+def test_build_lists_every_header():
+  """waveglow_amd/build.py keeps HEADERS by hand, and needs_build() compares only the listed files with the library: a
+  header of csrc/ that is not listed could be edited without a rebuild."""
+  from waveglow_amd import build
+  on_disk = sorted(f for f in os.listdir(build.CSRC) if f.endswith(".h"))
+  listed = sorted(h for h in build.HEADERS if os.sep not in h and "/" not in h)
+  assert listed == on_disk
+  assert all(os.path.isfile(os.path.join(build.CSRC, h)) for h in build.HEADERS)

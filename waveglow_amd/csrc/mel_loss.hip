@@ -1,17 +1,16 @@
 // Multi-scale mel-spectrogram loss (log-mel L1 + linear-mel L1) with its backward, fp32 on exact-fp32 MFMA
 // (v_mfma_f32_32x32x2_f32), for any scale (n_fft, hop, win, n_mels) inside the limits of stft_loss.hip.
 //
-// The two transforms and the transposed transform are the GEMM of stft_loss.hip (sl_gemm_kernel), copied here so that
-// that kernel's instantiations stay as they are: rows of the basis interleaved (re_k, im_k), row 1 the real part of bin
-// n_fft/2, only the taps under the window multiplied, the 64-frame x 64-tap operand tile gathered from the audio with the
-// reflect padding as index arithmetic.  Here the forward writes the (re, im) plane and nothing else, and the backward
-// takes its operand from a plane of d loss / d (re, im) that ml_gspec_kernel has written: the mel projection sits
-// between the transform and the loss, so the epilogue of the GEMM has nothing to reduce.
+// The two transforms and the transposed transform are the conv-STFT of stft_loss.hip, built from the same pieces
+// (wg_stftconv.h: the packed bases, the operand tile gathered from the audio with the reflect padding as index arithmetic,
+// the K loop of one chunk) around a GEMM kernel of its own.  Here the forward writes the (re, im) plane and nothing else,
+// and the backward takes its operand from a plane of d loss / d (re, im) that ml_gspec_kernel has written: the mel
+// projection sits between the transform and the loss, so the epilogue of the GEMM has nothing to reduce.
 //
 // The mel projection and its transpose are sparse: a row of the bank is multiplied over the span from its first to its
 // last non-zero bin, a bin over the rows whose span covers it, both in ascending index order, one thread per output.
 // Loss sums are reduced per thread and per workgroup in fp64 and combined by one fixed-order final kernel; overlapping
-// frames are summed per sample in ascending frame order (the scheme of sl_gather_kernel).  No floating-point atomics.
+// frames are summed per sample in ascending frame order by the gather of stft_loss.hip.  No floating-point atomics.
 //
 // Ragged batches: a device array lens gives utterance b its own N_b = lens[b] samples and F_b = N_b / hop + 1 frames
 // inside the dense layout.  Reflections use N_b, frames f >= F_b are neither stored nor read, a workgroup wholly behind
@@ -22,10 +21,6 @@
 #include "wg_melloss.h"
 
 namespace wgml {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kLd = kKC + 1;     // LDS row stride: 32 frames of one k fall on 32 banks
 
 enum { kFwd = 0, kBwd = 1 };
 
@@ -42,42 +37,6 @@ struct GemmArgs {
   int min_len;           // ragged batch: a length < min_len or > N counts as 0
 };
 
-// Sample count of utterance b in a ragged batch: a length outside [min_len, pitch] counts as 0, the utterance then
-// contributes nothing and nothing is indexed with it.
-__device__ __forceinline__ int ragged_len(const int* lens, int b, int pitch, int min_len) {
-  const int n = lens[b];
-  return (n < min_len || n > pitch) ? 0 : n;
-}
-__device__ __forceinline__ int ragged_frames(int n, int hop) { return n ? n / hop + 1 : 0; }
-
-// re^2 + im^2 with one rounding per operation, in the forward and in the backward alike (power() of stft_loss.hip)
-__device__ __forceinline__ float power(float re, float im) {
-  return __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im));
-}
-
-constexpr int kSt = kBN * kKC / 256;          // staged elements per thread and chunk
-
-// forward operand of chunk kc: taps lpad + 64 kc .. + 63 of 64 frames, read along the audio (reflect padding as index
-// arithmetic); element i = tid + 256 it is frame i >> 6, tap i & 63
-__device__ __forceinline__ void fetch_fwd(const GemmArgs& a, int kc, int f0, int b, int N, int F, int tid,
-                                          float (&pv)[kSt]) {
-  const float* x = a.audio + (size_t)b * a.N;
-  const int k0 = a.lpad + kc * kKC, half = a.n_fft / 2;
-#pragma unroll
-  for (int it = 0; it < kSt; ++it) {
-    const int i = tid + 256 * it;
-    const int f = f0 + (i >> 6), k = k0 + (i & 63);
-    float v = 0.0f;
-    if (f < F && k < a.n_fft) {
-      int s = f * a.hop + k - half;
-      if (s < 0) s = -s;
-      if (s >= N) s = 2 * (N - 1) - s;
-      v = x[s];
-    }
-    pv[it] = v;
-  }
-}
-
 // backward operand of chunk kc: rows 64 kc .. + 63 of the gradient plane at 64 frames, read along the frames; element
 // i = tid + 256 it is frame i & 63, row 64 kc + (i >> 6).  Zeros outside the transform.
 __device__ __forceinline__ void fetch_bwd(const GemmArgs& a, int kc, int f0, int b, int F, int tid, float (&pv)[kSt]) {
@@ -88,31 +47,6 @@ __device__ __forceinline__ void fetch_bwd(const GemmArgs& a, int kc, int f0, int
     float v = 0.0f;
     if (f < F && row < a.n_fft) v = a.gspec[((size_t)b * a.n_fft + row) * a.Fp + f];
     pv[it] = v;
-  }
-}
-
-// 32 K steps of one staged chunk for the wave's TW tiles (tile t at ap + toff[t]) x 2 frame tiles, with no branch
-// inside.  SWAP exchanges the operand roles: the accumulator then holds the transposed tile (basis index on the lanes).
-template <int TW, bool SWAP>
-__device__ __forceinline__ void mma_chunk(f32x16 (&acc)[TW][2], const float* bt, const float* ap,
-                                          const size_t (&toff)[TW], int col, int kk) {
-#pragma unroll 4
-  for (int ks = 0; ks < 32; ++ks) {
-    const float b0 = bt[col * kLd + 2 * ks + kk];
-    const float b1 = bt[(32 + col) * kLd + 2 * ks + kk];
-    float av[TW];
-#pragma unroll
-    for (int t = 0; t < TW; ++t) av[t] = ap[toff[t] + (size_t)ks * 64];
-#pragma unroll
-    for (int t = 0; t < TW; ++t) {
-      if (SWAP) {
-        acc[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, av[t], acc[t][0], 0, 0, 0);
-        acc[t][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, av[t], acc[t][1], 0, 0, 0);
-      } else {
-        acc[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b0, acc[t][0], 0, 0, 0);
-        acc[t][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b1, acc[t][1], 0, 0, 0);
-      }
-    }
   }
 }
 
@@ -404,64 +338,6 @@ __global__ void __launch_bounds__(256) ml_gspec_kernel(const GspecArgs a) {
   }
 }
 
-struct GatherArgs {
-  const float* G;     // [B][F][Wp]
-  float* gx;          // [B][N]
-  int n_fft, hop, win, lpad, N, F, Wp, accumulate;
-  const int* lens;
-  int min_len;
-};
-
-// d loss / d x[s]: the padded positions that hold x[s] (its own, and up to two reflected ones), each the sum over the
-// frames that cover it, ascending (sl_gather_kernel of stft_loss.hip).  One thread per sample.  grid (ceil(N / 256), B).
-__global__ void __launch_bounds__(256) ml_gather_kernel(const GatherArgs a) {
-  const int s = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-  if (s >= a.N) return;
-  const float* Gb = a.G + (size_t)b * a.F * a.Wp;
-  const int h = a.n_fft / 2;
-  int N = a.N, F = a.F;
-  if (a.lens) {
-    N = ragged_len(a.lens, b, a.N, a.min_len);
-    F = ragged_frames(N, a.hop);
-  }
-  auto at = [&](int p) -> float {
-    const int u = p - a.lpad;                               // tap offset of frame f: u - f hop in [0, win)
-    if (u < 0) return 0.0f;
-    int fhi = u / a.hop;
-    if (fhi > F - 1) fhi = F - 1;
-    const int flo = u - a.win + 1 <= 0 ? 0 : (u - a.win + a.hop) / a.hop;
-    float v = 0.0f;
-    for (int f = flo; f <= fhi; ++f) v += Gb[(size_t)f * a.Wp + (u - f * a.hop)];
-    return v;
-  };
-  float v = 0.0f;
-  if (s < N) {                                              // behind the utterance: 0
-    v = at(s + h);
-    if (s >= 1 && s <= h) v += at(h - s);
-    if (s >= N - 1 - h && s <= N - 2) v += at(2 * (N - 1) - s + h);
-  }
-  float* o = a.gx + (size_t)b * a.N + s;
-  *o = a.accumulate ? *o + v : v;
-}
-
-#define ML_LAUNCHED()                         \
-  do {                                        \
-    const hipError_t _e = hipGetLastError();  \
-    if (_e != hipSuccess) return _e;          \
-  } while (0)
-
-// The forward GEMM with as many M tiles per wave as the fullest workgroup needs: the small scales (n_fft <= 384) have
-// fewer than 16 row tiles, and a wave of the 4-tile instance would compute its spare tiles for nothing (a tile past the
-// end repeats the last one) at 206 VGPRs.  The arithmetic of a tile does not depend on the instance.
-static void launch_fwd_gemm(const GemmArgs& a, dim3 grid, hipStream_t s) {
-  switch (((a.MT + a.nby - 1) / a.nby + 3) / 4) {
-    case 1: hipLaunchKernelGGL((ml_gemm_kernel<kFwd, 1>), grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((ml_gemm_kernel<kFwd, 2>), grid, dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((ml_gemm_kernel<kFwd, 3>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((ml_gemm_kernel<kFwd, 4>), grid, dim3(256), 0, s, a); break;
-  }
-}
-
 hipError_t launch_ml_forward(const wg_melloss* h, const Layout& L, const float* audio, const float* target,
                              const int* lens, float factor_log, float factor_lin, float* out3, float* spectra,
                              float* mels, float* tmp, int B, int N, hipStream_t s) {
@@ -480,14 +356,14 @@ hipError_t launch_ml_forward(const wg_melloss* h, const Layout& L, const float* 
   fa.lens = lens;
   fa.B = B;
   fa.N = N;
-  fa.min_len = ragged_min_len(h);
+  fa.min_len = ragged_min_len(h->sc, h->n_scales);
   for (int i = 0; i < h->n_scales; ++i) {
     const Scale& r = h->sc[i];
     GemmArgs a{};
     a.A = r.d_Af;
     a.MT = r.MTf;
     a.KS = r.KSf;
-    a.nby = (r.MTf + 4 * kTW - 1) / (4 * kTW);
+    a.nby = gemm_nby(r.MTf);
     a.n_fft = r.n_fft;
     a.hop = r.hop;
     a.lpad = r.lpad;
@@ -514,22 +390,22 @@ hipError_t launch_ml_forward(const wg_melloss* h, const Layout& L, const float* 
     const dim3 grid(L.nbx[i], a.nby, B), mgrid(L.nbx[i], L.nmy[i], B);
     a.audio = target;
     a.spec = tplane;
-    launch_fwd_gemm(a, grid, s);
-    ML_LAUNCHED();
+    WGSC_LAUNCH_GEMM(ml_gemm_kernel, kFwd, grid, s, a);
+    if (hipError_t e = hipGetLastError()) return e;
     m.spec = tplane;
     m.mel = mel_y;
     m.mel_y = nullptr;
     hipLaunchKernelGGL(ml_mel_kernel, mgrid, dim3(256), 0, s, m);
-    ML_LAUNCHED();
+    if (hipError_t e = hipGetLastError()) return e;
     a.audio = audio;
     a.spec = saved ? spectra + L.spec[i] : xplane;
-    launch_fwd_gemm(a, grid, s);
-    ML_LAUNCHED();
+    WGSC_LAUNCH_GEMM(ml_gemm_kernel, kFwd, grid, s, a);
+    if (hipError_t e = hipGetLastError()) return e;
     m.spec = a.spec;
     m.mel = mel_x;
     m.mel_y = mel_y;
     hipLaunchKernelGGL(ml_mel_kernel, mgrid, dim3(256), 0, s, m);
-    ML_LAUNCHED();
+    if (hipError_t e = hipGetLastError()) return e;
     fa.part[i] = m.part;
     fa.nblk[i] = L.nbx[i] * L.nmy[i] * B;
     fa.cnt[i] = (double)B * r.n_mels * L.F[i];
@@ -537,7 +413,7 @@ hipError_t launch_ml_forward(const wg_melloss* h, const Layout& L, const float* 
     fa.n_mels[i] = r.n_mels;
   }
   hipLaunchKernelGGL(ml_final_kernel, dim3(1), dim3(256), 0, s, fa);
-  ML_LAUNCHED();
+  if (hipError_t e = hipGetLastError()) return e;
   return hipSuccess;
 }
 
@@ -547,7 +423,7 @@ hipError_t launch_ml_backward(const wg_melloss* h, const Layout& L, const float*
   float* gspec = tmp;
   float* gmel = tmp + L.plane_max;
   float* G = gmel + L.melp_max;
-  const int min_len = ragged_min_len(h);
+  const int min_len = ragged_min_len(h->sc, h->n_scales);
   for (int i = 0; i < h->n_scales; ++i) {
     const Scale& r = h->sc[i];
     GmelArgs gm{};
@@ -568,7 +444,7 @@ hipError_t launch_ml_backward(const wg_melloss* h, const Layout& L, const float*
     gm.lens = lens;
     gm.min_len = min_len;
     hipLaunchKernelGGL(ml_gmel_kernel, dim3(L.nbx[i], (r.n_mels + 3) / 4, B), dim3(256), 0, s, gm);
-    ML_LAUNCHED();
+    if (hipError_t e = hipGetLastError()) return e;
     GspecArgs gs{};
     gs.spec = spectra + L.spec[i];
     gs.gmel = gmel;
@@ -585,12 +461,12 @@ hipError_t launch_ml_backward(const wg_melloss* h, const Layout& L, const float*
     gs.min_len = min_len;
     const int K = r.n_fft / 2 + 1;
     hipLaunchKernelGGL(ml_gspec_kernel, dim3(L.nbx[i], (K + kMelRows - 1) / kMelRows, B), dim3(256), 0, s, gs);
-    ML_LAUNCHED();
+    if (hipError_t e = hipGetLastError()) return e;
     GemmArgs a{};
     a.A = r.d_Ab;
     a.MT = r.MTb;
     a.KS = r.KSb;
-    a.nby = (r.MTb + 4 * kTW - 1) / (4 * kTW);
+    a.nby = gemm_nby(r.MTb);
     a.n_fft = r.n_fft;
     a.hop = r.hop;
     a.lpad = r.lpad;
@@ -603,16 +479,9 @@ hipError_t launch_ml_backward(const wg_melloss* h, const Layout& L, const float*
     a.lens = lens;
     a.min_len = min_len;
     const dim3 grid(L.nbx[i], a.nby, B);
-    switch (((r.MTb + a.nby - 1) / a.nby + 3) / 4) {          // tiles per wave of the fullest workgroup
-      case 1: hipLaunchKernelGGL((ml_gemm_kernel<kBwd, 1>), grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((ml_gemm_kernel<kBwd, 2>), grid, dim3(256), 0, s, a); break;
-      case 3: hipLaunchKernelGGL((ml_gemm_kernel<kBwd, 3>), grid, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL((ml_gemm_kernel<kBwd, 4>), grid, dim3(256), 0, s, a); break;
-    }
-    ML_LAUNCHED();
-    GatherArgs ga{G, audio_grad_out, r.n_fft, r.hop, r.win, r.lpad, N, L.F[i], a.Wp, i > 0, lens, min_len};
-    hipLaunchKernelGGL(ml_gather_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, ga);
-    ML_LAUNCHED();
+    WGSC_LAUNCH_GEMM(ml_gemm_kernel, kBwd, grid, s, a);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = launch_gather(r, G, audio_grad_out, B, N, L.F[i], i > 0, lens, min_len, s)) return e;
   }
   return hipSuccess;
 }

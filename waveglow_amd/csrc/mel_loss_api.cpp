@@ -9,30 +9,16 @@ using namespace wgml;
 
 namespace {
 
-// device part of wg_melloss_create: per scale the packed Fourier bases (the fragments of stft_loss.hip), the dense bank
-// and the span tables of the sparse projection
+// device part of wg_melloss_create: per scale the packed Fourier bases, the dense bank and the span tables of the sparse
+// projection
 int upload(wg_melloss* h, const float* const* fwd_basis, const float* const* mel_basis) {
   DeviceGuard dev_guard;
   HIP_TRY(hipGetDevice(&dev_guard.prev));
   HIP_TRY(hipSetDevice(h->device));
   for (int i = 0; i < h->n_scales; ++i) {
     Scale& r = h->sc[i];
-    const int n = r.n_fft, K = n / 2 + 1;
-    const float* fb = fwd_basis[i];                         // [2K][n]: real rows, then imaginary rows
-    auto basis = [&](int row, int tap) -> float {
-      if (row >= n || tap >= n) return 0.0f;
-      const int ref = row == 0 ? 0 : row == 1 ? n / 2 : (row & 1) ? K + (row >> 1) : (row >> 1);
-      return fb[(size_t)ref * n + tap];
-    };
-    std::vector<float> af((size_t)r.MTf * r.KSf * 64), ab((size_t)r.MTb * r.KSb * 64);
-    for (int mt = 0; mt < r.MTf; ++mt)
-      for (int ks = 0; ks < r.KSf; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-          af[((size_t)mt * r.KSf + ks) * 64 + lane] = basis(mt * 32 + (lane & 31), r.lpad + 2 * ks + (lane >> 5));
-    for (int mt = 0; mt < r.MTb; ++mt)
-      for (int ks = 0; ks < r.KSb; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-          ab[((size_t)mt * r.KSb + ks) * 64 + lane] = basis(2 * ks + (lane >> 5), r.lpad + mt * 32 + (lane & 31));
+    if (int rc = upload_bases(r, fwd_basis[i])) return rc;
+    const int K = r.n_fft / 2 + 1;
     // spans: a row from its first to its last non-zero bin (an empty row: first = 1, last = 0); a bin from the lowest to
     // the highest row whose span covers it
     const float* w = mel_basis[i];
@@ -56,12 +42,8 @@ int upload(wg_melloss* h, const float* const* fwd_basis, const float* const* mel
         cover[2 * k + 1] = m;
       }
     }
-    HIP_TRY(hipMalloc((void**)&r.d_Af, af.size() * 4));
-    HIP_TRY(hipMalloc((void**)&r.d_Ab, ab.size() * 4));
     HIP_TRY(hipMalloc((void**)&r.d_W, (size_t)r.n_mels * K * 4));
     HIP_TRY(hipMalloc((void**)&r.d_span, span.size() * 4));
-    HIP_TRY(hipMemcpy(r.d_Af, af.data(), af.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r.d_Ab, ab.data(), ab.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(r.d_W, w, (size_t)r.n_mels * K * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(r.d_span, span.data(), span.size() * 4, hipMemcpyHostToDevice));
   }
@@ -89,10 +71,7 @@ int wg_melloss_create(int32_t n_scales, const int32_t* n_fft, const int32_t* hop
   if (n_scales < 1 || n_scales > kMaxScales) return fail(WG_ERR_INVALID, "mel loss: 1 to 8 scales");
   if (!(clamp > 0.0f) || !std::isfinite(clamp)) return fail(WG_ERR_INVALID, "mel loss: clamp must be positive and finite");
   for (int i = 0; i < n_scales; ++i) {
-    if (n_fft[i] < 32 || n_fft[i] > kMaxFft || n_fft[i] % 32)
-      return fail(WG_ERR_INVALID, "mel loss: n_fft must be a multiple of 32 in [32, 2048]");
-    if (hop[i] < 1 || hop[i] > n_fft[i]) return fail(WG_ERR_INVALID, "mel loss: hop must be in [1, n_fft]");
-    if (win[i] < 1 || win[i] > n_fft[i]) return fail(WG_ERR_INVALID, "mel loss: win must be in [1, n_fft]");
+    if (int rc = check_geom("mel loss: ", n_fft[i], hop[i], win[i])) return rc;
     if (n_mels[i] < 1 || n_mels[i] > n_fft[i] / 2 + 1)
       return fail(WG_ERR_INVALID, "mel loss: n_mels must be in [1, n_fft / 2 + 1]");
   }
@@ -106,16 +85,8 @@ int wg_melloss_create(int32_t n_scales, const int32_t* n_fft, const int32_t* hop
   h->n_scales = n_scales;
   h->clamp = clamp;
   for (int i = 0; i < n_scales; ++i) {
-    Scale& r = h->sc[i];
-    r.n_fft = n_fft[i];
-    r.hop = hop[i];
-    r.win = win[i];
-    r.n_mels = n_mels[i];
-    r.lpad = (r.n_fft - r.win) / 2;
-    r.MTf = r.n_fft / 32;
-    r.KSf = (r.win + kKC - 1) / kKC * (kKC / 2);
-    r.MTb = (r.win + 31) / 32;
-    r.KSb = (r.n_fft + kKC - 1) / kKC * (kKC / 2);
+    set_geom(h->sc[i], n_fft[i], hop[i], win[i]);
+    h->sc[i].n_mels = n_mels[i];
   }
   if (device_id >= 0) {   // a planning handle holds geometry and buffer sizes only
     const int rc = upload(h, fwd_basis, mel_basis);
@@ -132,8 +103,7 @@ int wg_melloss_destroy(wg_melloss* h) {
   if (!h) return WG_OK;
   for (int i = 0; i < h->n_scales; ++i) {
     Scale& r = h->sc[i];
-    if (r.d_Af) (void)hipFree(r.d_Af);
-    if (r.d_Ab) (void)hipFree(r.d_Ab);
+    free_bases(r);
     if (r.d_W) (void)hipFree(r.d_W);
     if (r.d_span) (void)hipFree(r.d_span);
   }

@@ -21,16 +21,12 @@
 #include <stdint.h>
 
 #include "wg_host.h"
+#include "wg_stftconv.h"
 
 namespace wgsl {
+using namespace wgsc;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBN = 64;          // frames per workgroup
-constexpr int kKC = 64;          // depth of one staged operand tile
-constexpr int kLd = kKC + 1;     // LDS row stride: 32 frames of one k fall on 32 banks
-constexpr int kTW = 4;           // M tiles per wave at most (x 2 frame tiles = 128 accumulator registers)
-constexpr int kMaxRes = 8, kMaxFft = 2048;
+constexpr int kMaxRes = 8;
 
 enum { kFwdY = 0, kFwdX = 1, kFwdXSave = 2, kBwd = 3 };
 
@@ -55,19 +51,6 @@ struct GemmArgs {
   const double* cnt;     // kBwd, ragged batch: K sum_b F_b of this resolution, written by sl_final_kernel
 };
 
-// Sample count of utterance b in a ragged batch, as ragged_len of stft.hip: a length outside [min_len, pitch] counts as
-// 0, the utterance then contributes nothing and nothing is indexed with it.
-__device__ __forceinline__ int ragged_len(const int* lens, int b, int pitch, int min_len) {
-  const int n = lens[b];
-  return (n < min_len || n > pitch) ? 0 : n;
-}
-__device__ __forceinline__ int ragged_frames(int n, int hop) { return n ? n / hop + 1 : 0; }
-
-// re^2 + im^2 with one rounding per operation, in the forward and in the backward alike, so both see the same clamp
-__device__ __forceinline__ float power(float re, float im) {
-  return __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im));
-}
-
 // d loss / d M(x), divided by M(x): the factor of (re, im).  Zero under the clamp; sign(0) = 0.
 __device__ __forceinline__ float grad_factor(float pw, float my, float eps, float cs, float cm) {
   if (!(pw >= eps)) return 0.0f;
@@ -77,33 +60,11 @@ __device__ __forceinline__ float grad_factor(float pw, float my, float eps, floa
   return (cs * (mx - my) - cm * sg / mx) / mx;
 }
 
-constexpr int kStF = kBN * kKC / 256;         // forward: staged samples per thread and chunk
 constexpr int kStB = kBN * (kKC / 2) / 256;   // backward: staged bins per thread and chunk
-
-// forward operand of chunk kc: taps lpad + 64 kc .. + 63 of 64 frames, read along the audio (reflect padding as index
-// arithmetic); element i = tid + 256 it is frame i >> 6, tap i & 63
-__device__ __forceinline__ void fetch_fwd(const GemmArgs& a, int kc, int f0, int b, int N, int F, int tid,
-                                          float (&pv)[kStF]) {
-  const float* x = a.audio + (size_t)b * a.N;
-  const int k0 = a.lpad + kc * kKC, half = a.n_fft / 2;
-#pragma unroll
-  for (int it = 0; it < kStF; ++it) {
-    const int i = tid + 256 * it;
-    const int f = f0 + (i >> 6), k = k0 + (i & 63);
-    float v = 0.0f;
-    if (f < F && k < a.n_fft) {
-      int s = f * a.hop + k - half;
-      if (s < 0) s = -s;
-      if (s >= N) s = 2 * (N - 1) - s;
-      v = x[s];
-    }
-    pv[it] = v;
-  }
-}
 
 // backward operand of chunk kc: (re, im) and M(y) of bins 32 kc .. + 31 at 64 frames, read along the frames; element
 // i = tid + 256 it is frame i & 63, bin 32 kc + (i >> 6).  Zeros (no gradient) outside the transform.
-__device__ __forceinline__ void fetch_bwd(const GemmArgs& a, int kc, int f0, int b, int F, int tid, float (&pv)[kStF],
+__device__ __forceinline__ void fetch_bwd(const GemmArgs& a, int kc, int f0, int b, int F, int tid, float (&pv)[kSt],
                                           float (&pm)[kStB], float& pm2) {
   const int half = a.n_fft / 2;
   const float* myb = a.my + (size_t)b * (half + 1) * a.Fp;
@@ -122,32 +83,6 @@ __device__ __forceinline__ void fetch_bwd(const GemmArgs& a, int kc, int f0, int
     pv[it] = re;
     pv[kStB + it] = im;
     pm[it] = my;
-  }
-}
-
-// 32 K steps of one staged chunk for the wave's TW tiles (tile t at ap + toff[t]) x 2 frame tiles, with no branch
-// inside: a guard around a tile's load and MFMAs keeps the compiler from issuing the A loads ahead of the products.
-// SWAP exchanges the operand roles: the accumulator then holds the transposed tile (basis index on the lanes).
-template <int TW, bool SWAP>
-__device__ __forceinline__ void mma_chunk(f32x16 (&acc)[TW][2], const float* bt, const float* ap,
-                                          const size_t (&toff)[TW], int col, int kk) {
-#pragma unroll 4
-  for (int ks = 0; ks < 32; ++ks) {
-    const float b0 = bt[col * kLd + 2 * ks + kk];
-    const float b1 = bt[(32 + col) * kLd + 2 * ks + kk];
-    float av[TW];
-#pragma unroll
-    for (int t = 0; t < TW; ++t) av[t] = ap[toff[t] + (size_t)ks * 64];
-#pragma unroll
-    for (int t = 0; t < TW; ++t) {
-      if (SWAP) {
-        acc[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, av[t], acc[t][0], 0, 0, 0);
-        acc[t][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, av[t], acc[t][1], 0, 0, 0);
-      } else {
-        acc[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b0, acc[t][0], 0, 0, 0);
-        acc[t][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], b1, acc[t][1], 0, 0, 0);
-      }
-    }
   }
 }
 
@@ -200,7 +135,7 @@ __global__ void __launch_bounds__(256, 2) sl_gemm_kernel(const GemmArgs a) {
 
   // The operand tile of chunk kc + 1 is loaded into registers before the products of chunk kc and written to LDS
   // after them, so its latency hides behind the MFMAs.
-  float pv[kStF], pm[kStB], pm2 = 0.0f;
+  float pv[kSt], pm[kStB], pm2 = 0.0f;
   const int nkc = a.KS / 32;
   if (MODE != kBwd) fetch_fwd(a, 0, f0, b, N, F, tid, pv);
   else fetch_bwd(a, 0, f0, b, F, tid, pv, pm, pm2);
@@ -209,7 +144,7 @@ __global__ void __launch_bounds__(256, 2) sl_gemm_kernel(const GemmArgs a) {
     if (MODE != kBwd) {
       // bt[frame][tap]: 64 consecutive taps of 64 frames
 #pragma unroll
-      for (int it = 0; it < kStF; ++it) {
+      for (int it = 0; it < kSt; ++it) {
         const int i = tid + 256 * it;
         bt[(i >> 6) * kLd + (i & 63)] = pv[it];
       }
@@ -428,12 +363,6 @@ __global__ void __launch_bounds__(256) sl_final_kernel(const FinalArgs a) {
   }
 }
 
-struct Res {
-  int n_fft, hop, win, lpad;
-  int MTf, KSf, MTb, KSb;      // forward: n_fft/32 row tiles x window taps; backward: window tap tiles x n_fft rows
-  float *d_Af = nullptr, *d_Ab = nullptr;
-};
-
 // workspace, in floats; every block a multiple of 64 floats
 struct Layout {
   int F[kMaxRes], Fp[kMaxRes], nbx[kMaxRes], nby[kMaxRes];
@@ -446,23 +375,17 @@ using namespace wgsl;
 struct wg_stftloss {
   int device = -1, n_res = 0;
   float eps = 1e-7f;
-  Res res[kMaxRes];
+  Geom res[kMaxRes];
 };
-
-static size_t up64(size_t n) { return (n + 63) / 64 * 64; }
-static int fwd_nby(const Res& r) { return (r.MTf + 4 * kTW - 1) / (4 * kTW); }
-static int bwd_nby(const Res& r) { return (r.MTb + 4 * kTW - 1) / (4 * kTW); }
 
 static bool layout(const wg_stftloss* h, int B, int N, bool saved, Layout& L) {
   if (!h || B < 1 || N < 1) return false;
   size_t off = 0, gmax = 0;
   for (int i = 0; i < h->n_res; ++i) {
-    const Res& r = h->res[i];
+    const Geom& r = h->res[i];
     if (N <= r.n_fft / 2) return false;                     // reflect padding needs N > n_fft / 2
-    L.F[i] = N / r.hop + 1;
-    L.Fp[i] = (L.F[i] + kBN - 1) / kBN * kBN;
-    L.nbx[i] = L.Fp[i] / kBN;
-    L.nby[i] = fwd_nby(r);
+    frame_counts(N, r.hop, L.F[i], L.Fp[i], L.nbx[i]);
+    L.nby[i] = gemm_nby(r.MTf);
     L.my[i] = off;
     off += up64((size_t)B * (r.n_fft / 2 + 1) * L.Fp[i]);
     L.part[i] = off;
@@ -482,34 +405,49 @@ static bool layout(const wg_stftloss* h, int B, int N, bool saved, Layout& L) {
   return true;
 }
 
+// The out-of-line part of wg_stftconv.h.
+namespace wgsc {
+
+int check_geom(const char* prefix, int n_fft, int hop, int win) {
+  if (n_fft < 32 || n_fft > kMaxFft || n_fft % 32)
+    return wg::fail(WG_ERR_INVALID, "%sn_fft must be a multiple of 32 in [32, 2048]", prefix);
+  if (hop < 1 || hop > n_fft) return wg::fail(WG_ERR_INVALID, "%shop must be in [1, n_fft]", prefix);
+  if (win < 1 || win > n_fft) return wg::fail(WG_ERR_INVALID, "%swin must be in [1, n_fft]", prefix);
+  return WG_OK;
+}
+
+int upload_bases(Geom& r, const float* fb) {
+  std::vector<float> af, ab;
+  pack_bases(r, fb, af, ab);
+  HIP_TRY(hipMalloc((void**)&r.d_Af, af.size() * 4));
+  HIP_TRY(hipMalloc((void**)&r.d_Ab, ab.size() * 4));
+  HIP_TRY(hipMemcpy(r.d_Af, af.data(), af.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(r.d_Ab, ab.data(), ab.size() * 4, hipMemcpyHostToDevice));
+  return WG_OK;
+}
+
+void free_bases(Geom& r) {
+  if (r.d_Af) (void)hipFree(r.d_Af);
+  if (r.d_Ab) (void)hipFree(r.d_Ab);
+  r.d_Af = r.d_Ab = nullptr;
+}
+
+hipError_t launch_gather(const Geom& r, const float* G, float* gx, int B, int N, int F, bool accumulate, const int* lens,
+                         int min_len, hipStream_t s) {
+  const GatherArgs ga{G, gx, r.n_fft, r.hop, r.win, r.lpad, N, F, r.MTb * 32, accumulate, lens, min_len};
+  hipLaunchKernelGGL(sl_gather_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, ga);
+  return hipGetLastError();
+}
+
+}  // namespace wgsc
+
 // device part of wg_stftloss_create: the packed bases of every resolution
-static int upload_bases(wg_stftloss* h, const float* const* fwd_basis) {
+static int upload_all(wg_stftloss* h, const float* const* fwd_basis) {
   wg::DeviceGuard dev_guard;
   HIP_TRY(hipGetDevice(&dev_guard.prev));
   HIP_TRY(hipSetDevice(h->device));
-  for (int i = 0; i < h->n_res; ++i) {
-    Res& r = h->res[i];
-    const int n = r.n_fft, K = n / 2 + 1;
-    const float* fb = fwd_basis[i];                         // [2K][n]: real rows, then imaginary rows
-    auto basis = [&](int row, int tap) -> float {
-      if (row >= n || tap >= n) return 0.0f;
-      const int ref = row == 0 ? 0 : row == 1 ? n / 2 : (row & 1) ? K + (row >> 1) : (row >> 1);
-      return fb[(size_t)ref * n + tap];
-    };
-    std::vector<float> af((size_t)r.MTf * r.KSf * 64), ab((size_t)r.MTb * r.KSb * 64);
-    for (int mt = 0; mt < r.MTf; ++mt)
-      for (int ks = 0; ks < r.KSf; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-          af[((size_t)mt * r.KSf + ks) * 64 + lane] = basis(mt * 32 + (lane & 31), r.lpad + 2 * ks + (lane >> 5));
-    for (int mt = 0; mt < r.MTb; ++mt)
-      for (int ks = 0; ks < r.KSb; ++ks)
-        for (int lane = 0; lane < 64; ++lane)
-          ab[((size_t)mt * r.KSb + ks) * 64 + lane] = basis(2 * ks + (lane >> 5), r.lpad + mt * 32 + (lane & 31));
-    HIP_TRY(hipMalloc((void**)&r.d_Af, af.size() * 4));
-    HIP_TRY(hipMalloc((void**)&r.d_Ab, ab.size() * 4));
-    HIP_TRY(hipMemcpy(r.d_Af, af.data(), af.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r.d_Ab, ab.data(), ab.size() * 4, hipMemcpyHostToDevice));
-  }
+  for (int i = 0; i < h->n_res; ++i)
+    if (int rc = upload_bases(h->res[i], fwd_basis[i])) return rc;
   return WG_OK;
 }
 
@@ -520,12 +458,8 @@ int wg_stftloss_create(int32_t n_res, const int32_t* n_fft, const int32_t* hop, 
   if (!n_fft || !hop || !win || !out) return wg::fail(WG_ERR_INVALID, "null argument");
   if (n_res < 1 || n_res > kMaxRes) return wg::fail(WG_ERR_INVALID, "stft loss: 1 to 8 resolutions");
   if (!(eps > 0.0f)) return wg::fail(WG_ERR_INVALID, "stft loss: eps must be positive");
-  for (int i = 0; i < n_res; ++i) {
-    if (n_fft[i] < 32 || n_fft[i] > kMaxFft || n_fft[i] % 32)
-      return wg::fail(WG_ERR_INVALID, "stft loss: n_fft must be a multiple of 32 in [32, 2048]");
-    if (hop[i] < 1 || hop[i] > n_fft[i]) return wg::fail(WG_ERR_INVALID, "stft loss: hop must be in [1, n_fft]");
-    if (win[i] < 1 || win[i] > n_fft[i]) return wg::fail(WG_ERR_INVALID, "stft loss: win must be in [1, n_fft]");
-  }
+  for (int i = 0; i < n_res; ++i)
+    if (int rc = check_geom("stft loss: ", n_fft[i], hop[i], win[i])) return rc;
   if (device_id >= 0) {
     if (!fwd_basis) return wg::fail(WG_ERR_INVALID, "null argument");
     for (int i = 0; i < n_res; ++i)
@@ -535,22 +469,12 @@ int wg_stftloss_create(int32_t n_res, const int32_t* n_fft, const int32_t* hop, 
   h->device = device_id;
   h->n_res = n_res;
   h->eps = eps;
-  for (int i = 0; i < n_res; ++i) {
-    Res& r = h->res[i];
-    r.n_fft = n_fft[i];
-    r.hop = hop[i];
-    r.win = win[i];
-    r.lpad = (r.n_fft - r.win) / 2;
-    r.MTf = r.n_fft / 32;
-    r.KSf = (r.win + kKC - 1) / kKC * (kKC / 2);
-    r.MTb = (r.win + 31) / 32;
-    r.KSb = (r.n_fft + kKC - 1) / kKC * (kKC / 2);
-  }
+  for (int i = 0; i < n_res; ++i) set_geom(h->res[i], n_fft[i], hop[i], win[i]);
   if (device_id < 0) {   // planning handle: geometry and workspace sizes only
     *out = h;
     return WG_OK;
   }
-  const int rc = upload_bases(h, fwd_basis);
+  const int rc = upload_all(h, fwd_basis);
   if (rc != WG_OK) {
     wg_stftloss_destroy(h);
     return rc;
@@ -561,10 +485,7 @@ int wg_stftloss_create(int32_t n_res, const int32_t* n_fft, const int32_t* hop, 
 
 int wg_stftloss_destroy(wg_stftloss* h) {
   if (!h) return WG_OK;
-  for (int i = 0; i < h->n_res; ++i) {
-    if (h->res[i].d_Af) (void)hipFree(h->res[i].d_Af);
-    if (h->res[i].d_Ab) (void)hipFree(h->res[i].d_Ab);
-  }
+  for (int i = 0; i < h->n_res; ++i) free_bases(h->res[i]);
   delete h;
   return WG_OK;
 }
@@ -573,13 +494,6 @@ size_t wg_stftloss_workspace_bytes(const wg_stftloss* h, int32_t B, int32_t n_sa
   Layout L;
   if (!layout(h, B, n_samples, saved != 0, L)) return 0;
   return L.total * 4;
-}
-
-// shortest length a ragged batch may hold: every resolution reflects about the utterance's own end
-static int ragged_min_len(const wg_stftloss* h) {
-  int n = 0;
-  for (int i = 0; i < h->n_res; ++i) n = h->res[i].n_fft > n ? h->res[i].n_fft : n;
-  return n / 2 + 1;
 }
 
 // Argument checks shared by the forward and the backward.  The ragged entry points (ragged = true, lens a device array
@@ -614,9 +528,9 @@ static int loss_forward(wg_stftloss* h, const float* audio, const float* target,
   fa.lens = lens;
   fa.B = B;
   fa.N = N;
-  fa.min_len = ragged_min_len(h);
+  fa.min_len = ragged_min_len(h->res, h->n_res);
   for (int i = 0; i < h->n_res; ++i) {
-    const Res& r = h->res[i];
+    const Geom& r = h->res[i];
     GemmArgs a{};
     a.A = r.d_Af;
     a.MT = r.MTf;
@@ -690,12 +604,12 @@ static int loss_backward(wg_stftloss* h, const float* g_out3, bool ragged, const
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   for (int i = 0; i < h->n_res; ++i) {
-    const Res& r = h->res[i];
+    const Geom& r = h->res[i];
     GemmArgs a{};
     a.A = r.d_Ab;
     a.MT = r.MTb;
     a.KS = r.KSb;
-    a.nby = bwd_nby(r);
+    a.nby = gemm_nby(r.MTb);
     a.n_fft = r.n_fft;
     a.hop = r.hop;
     a.lpad = r.lpad;
@@ -714,19 +628,12 @@ static int loss_backward(wg_stftloss* h, const float* g_out3, bool ragged, const
     a.G = ws + L.G;
     a.Wp = r.MTb * 32;
     a.lens = lens;
-    a.min_len = ragged_min_len(h);
+    a.min_len = ragged_min_len(h->res, h->n_res);
     a.cnt = lens ? (const double*)(ws + L.sums) + 2 * kMaxRes + i : nullptr;
     const dim3 grid(L.nbx[i], a.nby, B);
-    switch (((r.MTb + a.nby - 1) / a.nby + 3) / 4) {          // tiles per wave of the fullest workgroup
-      case 1: hipLaunchKernelGGL((sl_gemm_kernel<kBwd, 1>), grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((sl_gemm_kernel<kBwd, 2>), grid, dim3(256), 0, s, a); break;
-      case 3: hipLaunchKernelGGL((sl_gemm_kernel<kBwd, 3>), grid, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL((sl_gemm_kernel<kBwd, 4>), grid, dim3(256), 0, s, a); break;
-    }
+    WGSC_LAUNCH_GEMM(sl_gemm_kernel, kBwd, grid, s, a);
     HIP_TRY(hipGetLastError());
-    GatherArgs ga{a.G, audio_grad_out, r.n_fft, r.hop, r.win, r.lpad, N, L.F[i], a.Wp, i > 0, lens, a.min_len};
-    hipLaunchKernelGGL(sl_gather_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, ga);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_gather(r, a.G, audio_grad_out, B, N, L.F[i], i > 0, lens, a.min_len, s));
   }
   return WG_OK;
 }

@@ -5,24 +5,20 @@
 #include <stddef.h>
 #include <stdint.h>
 
-namespace wgml {
+#include "wg_stftconv.h"
 
-constexpr int kMaxScales = 8, kMaxFft = 2048;
-constexpr int kBN = 64;          // frames per workgroup of every kernel; the frame pitch Fp is F rounded up to it
-constexpr int kKC = 64;          // depth of one staged operand tile
-constexpr int kTW = 4;           // M tiles per wave at most
+namespace wgml {
+using namespace wgsc;            // the projection kernels take kBN frames per workgroup, as the GEMM
+
+constexpr int kMaxScales = 8;
 constexpr int kMelRows = 16;     // mel rows (forward) or bins (backward) per workgroup of the projection kernels
 
-struct Scale {
-  int n_fft, hop, win, lpad, n_mels;
-  int MTf, KSf, MTb, KSb;        // forward: n_fft/32 row tiles x window taps; backward: window tap tiles x n_fft rows
-  float *d_Af = nullptr, *d_Ab = nullptr;   // packed MFMA fragments of the windowed Fourier basis, as stft_loss.hip
+struct Scale : Geom {
+  int n_mels;
   float* d_W = nullptr;          // the dense bank [n_mels][n_fft/2 + 1]
   int* d_span = nullptr;         // [n_mels][2] first and last non-zero bin of a row (first > last: an empty row), then
                                  // [n_fft/2 + 1][2] lowest and highest row whose span covers a bin (lowest > highest: none)
 };
-
-inline size_t up64(size_t n) { return (n + 63) / 64 * 64; }
 
 // Offsets in floats; every block a multiple of 64 floats.
 //   spectra: per scale r   [B][n_fft][Fp_r]          rows interleaved: row 0 = re of bin 0, row 1 = re of bin n_fft/2,
@@ -47,12 +43,6 @@ struct wg_melloss {
 
 namespace wgml {
 
-inline int ragged_min_len(const wg_melloss* h) {
-  int n = 0;
-  for (int i = 0; i < h->n_scales; ++i) n = h->sc[i].n_fft > n ? h->sc[i].n_fft : n;
-  return n / 2 + 1;
-}
-
 inline bool make_layout(const wg_melloss* h, int B, int N, Layout& L) {
   if (!h || B < 1 || B > 65535 || N < 1) return false;
   size_t so = 0, mo = 0, po = 0;
@@ -60,9 +50,7 @@ inline bool make_layout(const wg_melloss* h, int B, int N, Layout& L) {
   for (int i = 0; i < h->n_scales; ++i) {
     const Scale& r = h->sc[i];
     if (N <= r.n_fft / 2) return false;                     // reflect padding needs N > n_fft / 2
-    L.F[i] = N / r.hop + 1;
-    L.Fp[i] = (L.F[i] + kBN - 1) / kBN * kBN;
-    L.nbx[i] = L.Fp[i] / kBN;
+    frame_counts(N, r.hop, L.F[i], L.Fp[i], L.nbx[i]);
     L.nmy[i] = (r.n_mels + kMelRows - 1) / kMelRows;
     const size_t plane = up64((size_t)B * r.n_fft * L.Fp[i]), melp = up64((size_t)B * r.n_mels * L.Fp[i]);
     const size_t g = up64((size_t)B * L.F[i] * r.MTb * 32);

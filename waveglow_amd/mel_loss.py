@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .stft_loss import check_geometry, check_lengths, forward_basis
+from .stft_loss import _WaveformLoss, check_geometry, forward_basis
 from .taco_stft import slaney_mel_filterbank
 
 DAC_N_FFTS = (32, 64, 128, 256, 512, 1024, 2048)
@@ -42,32 +42,7 @@ def check_scales(n_ffts, hop_sizes, win_lengths, n_mels):
       raise _lib.WgError(f"n_mels must be in [1, n_fft / 2 + 1], got {m} for n_fft {n}")
 
 
-class _LossFn(torch.autograd.Function):
-  """Inputs: the module, prediction and target [B, N], and the device copy of the lengths or None.  Output: the device
-  vector (log, lin, loss).  The forward keeps the two saved buffers and the lengths on ctx; the backward reads them and
-  writes neither, so a second backward under retain_graph gives the same bits."""
-
-  @staticmethod
-  def forward(ctx, crit, x, y, lens):
-    B, N = x.shape
-    out, spectra, mels = crit._run(x, y, saved=True, lens=lens)
-    ctx.crit, ctx.spectra, ctx.mels, ctx.dims, ctx.lens = crit, spectra, mels, (B, N), lens
-    return out
-
-  @staticmethod
-  def backward(ctx, g_out):
-    crit = ctx.crit
-    B, N = ctx.dims
-    g = g_out.to(torch.float32).contiguous()
-    gx = torch.empty((B, N), dtype=torch.float32, device=ctx.mels.device)
-    stream = torch.cuda.current_stream(ctx.mels.device).cuda_stream
-    _lib.check(crit.lib.wg_melloss_backward(crit._h, g.data_ptr(), ctx.lens.data_ptr() if ctx.lens is not None else None,
-                                            crit.factor_log, crit.factor_lin, ctx.spectra.data_ptr(),
-                                            ctx.mels.data_ptr(), gx.data_ptr(), B, N, C.c_void_p(stream)))
-    return None, gx, None, None
-
-
-class MultiScaleMelLoss(torch.nn.Module):
+class MultiScaleMelLoss(_WaveformLoss):
   """``crit(audio, target, lengths=None)`` -> 0-dim fp32 loss on the device with a graph back to ``audio``;
   ``crit.terms(audio, target, lengths=None)`` -> ``(log, lin)``.
 
@@ -90,6 +65,8 @@ class MultiScaleMelLoss(torch.nn.Module):
 
   Supported: 1 to 8 scales, ``n_fft`` a multiple of 32 in [32, 2048], ``1 <= hop, win <= n_fft``,
   ``1 <= n_mels <= n_fft / 2 + 1``, ``clamp > 0`` and finite.  Everything else raises WgError at construction."""
+
+  _NAME, _DESTROY = "MultiScaleMelLoss", "wg_melloss_destroy"
 
   def __init__(self, sampling_rate=22050, n_ffts=DAC_N_FFTS, hop_sizes=None, win_lengths=None, n_mels=DAC_N_MELS,
                fmin=0.0, fmax=None, clamp=1e-5, factor_log=1.0, factor_lin=0.0, device="cuda", mel_bases=None):
@@ -130,13 +107,6 @@ class MultiScaleMelLoss(torch.nn.Module):
     _lib.check(self.lib.wg_melloss_create(n, arr(n_ffts), arr(hop_sizes), arr(win_lengths), arr(n_mels), ptrs(bases),
                                           ptrs(banks), self.clamp, _lib.device_index(device), C.byref(self._h)))
 
-  def __del__(self):
-    try:
-      if getattr(self, "_h", None):
-        self.lib.wg_melloss_destroy(self._h)
-    except Exception:
-      pass
-
   def workspace_bytes(self, B: int, N: int) -> int:
     """Bytes one forward with a graph keeps until its backward (0 when N <= max(n_ffts) / 2): per scale the prediction's
     (re, im) [B, n_fft, F] and both linear mels [B, n_mels, F] (F rounded up to 64), and the cell counts."""
@@ -145,31 +115,8 @@ class MultiScaleMelLoss(torch.nn.Module):
   def _need(self):
     return max(s[0] for s in self.scales) // 2
 
-  def _check(self, x, y):
-    for name, t in (("audio", x), ("target", y)):
-      if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or \
-          _lib.device_index(t.device) != _lib.device_index(self.device):
-        raise _lib.WgError(f"MultiScaleMelLoss: {name} must be on {self.device} (no CPU fallback)")
-      if t.dtype != torch.float32:
-        raise _lib.WgError(f"MultiScaleMelLoss takes float32 {name}, got {t.dtype}")
-      if t.dim() != 2:
-        raise _lib.WgError(f"MultiScaleMelLoss takes {name} [B, N], got shape {tuple(t.shape)}")
-    if x.shape != y.shape:
-      raise _lib.WgError(f"audio {tuple(x.shape)} and target {tuple(y.shape)} differ in shape")
-    if y.requires_grad:
-      raise _lib.WgError("MultiScaleMelLoss: only audio gets a gradient; detach the target")
-    if x.shape[0] < 1 or x.shape[1] <= self._need():
-      raise _lib.WgError(f"audio of {x.shape[1]} samples is too short (reflect padding needs > {self._need()})")
-
-  def _lens(self, lengths, x):
-    """The checked lengths as an int32 tensor on x's device (one small copy), or None."""
-    if lengths is None:
-      return None
-    B, N = x.shape
-    return torch.tensor(check_lengths(lengths, B, N, self._need()), dtype=torch.int32).to(x.device)
-
   def _run(self, x, y, saved, lens=None):
-    """One library call on contiguous fp32 [B, N]: (out3, spectra, mels), the last two None without saved state.
+    """One library call on contiguous fp32 [B, N]: (out3, (spectra, mels)), the last two None without saved state.
     lens: int32 [B] on the device, or None."""
     x, y = x.detach().contiguous(), y.detach().contiguous()
     B, N = x.shape
@@ -184,19 +131,13 @@ class MultiScaleMelLoss(torch.nn.Module):
                                            lens.data_ptr() if lens is not None else None, self.factor_log,
                                            self.factor_lin, out.data_ptr(), spectra.data_ptr() if saved else None,
                                            mels.data_ptr() if saved else None, B, N, C.c_void_p(stream)))
-    return out, spectra, mels
+    return out, (spectra, mels)
 
-  def _out3(self, audio, target, lengths=None):
-    self._check(audio, target)
-    lens = self._lens(lengths, audio)
-    if torch.is_grad_enabled() and audio.requires_grad:
-      return _LossFn.apply(self, audio, target, lens)
-    return self._run(audio, target, saved=False, lens=lens)[0]
-
-  def terms(self, audio: torch.Tensor, target: torch.Tensor, lengths=None):
-    """(log, lin): the log-mel and the linear-mel L1 terms, each averaged over the scales."""
-    out = self._out3(audio, target, lengths)
-    return out[0], out[1]
-
-  def forward(self, audio: torch.Tensor, target: torch.Tensor, lengths=None) -> torch.Tensor:
-    return self._out3(audio, target, lengths)[2]
+  def _backward(self, state, g, lens, B, N):
+    spectra, mels = state
+    gx = torch.empty((B, N), dtype=torch.float32, device=mels.device)
+    stream = torch.cuda.current_stream(mels.device).cuda_stream
+    _lib.check(self.lib.wg_melloss_backward(self._h, g.data_ptr(), lens.data_ptr() if lens is not None else None,
+                                            self.factor_log, self.factor_lin, spectra.data_ptr(), mels.data_ptr(),
+                                            gx.data_ptr(), B, N, C.c_void_p(stream)))
+    return gx

@@ -81,35 +81,79 @@ def check_lengths(lengths, B: int, N: int, min_exclusive: int):
 
 
 class _LossFn(torch.autograd.Function):
-  """Inputs: the module, prediction and target [B, N], and the device copy of the lengths or None.  Output: the device
-  vector (sc, mag, loss).  The forward keeps the library's workspace and the lengths on ctx; the backward writes only to
-  that workspace's scratch part, so a second backward under retain_graph gives the same bits."""
+  """Inputs: the module (a _WaveformLoss), prediction and target [B, N], and the device copy of the lengths or None.
+  Output: the module's device vector of three.  The forward keeps what the module's _run saved and the lengths on ctx;
+  the module's _backward rewrites nothing a later backward reads, so a second backward under retain_graph gives the same
+  bits."""
 
   @staticmethod
   def forward(ctx, crit, x, y, lens):
-    B, N = x.shape
-    out, ws = crit._run(x, y, saved=True, lens=lens)
-    ctx.crit, ctx.ws, ctx.dims, ctx.lens = crit, ws, (B, N), lens
+    out, state = crit._run(x, y, saved=True, lens=lens)
+    ctx.crit, ctx.state, ctx.dims, ctx.lens = crit, state, tuple(x.shape), lens
     return out
 
   @staticmethod
   def backward(ctx, g_out):
-    crit, ws = ctx.crit, ctx.ws
     B, N = ctx.dims
-    g = g_out.to(torch.float32).contiguous()
-    gx = torch.empty((B, N), dtype=torch.float32, device=ws.device)
-    stream = torch.cuda.current_stream(ws.device).cuda_stream
-    if ctx.lens is None:
-      _lib.check(crit.lib.wg_stftloss_backward(crit._h, g.data_ptr(), crit.factor_sc, crit.factor_mag, gx.data_ptr(), B,
-                                               N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    else:
-      _lib.check(crit.lib.wg_stftloss_backward_ragged(crit._h, g.data_ptr(), ctx.lens.data_ptr(), crit.factor_sc,
-                                                      crit.factor_mag, gx.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
-                                                      C.c_void_p(stream)))
+    gx = ctx.crit._backward(ctx.state, g_out.to(torch.float32).contiguous(), ctx.lens, B, N)
     return None, gx, None, None
 
 
-class MultiResolutionSTFTLoss(torch.nn.Module):
+class _WaveformLoss(torch.nn.Module):
+  """What the waveform losses over conv-STFTs share: input checks, the upload of the lengths, the choice between the
+  graph and the no-graph path, and the handle's release.  A subclass sets ``_NAME`` (its name in messages) and
+  ``_DESTROY`` (the library function that frees ``self._h``), and supplies ``_need()`` (the largest ``n_fft // 2``),
+  ``_run(x, y, saved, lens) -> (out3, state)`` (one library call on fp32 [B, N]; ``state`` is what the backward needs,
+  nothing of it allocated unless ``saved``) and ``_backward(state, g, lens, B, N) -> gx``.  ``lens``: int32 [B] on the
+  device, or None."""
+
+  def __del__(self):
+    try:
+      if getattr(self, "_h", None):
+        getattr(self.lib, self._DESTROY)(self._h)
+    except Exception:
+      pass
+
+  def _check(self, x, y):
+    for name, t in (("audio", x), ("target", y)):
+      if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or \
+          _lib.device_index(t.device) != _lib.device_index(self.device):
+        raise _lib.WgError(f"{self._NAME}: {name} must be on {self.device} (no CPU fallback)")
+      if t.dtype != torch.float32:
+        raise _lib.WgError(f"{self._NAME} takes float32 {name}, got {t.dtype}")
+      if t.dim() != 2:
+        raise _lib.WgError(f"{self._NAME} takes {name} [B, N], got shape {tuple(t.shape)}")
+    if x.shape != y.shape:
+      raise _lib.WgError(f"audio {tuple(x.shape)} and target {tuple(y.shape)} differ in shape")
+    if y.requires_grad:
+      raise _lib.WgError(f"{self._NAME}: only audio gets a gradient; detach the target")
+    if x.shape[0] < 1 or x.shape[1] <= self._need():
+      raise _lib.WgError(f"audio of {x.shape[1]} samples is too short (reflect padding needs > {self._need()})")
+
+  def _lens(self, lengths, x):
+    """The checked lengths as an int32 tensor on x's device (one small copy), or None."""
+    if lengths is None:
+      return None
+    B, N = x.shape
+    return torch.tensor(check_lengths(lengths, B, N, self._need()), dtype=torch.int32).to(x.device)
+
+  def _out3(self, audio, target, lengths=None):
+    self._check(audio, target)
+    lens = self._lens(lengths, audio)
+    if torch.is_grad_enabled() and audio.requires_grad:
+      return _LossFn.apply(self, audio, target, lens)
+    return self._run(audio, target, saved=False, lens=lens)[0]
+
+  def terms(self, audio: torch.Tensor, target: torch.Tensor, lengths=None):
+    """The two terms of the loss (see the class), each averaged over the resolutions or scales."""
+    out = self._out3(audio, target, lengths)
+    return out[0], out[1]
+
+  def forward(self, audio: torch.Tensor, target: torch.Tensor, lengths=None) -> torch.Tensor:
+    return self._out3(audio, target, lengths)[2]
+
+
+class MultiResolutionSTFTLoss(_WaveformLoss):
   """``crit(audio, target, lengths=None)`` -> 0-dim fp32 loss on the device with a graph back to ``audio``;
   ``crit.terms(audio, target, lengths=None)`` -> ``(sc, mag)``.
 
@@ -127,6 +171,8 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
   Supported geometries: 1 to 8 resolutions, each with ``n_fft`` a multiple of 32 in [32, 2048], ``1 <= hop <= n_fft``
   (it need not divide ``n_fft``) and ``1 <= win_length <= n_fft``; ``window`` is any name ``scipy.signal.get_window``
   knows.  Everything else raises WgError at construction."""
+
+  _NAME, _DESTROY = "MultiResolutionSTFTLoss", "wg_stftloss_destroy"
 
   def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240),
                window="hann", factor_sc=1.0, factor_mag=1.0, eps=1e-7, device="cuda"):
@@ -150,43 +196,14 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
     _lib.check(self.lib.wg_stftloss_create(n, arr(fft_sizes), arr(hop_sizes), arr(win_lengths), ptrs, self.eps,
                                            _lib.device_index(device), C.byref(self._h)))
 
-  def __del__(self):
-    try:
-      if getattr(self, "_h", None):
-        self.lib.wg_stftloss_destroy(self._h)
-    except Exception:
-      pass
-
   def workspace_bytes(self, B: int, N: int) -> int:
     """Bytes one forward with a graph keeps until its backward (0 when N <= max(fft_sizes) / 2): per resolution the
     prediction's (re, im) [B, n_fft, F] and M(target) [B, n_fft / 2 + 1, F] (F rounded up to 64), the per-workgroup
     sums, and one frame-gradient scratch [B, F, win] that the backward reuses for every resolution."""
     return int(self.lib.wg_stftloss_workspace_bytes(self._h, B, N, 1))
 
-  def _check(self, x, y):
-    for name, t in (("audio", x), ("target", y)):
-      if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or \
-          _lib.device_index(t.device) != _lib.device_index(self.device):
-        raise _lib.WgError(f"MultiResolutionSTFTLoss: {name} must be on {self.device} (no CPU fallback)")
-      if t.dtype != torch.float32:
-        raise _lib.WgError(f"MultiResolutionSTFTLoss takes float32 {name}, got {t.dtype}")
-      if t.dim() != 2:
-        raise _lib.WgError(f"MultiResolutionSTFTLoss takes {name} [B, N], got shape {tuple(t.shape)}")
-    if x.shape != y.shape:
-      raise _lib.WgError(f"audio {tuple(x.shape)} and target {tuple(y.shape)} differ in shape")
-    if y.requires_grad:
-      raise _lib.WgError("MultiResolutionSTFTLoss: only audio gets a gradient; detach the target")
-    need = max(n for n, _, _ in self.resolutions) // 2
-    if x.shape[0] < 1 or x.shape[1] <= need:
-      raise _lib.WgError(f"audio of {x.shape[1]} samples is too short (reflect padding needs > {need})")
-
-  def _lens(self, lengths, x):
-    """The checked lengths as an int32 tensor on x's device (one small copy), or None."""
-    if lengths is None:
-      return None
-    B, N = x.shape
-    lens = check_lengths(lengths, B, N, max(n for n, _, _ in self.resolutions) // 2)
-    return torch.tensor(lens, dtype=torch.int32).to(x.device)
+  def _need(self):
+    return max(n for n, _, _ in self.resolutions) // 2
 
   def _run(self, x, y, saved, lens=None):
     """One library call on contiguous fp32 [B, N]: (out3, workspace).  lens: int32 [B] on the device, or None."""
@@ -208,17 +225,14 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
                     out.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     return out, ws
 
-  def _out3(self, audio, target, lengths=None):
-    self._check(audio, target)
-    lens = self._lens(lengths, audio)
-    if torch.is_grad_enabled() and audio.requires_grad:
-      return _LossFn.apply(self, audio, target, lens)
-    return self._run(audio, target, saved=False, lens=lens)[0]
-
-  def terms(self, audio: torch.Tensor, target: torch.Tensor, lengths=None):
-    """(sc, mag): the spectral-convergence and log-magnitude terms, each averaged over the resolutions."""
-    out = self._out3(audio, target, lengths)
-    return out[0], out[1]
-
-  def forward(self, audio: torch.Tensor, target: torch.Tensor, lengths=None) -> torch.Tensor:
-    return self._out3(audio, target, lengths)[2]
+  def _backward(self, ws, g, lens, B, N):
+    gx = torch.empty((B, N), dtype=torch.float32, device=ws.device)
+    stream = torch.cuda.current_stream(ws.device).cuda_stream
+    if lens is None:
+      _lib.check(self.lib.wg_stftloss_backward(self._h, g.data_ptr(), self.factor_sc, self.factor_mag, gx.data_ptr(), B,
+                                               N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    else:
+      _lib.check(self.lib.wg_stftloss_backward_ragged(self._h, g.data_ptr(), lens.data_ptr(), self.factor_sc,
+                                                      self.factor_mag, gx.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
+                                                      C.c_void_p(stream)))
+    return gx
