@@ -49,19 +49,39 @@ def _root(p):
   return torch.where(pos, torch.where(pos, p, torch.ones_like(p)).sqrt(), torch.zeros_like(p))
 
 
-def mag_stft(x, n_fft, hop, win, dtype):
+def spec_stft(x, n_fft, hop, win, dtype):
+  """(a)'s complex transform as (re, im), each [B, K, F]."""
   x = x.to(dtype)
   X = torch.stft(x, n_fft, hop, win, torch.hann_window(win, dtype=dtype), center=True, pad_mode="reflect",
                  return_complex=True)
-  return _root(X.real ** 2 + X.imag ** 2)                             # [B, K, F]
+  return X.real, X.imag
+
+
+def frames_unfold(x, n_fft, hop, dtype):
+  """The reflect-padded frames of (b): [B, F, n_fft]."""
+  xp = Fn.pad(x.to(dtype)[:, None, :], (n_fft // 2, n_fft // 2), mode="reflect")[:, 0]
+  return xp.unfold(1, n_fft, hop)
+
+
+def spec_of_frames(fr, n_fft, win):
+  """(b)'s transform of frames [B, F, n_fft] with the library's fp32 basis in the frames' dtype: (re, im), each [B, K, F]."""
+  X = torch.matmul(fr, _basis(n_fft, win).to(fr.dtype).t())            # [B, F, 2K]
+  K = n_fft // 2 + 1
+  return X[..., :K].transpose(1, 2), X[..., K:].transpose(1, 2)
+
+
+def spec_unfold(x, n_fft, hop, win, dtype):
+  return spec_of_frames(frames_unfold(x, n_fft, hop, dtype), n_fft, win)
+
+
+def mag_stft(x, n_fft, hop, win, dtype):
+  re, im = spec_stft(x, n_fft, hop, win, dtype)
+  return _root(re ** 2 + im ** 2)                                     # [B, K, F]
 
 
 def mag_unfold(x, n_fft, hop, win, dtype):
-  fwd = _basis(n_fft, win).to(dtype)
-  xp = Fn.pad(x.to(dtype)[:, None, :], (n_fft // 2, n_fft // 2), mode="reflect")[:, 0]
-  X = torch.matmul(xp.unfold(1, n_fft, hop), fwd.t())                  # [B, F, 2K]
-  K = n_fft // 2 + 1
-  return _root(X[..., :K] ** 2 + X[..., K:] ** 2).transpose(1, 2)
+  re, im = spec_unfold(x, n_fft, hop, win, dtype)
+  return _root(re ** 2 + im ** 2)
 
 
 def mels(mag_fn, x, scale, W, lengths, dtype):
@@ -101,22 +121,50 @@ def grad_of(fn, x, y, scales, **kw):
   return g
 
 
-def fragile_cells(x, y, scales, tau=1e-4, banks=None, clamp=CLAMP, lengths=None):
+def fragile_cells(x, y, scales, tau=1e-4, banks=None, clamp=CLAMP, lengths=None, frames=None, margin=None):
   """The number of mel cells with |lmel(x) - lmel(y)| < tau or |mel(x) - clamp| < tau clamp, from (a) alone.  A cell
   where both log-mels are exactly equal (a silent stretch in both signals) is as fragile as any other: inputs that must
-  qualify have none."""
+  qualify have none.  ``frames``: None, or ``frames[i][b]`` the frame indices of scale i and utterance b to which the
+  count is restricted (where prediction and target are equal by construction everywhere else, tests/_loss_cells.py).
+  ``margin``: None, or per scale an absolute distance that takes the place of ``tau``: a cell then counts when
+  |mel(x) - mel(y)| < margin or |mel(x) - clamp| < margin, i.e. when two mels that are each off by less than margin / 2
+  can exchange their order or cross the clamp."""
   banks = [bank(s) for s in scales] if banks is None else banks
+  B, N = x.shape
+  lens = [N] * B if lengths is None else lengths
   bad = 0
-  for s, W in zip(scales, banks):
-    mx = mels(mag_stft, x, s, W, lengths, torch.float64)
-    my = mels(mag_stft, y, s, W, lengths, torch.float64)
-    d = torch.clamp(mx, min=clamp).log() - torch.clamp(my, min=clamp).log()
-    bad += int(((d.abs() < tau) | ((mx - clamp).abs() < tau * clamp)).sum())
+  for i, (s, W) in enumerate(zip(scales, banks)):
+    for b, n in enumerate(lens):
+      mx = mels(mag_stft, x[b:b + 1, :n], s, W, None, torch.float64)
+      my = mels(mag_stft, y[b:b + 1, :n], s, W, None, torch.float64)
+      if frames is not None:
+        mx, my = mx[:, frames[i][b]], my[:, frames[i][b]]
+      if margin is not None:
+        bad += int((((mx - my).abs() < margin[i]) | ((mx - clamp).abs() < margin[i])).sum())
+        continue
+      d = torch.clamp(mx, min=clamp).log() - torch.clamp(my, min=clamp).log()
+      bad += int(((d.abs() < tau) | ((mx - clamp).abs() < tau * clamp)).sum())
   return bad
 
 
 def rel(a, b):
   return float((a.double() - b.double()).norm() / b.double().norm())
+
+
+DENSE_SCALE = (256, 64, 256, 12)
+
+
+def dense_bank():
+  """A bank [12, 129] that is no triangular one: rows that overlap widely, a row of zeros, negative entries, zeros inside a
+  span."""
+  gen = torch.Generator().manual_seed(5)
+  W = torch.rand(12, 129, generator=gen) * 0.1
+  W[:, 1::7] = 0.0
+  W[3] = 0.0
+  W[5, :100] = 0.0
+  W[7, 40:] = 0.0
+  W[9] -= 0.02
+  return W
 
 
 def noise(B, N, seed):

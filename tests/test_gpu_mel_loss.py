@@ -185,14 +185,8 @@ def test_bank_through_mel_bases():
   against (a) with the same bank."""
   B, N = 2, 2048
   x, y = _inputs(B, N)
-  sc = ((256, 64, 256, 12),)
-  gen = torch.Generator().manual_seed(5)
-  W = torch.rand(12, 129, generator=gen) * 0.1
-  W[:, 1::7] = 0.0
-  W[3] = 0.0
-  W[5, :100] = 0.0
-  W[7, 40:] = 0.0
-  W[9] -= 0.02
+  sc = (O.DENSE_SCALE,)
+  W = O.dense_bank()
   a = [float(v) for v in O.loss_stft(x, y, sc, banks=[W], factor_lin=1.0)]
   b = [float(v) for v in O.loss_unfold(x, y, sc, banks=[W], factor_lin=1.0, dtype=torch.float32)]
   crit = _crit(sc, mel_bases=[W.numpy()])

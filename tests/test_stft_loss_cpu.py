@@ -85,12 +85,15 @@ def grad_ref64(x, y, resolutions=DEFAULT_RES, eps=1e-7, factor_sc=1.0, factor_ma
   return g
 
 
-def fragile_bins(x, y, resolutions=DEFAULT_RES, eps=1e-7, tau=1e-5):
+def fragile_bins(x, y, resolutions=DEFAULT_RES, eps=1e-7, tau=1e-5, frames=None):
   """(fragile, total) in fp64: bins above the clamp whose log-magnitude difference is within tau of 0, plus bins whose
-  power is within tau (relative) of eps.  A condition on the inputs, computed from the reference alone."""
+  power is within tau (relative) of eps.  A condition on the inputs, computed from the reference alone.  ``frames``:
+  None, or per resolution the frame indices to which the count is restricted (tests/_loss_cells.py)."""
   bad = total = 0
-  for n_fft, hop, win in resolutions:
+  for i, (n_fft, hop, win) in enumerate(resolutions):
     px, py = power_stft64(x.double(), n_fft, hop, win), power_stft64(y.double(), n_fft, hop, win)
+    if frames is not None:
+      px, py = px[..., frames[i]], py[..., frames[i]]
     mx, my = torch.clamp(px, min=eps).sqrt(), torch.clamp(py, min=eps).sqrt()
     bad += int(((px > eps) & ((my.log() - mx.log()).abs() < tau)).sum())
     bad += int(((px / eps - 1).abs() < tau).sum())

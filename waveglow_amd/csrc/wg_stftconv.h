@@ -114,9 +114,14 @@ __device__ __forceinline__ int ragged_len(const int* lens, int b, int pitch, int
 }
 __device__ __forceinline__ int ragged_frames(int n, int hop) { return n ? n / hop + 1 : 0; }
 
-// re^2 + im^2 with one rounding per operation, in the forward and in the backward alike, so both see the same clamp
+// re^2 + im^2 with one rounding per operation, in the forward and in the backward alike, so both see the same clamp and
+// equal (re, im) give equal bits in every kernel.  __fmul_rn / __fadd_rn are plain * and + in this toolchain, which the
+// compiler may contract to an fma, differently from one kernel to the next (the backward of the STFT loss then saw
+// M(x) != M(y) on equal frames): the pragma, on operations written out here, is what keeps the three roundings.
 __device__ __forceinline__ float power(float re, float im) {
-  return __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im));
+#pragma clang fp contract(off)
+  const float a = re * re, b = im * im;
+  return a + b;
 }
 
 // forward operand of chunk kc: taps lpad + 64 kc .. + 63 of 64 frames, read along the audio (reflect padding as index
