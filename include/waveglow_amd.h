@@ -279,6 +279,55 @@ int wg_data_gather(const void* pool, int32_t pool_dtype, int64_t pool_elems, con
                    const int32_t* picks, float* audio_out, int32_t* status_out, int32_t B, int32_t segment_length,
                    void* stream);
 
+/* ---- Streaming synthesis: the windows of a step in, the chunks of a step out (not in the reference), no handle ------
+ * A step over B streams synthesises one window per stream as a ragged batch (wg_infer_ragged, wg_stft_denoise_ragged)
+ * and hands out the interior of each window.  Both tables are device arrays of B rows, read by the kernels only.
+ * wg_stream_gather, one launch: for row b with w = windows[b], n = w.count clamped to [0, w_max] and to the source's
+ *   pitch (a negative start or count counts as n = 0), cpf = cols_per_frame (256 / n_group: 32):
+ *     mel_out[b][m][f]        = w.mel[m * w.mel_pitch + w.start + f]                      m < n_mel, f < n; 0 elsewhere
+ *                               (mel_out is [B][n_mel_out][w_max], n_mel_out >= n_mel: the rows behind n_mel are 0)
+ *     z_init_out[b][c][l]     = w.z_init[c * w.noise_pitch + cpf * w.start + l]           c < n_rem, l < cpf * n; 0 elsewhere
+ *     z_early_out[i][b][c][l] = w.z_early[i][c * w.noise_pitch + cpf * w.start + l]       c < n_early_size, likewise
+ *   (z_init_out [B][n_rem][cpf * w_max], z_early_out: host array of n_early device arrays [B][n_early_size][cpf * w_max],
+ *   0 <= n_early <= WG_STREAM_MAX_EARLY, null allowed when n_early is 0).  Elements are io_dtype (WG_F32 / WG_F16) and
+ *   copied unchanged.  Every element of the outputs is written, so the result does not depend on what they held.  The
+ *   outputs are 16-byte aligned and cols_per_frame is a multiple of 8; noise rows move in 16-byte pieces where the source
+ *   (pointer and pitch) is 16-byte aligned too, element by element where it is not.  Nothing outside
+ *   [0, pitch) of a source row is read, whatever the table holds; the row counts of the sources are the caller's word.
+ * wg_stream_emit, one launch: for row b with c = crops[b], n = c.count clamped to [0, n_max], over i in [0, n):
+ *     x = c.raw[c.offset + i], y = c.denoised[c.offset + i] (fp32; the two may be the same array), g = y * c.gain,
+ *     pcm_out[b][i] = int16 of round-half-even(clip(g, -1, 1) * 32767) -- convert_wav(np.clip(y * gain, -1, 1), int16) of
+ *       audio_utils.py:36-64 in float32 arithmetic, bit for bit; NOT peak-normalised --, pcm_out[b][n:] = 0
+ *       (pcm_out is [B][n_max], n_max a multiple of 8, 16-byte aligned);
+ *     stats_out[b] = {min x, max x, min y, max y, the number of i with g > 1 or g < -1, f, 0, 0} (8 floats, device);
+ *       f = 1 when an x or a y is NaN or infinite, else 0; all 0 for n = 0.  A count above 2^24 is not exact as a float.
+ *   Minimum, maximum and an integer count do not depend on the order of the reduction; no atomics.  c.offset must not
+ *   be negative (such a row counts as n = 0); offset + count inside the source is the caller's word.
+ * Both are enqueue-only. */
+#define WG_STREAM_MAX_EARLY 8
+typedef struct wg_stream_window {
+  const void* mel;                            /* this stream's mel [n_mel][mel_pitch] */
+  const void* z_init;                         /* its noise [n_rem][noise_pitch] */
+  const void* z_early[WG_STREAM_MAX_EARLY];   /* [n_early_size][noise_pitch] each, descending flow index; the rest unused */
+  int64_t mel_pitch;                          /* elements between two mel rows (the buffer's capacity in frames) */
+  int64_t noise_pitch;                        /* elements between two noise rows */
+  int32_t start;                              /* first mel frame of the window */
+  int32_t count;                              /* mel frames of the window */
+} wg_stream_window;
+typedef struct wg_stream_crop {
+  const float* raw;                           /* raw audio of the window */
+  const float* denoised;                      /* denoised audio of the window (raw again without a denoiser) */
+  int32_t offset;                             /* first sample of the chunk inside the window */
+  int32_t count;                              /* samples of the chunk */
+  float gain;
+  int32_t reserved;                           /* 0 */
+} wg_stream_crop;
+int wg_stream_gather(const wg_stream_window* windows, void* mel_out, void* z_init_out, void* const* z_early_out,
+                     int32_t n_early, int32_t B, int32_t n_mel, int32_t n_mel_out, int32_t n_rem, int32_t n_early_size,
+                     int32_t w_max, int32_t cols_per_frame, int32_t io_dtype, void* stream);
+int wg_stream_emit(const wg_stream_crop* crops, int16_t* pcm_out, float* stats_out, int32_t B, int32_t n_max,
+                   void* stream);
+
 /* ---- Validation metrics of mel-spectrogram pairs (src/waveglow/validation.py:211-235), no handle --------------------
  * Ragged batches: arrays [B][C][tmax] fp32 device, frame counts int32 device [B], read by the kernels only.  A frame
  * count outside [1, min(tmax, 4096)] counts as 0: that utterance's MFCC columns are all 0 and its metrics NaN.  fp64

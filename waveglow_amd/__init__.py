@@ -44,6 +44,9 @@ def __getattr__(name):
   if name in ("validate", "ValidationEntry", "ValidationEntries"):
     from . import validation
     return getattr(validation, name)
+  if name in ("StreamSession", "StreamChunk", "stream_halo"):
+    from . import streaming
+    return getattr(streaming, name)
   if name == "Denoiser":
     from .denoiser import Denoiser
     return Denoiser

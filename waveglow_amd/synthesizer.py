@@ -239,3 +239,45 @@ class Synthesizer:
                       was_overamplified=bool(raw[b, 0] < -1.0 or raw[b, 1] > 1.0),
                       peak=float(stats[b, pcm.DEN_PEAK]), inference_duration_s=inf_s / B,
                       denoising_duration_s=den_s / B, timepoint=timepoint) for b in range(B)]
+
+  # ------------------------------------------------------------------ streaming (waveglow_amd/streaming.py)
+  def open_stream(self, *, sigma: float = 1.0, denoiser_strength: float = 0.0005, seed: int = 0, chunk_frames: int = 32,
+                  total_frames: Optional[int] = None, gain: float = 1.0, dtype: Optional[torch.dtype] = None):
+    """A ``StreamSession``: push mel frames as they arrive, take audio in chunks of ``chunk_frames`` frames through
+    ``stream_step``.  The chunks, concatenated, have the bits of whole-utterance synthesis -- with ``total_frames`` given
+    those of ``infer(mel, seed=seed)`` (the noise is drawn here, once, as that call draws it, which resets the global
+    generators as that call does), open-ended those of ``model.infer_with_noise(mel, *session.noise())`` (a generator of
+    the session's own, drawn from at every push).  A chunk leaves once ``Hr`` frames behind it have arrived
+    (``streaming.halo_frames``: 99 for the default model with the denoiser on) or the stream is closed.  ``dtype``: the
+    mel's (float32 or float16), by default the model's parameter dtype.  WgError before any device work for
+    ``chunk_frames < 1`` and for a known length below 4 frames with the denoiser on (the whole-utterance path's limit)."""
+    from .streaming import StreamSession
+    if dtype is None:
+      dtype = next(self.model.parameters()).dtype
+    return StreamSession(self, sigma=sigma, denoiser_strength=denoiser_strength, seed=seed, chunk_frames=chunk_frames,
+                         total_frames=total_frames, gain=gain, dtype=dtype)
+
+  def stream_step(self, sessions, pcm: bool = True) -> list:
+    """Advance every session that has a chunk ready by ONE chunk, all of them in one launch sequence (one table upload,
+    one ``wg_stream_gather``, one ragged flow, one ragged denoiser call, one ``wg_stream_emit``, one pinned copy and one
+    synchronise).  Returns one entry per session: None where nothing was ready (that session is not touched), else a
+    ``StreamChunk``.  ``pcm=True``: int16 samples on the host, ``convert_wav(np.clip(denoised * gain, -1, 1), np.int16)``
+    -- NOT peak-normalised: the utterance's peak is not known while it streams -- with the raw audio's extrema and the
+    number of clipped samples; a chunk with NaN or infinite samples raises WgError naming the session, and no session
+    advances.  ``pcm=False``: fp32 device tensors ``raw`` and ``denoised``; nothing is copied or synchronised.  The
+    sessions of a step share dtype, sigma and -- those with the denoiser on -- its strength (WgError otherwise)."""
+    from .streaming import stream_step
+    return stream_step(self, list(sessions), pcm)
+
+  def infer_stream(self, mel: torch.Tensor, *, chunk_frames: int = 32, pcm: bool = True, **kw):
+    """Generator over one finished mel ``[1 or -, n_mel, T]``: ``open_stream(total_frames=T)``, ``push``, ``close``, then
+    one ``StreamChunk`` per step until the final one.  The audio is that of ``infer(mel, ...)`` with the same keywords."""
+    m = mel[0] if mel.dim() == 3 else mel
+    s = self.open_stream(chunk_frames=chunk_frames, total_frames=int(m.shape[-1]), dtype=m.dtype, **kw)
+    s.push(m)
+    s.close()
+    while True:
+      chunk = self.stream_step([s], pcm=pcm)[0]
+      yield chunk
+      if chunk.final:
+        return
