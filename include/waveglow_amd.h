@@ -171,6 +171,34 @@ int wg_loss_dev(const float* z, int64_t z_elems, const float* const* log_s, cons
  * them (for roofline reporting). */
 double wg_macs_per_group_step(const wg_handle* h);
 
+/* Which WN-layer kernel variant a call of this size runs on a device with n_cu compute units: the answer of the very
+ * functions the launch code calls (csrc/wg_plan.h).  Pure host arithmetic: no handle, no GPU, nothing is enqueued.
+ *   direction  WG_PLAN_INFER (wg_infer / wg_infer_ragged), WG_PLAN_FORWARD (wg_forward / wg_forward_ragged: the same
+ *              rules), WG_PLAN_TRAIN (the fused layer kernel of wg_train_forward / wg_train_infer_forward, whose tile
+ *              width the backward chain takes over), at audio_len = upsample_stride * n_frames.
+ * The test switches WG_FORCE_BN, WG_RESIDENT, WG_DISABLE_DEEP and WG_TRAIN_HALVES are read from the environment at the
+ * call, as the library reads them (WG_FORCE_BN of the first two directions: at wg_create).  Variants that differ in
+ * block_n, form or deep are different kernels; the library promises the same bits from all of them
+ * (tests/test_gpu_dispatch_identity.py). */
+typedef enum wg_plan_direction { WG_PLAN_INFER = 0, WG_PLAN_FORWARD = 1, WG_PLAN_TRAIN = 2 } wg_plan_direction;
+typedef enum wg_plan_form {
+  WG_PLAN_SINGLE = 0,       /* one tile per workgroup */
+  WG_PLAN_PAIR = 1,         /* two tiles per workgroup */
+  WG_PLAN_RESIDENT = 2      /* resident tile walk: resident_wgs workgroups walk all tiles */
+} wg_plan_form;
+typedef struct wg_plan_result {
+  int32_t block_n;            /* columns per tile: 64 or 128 */
+  int32_t form;               /* wg_plan_form */
+  int32_t resident_wgs;       /* grid of the resident walk, 0 otherwise */
+  int32_t deep;               /* 1: the two-step-deep weight prefetch kernel (256 channels, 64 columns, single tiles) */
+  int32_t frag16;             /* 1: GEMM 1 on 16x16x32 MFMAs from its own weight packing (256 channels, 128 columns) */
+  int32_t halves;             /* WG_PLAN_TRAIN: 2 = the batch runs as two half-batch chains; otherwise 1 */
+  int32_t rows_per_utterance; /* Fp: frames + guard frames (padded up with halves = 2) */
+  int32_t rows_per_phase;     /* Rp: B * Fp rounded up to 128 (B * Fp with halves = 2) */
+  int32_t n_tiles;            /* tiles of one layer launch: 32 * Rp / block_n (per half with halves = 2) */
+} wg_plan_result;
+int wg_plan(const wg_config* cfg, int32_t direction, int32_t B, int32_t n_frames, int32_t n_cu, wg_plan_result* out);
+
 /* Per-kernel device timing: when enabled, wg_infer brackets its kernels with hipEvents on `stream`;
  * wg_profile_read synchronises those events and returns accumulated milliseconds per kernel class.
  * classes: 0 = mel_pack, 1 = flow/start, 2 = wn_layer, 3 = memset; with n_classes = 8 also the training direction

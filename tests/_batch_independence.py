@@ -48,6 +48,12 @@ CASES = {
   "c256_l8": (dict(n_channels=256, n_layers=8, n_flows=4, n_early_every=2), 4, 13, 24, 6),
   # flow widths 8, 6, 4, 2 in one model (tests/_corners.py), training direction only
   "c2": (K.LAYOUTS["c2"], 3, 7, 24, None),
+  # The batch and a single utterance on different kernels at the library's own choice (tests/test_gpu_dispatch_identity.py):
+  # 12 x (80 + 8) = 1056 rows per phase are 288 tiles of 128 columns, at least one per CU of a 256-CU device, so the batch
+  # runs the fused layer kernel on 128-column tiles and an utterance alone (88 rows) on 64-column ones (wg_plan says so, and
+  # tests/test_dispatch_cpu.py asserts it); GPU only, unpinned
+  "c256_wide": (dict(n_channels=256, n_layers=8, n_flows=4, n_early_every=2), 12, 80, 24, 6),
+  "c64_wide": (dict(n_channels=64, n_layers=8, n_flows=4, n_early_every=2), 12, 80, 24, 6),
 }
 
 # Worst per-tensor ||g(batch) - sum_b g(utterance b)|| / ||g(batch)|| of the float32 oracle (``measure_f32``): the larger of
@@ -57,6 +63,9 @@ F32_RATIO = {
   ("c64_l10", "fwd"): 8.9e-7, ("c64_l10", "inv"): 1.17e-6,
   ("c256_l8", "fwd"): 1.36e-6, ("c256_l8", "inv"): 1.72e-6,
   ("c2", "fwd"): 9.1e-7,
+  # 12 utterances of 2557 / 2560 columns: the bias gradients, sums over 30 720 positions, lead
+  ("c64_wide", "fwd"): 5.1e-6, ("c64_wide", "inv"): 5.07e-6,
+  ("c256_wide", "fwd"): 4.88e-6, ("c256_wide", "inv"): 4.88e-6,
 }
 
 

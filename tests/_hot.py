@@ -127,7 +127,7 @@ class _ConvWgradLast(torch.autograd.Function):
 
 class Prec:
   """What is rounded (``r16``: fp16 operands and saved activations; ``gscale``: fp16 gradient planes at that loss scale),
-  which fault is planted, and an optional trace of the pre-activations and ``log_s``.
+  which fault is planted, and an optional trace of the pre-activations, the ``x`` / ``acts`` planes and ``log_s``.
   Faults: "winv_t" (W^T for W^-1 in synthesis), "logdet_grad" (W for W^-T in the logdet gradient), "no_logdet" (the logdet
   term dropped from the loss), "clamp4" (the tanh argument clamped to +-4: a clamp on a instead of on the exponent),
   "clamp_b4" (the same clamp on the sigmoid's argument), ("leak", k, i) (a batch leak: in layer i of flow k the right-hand
@@ -229,6 +229,9 @@ def _wn(w, k, a0, spect, cfg, P):
       P.trace.setdefault("b", []).append(a[:, C:].detach())
     acts = P.gate(a[:, :C], a[:, C:])
     acts = _Q.apply(acts, True, None, P.dither) if P.r16 else acts
+    if P.trace is not None:             # the two fp16 planes a layer's GEMMs read (rounded when ``r16``)
+      P.trace.setdefault("x", []).append(x.detach())
+      P.trace.setdefault("acts", []).append(acts.detach())
     wrs, brs = w[p + f"res_skip_layers.{i}.weight"], w[p + f"res_skip_layers.{i}.bias"]
     if i < cfg.n_layers - 1:
       x = P.plane(x + F.conv1d(acts, P.weight(wrs[:C]), brs[:C]))

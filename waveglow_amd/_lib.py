@@ -17,6 +17,8 @@ WG_PCM_I16, WG_PCM_F32 = 0, 1   # pool_dtype of wg_data_gather
 WG_PCM_F64 = 2                  # d_out_dtype of wg_resample_backward only
 WG_RESAMPLE_CLIP = 1           # flag of wg_resample
 WG_SDTW_L2, WG_SDTW_SQ = 0, 1   # cost of wg_softdtw_forward / wg_softdtw_backward
+WG_PLAN_INFER, WG_PLAN_FORWARD, WG_PLAN_TRAIN = 0, 1, 2     # direction of wg_plan
+WG_PLAN_SINGLE, WG_PLAN_PAIR, WG_PLAN_RESIDENT = 0, 1, 2    # wg_plan_result.form
 WG_TRAIN_RECOMPUTE = 1       # flag of the wg_train_* entry points that take flags (include/waveglow_amd.h)
 
 
@@ -51,6 +53,12 @@ class WgPitchParams(C.Structure):
 class WgStoiParams(C.Structure):
   """wg_stoi_params (include/waveglow_amd.h): device pointers to the window, the band table and the cos/sin table."""
   _fields_ = [(n, C.c_void_p) for n in ("window", "bands", "cossin")]
+
+
+class WgPlanResult(C.Structure):
+  """wg_plan_result (include/waveglow_amd.h): the kernel variant of a call, from wg_plan."""
+  _fields_ = [(n, C.c_int32) for n in (
+    "block_n", "form", "resident_wgs", "deep", "frag16", "halves", "rows_per_utterance", "rows_per_phase", "n_tiles")]
 
 
 class WgError(RuntimeError):
@@ -213,6 +221,7 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
   "wg_melloss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+  "wg_plan": (C.c_int, [C.POINTER(WgConfig), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(WgPlanResult)]),
   "wg_debug_set_stamp_buffer":(C.c_int, [C.c_void_p, C.c_void_p]),
   "wg_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),
   "wg_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int32]),
@@ -234,6 +243,13 @@ def load() -> C.CDLL:
     fn.argtypes = args
   _lib = lib
   return lib
+
+
+def plan(cfg: WgConfig, direction: int, B: int, n_frames: int, n_cu: int) -> WgPlanResult:
+  """wg_plan: the WN-layer kernel variant a call of this size runs on a device with ``n_cu`` compute units (no GPU needed)."""
+  out = WgPlanResult()
+  check(load().wg_plan(C.byref(cfg), direction, B, n_frames, n_cu, C.byref(out)))
+  return out
 
 
 def device_index(device) -> int:

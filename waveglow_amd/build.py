@@ -16,7 +16,7 @@ LIB = os.path.join(CSRC, "libwaveglow_amd.so")
 SOURCES = ["kernels.hip", "stft.hip", "stft_loss.hip", "train.hip", "train_prep.hip", "wav.hip", "metrics.hip", "data.hip", "api.cpp", "stft_api.cpp", "train_api.cpp", "metrics_api.cpp",
            "data_api.cpp", "pitch.hip", "pitch_api.cpp", "resample.hip", "resample_grad.hip", "resample_api.cpp", "stoi.hip", "stoi_grad.hip", "stoi_api.cpp",
            "likelihood.hip", "likelihood_api.cpp", "softdtw.hip", "softdtw_api.cpp", "mel_loss.hip", "mel_loss_api.cpp", "stream.hip", "stream_api.cpp"]
-HEADERS = ["wg_stream.h", "wg_stftconv.h", "wg_melloss.h","wg_softdtw.h", "wg_likelihood.h","wg_common.h", "wg_train.h", "wg_host.h", "wg_stft.h", "wg_metrics.h", "wg_pitch.h", "wg_resample.h", "wg_stoi.h", os.path.join("..", "..", "include", "waveglow_amd.h")]
+HEADERS = ["wg_plan.h", "wg_stream.h", "wg_stftconv.h", "wg_melloss.h","wg_softdtw.h", "wg_likelihood.h","wg_common.h", "wg_train.h", "wg_host.h", "wg_stft.h", "wg_metrics.h", "wg_pitch.h", "wg_resample.h", "wg_stoi.h", os.path.join("..", "..", "include", "waveglow_amd.h")]
 
 
 def _hipcc() -> str:

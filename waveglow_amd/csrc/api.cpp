@@ -499,10 +499,15 @@ static int build_blob(wg_handle* h, std::vector<char>& blob) {
         // ONE K-step for the three taps (wn_layer_kernel A0G): K index kk = 8 tap + j against a B tile whose 16-byte chunk
         // `tap` is the first chunk (a0 | 1 | 0 0 0) of that tap's a0-plane row
         lo.wA1f = reserve((size_t)2 * NW * MT * 2 * 64 * 8 * 2);
-        pack32(lo.wA1f, 2, 24, [&](int m, int, int kk) { return fold[((size_t)m * 3 + (kk >> 3)) * 8 + (kk & 7)]; });
+        // Both packings take the fold as ONE float value per weight: the gate scale is then applied and the product rounded to
+        // fp16 by the same float arithmetic in pack32 and pack16.  (wA1f used to take the double itself: the scaled value
+        // then landed on the neighbouring fp16 number for a few weights per flow, and the 64-column tiles differed in bits
+        // from the 128-column ones at 256 channels -- tests/test_gpu_dispatch_identity.py)
+        auto fold_weight = [&](int m, int, int kk) { return kk < 24 ? (float)fold[((size_t)m * 3 + (kk >> 3)) * 8 + (kk & 7)] : 0.0f; };
+        pack32(lo.wA1f, 2, 24, fold_weight);
         if (f16) {
           lo.wA1fx = reserve((size_t)2 * NW * 4 * 64 * 8 * 2);
-          pack16(lo.wA1fx, 2, [&](int m, int, int kk) { return kk < 24 ? (float)fold[((size_t)m * 3 + (kk >> 3)) * 8 + (kk & 7)] : 0.0f; });
+          pack16(lo.wA1fx, 2, fold_weight);
         }
       }
       lo.bias1 = reserve((size_t)2 * C * 4);
@@ -660,18 +665,7 @@ size_t wg_forward_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frame
 static int run_wn(wg_handle* h, int k, const RowGeom& g, Workspace& w, _Float16*& cur, _Float16*& oth, hipStream_t s) {
   const wg_config& c = h->cfg;
   const int C = c.n_channels;
-  int BN = wn_block_n(C);
-  // Small workloads: 64-column tiles double the workgroup count when 128-column tiles would leave CUs idle -- when that
-  // buys whole rounds.  A 64-column tile takes ~0.6 of a 128-column tile's time (measured at 256 channels: 22.7 vs 38.5 us
-  // for a one-round launch), so compare rounds x tile time: 128 tiles on 256 CUs -> 64-column tiles fill the chip in one
-  // round (configs[0]); 224 tiles -> two rounds of 64-column tiles lose to one round of 128-column ones (+18 % at 1 x 80x864).
-  if (BN == 128) {
-    const int64_t t128 = (int64_t)kPhases * (g.Rp / 128), ncu = h->n_cu > 0 ? h->n_cu : 1;
-    const int64_t r128 = (t128 + ncu - 1) / ncu, r64 = (2 * t128 + ncu - 1) / ncu;
-    if (t128 < 4 * ncu && 6 * r64 < 10 * r128) BN = 64;
-  }
-  if (BN == 128 && h->force_bn == 64) BN = 64;
-  if (h->force_bn == 128 && wn_block_n(C) == 128) BN = 128;
+  const int BN = plan_infer_bn(C, g.Rp, h->n_cu, h->force_bn);   // 64-column tiles for small workloads: wg_plan.h
   const FlowOffsets& fo = h->flows[k];
   for (int i = 0; i < c.n_layers; ++i) {
     const LayerOffsets& lo = fo.layers[i];
@@ -977,6 +971,46 @@ double wg_macs_per_group_step(const wg_handle* h) {
             (c.n_layers - 1) * (C * 2 * C) + C * C + C * 2 * hk + ck * ck;
   }
   return macs;
+}
+
+int wg_plan(const wg_config* cfg, int32_t direction, int32_t B, int32_t n_frames, int32_t n_cu, wg_plan_result* out) {
+  if (!cfg || !out) return fail(WG_ERR_INVALID, "null argument");
+  const wg_config& c = *cfg;
+  if (wn_block_n(c.n_channels) == 0 || c.n_layers < 1 || c.n_layers > 10 || c.n_group != 8 || c.upsample_stride != 256 ||
+      c.n_mel_channels < 16 || c.n_mel_channels % 16 != 0)
+    return fail(WG_ERR_INVALID, "wg_plan: unsupported configuration (see wg_create)");
+  if (direction != WG_PLAN_INFER && direction != WG_PLAN_FORWARD && direction != WG_PLAN_TRAIN)
+    return fail(WG_ERR_INVALID, "wg_plan: bad direction");
+  if (B < 1 || n_frames < 1 || n_cu < 1) return fail(WG_ERR_INVALID, "wg_plan: bad B / n_frames / n_cu");
+  const int L = n_frames * c.upsample_stride / c.n_group;
+  if (int rc = check_envelope(c, B, L)) return rc;
+  RowGeom g = make_geom(c, B, L, n_frames);
+  const PlanSwitches sw = read_plan_switches();
+  const int C = c.n_channels;
+  memset(out, 0, sizeof *out);
+  out->halves = 1;
+  if (direction == WG_PLAN_TRAIN) {
+    // train_api.cpp: setup, then fwd_block_n on the (padded) rows; every layer is one single-tile launch per half
+    int fp, rp;
+    out->halves = plan_train_halves(B, g.Fp, g.Rp, n_cu, sw.train_halves, fp, rp);
+    g.Fp = fp;
+    g.Rp = rp;
+    out->block_n = plan_train_bn(C, g.Rp, n_cu, sw.force_bn);
+    out->form = WG_PLAN_SINGLE;
+    out->n_tiles = kPhases * (g.Rp / out->halves / out->block_n);
+  } else {
+    // run_wn, then launch_wn_layer on 32 Rp / BN tiles: the same for every layer of every flow
+    out->block_n = plan_infer_bn(C, g.Rp, n_cu, sw.force_bn);
+    out->n_tiles = kPhases * (g.Rp / out->block_n);
+    const WnLaunchPlan p = plan_wn_launch(C, out->block_n, out->n_tiles, n_cu, c.n_mel_channels / 16, sw);
+    out->form = p.form == kPlanResident ? WG_PLAN_RESIDENT : p.form == kPlanPair ? WG_PLAN_PAIR : WG_PLAN_SINGLE;
+    out->resident_wgs = 8 * p.resident_wgs;
+    out->deep = p.deep ? 1 : 0;
+  }
+  out->frag16 = direction != WG_PLAN_TRAIN && wn_frag16(C, out->block_n) ? 1 : 0;
+  out->rows_per_utterance = g.Fp;
+  out->rows_per_phase = g.Rp;
+  return WG_OK;
 }
 
 int wg_debug_set_stamp_buffer(wg_handle* h, void* device_buffer) {

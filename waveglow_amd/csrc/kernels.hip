@@ -91,12 +91,7 @@ __device__ __forceinline__ void gload16(half8& dst, const void* sbase, unsigned 
 #define WG_STAMP(i) do {} while (0)
 #endif
 
-// Cross-tile prefetch inside a workgroup: see the tile loop of wn_layer_kernel.
-// (The next tile's A fragments are NOT prefetched under the epilogue: between such an inline-asm load and its
-// wait lies a long stretch of compiler-scheduled code, and hipcc moved the still-in-flight destination registers
-// there -- wrong results.  They are loaded at the tile top: ~1 L2 latency exposed per tile.)
-constexpr int kTilesPerWG = 2;        // tiles per workgroup (template TPW), fully unrolled; 1 for small workloads;
-                                      // the unrolled group of the resident tile walk (template RESIDENT)
+// kTilesPerWG (tiles per workgroup, the cross-tile prefetch): wg_plan.h, with every rule that picks a launch.
 // Tried and measured slower on MI355X, kept out of the source: staging B tiles global -> VGPR -> ds_write instead
 // of LDS-DMA (K loop 59.3k vs 57.6k cycles per tile); offsetting the VMEM slots of the two waves of a SIMD
 // (two copies of the loop made hipcc spill).
@@ -122,7 +117,7 @@ __device__ __forceinline__ void mfma16_acc(f32x4& c, const half8& a, const half8
 
 template <int C> struct WnCfg {
   static constexpr int NW = (C >= 256) ? 8 : C / 32;   // waves per workgroup
-  static constexpr int BN = (C >= 512) ? 64 : 128;     // columns (group-timesteps) per workgroup
+  static constexpr int BN = plan_default_bn(C);        // columns (group-timesteps) per workgroup: 128, 64 at 512 channels
 };
 
 // "wait until at most N VMEM ops are outstanding" for the hand-issued loads.  Deliberately NOT tied to the
@@ -1332,59 +1327,40 @@ static hipError_t launch_wn_tttt(const WnLayerArgs& a, hipStream_t s, int reside
   hipLaunchKernelGGL((wn_layer_kernel<C, NW, BN, HAS_RES, TPW, CX, MODE, NTAPS, HAS_COND, DEEP, M16, RESIDENT>), dim3(grid), dim3(NW * 64), smem, s, a);
   return hipGetLastError();
 }
+// The test switches as the library reads them: WG_RESIDENT, WG_DISABLE_DEEP and WG_TRAIN_HALVES on every call, WG_FORCE_BN
+// here for the training direction and wg_plan (a handle keeps the value of its wg_create: wg_handle::force_bn)
+PlanSwitches read_plan_switches() {
+  PlanSwitches sw;
+  if (const char* e = getenv("WG_FORCE_BN")) sw.force_bn = atoi(e);
+  if (const char* e = getenv("WG_RESIDENT")) sw.resident = *e ? atoi(e) : -1;
+  if (const char* e = getenv("WG_DISABLE_DEEP")) sw.disable_deep = *e == '1';
+  if (const char* e = getenv("WG_TRAIN_HALVES")) sw.train_halves = atoi(e);
+  return sw;
+}
+
+// deep: the two-step-deep weight prefetch kernel (plan_wn_launch; it exists at plan_deep_shape only)
 template <int C, int BN, bool HAS_RES, int TPW, bool RESIDENT = false>
-static hipError_t launch_wn_ttt(const WnLayerArgs& a, hipStream_t s, int resident_wgs = 0) {
-  // small workloads (one tile per workgroup, 64 columns) at 256 channels / 80 mel channels: two-step-deep weight prefetch.
-  // WG_DISABLE_DEEP=1 (read per launch, tests only) takes the one-step ring instead: the two must agree bit for bit.
-  if constexpr (C == 256 && BN == 64 && TPW == 1) {
-    const char* e = getenv("WG_DISABLE_DEEP");
-    if (a.n_cond_steps == 5 && !(e && *e == '1')) {
+static hipError_t launch_wn_ttt(const WnLayerArgs& a, hipStream_t s, bool deep, int resident_wgs = 0) {
+  if constexpr (plan_deep_shape(C, BN, TPW) && !RESIDENT) {
+    if (deep) {
       if (a.a0_fold) return launch_wn_tttt<C, BN, HAS_RES, TPW, 1, 0, 1, true, true>(a, s);
       return launch_wn_tttt<C, BN, HAS_RES, TPW, C / 64, 0, 3, true, true>(a, s);
     }
+  } else if (deep) {
+    return hipErrorInvalidValue;
   }
   // first layer with the start fold: the three taps of the a0 plane in one gathered K-step (A0G; wA1 is packed for it)
   if (a.a0_fold)
     return a.x_chunks_per_tap == 1 ? launch_wn_tttt<C, BN, HAS_RES, TPW, 1, 0, 1, true, false, RESIDENT>(a, s, resident_wgs) : hipErrorInvalidValue;
   return launch_wn_tttt<C, BN, HAS_RES, TPW, C / 64, 0, 3, true, false, RESIDENT>(a, s, resident_wgs);
 }
+// resident tile walk, two tiles per workgroup or one (with or without the deep prefetch): plan_wn_launch decides (wg_plan.h)
 template <int C, int BN, bool HAS_RES>
 static hipError_t launch_wn_tt(const WnLayerArgs& a, hipStream_t s) {
-  const int ncu = a.n_cu > 0 ? a.n_cu : 1;
-  // Resident tile walk where a CU has at least two tiles to walk: at most one workgroup per CU, each walking its share of its
-  // XCD label's run tile by tile, so the workgroup start (dispatch, bias / end x skip staging, a cold first B tile) is paid
-  // once per CU and launch instead of once per pair, and every tile seam has the B-tile prefetch.  The workgroups do not
-  // communicate: nothing depends on their being co-resident or on the block -> XCD mapping (speed only, as above).
-  // WG_RESIDENT (read per launch, tests only): 0 = the launches below; N > 0 = the resident launch with 8 ceil(N / 8)
-  // workgroups whatever the size.  The two must agree bit for bit.
-  {
-    const char* e = getenv("WG_RESIDENT");
-    const int forced = e && *e ? atoi(e) : -1;
-    const int per_label_tiles = (a.n_tiles + 7) / 8;
-    int wgs = 0;
-    if (forced > 0) wgs = (forced + 7) / 8;
-    // Not with a sparse tail: the walk is static, so n_tiles mod CUs workgroups run the last tile-round alone after every CU
-    // has run all the full ones, where the dispatcher spreads today's pairs over that tail.  Measured at 6 x 80x864 (1312
-    // tiles on 256 CUs = 5.125 rounds): +2.4 %, outside both spreads; the next sparsest tail measured, 0.375 of a round,
-    // gains.  The quarter lies between the two.  (Too wide at many rounds: at 13 x 80x864, 11.125 rounds, the walk would
-    // gain 1.3 % -- DESIGN.md section 8.)
-    // By default only where the walk was measured against today's launches: 256 channels on 128-column tiles.  Every other
-    // width keeps today's launch -- in particular 64-column tiles at 256 channels, which api.cpp run_wn picks for 514 .. 768
-    // narrow tiles on 256 CUs (2 .. 3 tiles per CU) and which run the two-step-deep prefetch kernel (DEEP, single tiles):
-    // the walk has no DEEP form and would trade that kernel's ~10 % of a launch for its own 1 - 1.5 %.
-    else if (forced < 0 && C == 256 && BN == 128 && a.n_tiles >= 2 * ncu && !(a.n_tiles % ncu > 0 && 4 * (a.n_tiles % ncu) < ncu)) {
-      const int by_tiles = (per_label_tiles + kTilesPerWG - 1) / kTilesPerWG, by_cus = (ncu + 7) / 8;
-      wgs = by_tiles < by_cus ? by_tiles : by_cus;
-    }
-    if (wgs > 0) return launch_wn_ttt<C, BN, HAS_RES, kTilesPerWG, true>(a, s, wgs);
-  }
-  // Below two tiles per CU (and under WG_RESIDENT=0): workgroups that end after one or two tiles.  Two tiles per workgroup
-  // amortise the launch and prefetch across the tile seam, but need >= 2 tiles per CU -- and must not cost a round: 1120 tiles
-  // on 256 CUs are 5 rounds of single tiles but 3 rounds of pairs = 6 tile times (batch 5 x 80x864)
-  const int rounds1 = (a.n_tiles + ncu - 1) / ncu;
-  const int rounds2 = ((a.n_tiles + kTilesPerWG - 1) / kTilesPerWG + ncu - 1) / ncu * kTilesPerWG;
-  if (a.n_tiles >= 2 * kTilesPerWG * ncu && rounds2 <= rounds1) return launch_wn_ttt<C, BN, HAS_RES, kTilesPerWG>(a, s);
-  return launch_wn_ttt<C, BN, HAS_RES, 1>(a, s);
+  const WnLaunchPlan p = plan_wn_launch(C, BN, a.n_tiles, a.n_cu, a.n_cond_steps, read_plan_switches());
+  if (p.form == kPlanResident) return launch_wn_ttt<C, BN, HAS_RES, kTilesPerWG, true>(a, s, false, p.resident_wgs);
+  if (p.form == kPlanPair) return launch_wn_ttt<C, BN, HAS_RES, kTilesPerWG>(a, s, false);
+  return launch_wn_ttt<C, BN, HAS_RES, 1>(a, s, p.deep);
 }
 template <int C>
 static hipError_t launch_wn_t(const WnLayerArgs& a, int bn, hipStream_t s) {

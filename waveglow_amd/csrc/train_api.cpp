@@ -137,30 +137,17 @@ int setup(wg_handle* h, int32_t B, int32_t n_frames, int32_t audio_len, void* wo
   const int L = audio_len / c.n_group;
   x.g = make_geom(h->cfg, B, L, n_frames);
   x.n_cu = h->n_cu;     // of the handle's device: decides the chain geometry (workspace layout) below
-  // Chains.  A WN-layer launch runs ceil(tiles / CUs) rounds and the next layer waits for its last, partly filled
-  // round (config 4: 576 tiles of 128 columns on 256 CUs = 2.25 rounds, a quarter of the chip-time idle).  The two
-  // halves of the batch never exchange data inside a WN, so they run as two chains of half-size launches on two
-  // streams and fill each other's idle CUs.  That needs the first B/2 utterances to end on a tile boundary: the rows
-  // per utterance Fp are padded up (71 -> 72 at config 4: 16 x 72 = 9 tiles, the same 2304 rows per phase as before).
-  // Rows past an utterance's last frame are guard rows like the others: never valid, always written as zeros -- the
-  // only rows of the other half a chain's dilated taps can reach.
-  x.halves = 1;
+  // Chains: the two halves of an even batch as two chains of half-size launches on two streams where that fills idle CUs
+  // (plan_train_halves, wg_plan.h; WG_TRAIN_HALVES = 1: never, 2: always (tests)).  The rows per utterance Fp are then
+  // padded up so that the first B/2 utterances end on a tile boundary.  Rows past an utterance's last frame are guard rows
+  // like the others: never valid, always written as zeros -- the only rows of the other half a chain's dilated taps can reach.
   {
-    const char* e = getenv("WG_TRAIN_HALVES");
-    const int want = e ? atoi(e) : 0;               // 1: never, 2: always (tests), otherwise by shape
-    if (B % 2 == 0 && want != 1) {
-      int fp = x.g.Fp;
-      while ((B / 2 * fp) % 128) ++fp;
-      const int rp = B * fp;
-      const long long tiles = (long long)kPhases * (x.g.Rp / 128);
-      const long long idle = (tiles + x.n_cu - 1) / x.n_cu * x.n_cu - tiles;
-      const bool helps = tiles > x.n_cu && idle * 10 >= tiles && rp <= x.g.Rp + x.g.Rp / 32;
-      if (want == 2 || helps) {
-        x.g.Fp = fp;
-        x.g.Rp = rp;
-        x.g.R = kPhases * rp + 2 * kRowPad;
-        x.halves = 2;
-      }
+    int fp, rp;
+    x.halves = plan_train_halves(B, x.g.Fp, x.g.Rp, x.n_cu, read_plan_switches().train_halves, fp, rp);
+    if (x.halves == 2) {
+      x.g.Fp = fp;
+      x.g.Rp = rp;
+      x.g.R = kPhases * rp + 2 * kRowPad;
     }
     const char* se = getenv("WG_TRAIN_SERIAL");
     x.serial = se && *se == '1';
@@ -263,17 +250,9 @@ PRun run_of(const _Float16* base, int n_chunks, int dt) {
 }
 
 
-// tile width of the fused layer kernel in the training forward: as the inference path chooses it (api.cpp: run_wn)
-int fwd_block_n(const Ctx& x) {
-  const int C = x.C;
-  int BNw = wn_block_n(C);
-  if (BNw == 128 && (int64_t)kPhases * (x.g.Rp / 128) < (int64_t)x.n_cu) BNw = 64;
-  if (const char* e = getenv("WG_FORCE_BN")) {
-    const int f = atoi(e);
-    if (f == 64 || (f == 128 && wn_block_n(C) == 128)) BNw = f;
-  }
-  return BNw;
-}
+// tile width of the fused layer kernel in the training forward and the gradient paths (plan_train_bn, wg_plan.h); WG_FORCE_BN
+// is read on every call
+int fwd_block_n(const Ctx& x) { return plan_train_bn(x.C, x.g.Rp, x.n_cu, read_plan_switches().force_bn); }
 
 // stream of the forward's second chain (the caller's stream `s` is the first): see setup
 int second_chain_stream(wg_handle* h, const Ctx& x, hipStream_t s, hipStream_t& sB) {

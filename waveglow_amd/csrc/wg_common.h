@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wg_plan.h"
+
 namespace wg {
 
 // ---------------------------------------------------------------------------------------------
@@ -54,7 +56,6 @@ struct RowGeom {
 };
 constexpr int kRowPad = 16;      // zero slack rows in front of / behind every plane chunk (taps of the first / last tile reach up to
                                  // Gf <= 16 rows past it: the guard rows of a tile read as far outside as its valid rows do)
-constexpr int kPhases = 32;
 
 // GEMM 1 of the inference layer on 16x16x32 MFMAs (wn_layer_kernel M16) for this tile shape: its A fragments are packed
 // differently (api.cpp wg_finalize packs both orders when a model can run either tile width)
@@ -173,6 +174,7 @@ hipError_t launch_start_replay(const FlowArgs& a, hipStream_t s);
 hipError_t launch_wn_layer(const WnLayerArgs& a, int C, int bn, hipStream_t s);   // bn = 128 (default) or 64
 hipError_t launch_wn_layer_train(const WnLayerArgs& a, int C, int bn, hipStream_t s);   // training forward (a.sp, a.save_*)
 hipError_t launch_wn_plain(const WnLayerArgs& a, int C, int kind, int bn, hipStream_t s);   // backward dgrad GEMMs (kind 2 / 3)
+PlanSwitches read_plan_switches();   // the test switches of wg_plan.h from the environment, as of this call
 int wn_block_n(int C);   // default BN for channel count C
 int wn_waves(int C);     // waves per workgroup for channel count C
 
