@@ -94,20 +94,16 @@ size_t wg_forward_workspace_bytes(const wg_handle* h, int32_t B, int32_t n_frame
  *   z_init   [B, n_rem, L]                  io_dtype
  *   z_early  n_z_early device pointers, each [B, n_early_size, L], io_dtype
  *   audio    [B, n_frames*upsample_stride]  io_dtype (output)
- * Arithmetic: fp16 MFMA operands, fp32 accumulation, fp32 flow state. */
-int wg_infer(wg_handle* h, const void* mel, const void* z_init, const void* const* z_early,
-             int32_t n_z_early, float sigma, void* audio, int32_t B, int32_t n_frames,
-             int32_t io_dtype, void* workspace, size_t workspace_bytes, void* stream);
-
-/* wg_infer for a batch of utterances of DIFFERENT lengths (serving; the reference's commented-out --batch-size,
- * src/waveglow_cli/inference_v2.py:64): `frames` is a device array of B mel-frame counts, each <= n_frames; mel / noise /
- * audio are padded to n_frames as in wg_infer (contents behind an utterance's own length are ignored, its audio tail is
- * zero).  Every utterance gets exactly the result of a batch-of-one call on its own frames: the padding columns are never
- * written, so they are the zero padding the convolutions see at the end of the sequence (model.py:98-102).
- * frames == NULL is wg_infer. */
-int wg_infer_ragged(wg_handle* h, const void* mel, const int32_t* frames, const void* z_init,
-                    const void* const* z_early, int32_t n_z_early, float sigma, void* audio, int32_t B,
-                    int32_t n_frames, int32_t io_dtype, void* workspace, size_t workspace_bytes, void* stream);
+ * Arithmetic: fp16 MFMA operands, fp32 accumulation, fp32 flow state.
+ * With `frames`, a batch of utterances of DIFFERENT lengths (serving; the reference's commented-out --batch-size,
+ * src/waveglow_cli/inference_v2.py:64): a device array of B mel-frame counts, each <= n_frames; mel / noise / audio are
+ * padded to n_frames (contents behind an utterance's own length are ignored, its audio tail is zero).  Every utterance
+ * gets exactly the result of a batch-of-one call on its own frames: the padding columns are never written, so they are
+ * the zero padding the convolutions see at the end of the sequence (model.py:98-102).  frames == NULL: every utterance
+ * has n_frames frames. */
+int wg_infer(wg_handle* h, const void* mel, const int32_t* frames, const void* z_init, const void* const* z_early,
+             int32_t n_z_early, float sigma, void* audio, int32_t B, int32_t n_frames, int32_t io_dtype,
+             void* workspace, size_t workspace_bytes, void* stream);
 
 /* WaveGlow.forward (model.py:178-221), inference of the normalising direction (no autograd).
  *   mel      [B, n_mel, n_frames]     io_dtype
@@ -115,26 +111,20 @@ int wg_infer_ragged(wg_handle* h, const void* mel, const int32_t* frames, const 
  *                                     audio_len <= (n_frames-1)*stride + kernel  (model.py:187)
  *   z        [B, n_group, L]          fp32 out, L = audio_len / n_group
  *   log_s    n_flows device pointers, log_s[k] is [B, h_k, L] fp32 out
- *   log_det_W  HOST pointer to n_flows floats: B*L*logdet(W_k) (model.py:63), written before return */
-int wg_forward(wg_handle* h, const void* mel, const void* audio, float* z, float* const* log_s,
-               float* log_det_W, int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype,
-               void* workspace, size_t workspace_bytes, void* stream);
+ *   log_det_W  HOST pointer to n_flows floats: B*L*logdet(W_k) (model.py:63), written before return
+ * With `frames`, a batch of utterances of DIFFERENT lengths (scoring held-out audio): a device array of B mel-frame
+ * counts as in wg_infer; utterance b is audio[b, :256 * frames[b]] under mel[b, :, :frames[b]].  audio_len must then be
+ * 256 * n_frames and n_frames <= INT32_MAX >> 8 (WG_ERR_INVALID otherwise); size range and workspace are unchanged.
+ * Every utterance gets, bit for bit, the z and log_s of a batch-of-one call on its own frames; z and every log_s[k] are
+ * exactly 0 behind column 32 * frames[b].  Mel and audio behind an utterance are never used (they may hold NaN).  The
+ * counts are never read on the host: one outside [1, n_frames] reads and writes nothing outside the buffers, and that
+ * utterance's z and log_s are 0.  log_det_W may then be null (per column it is the handle's constant, see wg_nll) and
+ * is filled when it is not.  frames == NULL: every utterance has audio_len samples, and log_det_W is required. */
+int wg_forward(wg_handle* h, const void* mel, const int32_t* frames, const void* audio, float* z, float* const* log_s,
+               float* log_det_W, int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype, void* workspace,
+               size_t workspace_bytes, void* stream);
 
-/* wg_forward for a batch of utterances of DIFFERENT lengths (scoring held-out audio): `frames` is a device array of B
- * mel-frame counts as in wg_infer_ragged; utterance b is audio[b, :256 * frames[b]] under mel[b, :, :frames[b]].
- *   audio    [B, 256 * n_frames]      io_dtype
- *   z, log_s as in wg_forward with L = 32 * n_frames; same size range and workspace (wg_forward_workspace_bytes at
- *            audio_len = 256 * n_frames)
- * Every utterance gets, bit for bit, the z and log_s of a batch-of-one wg_forward call on its own frames; z and every
- * log_s[k] are exactly 0 behind column 32 * frames[b].  Mel and audio behind an utterance are never used (they may hold
- * NaN).  The counts are never read on the host: one outside [1, n_frames] reads and writes nothing outside the buffers,
- * and that utterance's z and log_s are 0.  No log_det_W: per column it is the handle's constant (see wg_nll).
- * frames == NULL is wg_forward at audio_len = 256 * n_frames. */
-int wg_forward_ragged(wg_handle* h, const void* mel, const int32_t* frames, const void* audio, float* z,
-                      float* const* log_s, int32_t B, int32_t n_frames, int32_t io_dtype, void* workspace,
-                      size_t workspace_bytes, void* stream);
-
-/* Negative log-likelihood per utterance and per mel frame from the outputs of wg_forward / wg_forward_ragged:
+/* Negative log-likelihood per utterance and per mel frame from the outputs of wg_forward:
  * WaveGlowLoss (src/waveglow/train.py:31-45) of every utterance alone.  With L_b = 32 * frames[b] columns (L when
  * frames == NULL, the dense batch; with counts L must be a multiple of 32), n_b = 8 * L_b samples and
  * logdet = sum_k log|det W_k| of the handle (fp64, the value wg_forward multiplies by B * L, model.py:63):
@@ -173,9 +163,9 @@ double wg_macs_per_group_step(const wg_handle* h);
 
 /* Which WN-layer kernel variant a call of this size runs on a device with n_cu compute units: the answer of the very
  * functions the launch code calls (csrc/wg_plan.h).  Pure host arithmetic: no handle, no GPU, nothing is enqueued.
- *   direction  WG_PLAN_INFER (wg_infer / wg_infer_ragged), WG_PLAN_FORWARD (wg_forward / wg_forward_ragged: the same
- *              rules), WG_PLAN_TRAIN (the fused layer kernel of wg_train_forward / wg_train_infer_forward, whose tile
- *              width the backward chain takes over), at audio_len = upsample_stride * n_frames.
+ *   direction  WG_PLAN_INFER (wg_infer), WG_PLAN_FORWARD (wg_forward: the same rules), WG_PLAN_TRAIN (the fused layer
+ *              kernel of wg_train_forward / wg_train_infer_forward, whose tile width the backward chain takes over), at
+ *              audio_len = upsample_stride * n_frames.
  * The test switches WG_FORCE_BN, WG_RESIDENT, WG_DISABLE_DEEP and WG_TRAIN_HALVES are read from the environment at the
  * call, as the library reads them (WG_FORCE_BN of the first two directions: at wg_create).  Variants that differ in
  * block_n, form or deep are different kernels; the library promises the same bits from all of them
@@ -213,41 +203,33 @@ int wg_profile_read(wg_handle* h, double* ms_per_class, int64_t* launches_per_cl
  * wg_stft_denoise: audio [B][n_samples] fp32 device (n_samples % 256 == 0) ->
  *   audio_out [B][n_samples] = istft(max(|X| - strength*bias_mag, 0) * exp(i*arg X))   (Denoiser.forward), and/or
  *   mag0_out [B][513] = |X| of frame 0 (what Denoiser.__init__ keeps as bias_spec).  bias_mag null => no subtraction;
- *   audio_out null => transform only.  Enqueue-only. */
+ *   audio_out null => transform only.  Enqueue-only.
+ * With `lens`, a batch of utterances of DIFFERENT lengths (Denoiser.forward per utterance, denoiser.py:51-57 on
+ *   stft.py:134-198): a device array of B sample counts, each a multiple of 256 in [1024, n_samples]; n_samples is the
+ *   row pitch of audio / audio_out and sizes the workspace.  Utterance b gets bit for bit what the call with B = 1,
+ *   n_samples = lens[b] and a null lens gives it: reflect padding about its own last sample, lens[b]/256 + 1 frames, the
+ *   window-sum-square of those frames, cropping to lens[b]; audio_out[b][lens[b]:] = 0.  lens is read by the kernels
+ *   only (enqueue-only, nothing synchronised); a length outside the limits is treated as 0: that row comes out all zero
+ *   (its mag0_out row is not written) and nothing is indexed with it.  lens == NULL: every row has n_samples samples. */
 typedef struct wg_stft wg_stft;
 int wg_stft_create(const float* fwd_basis, const float* inv_basis, const float* win_sq, int32_t filter_length,
                    int32_t hop_length, int32_t device_id, wg_stft** out);
 int wg_stft_destroy(wg_stft* h);
 size_t wg_stft_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples);
-int wg_stft_denoise(wg_stft* h, const float* audio, const float* bias_mag, float strength, float* audio_out,
-                    float* mag0_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                    void* stream);
-/* The denoiser for a batch of utterances of DIFFERENT lengths (Denoiser.forward per utterance, denoiser.py:51-57 on
- * stft.py:134-198): `lens` is a device array of B sample counts, each a multiple of 256 in [1024, n_samples]; n_samples
- * is the row pitch of audio / audio_out and sizes the workspace as in the uniform call.  Utterance b gets bit for bit what
- * the uniform call with B = 1 and n_samples = lens[b] gives it: reflect padding about its own last sample, lens[b]/256 + 1
- * frames, the window-sum-square of those frames, cropping to lens[b]; audio_out[b][lens[b]:] = 0.  lens is read by the
- * kernels only (enqueue-only, nothing synchronised); a length outside the limits is treated as 0: that row comes out
- * all zero (its mag0_out row is not written) and nothing is indexed with it. */
-int wg_stft_denoise_ragged(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag, float strength,
-                           float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
-                           size_t workspace_bytes, void* stream);
+int wg_stft_denoise(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag, float strength,
+                    float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 /* Mel front-end, TacotronSTFT.mel_spectrogram (src/waveglow/taco_stft.py:84-104): STFT magnitudes (reflect padding,
  * stft.py:141-152) x mel filterbank -> log(clamp(., 1e-5)).  audio [B][n_samples] fp32 device (any n_samples > 512),
- * mel_basis [n_mel][513] fp32 DEVICE, mel_out [B][n_mel][n_samples/256 + 1] fp32 device.  Enqueue-only. */
+ * mel_basis [n_mel][513] fp32 DEVICE, mel_out [B][n_mel][n_samples/256 + 1] fp32 device.  Enqueue-only.
+ * With `lens`, a batch of utterances of DIFFERENT lengths (taco_stft.py:84-103 per utterance): a device array of B sample
+ * counts, each in (512, n_samples]; n_samples is the row pitch of audio and sizes the workspace.  Columns of mel_out
+ * below lens[b]/256 + 1 are bit for bit those of the call with a null lens on that utterance alone, the others are 0.
+ * A length outside the limits is treated as 0 (row all zero).  lens == NULL: every row has n_samples samples. */
 size_t wg_stft_mel_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples);
-int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out, int32_t B,
-                int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
-/* The same for a batch of utterances of DIFFERENT lengths (taco_stft.py:84-103 per utterance): `lens` is a device array
- * of B sample counts, each in (512, n_samples]; n_samples is the row pitch of audio.  mel_out is
- * [B][n_mel][n_samples/256 + 1]: columns below lens[b]/256 + 1 are bit for bit those of the uniform call on that
- * utterance alone, the others are 0.  A length outside the limits is treated as 0 (row all zero).  The gradient
- * variant is wg_stft_mel_forward_saved_ragged / wg_stft_mel_backward_ragged below.
- * Workspace as in the uniform call.  Enqueue-only. */
-int wg_stft_mel_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
-                       float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                       void* stream);
+int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
+                float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Mel front-end with an audio gradient, TacotronSTFT.mel_spectrogram_differentiable (taco_stft.py:84-104 without the
  * detach at :99; conv-STFT of stft.py:135-163).  Same arguments and n_samples rule as wg_stft_mel (n_mel <= 128).
@@ -257,26 +239,19 @@ int wg_stft_mel_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const 
  *   d audio, through log(clamp(., 1e-5)) (gradient where the sum >= 1e-5), the mel projection, |X| (0 where |X| = 0),
  *   the conv-STFT and the reflect padding.  Reads the workspace of a forward_saved call with the same mel_basis, n_mel,
  *   B and n_samples; leaves that call's saved state intact, so it may run more than once.
+ * With `lens` (as in wg_stft_mel: device [B], each in (512, n_samples], anything else counts as 0; read by the kernels
+ *   only; n_samples the row pitch): mel_out of the forward is 0 at and behind column lens[b]/256 + 1; g_mel at and behind
+ *   an utterance's frame count is not read; audio_grad_out[b][:lens[b]] is bit for bit the backward of that utterance
+ *   alone with a null lens (reflect padding folded about its own sample lens[b] - 1), audio_grad_out[b][lens[b]:] = 0.
+ *   Pass the backward the lens of its forward.  lens == NULL: every row has n_samples samples.
  * One workspace of wg_stft_mel_grad_workspace_bytes serves both.  Enqueue-only. */
 size_t wg_stft_mel_grad_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples);
-int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out,
-                              int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
-int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
-                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
-/* The same for a batch of utterances of DIFFERENT lengths: `lens` as in wg_stft_mel_ragged (device [B], each in
- * (512, n_samples], anything else counts as 0; read by the kernels only), n_samples the row pitch, the workspace that of
- * wg_stft_mel_grad_workspace_bytes(B, n_samples).
- * wg_stft_mel_forward_saved_ragged: mel_out bit for bit that of wg_stft_mel_ragged (0 at and behind column lens[b]/256
- *   + 1); keeps the state of the backward.
- * wg_stft_mel_backward_ragged: g_mel at and behind an utterance's frame count is not read; audio_grad_out[b][:lens[b]]
- *   is bit for bit the dense backward of that utterance alone (reflect padding folded about its own sample lens[b] - 1),
- *   audio_grad_out[b][lens[b]:] = 0.  Pass the lens of the forward.  A null lens is an argument error. */
-int wg_stft_mel_forward_saved_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio,
-                                     const int32_t* lens, float* mel_out, int32_t B, int32_t n_samples, void* workspace,
-                                     size_t workspace_bytes, void* stream);
-int wg_stft_mel_backward_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel,
-                                const int32_t* lens, float* audio_grad_out, int32_t B, int32_t n_samples,
-                                void* workspace, size_t workspace_bytes, void* stream);
+int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
+                              float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, const int32_t* lens,
+                         float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 /* ---- PCM finishing of a synthesised batch (src/waveglow/audio_utils.py:36-95, :132-138), no handle -----------------
  * raw, denoised [B][n_samples] fp32 device (they may be the same array), lens device [B] sample counts (clamped to
@@ -308,7 +283,7 @@ int wg_data_gather(const void* pool, int32_t pool_dtype, int64_t pool_elems, con
                    void* stream);
 
 /* ---- Streaming synthesis: the windows of a step in, the chunks of a step out (not in the reference), no handle ------
- * A step over B streams synthesises one window per stream as a ragged batch (wg_infer_ragged, wg_stft_denoise_ragged)
+ * A step over B streams synthesises one window per stream as a ragged batch (wg_infer, wg_stft_denoise with lengths)
  * and hands out the interior of each window.  Both tables are device arrays of B rows, read by the kernels only.
  * wg_stream_gather, one launch: for row b with w = windows[b], n = w.count clamped to [0, w_max] and to the source's
  *   pitch (a negative start or count counts as n = 0), cpf = cols_per_frame (256 / n_group: 32):
@@ -616,47 +591,36 @@ int wg_resample_backward(const void* d_out, int32_t d_out_dtype, const int32_t* 
  * wg_stftloss_create: 1..8 resolutions; n_fft a multiple of 32 in [32, 2048], 1 <= hop <= n_fft, 1 <= win <= n_fft;
  *   fwd_basis[r] is the windowed Fourier basis [2*(n_fft/2+1)][n_fft] (real rows, then imaginary rows), HOST pointers,
  *   packed once.  device_id < 0 makes a planning handle (no device work, fwd_basis may be null): workspace sizes only.
- * wg_stftloss_workspace_bytes: 0 unless B >= 1 and n_samples > max n_fft / 2.  saved = 0 sizes wg_stftloss_forward,
- *   saved = 1 sizes wg_stftloss_forward_saved + wg_stftloss_backward (one workspace serves both).
- * wg_stftloss_forward[_saved]: audio, target [B][n_samples] fp32 device -> out3 = {sc, mag, factor_sc sc + factor_mag
- *   mag} fp32 device.  _saved also keeps the prediction's (re, im), M(target) and the two norms in the workspace.
+ * wg_stftloss_workspace_bytes: 0 unless B >= 1 and n_samples > max n_fft / 2.  saved = 0 sizes wg_stftloss_forward with
+ *   saved = 0, saved = 1 sizes wg_stftloss_forward with saved = 1 + wg_stftloss_backward (one workspace serves both).
+ * wg_stftloss_forward: audio, target [B][n_samples] fp32 device -> out3 = {sc, mag, factor_sc sc + factor_mag mag} fp32
+ *   device.  saved = 1 also keeps the prediction's (re, im), M(target) and the two norms in the workspace; saved = 0
+ *   gives the same out3 bits and keeps nothing.  Any other value is WG_ERR_INVALID.
  * wg_stftloss_backward: g_out3 [3] fp32 DEVICE = d loss / d out3 -> audio_grad_out [B][n_samples] = d loss / d audio
- *   (no gradient under the clamp, sign(0) = 0).  Reads the workspace of a forward_saved call with the same factors, B
- *   and n_samples and leaves its saved state intact, so it may run more than once.
- * wg_stftloss_*_ragged: the same for utterances of DIFFERENT lengths inside the dense [B][n_samples] arrays.  `lens` is a
- *   device array of B sample counts, read by the kernels only.  Utterance b is transformed as its own crop
- *   x[b][:lens[b]] (reflect padding about its own last sample, F_b = lens[b] / hop + 1 frames); the norms of sc_r run
- *   over the frames f < F_b of every utterance and mag_r divides by K sum_b F_b, formed on the device: the loss of the
- *   cropped utterances with their frames concatenated.  audio_grad_out[b][lens[b]:] = 0.  A length outside
- *   (max n_fft / 2, n_samples] counts as 0: that utterance contributes nothing, gets a zero gradient row, and nothing is
- *   indexed with it; if every length counts as 0, out3 and the gradient are zeros.  The workspace is the dense one for
- *   (B, n_samples); the backward takes the lens of its forward.  With every length equal to n_samples the results are
- *   bit for bit those of the dense entry points.  A null lens is an argument error, reported (like bad sizes) before the
- *   refusal of a planning handle.
+ *   (no gradient under the clamp, sign(0) = 0).  Reads the workspace of a forward call with saved = 1 and the same lens,
+ *   factors, B and n_samples and leaves its saved state intact, so it may run more than once.
+ * With `lens`, utterances of DIFFERENT lengths inside the dense [B][n_samples] arrays: a device array of B sample counts,
+ *   read by the kernels only.  Utterance b is transformed as its own crop x[b][:lens[b]] (reflect padding about its own
+ *   last sample, F_b = lens[b] / hop + 1 frames); the norms of sc_r run over the frames f < F_b of every utterance and
+ *   mag_r divides by K sum_b F_b, formed on the device: the loss of the cropped utterances with their frames
+ *   concatenated.  audio_grad_out[b][lens[b]:] = 0.  A length outside (max n_fft / 2, n_samples] counts as 0: that
+ *   utterance contributes nothing, gets a zero gradient row, and nothing is indexed with it; if every length counts as
+ *   0, out3 and the gradient are zeros.  The workspace is that of (B, n_samples).  With every length equal to n_samples
+ *   the results are bit for bit those of a null lens.  lens == NULL: every row has n_samples samples.
  * Sums are reduced in a fixed order (no floating-point atomics): results are bit-reproducible.  Enqueue-only; argument
- * checks run before any device work. */
+ * checks (null arguments and sizes, then the workspace size, then the refusal of a planning handle with WG_ERR_STATE) run
+ * before any device work. */
 typedef struct wg_stftloss wg_stftloss;
 int wg_stftloss_create(int32_t n_res, const int32_t* n_fft, const int32_t* hop, const int32_t* win,
                        const float* const* fwd_basis, float eps, int32_t device_id, wg_stftloss** out);
 int wg_stftloss_destroy(wg_stftloss* h);
 size_t wg_stftloss_workspace_bytes(const wg_stftloss* h, int32_t B, int32_t n_samples, int32_t saved);
-int wg_stftloss_forward(wg_stftloss* h, const float* audio, const float* target, float factor_sc, float factor_mag,
-                        float* out3, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                        void* stream);
-int wg_stftloss_forward_saved(wg_stftloss* h, const float* audio, const float* target, float factor_sc,
-                              float factor_mag, float* out3, int32_t B, int32_t n_samples, void* workspace,
-                              size_t workspace_bytes, void* stream);
-int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, float factor_mag, float* audio_grad_out,
-                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream);
-int wg_stftloss_forward_ragged(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens,
-                               float factor_sc, float factor_mag, float* out3, int32_t B, int32_t n_samples,
-                               void* workspace, size_t workspace_bytes, void* stream);
-int wg_stftloss_forward_saved_ragged(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens,
-                                     float factor_sc, float factor_mag, float* out3, int32_t B, int32_t n_samples,
-                                     void* workspace, size_t workspace_bytes, void* stream);
-int wg_stftloss_backward_ragged(wg_stftloss* h, const float* g_out3, const int32_t* lens, float factor_sc,
-                                float factor_mag, float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace,
-                                size_t workspace_bytes, void* stream);
+int wg_stftloss_forward(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens, float factor_sc,
+                        float factor_mag, float* out3, int32_t B, int32_t n_samples, int32_t saved, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, const int32_t* lens, float factor_sc, float factor_mag,
+                         float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 /* ---- Multi-scale mel-spectrogram loss (log-mel L1 + linear-mel L1), fp32, with its backward ---------------------------
  * HiFi-GAN's mel L1 in the multi-scale form of DAC and BigVGAN; the reference has no counterpart.  For scale
@@ -881,15 +845,31 @@ int wg_train_backward(wg_handle* h, const wg_train_weights* w, const wg_train_gr
  * Forward: mel [B][n_mel][n_frames] fp32, z_init [B][c_last][L] fp32, z_early[i] [B][n_early_size][L] fp32 in descending
  * flow order (as wg_infer), audio [B][256 n_frames] fp32 out; L = 32 n_frames.  `fresh`, flags (WG_TRAIN_RECOMPUTE: flows
  * 1 and 0 stay in the two slots) and the streams as for wg_train_forward.  The workspace must stay untouched until
- * wg_train_infer_backward has run.  Enqueue-only. */
+ * wg_train_infer_backward has run.  Enqueue-only.
+ *
+ * With `frames` (both calls), a batch of utterances of DIFFERENT lengths: a device array of B mel-frame counts as in
+ * wg_infer; same workspace.  Utterance b is mel[b, :, :frames[b]] with z_init[b, :, :32 frames[b]] and
+ * z_early[i][b, :, :32 frames[b]], synthesised alone (src/waveglow/model.py:223-273 on that utterance; the reference has
+ * no ragged mode, its convolutions' zero padding at the end of a sequence, model.py:98-102, is what the padding columns
+ * stand for):
+ *   forward   audio[b, :256 frames[b]] has the bits of the batch-of-one call on the utterance, audio behind it is 0.
+ *   backward  g_mel, g_z_init and g_z_early[i] are 0 behind the count and have the bits of the batch-of-one call (same
+ *             scale) in front of it; every entry of `grads` is the sum over the utterances of the batch-of-one calls'
+ *             (up to accumulation order).  The backward takes the counts of its forward.
+ * Nothing behind an utterance's count is read: mel, noise and g_audio may hold NaN there.  The counts are never read on
+ * the host and nothing synchronises: a count <= 0 makes its utterance all padding (zero audio, zero gradients, nothing
+ * added to `grads`), a count above n_frames counts as n_frames; neither reads or writes outside the buffers.
+ * With counts the forward clears the workspace's planes on every call, whatever `fresh` says (the layer kernels leave
+ * padding columns unwritten, and a reused workspace may hold another batch there).
+ * frames == NULL: every utterance has n_frames frames. */
 int wg_train_infer_forward(wg_handle* h, const wg_train_weights* w, const void* mel, const void* z_init,
                            const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
-                           int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
-                           void* stream);
+                           int32_t n_frames, const int32_t* frames, int32_t fresh, void* workspace,
+                           size_t workspace_bytes, int32_t flags, void* stream);
 
-/* Backward of the last wg_train_infer_forward on this workspace, with the flags of that forward (WG_TRAIN_RECOMPUTE:
- * flows 2.. are replayed).  g_audio [B][256 n_frames] fp32 is the gradient of the returned audio; `scale` (> 0)
- * multiplies it on entry (fp16 gradient planes) and is divided out of every result.  Flows in ascending order.
+/* Backward of the last wg_train_infer_forward on this workspace, with the flags and `frames` of that forward
+ * (WG_TRAIN_RECOMPUTE: flows 2.. are replayed).  g_audio [B][256 n_frames] fp32 is the gradient of the returned audio;
+ * `scale` (> 0) multiplies it on entry (fp16 gradient planes) and is divided out of every result.  Flows in ascending order.
  * Outputs, each optional (null: not computed) and written entirely (no accumulation): g_mel [B][n_mel][n_frames],
  * g_z_init [B][c_last][L], g_z_early[i] [B][n_early_size][L] (g_z_early itself or any entry may be null).
  *   grads   null: the data gradients alone, on `stream` alone.  Otherwise also the gradients of the weights through
@@ -906,32 +886,7 @@ int wg_train_infer_forward(wg_handle* h, const wg_train_weights* w, const void* 
 int wg_train_infer_backward(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads,
                             const float* g_audio, float scale, float sigma, float* g_mel, float* g_z_init,
                             float* const* g_z_early, int32_t n_z_early, int32_t B, int32_t n_frames,
-                            void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
-
-/* wg_train_infer_forward / wg_train_infer_backward for a batch of utterances of DIFFERENT lengths: `frames` is a device
- * array of B mel-frame counts as in wg_infer_ragged, directly after n_frames; every other argument as in the dense calls,
- * which are these calls with frames == NULL (one implementation; same workspace, wg_train_workspace_bytes).  Utterance b is
- * mel[b, :, :frames[b]] with z_init[b, :, :32 frames[b]] and z_early[i][b, :, :32 frames[b]], synthesised alone
- * (src/waveglow/model.py:223-273 on that utterance; the reference has no ragged mode, its convolutions' zero padding at
- * the end of a sequence, model.py:98-102, is what the padding columns stand for):
- *   forward   audio[b, :256 frames[b]] has the bits of the batch-of-one call on the utterance, audio behind it is 0.
- *   backward  g_mel, g_z_init and g_z_early[i] are 0 behind the count and have the bits of the batch-of-one call (same
- *             scale) in front of it; every entry of `grads` is the sum over the utterances of the batch-of-one calls'
- *             (up to accumulation order).  The backward takes the counts of its forward.
- * Nothing behind an utterance's count is read: mel, noise and g_audio may hold NaN there.  The counts are never read on
- * the host and nothing synchronises: a count <= 0 makes its utterance all padding (zero audio, zero gradients, nothing
- * added to `grads`), a count above n_frames counts as n_frames; neither reads or writes outside the buffers.
- * With counts the forward clears the workspace's planes on every call, whatever `fresh` says (the layer kernels leave
- * padding columns unwritten, and a reused workspace may hold another batch there). */
-int wg_train_infer_forward_ragged(wg_handle* h, const wg_train_weights* w, const void* mel, const void* z_init,
-                                  const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
-                                  int32_t n_frames, const int32_t* frames, int32_t fresh, void* workspace,
-                                  size_t workspace_bytes, int32_t flags, void* stream);
-int wg_train_infer_backward_ragged(wg_handle* h, const wg_train_weights* w, const wg_train_grads* grads,
-                                   const float* g_audio, float scale, float sigma, float* g_mel, float* g_z_init,
-                                   float* const* g_z_early, int32_t n_z_early, int32_t B, int32_t n_frames,
-                                   const int32_t* frames, void* workspace, size_t workspace_bytes, int32_t flags,
-                                   void* stream);
+                            const int32_t* frames, void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
 
 /* Diagnostic builds only (-DWG_STAMPS): device buffer of n_tiles*8 uint64 that the WN-layer kernel fills with
  * s_memtime stamps at its phase boundaries (last launch wins).  A no-op pointer in the shipped library. */

@@ -122,25 +122,19 @@ def four_runs(monkeypatch, call, what, excluded=()):
 G = "tests/test_gpu_dirty_workspace.py::"
 R = "tests/test_gpu_workspace_reuse.py::"
 
-# C function -> the GPU tests that reach it.  wg_infer, wg_train_infer_forward and wg_train_infer_backward are their
-# _ragged entries with null counts (one implementation each: api.cpp, train_api.cpp), which is how the Python layer calls
-# them; wg_loss (the loss with log_det_W as host floats) has no Python caller and is called through ctypes by its test.
+# C function -> the GPU tests that reach it.  A call with per-utterance lengths is the dense call with a non-null `frames` /
+# `lens`: one row each, naming the tests that run it both ways.  wg_loss (the loss with log_det_W as host floats) has no
+# Python caller and is called through ctypes by its test.
 ENTRY_POINTS = {
-  "wg_infer": (G + "test_inference",),
-  "wg_infer_ragged": (G + "test_inference", G + "test_inference_graph_replays"),
+  "wg_infer": (G + "test_inference", G + "test_inference_graph_replays"),
   "wg_forward": (G + "test_no_grad_forward_and_likelihood",),
-  "wg_forward_ragged": (G + "test_no_grad_forward_and_likelihood",),
   "wg_nll": (G + "test_no_grad_forward_and_likelihood",),
   "wg_loss": (G + "test_no_grad_forward_and_likelihood",),
   "wg_loss_dev": (G + "test_no_grad_forward_and_likelihood", G + "test_training_step_on_a_new_slot"),
   "wg_stft_denoise": (G + "test_denoiser",),
-  "wg_stft_denoise_ragged": (G + "test_denoiser",),
   "wg_stft_mel": (G + "test_mel_front_end",),
-  "wg_stft_mel_ragged": (G + "test_mel_front_end",),
   "wg_stft_mel_forward_saved": (G + "test_mel_front_end_gradient",),
   "wg_stft_mel_backward": (G + "test_mel_front_end_gradient",),
-  "wg_stft_mel_forward_saved_ragged": (G + "test_mel_front_end_gradient",),
-  "wg_stft_mel_backward_ragged": (G + "test_mel_front_end_gradient",),
   "wg_wav_finish": (G + "test_outputs_without_a_workspace",),
   "wg_metrics_mfcc": (G + "test_mel_metrics",),
   "wg_metrics_mel": (G + "test_mel_metrics",),
@@ -149,15 +143,9 @@ ENTRY_POINTS = {
   "wg_stoi_forward": (G + "test_stoi_loss",),
   "wg_stoi_backward": (G + "test_stoi_loss",),
   "wg_stftloss_forward": (G + "test_stft_loss",),
-  "wg_stftloss_forward_saved": (G + "test_stft_loss",),
   "wg_stftloss_backward": (G + "test_stft_loss",),
-  "wg_stftloss_forward_ragged": (G + "test_stft_loss",),
-  "wg_stftloss_forward_saved_ragged": (G + "test_stft_loss",),
-  "wg_stftloss_backward_ragged": (G + "test_stft_loss",),
   "wg_train_forward": (G + "test_training_step_on_a_new_slot", R + "test_alternating_directions_on_one_slot"),
   "wg_train_backward": (G + "test_training_step_on_a_new_slot", R + "test_alternating_directions_on_one_slot"),
   "wg_train_infer_forward": (G + "test_infer_differentiable", R + "test_alternating_directions_on_one_slot"),
   "wg_train_infer_backward": (G + "test_infer_differentiable", R + "test_alternating_directions_on_one_slot"),
-  "wg_train_infer_forward_ragged": (G + "test_infer_differentiable", R + "test_alternating_directions_on_one_slot"),
-  "wg_train_infer_backward_ragged": (G + "test_infer_differentiable", R + "test_alternating_directions_on_one_slot"),
 }

@@ -1,4 +1,4 @@
-"""The accepted size range of ``wg_infer`` / ``wg_infer_ragged`` / ``wg_forward`` in plain Python: a restatement of
+"""The accepted size range of ``wg_infer`` / ``wg_forward`` in plain Python: a restatement of
 ``make_geom`` (waveglow_amd/csrc/wg_host.h) and of the one size check in front of it (``kMaxRowsPerPhase``), plus the
 named shapes at the top of that range that tests/test_envelope_cpu.py and tests/test_gpu_envelope.py share.
 

@@ -31,10 +31,18 @@ def test_header_symbols_all_exported_and_bound(lib):
     assert s in _lib.SIGNATURES, f"{s} declared in the header but not bound in _lib.SIGNATURES"
   assert sorted(_lib.SIGNATURES) == syms
   # one entry point per call: no suffixed variant of a name, and the natural-order packing entry is gone everywhere
-  assert not [s for s in syms if re.search(r"_(ex|flags|flows|params)$", s)]
+  assert not [s for s in syms if re.search(r"_(ex|flags|flows|params|ragged)$", s)]
   text = open(os.path.join(ROOT, "include", "waveglow_amd.h")).read()
   for gone in ("wg_train_" + n for n in ("pack", "plain")):
     assert gone not in text and gone not in _lib.SIGNATURES and not hasattr(lib, gone), gone
+  # the per-utterance lengths are a nullable pointer of the one call, and `saved` an argument of wg_stftloss_forward
+  twins = ("wg_infer", "wg_forward", "wg_train_infer_forward", "wg_train_infer_backward", "wg_stft_denoise", "wg_stft_mel",
+           "wg_stft_mel_forward_saved", "wg_stft_mel_backward", "wg_stftloss_forward", "wg_stftloss_forward_saved",
+           "wg_stftloss_backward")
+  removed = [n + "_ragged" for n in twins] + ["wg_stftloss_forward_saved"]
+  assert len(removed) == 12
+  for gone in removed:
+    assert not re.search(rf"\b{gone}\b", text) and gone not in _lib.SIGNATURES and not hasattr(lib, gone), gone
 
 
 def _struct_listing(name):
@@ -75,7 +83,7 @@ def test_create_validates_configuration(lib):
   # infer before finalize -> state error, not a crash
   import ctypes
   buf = ctypes.create_string_buffer(64)
-  rc = lib.wg_infer(h, buf, buf, None, 0, 1.0, buf, 1, 1, 0, buf, 64, None)
+  rc = lib.wg_infer(h, buf, None, buf, None, 0, 1.0, buf, 1, 1, 0, buf, 64, None)
   assert rc == -2
   # unknown tensor name rejected
   import numpy as np

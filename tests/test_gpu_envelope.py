@@ -182,8 +182,8 @@ WIDE_CASES = [
 @pytest.mark.parametrize("channels,name,dtype,force_bn", WIDE_CASES,
                          ids=[f"c{c}-{n}-{str(d).split('.')[1]}-bn{b or 'auto'}" for c, n, d, b in WIDE_CASES])
 def test_wide_ragged_batch_equals_slices_of_256(pool, channels, name, dtype, force_bn):
-  """wg_infer_ragged on 8 193 / 16 382 utterances of up to 56 frames: every utterance equals, bit for bit, its result in
-  a call on its slice of 256 utterances, and is zero behind its own end."""
+  """wg_infer with frame counts on 8 193 / 16 382 utterances of up to 56 frames: every utterance equals, bit for bit, its
+  result in a call on its slice of 256 utterances, and is zero behind its own end."""
   model = _model(pool, channels, force_bn)
   try:
     with _Clock(f"infer ragged c{channels} {name} {dtype} bn={force_bn or 'auto'}"):
@@ -406,12 +406,12 @@ def test_first_refused_shapes_raise_before_anything_is_allocated(pool, name, dir
   stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
   if direction == "infer":
     ze = (C.c_void_p * 1)(args[2][0].data_ptr())
-    rc = eng.lib.wg_infer_ragged(eng.handle, mel.data_ptr(), None, args[1].data_ptr(), ze, 1, SIGMA, ws.data_ptr(), B, T,
-                                 _lib.WG_F16, ws.data_ptr(), ws.numel(), stream)
+    rc = eng.lib.wg_infer(eng.handle, mel.data_ptr(), None, args[1].data_ptr(), ze, 1, SIGMA, ws.data_ptr(), B, T,
+                          _lib.WG_F16, ws.data_ptr(), ws.numel(), stream)
   else:
     ls = (C.c_void_p * 4)(*[ws.data_ptr()] * 4)
     ld = (C.c_float * 4)()
-    rc = eng.lib.wg_forward(eng.handle, mel.data_ptr(), audio.data_ptr(), ws.data_ptr(), ls, ld, B, T, 256 * T, _lib.WG_F16,
+    rc = eng.lib.wg_forward(eng.handle, mel.data_ptr(), None, audio.data_ptr(), ws.data_ptr(), ls, ld, B, T, 256 * T, _lib.WG_F16,
                             ws.data_ptr(), ws.numel(), stream)
   assert rc != 0 and b"batch too large" in eng.lib.wg_last_error()
   assert eng.lib.wg_infer_workspace_bytes(eng.handle, B, T) == 0

@@ -1,4 +1,4 @@
-"""GPU checks of the per-utterance likelihood: the ragged no-grad forward (wg_forward_ragged) against batch-of-one calls of
+"""GPU checks of the per-utterance likelihood: the ragged no-grad forward (wg_forward with frames) against batch-of-one calls of
 the dense one, the fp64 reduction (wg_nll) against the numpy restatement tests/_likelihood_oracle.py on the device's own z
 and log_s, the dense batch against WaveGlowLoss, the golden cases of the reference, and ``validate --likelihood``."""
 import numpy as np
@@ -69,7 +69,7 @@ def _logdets(model):
   (64, None, torch.float32, [1, 9, 3]),
 ])
 def test_ragged_forward_equals_batch_of_one_calls(channels, force_bn, dtype, lens, monkeypatch):
-  """wg_forward_ragged: every utterance of a padded batch gets, bit for bit, the z and log_s of the dense forward on its own
+  """wg_forward with frames: every utterance of a padded batch gets, bit for bit, the z and log_s of the dense forward on its own
   crop, and exact zeros behind its columns; mel and audio behind an utterance hold NaN."""
   if force_bn:
     monkeypatch.setenv("WG_FORCE_BN", force_bn)

@@ -484,15 +484,16 @@ def test_denoiser_stft_vs_numpy_oracle():
     out = torch.empty_like(xd)
     mag0 = torch.empty((B, 513), dtype=torch.float32, device="cuda")
     ws = torch.empty(lib.wg_stft_workspace_bytes(h, B, 256 * T), dtype=torch.uint8, device="cuda")
-    _lib.check(lib.wg_stft_denoise(h, xd.data_ptr(), bd.data_ptr(), strength, out.data_ptr(), mag0.data_ptr(), B, 256 * T,
-                                   ws.data_ptr(), ws.numel(), None))
+    _lib.check(lib.wg_stft_denoise(h, xd.data_ptr(), None, bd.data_ptr(), strength, out.data_ptr(), mag0.data_ptr(), B,
+                                   256 * T, ws.data_ptr(), ws.numel(), None))
     torch.cuda.synchronize()
     err = float(np.abs(out.cpu().numpy() - ref).max())
     print(f"denoise B{B} T{T}: max err {err:.2e}  mag0 err {float(np.abs(mag0.cpu().numpy() - mag0_ref).max()):.2e}")
     assert err <= 2e-5
     np.testing.assert_allclose(mag0.cpu().numpy(), mag0_ref, rtol=1e-4, atol=1e-4)
     # strength 0 / no bias -> identity (perfect reconstruction of the STFT pair)
-    _lib.check(lib.wg_stft_denoise(h, xd.data_ptr(), None, 0.0, out.data_ptr(), None, B, 256 * T, ws.data_ptr(), ws.numel(), None))
+    _lib.check(lib.wg_stft_denoise(h, xd.data_ptr(), None, None, 0.0, out.data_ptr(), None, B, 256 * T, ws.data_ptr(), ws.numel(),
+                                   None))
     torch.cuda.synchronize()
     assert float((out - xd).abs().max()) <= 2e-5
   lib.wg_stft_destroy(h)
@@ -500,7 +501,7 @@ def test_denoiser_stft_vs_numpy_oracle():
 
 @pytest.mark.parametrize("channels,force_bn", [(64, None), (256, "128"), (256, "64"), (512, None)])
 def test_ragged_batch_equals_batch_of_one_calls(channels, force_bn, monkeypatch):
-  """wg_infer_ragged: utterances of different lengths padded into one batch give, each, bit-for-bit the audio of a
+  """wg_infer with frame counts: utterances of different lengths padded into one batch give, each, bit-for-bit the audio of a
   batch-of-one call on their own frames (same injected noise), and zeros behind their own length."""
   if force_bn:
     monkeypatch.setenv("WG_FORCE_BN", force_bn)

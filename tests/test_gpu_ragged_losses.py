@@ -180,10 +180,10 @@ def test_lengths_the_library_counts_as_zero():
     g3 = torch.tensor([0.0, 0.0, 1.0], device=DEV)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
     stream = C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-    assert crit.lib.wg_stftloss_forward_saved_ragged(crit._h, x.data_ptr(), y.data_ptr(), ld.data_ptr(), 1.0, 1.0,
-                                                     out.data_ptr(), B, N, ws.data_ptr(), nbytes, stream) == 0
-    assert crit.lib.wg_stftloss_backward_ragged(crit._h, g3.data_ptr(), ld.data_ptr(), 1.0, 1.0, gx.data_ptr(), B, N,
-                                                ws.data_ptr(), nbytes, stream) == 0
+    assert crit.lib.wg_stftloss_forward(crit._h, x.data_ptr(), y.data_ptr(), ld.data_ptr(), 1.0, 1.0, out.data_ptr(), B, N,
+                                        1, ws.data_ptr(), nbytes, stream) == 0
+    assert crit.lib.wg_stftloss_backward(crit._h, g3.data_ptr(), ld.data_ptr(), 1.0, 1.0, gx.data_ptr(), B, N,
+                                         ws.data_ptr(), nbytes, stream) == 0
     return out, gx
 
   for bad in ([0, 1024, N + 1], [-1, -(2 ** 31), 2 ** 31 - 1]):

@@ -1,5 +1,5 @@
 """What follows the flow in a batched synthesis, and what precedes it in ``synthesize-wav``, on ragged batches: the
-denoiser (``wg_stft_denoise_ragged``), the mel front-end (``wg_stft_mel_ragged``) and the int16 finishing
+denoiser (``wg_stft_denoise`` with ``lens``), the mel front-end (``wg_stft_mel`` with ``lens``) and the int16 finishing
 (``wg_wav_finish``).  Every utterance of a batch must come out BIT FOR BIT as its single call / the host functions give
 it: no tolerance anywhere in this file."""
 import numpy as np

@@ -58,7 +58,7 @@ class _Stft:
     out = torch.full_like(xd, float("nan"))
     mag0 = torch.full((B, 513), float("nan"), dtype=torch.float32, device=DEV)
     ws = self._workspace(B, N)
-    _lib.check(self.lib.wg_stft_denoise(self.h, xd.data_ptr(), bd.data_ptr(), float(strength), out.data_ptr(),
+    _lib.check(self.lib.wg_stft_denoise(self.h, xd.data_ptr(), None, bd.data_ptr(), float(strength), out.data_ptr(),
                                         mag0.data_ptr(), B, N, ws.data_ptr(), ws.numel(), None))
     torch.cuda.synchronize()
     return out.cpu().numpy(), mag0.cpu().numpy()
@@ -69,8 +69,8 @@ class _Stft:
     ld = torch.tensor(lens, dtype=torch.int32).to(DEV)
     out = torch.full_like(xd, float("nan"))
     ws = self._workspace(B, N)
-    _lib.check(self.lib.wg_stft_denoise_ragged(self.h, xd.data_ptr(), ld.data_ptr(), bd.data_ptr(), float(strength),
-                                               out.data_ptr(), None, B, N, ws.data_ptr(), ws.numel(), None))
+    _lib.check(self.lib.wg_stft_denoise(self.h, xd.data_ptr(), ld.data_ptr(), bd.data_ptr(), float(strength),
+                                        out.data_ptr(), None, B, N, ws.data_ptr(), ws.numel(), None))
     torch.cuda.synchronize()
     return out.cpu().numpy()
 
@@ -105,7 +105,7 @@ def test_denoise_matches_reference(fx, stft, name, T, B, strength, kind):
 
 
 def test_denoise_ragged_rows_match_reference(fx, stft):
-  """The five lengths as ONE wg_stft_denoise_ragged call (the longest not first): every row is bit for bit its single call
+  """The five lengths as ONE wg_stft_denoise call with lengths (the longest not first): every row is bit for bit its single call
   and therefore within the same bar of the reference; zeros behind every utterance."""
   assert sorted(R.RAGGED_ORDER) == sorted(R.DENOISE_T) and R.RAGGED_ORDER[0] != max(R.RAGGED_ORDER)
   lens = [256 * T for T in R.RAGGED_ORDER]

@@ -20,7 +20,20 @@ from waveglow_amd._lib import WgError
 from waveglow_amd.model import WaveGlow
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("wg_train_infer_forward_ragged", "wg_train_infer_backward_ragged")
+NEW = ("wg_train_infer_forward", "wg_train_infer_backward")
+# the calls that take per-utterance lengths: (the nullable pointer, the argument it follows, the number of arguments)
+LENGTHS = {
+  "wg_infer": ("frames", "const void* mel", 14),
+  "wg_forward": ("frames", "const void* mel", 14),
+  "wg_train_infer_forward": ("frames", "int32_t n_frames", 16),
+  "wg_train_infer_backward": ("frames", "int32_t n_frames", 17),
+  "wg_stft_denoise": ("lens", "const float* audio", 12),
+  "wg_stft_mel": ("lens", "const float* audio", 11),
+  "wg_stft_mel_forward_saved": ("lens", "const float* audio", 11),
+  "wg_stft_mel_backward": ("lens", "const float* g_mel", 11),
+  "wg_stftloss_forward": ("lens", "const float* target", 13),
+  "wg_stftloss_backward": ("lens", "const float* g_out3", 11),
+}
 _KINDS = {C.c_float: "float", C.c_int32: "int32_t", C.c_size_t: "size_t"}      # (c_int32 is c_int where int has 32 bits)
 
 
@@ -85,22 +98,21 @@ def _kinds(args):
   return ["ptr" if "*" in a else a.split()[0] for a in args]
 
 
-@pytest.mark.parametrize("name", NEW)
+@pytest.mark.parametrize("name", sorted(LENGTHS))
 def test_header_and_binding_agree_argument_by_argument(name):
   """Return type and every argument: pointer / float / int32_t / size_t in the header is the same kind, at the same place,
-  in _lib.SIGNATURES; and the new call is its dense call with ``const int32_t* frames`` directly after n_frames."""
+  in _lib.SIGNATURES; and the call takes its per-utterance lengths as ``const int32_t* frames`` / ``lens`` where the ABI
+  puts them: directly after mel (wg_infer, wg_forward), after n_frames (wg_train_infer_*), after the audio or gradient
+  input (the STFT calls)."""
   ret, args = _header_decl(name)
   res, argtypes = _lib.SIGNATURES[name]
   assert (ret, res) == ("int", C.c_int)
   assert _kinds(args) == [_KINDS.get(t, "ptr") for t in argtypes]
-  dense = name[:-len("_ragged")]
-  dret, dargs = _header_decl(dense)
-  at = dargs.index("int32_t n_frames") + 1
-  assert dret == "int" and args == dargs[:at] + ["const int32_t* frames"] + dargs[at:]
-  _, dtypes = _lib.SIGNATURES[dense]
-  assert list(argtypes) == list(dtypes[:at]) + [C.c_void_p] + list(dtypes[at:])
-  # the dense calls keep their arity
-  assert len(dargs) == {"wg_train_infer_forward": 15, "wg_train_infer_backward": 16}[dense] and len(args) == len(dargs) + 1
+  pointer, after, arity = LENGTHS[name]
+  at = args.index(after) + 1
+  assert args[at] == f"const int32_t* {pointer}" and argtypes[at] is C.c_void_p
+  assert [a for a in args if a.split()[-1] in ("frames", "lens")] == [args[at]]       # the one pointer, once
+  assert len(args) == len(argtypes) == arity
 
 
 def test_argument_checks_need_no_device():
@@ -113,7 +125,7 @@ def test_argument_checks_need_no_device():
   p = C.cast(buf, C.c_void_p)
   w, g = _lib.WgTrainWeights(), _lib.WgTrainGrads()
   ze = (C.c_void_p * 1)(p)
-  fwd, bwd = lib.wg_train_infer_forward_ragged, lib.wg_train_infer_backward_ragged
+  fwd, bwd = lib.wg_train_infer_forward, lib.wg_train_infer_backward
   # forward: (h, w, mel, z_init, z_early, n_z_early, sigma, audio, B, n_frames, frames, fresh, workspace, bytes, flags, stream)
   ok = [None, C.byref(w), p, p, ze, 1, 0.7, p, 1, 1, p, 1, p, 64, 0, None]
   for i in (1, 2, 3, 4, 7, 12):                      # every pointer the call dereferences; frames and stream may be null
@@ -137,8 +149,8 @@ def test_argument_checks_need_no_device():
     a[4] = scale
     assert bwd(*a) == -1 and b"scale must be positive" in lib.wg_last_error()
   assert bwd(*ok) == -1 and b"null handle" in lib.wg_last_error()
-  # the dense entry points are these calls with frames == NULL: the same answers
-  assert lib.wg_train_infer_backward(None, C.byref(w), C.byref(g), p, 0.0, 0.7, p, p, ze, 1, 1, 1, p, 64, 0, None) == -1
+  # the dense batch is this call with frames == NULL: the same answers
+  assert bwd(None, C.byref(w), C.byref(g), p, 0.0, 0.7, p, p, ze, 1, 1, 1, None, p, 64, 0, None) == -1
   assert b"scale must be positive" in lib.wg_last_error()
 
 

@@ -126,8 +126,8 @@ def test_header_and_binding_agree_argument_by_argument(name):
   res, argtypes = _lib.SIGNATURES[name]
   assert (ret, res) in (("int", C.c_int), ("size_t", C.c_size_t))
   assert ["ptr" if "*" in a else a.split()[0] for a in args] == [_KINDS.get(t, "ptr") for t in argtypes]
-  want_len = {"wg_train_workspace_bytes": 5, "wg_train_forward": 14, "wg_train_backward": 18, "wg_train_infer_forward": 15,
-              "wg_train_infer_backward": 16}[name]
+  want_len = {"wg_train_workspace_bytes": 5, "wg_train_forward": 14, "wg_train_backward": 18, "wg_train_infer_forward": 16,
+              "wg_train_infer_backward": 17}[name]
   assert len(args) == want_len
 
 
@@ -142,8 +142,8 @@ def test_abi_of_the_new_entry_points():
       kinds.append("ptr")
     else:
       kinds.append(a.split()[0])
-  want = ["ptr", "ptr", "ptr", "ptr", "float", "float", "ptr", "ptr", "ptr", "int32_t", "int32_t", "int32_t", "ptr", "size_t",
-          "int32_t", "ptr"]
+  want = ["ptr", "ptr", "ptr", "ptr", "float", "float", "ptr", "ptr", "ptr", "int32_t", "int32_t", "int32_t", "ptr", "ptr",
+          "size_t", "int32_t", "ptr"]
   assert kinds == want
   res, argtypes = _lib.SIGNATURES["wg_train_infer_backward"]
   assert res is C.c_int and hasattr(lib, "wg_train_infer_backward")
@@ -166,9 +166,9 @@ def test_abi_of_the_new_entry_points():
   dummy = (C.c_char * 64)()
   d = C.addressof(dummy)
   w = _lib.WgTrainWeights()
-  assert lib.wg_train_infer_backward(h, C.byref(w), None, None, 1.0, 1.0, None, None, None, 0, 1, 8, d, 64, 0, None) == -1
+  assert lib.wg_train_infer_backward(h, C.byref(w), None, None, 1.0, 1.0, None, None, None, 0, 1, 8, None, d, 64, 0, None) == -1
   assert b"null argument" in lib.wg_last_error()
-  assert lib.wg_train_infer_backward(h, C.byref(w), None, d, 0.0, 1.0, None, None, None, 0, 1, 8, d, 64, 0, None) == -1
+  assert lib.wg_train_infer_backward(h, C.byref(w), None, d, 0.0, 1.0, None, None, None, 0, 1, 8, None, d, 64, 0, None) == -1
   assert b"scale" in lib.wg_last_error()
   # wg_train_prepare: a winv array with a null entry is refused
   nulls = (C.c_void_p * 12)()

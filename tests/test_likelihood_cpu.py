@@ -1,6 +1,6 @@
 """CPU-side checks of the per-utterance likelihood: the numpy restatement the GPU tests compare against (tests/
 _likelihood_oracle.py) pinned to the reference's own forward outputs and loss, hand cases, the ``validate`` flag, the
-table's columns, and the argument refusals of ``wg_nll`` / ``wg_forward_ragged`` and of the Python layer that need no
+table's columns, and the argument refusals of ``wg_nll`` / ``wg_forward`` and of the Python layer that need no
 device."""
 import ctypes as C
 import datetime
@@ -125,7 +125,7 @@ def test_get_df_columns_with_and_without_likelihood_fields():
 
 
 def test_entry_points_validate_arguments_without_a_gpu():
-  """The argument checks of wg_nll and wg_forward_ragged run before any device work: -1 with a message."""
+  """The argument checks of wg_nll and wg_forward run before any device work: -1 with a message."""
   from waveglow_amd import _lib, build
   build.build_library()
   lib = _lib.load()
@@ -152,14 +152,23 @@ def test_entry_points_validate_arguments_without_a_gpu():
     assert nll(h, p, ls, None, 1.0, B, L, p, None, p, big, None) == -1 and b"nll" in lib.wg_last_error()
   assert nll(h, p, ls, p, 1.0, 1, 65, p, None, p, big, None) == -1 and b"32 columns" in lib.wg_last_error()
   assert nll(h, p, ls, None, 1.0, 1, 64, p, None, p, big, None) == -2        # nothing was finalised: refused, not run
-  # wg_forward_ragged: null arguments, then the call order
-  fwd = lambda *a: lib.wg_forward_ragged(*a)     # noqa: E731
-  assert fwd(None, p, p, p, p, ls, 1, 8, 0, p, big, None) == -1 and b"null" in lib.wg_last_error()
+  # wg_forward with frame counts: null arguments, then the geometry the counts fix, then the call order
+  # (h, mel, frames, audio, z, log_s, log_det_W, B, n_frames, audio_len, io_dtype, workspace, workspace_bytes, stream)
+  fwd = lambda *a: lib.wg_forward(*a)     # noqa: E731
+  ld = (C.c_float * 12)()
+  assert fwd(None, p, p, p, p, ls, None, 1, 8, 2048, 0, p, big, None) == -1 and b"null" in lib.wg_last_error()
   for mel, audio, z, lsp, ws in ((None, p, p, ls, p), (p, None, p, ls, p), (p, p, None, ls, p), (p, p, p, None, p),
                                  (p, p, p, ls, None)):
-    assert fwd(h, mel, p, audio, z, lsp, 1, 8, 0, ws, big, None) == -1 and b"null" in lib.wg_last_error()
-  assert fwd(h, p, p, p, p, ls, 1, 0, 0, p, big, None) == -1
-  assert fwd(h, p, p, p, p, ls, 1, 8, 0, p, big, None) == -2
+    assert fwd(h, mel, p, audio, z, lsp, None, 1, 8, 2048, 0, ws, big, None) == -1 and b"null" in lib.wg_last_error()
+  assert fwd(h, p, p, p, p, ls, None, 1, 0, 0, 0, p, big, None) == -1
+  for audio_len in (2040, 2056, 8):                      # with counts the batch is whole frames: 256 * n_frames samples
+    assert fwd(h, p, p, p, p, ls, None, 1, 8, audio_len, 0, p, big, None) == -1 and b"256 * n_frames" in lib.wg_last_error()
+  assert fwd(h, p, p, p, p, ls, None, 1, (1 << 23) + 1, 0, 0, p, big, None) == -1          # n_frames above INT32_MAX >> 8
+  # log_det_W: required without counts, optional with them (a null one passes the null checks and reaches the call order)
+  assert fwd(h, p, None, p, p, ls, None, 1, 8, 2048, 0, p, big, None) == -1 and b"null" in lib.wg_last_error()
+  assert fwd(h, p, None, p, p, ls, ld, 1, 8, 2048, 0, p, big, None) == -2
+  assert fwd(h, p, p, p, p, ls, None, 1, 8, 2048, 0, p, big, None) == -2
+  assert fwd(h, p, p, p, p, ls, ld, 1, 8, 2048, 0, p, big, None) == -2
   assert lib.wg_destroy(h) == 0
 
 

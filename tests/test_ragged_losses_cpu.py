@@ -78,8 +78,8 @@ def lib():
 
 
 def test_ragged_entry_points_validate_arguments_without_a_gpu(lib):
-  """A null lens and mismatched sizes are argument errors, reported before the planning handle (device_id < 0) is
-  refused; with sound arguments the planning handle is refused as by the dense entry points."""
+  """One order of argument checks, with lens or without (a null lens is the dense batch): null arguments, then sizes, then
+  the workspace size, and only then the refusal of the planning handle (device_id < 0)."""
   n_fft, hop, win = (1024, 2048, 512), (120, 240, 50), (600, 1200, 240)
   arr = lambda v: (C.c_int32 * len(v))(*v)
   h = C.c_void_p()
@@ -88,25 +88,40 @@ def test_ragged_entry_points_validate_arguments_without_a_gpu(lib):
   p = C.addressof(dummy)
   need = lib.wg_stftloss_workspace_bytes(h, 2, 4096, 1)
   assert need > 0
-  for fwd, saved in ((lib.wg_stftloss_forward_ragged, 0), (lib.wg_stftloss_forward_saved_ragged, 1)):
+  # (h, audio, target, lens, factor_sc, factor_mag, out3, B, n_samples, saved, workspace, workspace_bytes, stream)
+  fwd = lib.wg_stftloss_forward
+  for saved in (0, 1):
     need = lib.wg_stftloss_workspace_bytes(h, 2, 4096, saved)
-    assert fwd(h, p, p, None, 1.0, 1.0, p, 2, 4096, p, need, None) == -1 and b"null" in lib.wg_last_error()
-    assert fwd(h, None, p, p, 1.0, 1.0, p, 2, 4096, p, need, None) == -1 and b"null" in lib.wg_last_error()
-    assert fwd(None, p, p, p, 1.0, 1.0, p, 2, 4096, p, need, None) == -1
-    assert fwd(h, p, p, p, 1.0, 1.0, p, 2, 1024, p, need, None) == -1 and b"n_samples" in lib.wg_last_error()
-    assert fwd(h, p, p, p, 1.0, 1.0, p, 0, 4096, p, need, None) == -1
-    assert fwd(h, p, p, p, 1.0, 1.0, p, 2, 4096, p, need - 1, None) == -4 and b"workspace" in lib.wg_last_error()
-    assert fwd(h, p, p, p, 1.0, 1.0, p, 2, 4096, p, need, None) == -2 and b"planning" in lib.wg_last_error()
-  bwd = lib.wg_stftloss_backward_ragged
-  assert bwd(h, p, None, 1.0, 1.0, p, 2, 4096, p, need, None) == -1 and b"null" in lib.wg_last_error()
-  assert bwd(h, p, p, 1.0, 1.0, None, 2, 4096, p, need, None) == -1
-  assert bwd(h, p, p, 1.0, 1.0, p, 2, 1024, p, need, None) == -1 and b"n_samples" in lib.wg_last_error()
-  assert bwd(h, p, p, 1.0, 1.0, p, 2, 4096, p, need - 1, None) == -4
-  assert bwd(h, p, p, 1.0, 1.0, p, 2, 4096, p, need, None) == -2
-  # the dense entry points keep their order: the planning handle is refused first
-  assert lib.wg_stftloss_forward(h, p, p, 1.0, 1.0, p, 2, 1024, p, need, None) == -2
+    assert fwd(h, None, p, p, 1.0, 1.0, p, 2, 4096, saved, p, need, None) == -1 and b"null" in lib.wg_last_error()
+    assert fwd(None, p, p, p, 1.0, 1.0, p, 2, 4096, saved, p, need, None) == -1
+    for lens in (p, None):
+      assert fwd(h, p, p, lens, 1.0, 1.0, p, 2, 1024, saved, p, need, None) == -1 and b"n_samples" in lib.wg_last_error()
+      assert fwd(h, p, p, lens, 1.0, 1.0, p, 0, 4096, saved, p, need, None) == -1
+      assert fwd(h, p, p, lens, 1.0, 1.0, p, 2, 4096, saved, p, need - 1, None) == -4 and b"workspace" in lib.wg_last_error()
+      # sound arguments: the planning handle is refused, with a null lens exactly as with one
+      assert fwd(h, p, p, lens, 1.0, 1.0, p, 2, 4096, saved, p, need, None) == -2 and b"planning" in lib.wg_last_error()
+  for lens in (p, None):
+    for saved in (2, -1):                            # `saved` is the flag of wg_stftloss_workspace_bytes: 0 or 1
+      assert fwd(h, p, p, lens, 1.0, 1.0, p, 2, 4096, saved, p, need, None) == -1 and b"saved" in lib.wg_last_error()
+  # (h, g_out3, lens, factor_sc, factor_mag, audio_grad_out, B, n_samples, workspace, workspace_bytes, stream)
+  bwd = lib.wg_stftloss_backward
+  assert bwd(h, None, p, 1.0, 1.0, p, 2, 4096, p, need, None) == -1 and b"null" in lib.wg_last_error()
+  for lens in (p, None):
+    assert bwd(h, p, lens, 1.0, 1.0, None, 2, 4096, p, need, None) == -1
+    assert bwd(h, p, lens, 1.0, 1.0, p, 2, 1024, p, need, None) == -1 and b"n_samples" in lib.wg_last_error()
+    assert bwd(h, p, lens, 1.0, 1.0, p, 2, 4096, p, need - 1, None) == -4
+    assert bwd(h, p, lens, 1.0, 1.0, p, 2, 4096, p, need, None) == -2 and b"planning" in lib.wg_last_error()
   assert lib.wg_stftloss_destroy(h) == 0
-  # mel gradients: null arguments are refused before anything else
-  for fn in (lib.wg_stft_mel_forward_saved_ragged, lib.wg_stft_mel_backward_ragged):
-    assert fn(None, p, 80, p, p, p, 2, 4096, p, 1 << 30, None) == -1 and b"null" in lib.wg_last_error()
-    assert fn(p, p, 80, p, None, p, 2, 4096, p, 1 << 30, None) == -1 and b"null" in lib.wg_last_error()
+  # mel gradients: null arguments are refused before anything else; a null lens is not one of them (the dense batch) and
+  # gets the answer of the call with lens.  Compared at the last refusal that needs no device, a workspace one byte short:
+  # past it the call enqueues work.
+  # (h, mel_basis, n_mel, audio / g_mel, lens, mel_out / audio_grad_out, B, n_samples, workspace, workspace_bytes, stream)
+  need = lib.wg_stft_mel_grad_workspace_bytes(p, 2, 4096)
+  assert need > 0
+  for fn in (lib.wg_stft_mel_forward_saved, lib.wg_stft_mel_backward):
+    assert fn(None, p, 80, p, p, p, 2, 4096, p, need, None) == -1 and b"null" in lib.wg_last_error()
+    assert fn(p, p, 80, None, p, p, 2, 4096, p, need, None) == -1 and b"null" in lib.wg_last_error()
+    answers = []
+    for lens in (p, None):
+      answers.append((fn(p, p, 80, p, lens, p, 2, 4096, p, need - 1, None), lib.wg_last_error()))
+    assert answers[0] == answers[1] and answers[0][0] == -4 and b"workspace" in answers[0][1]

@@ -1,5 +1,5 @@
-"""CPU-side checks of the batched post-processing entry points (wg_stft_denoise_ragged, wg_stft_mel_ragged,
-wg_wav_finish): exported, bound, and refusing null arguments before any device work."""
+"""CPU-side checks of the batched post-processing entry points (wg_stft_denoise and wg_stft_mel with per-utterance
+lengths, wg_wav_finish): exported, bound, and refusing null arguments before any device work."""
 import ctypes as C
 
 import numpy as np
@@ -7,7 +7,7 @@ import pytest
 
 from waveglow_amd import _lib, build
 
-NEW = ("wg_stft_denoise_ragged", "wg_stft_mel_ragged", "wg_wav_finish")
+NEW = ("wg_stft_denoise", "wg_stft_mel", "wg_wav_finish")
 
 
 @pytest.fixture(scope="module")
@@ -24,11 +24,18 @@ def test_new_symbols_exported_and_bound(lib):
 
 def test_null_arguments_are_refused_without_a_device(lib):
   buf = C.addressof((C.c_char * 64)())
-  assert lib.wg_stft_denoise_ragged(None, None, None, None, 0.5, None, None, 2, 2048, None, 0, None) == -1
+  assert lib.wg_stft_denoise(None, None, None, None, 0.5, None, None, 2, 2048, None, 0, None) == -1
   assert b"null" in lib.wg_last_error()
-  # a handle-shaped pointer does not help while the lengths are missing
-  assert lib.wg_stft_denoise_ragged(buf, buf, None, None, 0.5, buf, None, 2, 2048, buf, 1 << 30, None) == -1
-  assert lib.wg_stft_mel_ragged(None, None, 80, None, None, None, 2, 2048, None, 0, None) == -1
+  # null lengths are the dense batch, not an argument error: with a handle-shaped pointer and otherwise sound arguments
+  # the call gets the answer of the call with lengths.  Compared at the last refusal that needs no device, a workspace
+  # one byte short: past it the call enqueues work.
+  need = lib.wg_stft_workspace_bytes(buf, 2, 2048)
+  assert need > 0
+  answers = [(lib.wg_stft_denoise(buf, buf, lens, None, 0.5, buf, None, 2, 2048, buf, need - 1, None), lib.wg_last_error())
+             for lens in (buf, None)]
+  assert answers[0] == answers[1] and answers[0][0] == -4 and b"workspace" in answers[0][1]
+  assert lib.wg_stft_denoise(buf, None, None, None, 0.5, buf, None, 2, 2048, buf, need, None) == -1
+  assert lib.wg_stft_mel(None, None, 80, None, None, None, 2, 2048, None, 0, None) == -1
   assert lib.wg_wav_finish(None, None, None, None, None, 2, 2048, None, 0, None) == -1
   assert b"null" in lib.wg_last_error()
   assert lib.wg_wav_finish(buf, buf, None, buf, buf, 2, 2048, buf, 1 << 20, None) == -1

@@ -79,11 +79,11 @@ def test_flags_must_match_the_workspace_size(handle):
 
   def ifwd(nbytes, flags):
     ze = (C.c_void_p * 2)(p, p)
-    return lib.wg_train_infer_forward(h, C.byref(w), p, p, ze, 2, C.c_float(1.0), p, B, T, 0, p, nbytes, flags, None)
+    return lib.wg_train_infer_forward(h, C.byref(w), p, p, ze, 2, C.c_float(1.0), p, B, T, None, 0, p, nbytes, flags, None)
 
   def ibwd(nbytes, flags):
-    return lib.wg_train_infer_backward(h, C.byref(w), None, p, C.c_float(1.0), C.c_float(1.0), None, None, None, 2, B, T, p,
-                                       nbytes, flags, None)
+    return lib.wg_train_infer_backward(h, C.byref(w), None, p, C.c_float(1.0), C.c_float(1.0), None, None, None, 2, B, T, None,
+                                       p, nbytes, flags, None)
 
   for call in (fwd, bwd, ifwd, ibwd):
     assert call(full, RC) == -1 and b"do not match" in lib.wg_last_error(), call.__name__

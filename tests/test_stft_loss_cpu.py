@@ -212,10 +212,10 @@ def test_entry_points_validate_arguments_without_a_gpu(lib):
   assert floor <= two
   dummy = (C.c_char * 64)()
   p = C.addressof(dummy)
-  assert lib.wg_stftloss_forward(h, p, p, 1.0, 1.0, p, 1, 4096, p, 1 << 40, None) == -2    # planning handle
-  assert lib.wg_stftloss_forward(h, None, p, 1.0, 1.0, p, 1, 4096, p, 1 << 40, None) == -1
+  assert lib.wg_stftloss_forward(h, p, p, None, 1.0, 1.0, p, 1, 4096, 0, p, 1 << 40, None) == -2    # planning handle
+  assert lib.wg_stftloss_forward(h, None, p, None, 1.0, 1.0, p, 1, 4096, 1, p, 1 << 40, None) == -1
   assert b"null" in lib.wg_last_error()
-  assert lib.wg_stftloss_backward(h, p, 1.0, 1.0, None, 1, 4096, p, 1 << 40, None) == -1
+  assert lib.wg_stftloss_backward(h, p, None, 1.0, 1.0, None, 1, 4096, p, 1 << 40, None) == -1
   assert lib.wg_stftloss_destroy(h) == 0
   # the Python surface refuses the same geometries before it touches a device
   from waveglow_amd.stft_loss import check_geometry

@@ -79,16 +79,11 @@ SIGNATURES = {
   "wg_finalize": (C.c_int, [C.c_void_p]),
   "wg_infer_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
   "wg_forward_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
-  "wg_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_float,
+  "wg_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_float,
                          C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_infer_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32,
-                                C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
-                                C.c_void_p]),
-  "wg_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+  "wg_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
                            C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                            C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_forward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
-                                  C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_nll_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
   "wg_nll": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_int32, C.c_int32,
                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -116,40 +111,25 @@ SIGNATURES = {
                                   C.c_int32, C.c_void_p]),
   "wg_train_infer_forward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.c_void_p, C.c_int32,
-                                       C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+                                       C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
+                                       C.c_void_p]),
   "wg_train_infer_backward": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
                                         C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
-                                        C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
-                                        C.c_void_p]),
-  "wg_train_infer_forward_ragged": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.c_void_p, C.c_void_p,
-                                              C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.c_void_p, C.c_int32,
-                                              C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
-                                              C.c_void_p]),
-  "wg_train_infer_backward_ragged": (C.c_int, [C.c_void_p, C.POINTER(WgTrainWeights), C.POINTER(WgTrainGrads), C.c_void_p,
-                                               C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
-                                               C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
-                                               C.c_int32, C.c_void_p]),
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_int32, C.c_void_p]),
   "wg_stft_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stft_destroy": (C.c_int, [C.c_void_p]),
   "wg_stft_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
-  "wg_stft_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
-                                C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stft_denoise_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                       C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stft_mel_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
-  "wg_stft_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                            C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stft_mel_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                   C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                            C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stft_mel_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
-  "wg_stft_mel_forward_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
-                                          C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stft_mel_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                     C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stft_mel_forward_saved_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stft_mel_backward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_mel_forward_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_mel_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_wav_finish_workspace_bytes": (C.c_size_t, [C.c_int32]),
   "wg_wav_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -199,18 +179,10 @@ SIGNATURES = {
                                   C.POINTER(C.c_void_p), C.c_float, C.c_int32, C.POINTER(C.c_void_p)]),
   "wg_stftloss_destroy": (C.c_int, [C.c_void_p]),
   "wg_stftloss_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
-  "wg_stftloss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int32,
-                                    C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stftloss_forward_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
-                                          C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stftloss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_int32,
-                                     C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stftloss_forward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stftloss_forward_saved_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                                 C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-  "wg_stftloss_backward_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
-                                            C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stftloss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stftloss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p,
+                                     C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_melloss_create": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_float, C.c_int32,
                                  C.POINTER(C.c_void_p)]),

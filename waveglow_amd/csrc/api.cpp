@@ -233,7 +233,7 @@ hipEvent_t wg_internal_sync_event(wg_handle* h) {
 
 extern "C" {
 
-const char* wg_version(void) { return "waveglow_amd 0.2 (gfx950)"; }
+const char* wg_version(void) { return "waveglow_amd 0.3 (gfx950)"; }
 const char* wg_last_error(void) { return g_err.c_str(); }
 
 int wg_create(const wg_config* cfg, int device_id, wg_handle** out) {
@@ -710,16 +710,10 @@ static int run_wn(wg_handle* h, int k, const RowGeom& g, Workspace& w, _Float16*
   return WG_OK;
 }
 
-int wg_infer(wg_handle* h, const void* mel, const void* z_init, const void* const* z_early, int32_t n_z_early,
-             float sigma, void* audio, int32_t B, int32_t n_frames, int32_t io_dtype, void* workspace,
+// `frames` (device, or null): per-utterance mel-frame counts of a ragged batch.
+int wg_infer(wg_handle* h, const void* mel, const int32_t* frames, const void* z_init, const void* const* z_early,
+             int32_t n_z_early, float sigma, void* audio, int32_t B, int32_t n_frames, int32_t io_dtype, void* workspace,
              size_t workspace_bytes, void* stream) {
-  return wg_infer_ragged(h, mel, nullptr, z_init, z_early, n_z_early, sigma, audio, B, n_frames, io_dtype, workspace,
-                         workspace_bytes, stream);
-}
-
-int wg_infer_ragged(wg_handle* h, const void* mel, const int32_t* frames, const void* z_init, const void* const* z_early,
-                    int32_t n_z_early, float sigma, void* audio, int32_t B, int32_t n_frames, int32_t io_dtype,
-                    void* workspace, size_t workspace_bytes, void* stream) {
   if (!h) return fail(WG_ERR_INVALID, "null handle");
   if (!h->finalized) return fail(WG_ERR_STATE, "wg_finalize has not been called");
   if (!mel || !z_init || !audio || !workspace) return fail(WG_ERR_INVALID, "null buffer");
@@ -823,12 +817,15 @@ int wg_infer_ragged(wg_handle* h, const void* mel, const int32_t* frames, const 
   return WG_OK;
 }
 
-// The no-grad forward of both entry points.  `frames` (device, or null): per-utterance mel-frame counts of a ragged batch.
-static int forward_impl(wg_handle* h, const void* mel, const int32_t* frames, const void* audio, float* z, float* const* log_s,
-                        int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype, void* workspace,
-                        size_t workspace_bytes, void* stream) {
+// `frames` (device, or null): per-utterance mel-frame counts of a ragged batch, which fixes the geometry to whole frames.
+int wg_forward(wg_handle* h, const void* mel, const int32_t* frames, const void* audio, float* z, float* const* log_s,
+               float* log_det_W, int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype, void* workspace,
+               size_t workspace_bytes, void* stream) {
   if (!h) return fail(WG_ERR_INVALID, "null handle");
-  if (!mel || !audio || !z || !log_s || !workspace) return fail(WG_ERR_INVALID, "null buffer");
+  if (!mel || !audio || !z || !log_s || !workspace || (!frames && !log_det_W)) return fail(WG_ERR_INVALID, "null buffer");
+  if (frames && (n_frames < 1 || n_frames > (INT32_MAX >> 8))) return fail(WG_ERR_INVALID, "bad B/n_frames");
+  if (frames && audio_len != n_frames * 256)
+    return fail(WG_ERR_INVALID, "with frame counts audio_len must be 256 * n_frames (%d), got %d", n_frames * 256, audio_len);
   if (!h->finalized) return fail(WG_ERR_STATE, "wg_finalize has not been called");
   if (io_dtype != WG_F32 && io_dtype != WG_F16) return fail(WG_ERR_INVALID, "bad io_dtype");
   const wg_config& c = h->cfg;
@@ -838,7 +835,7 @@ static int forward_impl(wg_handle* h, const void* mel, const int32_t* frames, co
   if ((int64_t)(n_frames - 1) * c.upsample_stride + c.upsample_kernel < audio_len)
     return fail(WG_ERR_INVALID, "upsampled mel (%d frames) shorter than audio (%d)", n_frames, audio_len);
   const int L = audio_len / c.n_group;
-  if (int rc = check_envelope(c, B, L)) return rc;   // as in wg_infer_ragged: the one size check, before the workspace's
+  if (int rc = check_envelope(c, B, L)) return rc;   // as in wg_infer: the one size check, before the workspace's
   RowGeom g = make_geom(c, B, L, n_frames);
   g.frames = (const int*)frames;   // the mel pack, the WN layers and the flow steps all take the padding columns from here
   Workspace w = carve(h, g, (char*)workspace);
@@ -908,26 +905,9 @@ static int forward_impl(wg_handle* h, const void* mel, const int32_t* frames, co
       if (rc) return rc;
     }
   }
+  if (log_det_W)
+    for (int k = 0; k < c.n_flows; ++k) log_det_W[k] = (float)((double)B * L * h->flows[k].logdet);   // model.py:63
   return WG_OK;
-}
-
-int wg_forward(wg_handle* h, const void* mel, const void* audio, float* z, float* const* log_s, float* log_det_W,
-               int32_t B, int32_t n_frames, int32_t audio_len, int32_t io_dtype, void* workspace,
-               size_t workspace_bytes, void* stream) {
-  if (!log_det_W) return fail(WG_ERR_INVALID, "null buffer");
-  const int rc = forward_impl(h, mel, nullptr, audio, z, log_s, B, n_frames, audio_len, io_dtype, workspace, workspace_bytes,
-                              stream);
-  if (rc != WG_OK) return rc;
-  const int64_t L = audio_len / h->cfg.n_group;
-  for (int k = 0; k < h->cfg.n_flows; ++k) log_det_W[k] = (float)((double)B * L * h->flows[k].logdet);   // model.py:63
-  return WG_OK;
-}
-
-int wg_forward_ragged(wg_handle* h, const void* mel, const int32_t* frames, const void* audio, float* z, float* const* log_s,
-                      int32_t B, int32_t n_frames, int32_t io_dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  if (n_frames < 1 || n_frames > (INT32_MAX >> 8)) return fail(WG_ERR_INVALID, "bad B/n_frames");
-  return forward_impl(h, mel, frames, audio, z, log_s, B, n_frames, n_frames * 256, io_dtype, workspace, workspace_bytes,
-                      stream);
 }
 
 static int loss_impl(const float* z, int64_t z_elems, const float* const* log_s, const int64_t* log_s_elems, int32_t n_flows,

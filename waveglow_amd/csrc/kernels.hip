@@ -1717,7 +1717,7 @@ __global__ void __launch_bounds__(FL_ROWS) flow_kernel(const FlowArgs a) {
         }
       } else {
         // ------------------------------------------------ forward flow (model.py:200-218)
-        // ragged batch (wg_forward_ragged): a padding column carries an all-zero state through every flow and writes 0 to
+        // ragged batch (wg_forward, frames): a padding column carries an all-zero state through every flow and writes 0 to
         // z and log_s -- its audio is never loaded (it may be NaN) and the out plane of its row is never read (exp of
         // out_init, twelve times over, need not stay finite).  A count outside [1, T] makes the whole utterance padding.
         if (a.g.frames != nullptr && (unsigned)a.g.frames[b] - 1u >= (unsigned)a.g.T) pad_row = true;

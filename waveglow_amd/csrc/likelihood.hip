@@ -1,6 +1,6 @@
 // gfx950 kernels of the per-utterance likelihood (include/waveglow_amd.h: wg_nll): the negative log-likelihood that
 // WaveGlowLoss (src/waveglow/train.py:31-45) takes of a whole batch, per utterance and per mel frame, from the z and
-// log_s of the no-grad forward (src/waveglow/model.py:178-221; wg_forward / wg_forward_ragged).
+// log_s of the no-grad forward (src/waveglow/model.py:178-221; wg_forward).
 //
 //   nll_frames_kernel   one workgroup per (utterance b, mel frame q): its 32 columns of the 8 z rows and of every log_s
 //                       row (8 + sum_k h_k rows x 128 bytes, 5.6 KB at the default model) -> three fp64 partials

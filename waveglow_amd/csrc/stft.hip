@@ -6,7 +6,7 @@
 // Mel gradients (TacotronSTFT.mel_spectrogram_differentiable): mel_kernel also keeps the pre-log sums, mel_bwd_kernel
 // turns d mel into d (re, im) in the inverse's [B][1056][Fs] layout, istft_kernel<true> is the transposed conv-STFT
 // with the forward basis, and reflect_fold_kernel adds the reflect-padded edges back onto the audio gradient.
-// With per-utterance lengths (wg_stft_mel_*_ragged) the three take the utterance's own frames and samples: d (re, im)
+// With per-utterance lengths (a non-null lens) the three take the utterance's own frames and samples: d (re, im)
 // behind its frames stays zero, the interior is stored up to its length, the edges fold about its own last sample.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,7 +23,7 @@ constexpr int kMT = kRows / 32;        // 33
 // of a B-fragment read (same k, frames 256 apart) hit 32 different banks
 __device__ __forceinline__ int seg_idx(int pos) { return pos + (pos >> 8); }
 
-// Sample count of utterance b in a ragged batch (wg_stft_denoise_ragged, wg_stft_mel_ragged).  A length the entry point
+// Sample count of utterance b in a ragged batch (wg_stft_denoise, wg_stft_mel with lens).  A length the entry point
 // does not allow (below min_len, above the row pitch, or with bits of mask set) counts as 0: the row comes out all zero
 // and nothing is indexed with it.
 __device__ __forceinline__ int ragged_len(const int* lens, int b, int pitch, int min_len, int mask) {

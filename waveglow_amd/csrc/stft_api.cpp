@@ -74,9 +74,10 @@ size_t wg_stft_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples) {
 }
 
 // lens == nullptr: every row has n_samples samples.  Otherwise lens is a device array read by the kernels only.
-static int denoise(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag, float strength,
-                   float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
-                   size_t workspace_bytes, void* stream) {
+int wg_stft_denoise(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag, float strength,
+                    float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  if (!h || !audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
   if (B < 1 || n_samples < kFL || n_samples % kHop)
     return fail(WG_ERR_INVALID, "n_samples must be a multiple of 256 and >= 1024");
   const size_t need = wg_stft_workspace_bytes(h, B, n_samples);
@@ -94,29 +95,15 @@ static int denoise(wg_stft* h, const float* audio, const int32_t* lens, const fl
   return WG_OK;
 }
 
-int wg_stft_denoise(wg_stft* h, const float* audio, const float* bias_mag, float strength, float* audio_out,
-                    float* mag0_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                    void* stream) {
-  if (!h || !audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
-  return denoise(h, audio, nullptr, bias_mag, strength, audio_out, mag0_out, B, n_samples, workspace, workspace_bytes,
-                 stream);
-}
-
-int wg_stft_denoise_ragged(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag, float strength,
-                           float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  if (!h || !audio || !lens || !workspace) return fail(WG_ERR_INVALID, "null argument");
-  return denoise(h, audio, lens, bias_mag, strength, audio_out, mag0_out, B, n_samples, workspace, workspace_bytes,
-                 stream);
-}
-
 size_t wg_stft_mel_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples) {
   if (!h || B < 1 || n_samples < kFL / 2 + 1) return 0;          // reflect padding needs n_samples > filter/2
   return (size_t)B * kCut * (n_samples / kHop + 1) * 4;
 }
 
-static int mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
-               float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+// lens as in wg_stft_denoise.
+int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
+                float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!h || !mel_basis || !audio || !mel_out || !workspace) return fail(WG_ERR_INVALID, "null argument");
   const size_t need = wg_stft_mel_workspace_bytes(h, B, n_samples);
   if (!need || n_mel < 1 || n_mel > 128) return fail(WG_ERR_INVALID, "bad B / n_samples / n_mel");
   if (workspace_bytes < need) return fail(WG_ERR_WORKSPACE, "mel workspace too small");
@@ -128,19 +115,6 @@ static int mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* a
   MelArgs m{(const float*)workspace, mel_basis, mel_out, n_mel, F, nullptr, lens, n_samples};
   HIP_TRY(launch_mel(m, B, s));
   return WG_OK;
-}
-
-int wg_stft_mel(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out, int32_t B,
-                int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!h || !mel_basis || !audio || !mel_out || !workspace) return fail(WG_ERR_INVALID, "null argument");
-  return mel(h, mel_basis, n_mel, audio, nullptr, mel_out, B, n_samples, workspace, workspace_bytes, stream);
-}
-
-int wg_stft_mel_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
-                       float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                       void* stream) {
-  if (!h || !mel_basis || !audio || !lens || !mel_out || !workspace) return fail(WG_ERR_INVALID, "null argument");
-  return mel(h, mel_basis, n_mel, audio, lens, mel_out, B, n_samples, workspace, workspace_bytes, stream);
 }
 
 // Mel-gradient workspace, in floats: [rec | gX | edge] (zeroed by the call that fills it) then [mag | pre].
@@ -178,9 +152,9 @@ static int mel_grad_check(wg_stft* h, const float* mel_basis, int32_t n_mel, con
 }
 
 // lens == nullptr: every row has n_samples samples.  Otherwise lens is a device array read by the kernels only.
-static int mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, const int32_t* lens,
-                             float* mel_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                             void* stream) {
+int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio,
+                              const int32_t* lens, float* mel_out, int32_t B, int32_t n_samples, void* workspace,
+                              size_t workspace_bytes, void* stream) {
   const int rc = mel_grad_check(h, mel_basis, n_mel, audio, mel_out, B, n_samples, workspace, workspace_bytes);
   if (rc != WG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -195,9 +169,9 @@ static int mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, 
   return WG_OK;
 }
 
-static int mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, const int32_t* lens,
-                        float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                        void* stream) {
+int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, const int32_t* lens,
+                         float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
+                         void* stream) {
   const int rc = mel_grad_check(h, mel_basis, n_mel, g_mel, audio_grad_out, B, n_samples, workspace, workspace_bytes);
   if (rc != WG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -209,33 +183,6 @@ static int mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const
   IstftArgs t{ws + L.gX, h->d_fwdT, nullptr, audio_grad_out, n_samples, L.F, L.Fs, ws + L.edge, lens};
   HIP_TRY(launch_stft_grad(t, B, s));
   return WG_OK;
-}
-
-int wg_stft_mel_forward_saved(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio, float* mel_out,
-                              int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
-  return mel_forward_saved(h, mel_basis, n_mel, audio, nullptr, mel_out, B, n_samples, workspace, workspace_bytes,
-                           stream);
-}
-
-int wg_stft_mel_backward(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel, float* audio_grad_out,
-                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
-  return mel_backward(h, mel_basis, n_mel, g_mel, nullptr, audio_grad_out, B, n_samples, workspace, workspace_bytes,
-                      stream);
-}
-
-int wg_stft_mel_forward_saved_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* audio,
-                                     const int32_t* lens, float* mel_out, int32_t B, int32_t n_samples, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-  if (!lens) return fail(WG_ERR_INVALID, "null argument");
-  return mel_forward_saved(h, mel_basis, n_mel, audio, lens, mel_out, B, n_samples, workspace, workspace_bytes, stream);
-}
-
-int wg_stft_mel_backward_ragged(wg_stft* h, const float* mel_basis, int32_t n_mel, const float* g_mel,
-                                const int32_t* lens, float* audio_grad_out, int32_t B, int32_t n_samples,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-  if (!lens) return fail(WG_ERR_INVALID, "null argument");
-  return mel_backward(h, mel_basis, n_mel, g_mel, lens, audio_grad_out, B, n_samples, workspace, workspace_bytes,
-                      stream);
 }
 
 }  // extern "C"

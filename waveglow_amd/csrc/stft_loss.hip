@@ -13,7 +13,7 @@
 // positions in ascending frame order.  Sums are reduced per thread and per workgroup in fp64 and combined by one
 // fixed-order final kernel: no floating-point atomics anywhere.
 //
-// Ragged batches (wg_stftloss_*_ragged): a device array lens gives utterance b its own N_b = lens[b] samples and
+// Ragged batches (a non-null lens): a device array lens gives utterance b its own N_b = lens[b] samples and
 // F_b = N_b / hop + 1 frames inside the dense [B][n_samples] layout.  Reflections use N_b, frames f >= F_b add nothing
 // and store nothing, a workgroup wholly behind its utterance does no GEMM, and the term count K sum_b F_b is formed on
 // the device.  With lens == nullptr every kernel takes a uniform branch to the dense geometry.
@@ -496,26 +496,25 @@ size_t wg_stftloss_workspace_bytes(const wg_stftloss* h, int32_t B, int32_t n_sa
   return L.total * 4;
 }
 
-// Argument checks shared by the forward and the backward.  The ragged entry points (ragged = true, lens a device array
-// that only kernels read) report a null lens and bad sizes before the planning-handle refusal, the dense ones keep
-// their order.
-static int loss_check(const wg_stftloss* h, bool any_null, bool ragged, const int32_t* lens, int32_t B, int32_t N,
-                      bool saved, size_t workspace_bytes, Layout& L) {
-  if (!h || any_null || (ragged && !lens)) return wg::fail(WG_ERR_INVALID, "null argument");
-  if (!ragged && h->device < 0)
-    return wg::fail(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
-  if (!layout(h, B, N, saved, L) || B > 65535)
+// Argument checks shared by the forward and the backward: null arguments, then sizes, then the workspace size, then the
+// planning-handle refusal (the order of wg_melloss_*).
+static int loss_check(const wg_stftloss* h, bool any_null, int32_t B, int32_t N, int32_t saved, size_t workspace_bytes,
+                      Layout& L) {
+  if (!h || any_null) return wg::fail(WG_ERR_INVALID, "null argument");
+  if (saved != 0 && saved != 1) return wg::fail(WG_ERR_INVALID, "stft loss: saved must be 0 or 1");
+  if (!layout(h, B, N, saved != 0, L) || B > 65535)
     return wg::fail(WG_ERR_INVALID, "stft loss: bad B, or n_samples <= max n_fft / 2");
   if (workspace_bytes < L.total * 4) return wg::fail(WG_ERR_WORKSPACE, "stft loss workspace too small");
   if (h->device < 0) return wg::fail(WG_ERR_STATE, "stft loss: planning handle (device_id < 0) cannot compute");
   return WG_OK;
 }
 
-static int loss_forward(wg_stftloss* h, const float* audio, const float* target, bool ragged, const int32_t* lens,
-                        float factor_sc, float factor_mag, float* out3, int32_t B, int32_t N, void* workspace,
-                        size_t workspace_bytes, void* stream, bool saved) {
+// lens == nullptr: every row has n_samples samples.  Otherwise lens is a device array read by the kernels only.
+int wg_stftloss_forward(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens, float factor_sc,
+                        float factor_mag, float* out3, int32_t B, int32_t N, int32_t saved, void* workspace,
+                        size_t workspace_bytes, void* stream) {
   Layout L;
-  const int rc = loss_check(h, !audio || !target || !out3 || !workspace, ragged, lens, B, N, saved, workspace_bytes, L);
+  const int rc = loss_check(h, !audio || !target || !out3 || !workspace, B, N, saved, workspace_bytes, L);
   if (rc != WG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
@@ -567,39 +566,11 @@ static int loss_forward(wg_stftloss* h, const float* audio, const float* target,
   return WG_OK;
 }
 
-int wg_stftloss_forward(wg_stftloss* h, const float* audio, const float* target, float factor_sc, float factor_mag,
-                        float* out3, int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes,
-                        void* stream) {
-  return loss_forward(h, audio, target, false, nullptr, factor_sc, factor_mag, out3, B, n_samples, workspace,
-                      workspace_bytes, stream, false);
-}
-
-int wg_stftloss_forward_saved(wg_stftloss* h, const float* audio, const float* target, float factor_sc,
-                              float factor_mag, float* out3, int32_t B, int32_t n_samples, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-  return loss_forward(h, audio, target, false, nullptr, factor_sc, factor_mag, out3, B, n_samples, workspace,
-                      workspace_bytes, stream, true);
-}
-
-int wg_stftloss_forward_ragged(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens,
-                               float factor_sc, float factor_mag, float* out3, int32_t B, int32_t n_samples,
-                               void* workspace, size_t workspace_bytes, void* stream) {
-  return loss_forward(h, audio, target, true, lens, factor_sc, factor_mag, out3, B, n_samples, workspace,
-                      workspace_bytes, stream, false);
-}
-
-int wg_stftloss_forward_saved_ragged(wg_stftloss* h, const float* audio, const float* target, const int32_t* lens,
-                                     float factor_sc, float factor_mag, float* out3, int32_t B, int32_t n_samples,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-  return loss_forward(h, audio, target, true, lens, factor_sc, factor_mag, out3, B, n_samples, workspace,
-                      workspace_bytes, stream, true);
-}
-
-static int loss_backward(wg_stftloss* h, const float* g_out3, bool ragged, const int32_t* lens, float factor_sc,
-                         float factor_mag, float* audio_grad_out, int32_t B, int32_t N, void* workspace,
-                         size_t workspace_bytes, void* stream) {
+int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, const int32_t* lens, float factor_sc, float factor_mag,
+                         float* audio_grad_out, int32_t B, int32_t N, void* workspace, size_t workspace_bytes,
+                         void* stream) {
   Layout L;
-  const int rc = loss_check(h, !g_out3 || !audio_grad_out || !workspace, ragged, lens, B, N, true, workspace_bytes, L);
+  const int rc = loss_check(h, !g_out3 || !audio_grad_out || !workspace, B, N, 1, workspace_bytes, L);
   if (rc != WG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
@@ -636,19 +607,6 @@ static int loss_backward(wg_stftloss* h, const float* g_out3, bool ragged, const
     HIP_TRY(launch_gather(r, a.G, audio_grad_out, B, N, L.F[i], i > 0, lens, a.min_len, s));
   }
   return WG_OK;
-}
-
-int wg_stftloss_backward(wg_stftloss* h, const float* g_out3, float factor_sc, float factor_mag, float* audio_grad_out,
-                         int32_t B, int32_t n_samples, void* workspace, size_t workspace_bytes, void* stream) {
-  return loss_backward(h, g_out3, false, nullptr, factor_sc, factor_mag, audio_grad_out, B, n_samples, workspace,
-                       workspace_bytes, stream);
-}
-
-int wg_stftloss_backward_ragged(wg_stftloss* h, const float* g_out3, const int32_t* lens, float factor_sc,
-                                float factor_mag, float* audio_grad_out, int32_t B, int32_t n_samples, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-  return loss_backward(h, g_out3, true, lens, factor_sc, factor_mag, audio_grad_out, B, n_samples, workspace,
-                       workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // The two memory kernels of a streaming step (include/waveglow_amd.h: wg_stream_gather, wg_stream_emit).  A step over B
-// streams runs one window per stream through wg_infer_ragged and the ragged denoiser; stream_gather_kernel forms the
+// streams runs one window per stream through wg_infer and the denoiser as a ragged batch; stream_gather_kernel forms the
 // padded batch tensors of those windows out of the streams' own mel and noise buffers in ONE launch (instead of
 // 2 + n_early slice copies and as many zero fills per stream), stream_emit_kernel crops the chunks out of the window
 // audio, converts them to int16 and reduces their statistics in ONE launch (instead of a crop, two extrema and a count

@@ -955,16 +955,8 @@ void infer_next(const Ctx& x, const wg_train_weights* wt, int j, FlowArgs& f) {
 
 int wg_train_infer_forward(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* z_init,
                            const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
-                           int32_t n_frames, int32_t fresh, void* workspace, size_t workspace_bytes, int32_t flags,
-                           void* stream) {
-  return wg_train_infer_forward_ragged(h, wt, mel, z_init, z_early, n_z_early, sigma, audio, B, n_frames, nullptr, fresh,
-                                       workspace, workspace_bytes, flags, stream);
-}
-
-int wg_train_infer_forward_ragged(wg_handle* h, const wg_train_weights* wt, const void* mel, const void* z_init,
-                                  const void* const* z_early, int32_t n_z_early, float sigma, float* audio, int32_t B,
-                                  int32_t n_frames, const int32_t* frames, int32_t fresh, void* workspace,
-                                  size_t workspace_bytes, int32_t flags, void* stream) {
+                           int32_t n_frames, const int32_t* frames, int32_t fresh, void* workspace,
+                           size_t workspace_bytes, int32_t flags, void* stream) {
   if (!wt || !mel || !z_init || !audio || !workspace || (n_z_early > 0 && !z_early))
     return fail(WG_ERR_INVALID, "null argument");
   Ctx x;
@@ -1032,16 +1024,8 @@ int wg_train_infer_forward_ragged(wg_handle* h, const wg_train_weights* wt, cons
 
 int wg_train_infer_backward(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_audio,
                             float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
-                            int32_t n_z_early, int32_t B, int32_t n_frames, void* workspace, size_t workspace_bytes,
-                            int32_t flags, void* stream) {
-  return wg_train_infer_backward_ragged(h, wt, gr, g_audio, scale, sigma, g_mel, g_z_init, g_z_early, n_z_early, B, n_frames,
-                                        nullptr, workspace, workspace_bytes, flags, stream);
-}
-
-int wg_train_infer_backward_ragged(wg_handle* h, const wg_train_weights* wt, const wg_train_grads* gr, const float* g_audio,
-                                   float scale, float sigma, float* g_mel, float* g_z_init, float* const* g_z_early,
-                                   int32_t n_z_early, int32_t B, int32_t n_frames, const int32_t* frames, void* workspace,
-                                   size_t workspace_bytes, int32_t flags, void* stream) {
+                            int32_t n_z_early, int32_t B, int32_t n_frames, const int32_t* frames, void* workspace,
+                            size_t workspace_bytes, int32_t flags, void* stream) {
   if (!wt || !g_audio || !workspace) return fail(WG_ERR_INVALID, "null argument");
   if (!(scale > 0.f)) return fail(WG_ERR_INVALID, "scale must be positive");
   Ctx x;

@@ -65,7 +65,7 @@ inline RowGeom make_geom(const wg_config& c, int B, int L, int T) {
   return g;
 }
 
-// The accepted size range of wg_infer / wg_infer_ragged / wg_forward (DESIGN.md sections 2 and 8).  A 64-channel chunk
+// The accepted size range of wg_infer / wg_forward (DESIGN.md sections 2 and 8).  A 64-channel chunk
 // plane holds R * 128 bytes, and the first layer of every WN keeps a byte offset into the a0 plane in an unsigned 32-bit
 // register (wn_layer_kernel A0G), so R * 128 < 2^32: with R = 32 Rp + 32 and Rp a multiple of 128 that is
 // Rp <= 2^20 - 128, i.e. B * Fp <= 1 048 448 rows per phase block.  Every other 32-bit quantity of the two directions

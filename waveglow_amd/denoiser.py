@@ -68,7 +68,8 @@ class Denoiser(torch.nn.Module):
     except Exception:
       pass
 
-  def _run(self, audio, bias, strength, out, mag0):
+  def _run(self, audio, bias, strength, out, mag0, lengths_dev=None):
+    """The one wg_stft_denoise call: fp32 ``audio`` [B, N], ``lengths_dev`` int32 [B] on the device or None."""
     audio = audio.contiguous()
     B, N = audio.shape
     nbytes = self.lib.wg_stft_workspace_bytes(self._h, B, N)
@@ -76,8 +77,10 @@ class Denoiser(torch.nn.Module):
       raise _lib.WgError(f"denoiser: unsupported audio length {N} (multiple of 256, >= 1024)")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
     stream = torch.cuda.current_stream(audio.device).cuda_stream
-    _lib.check(self.lib.wg_stft_denoise(self._h, audio.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                        float(strength), out.data_ptr() if out is not None else None,
+    _lib.check(self.lib.wg_stft_denoise(self._h, audio.data_ptr(),
+                                        lengths_dev.data_ptr() if lengths_dev is not None else None,
+                                        bias.data_ptr() if bias is not None else None, float(strength),
+                                        out.data_ptr() if out is not None else None,
                                         mag0.data_ptr() if mag0 is not None else None, B, N, ws.data_ptr(),
                                         ws.numel(), C.c_void_p(stream)))
 
@@ -97,7 +100,7 @@ class Denoiser(torch.nn.Module):
     return out[:, None, :]
 
   def run_ragged(self, audio, lengths, lengths_dev, strength, out):
-    """One wg_stft_denoise_ragged call on fp32 ``audio`` [B, N] into ``out``; ``lengths`` is checked here on the host,
+    """One wg_stft_denoise call with lengths on fp32 ``audio`` [B, N] into ``out``; ``lengths`` is checked here on the host,
     ``lengths_dev`` is the same as an int32 tensor on the device (the library never reads it on the host)."""
     audio = audio.contiguous()
     B, N = audio.shape
@@ -106,11 +109,4 @@ class Denoiser(torch.nn.Module):
     for n in lengths:
       if n < 1024 or n % 256 or n > N:
         raise _lib.WgError(f"denoiser: unsupported utterance length {n} (multiple of 256, >= 1024, <= {N})")
-    nbytes = self.lib.wg_stft_workspace_bytes(self._h, B, N)
-    if nbytes == 0:
-      raise _lib.WgError(f"denoiser: unsupported audio length {N} (multiple of 256, >= 1024)")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
-    stream = torch.cuda.current_stream(audio.device).cuda_stream
-    _lib.check(self.lib.wg_stft_denoise_ragged(self._h, audio.data_ptr(), lengths_dev.data_ptr(),
-                                               self.bias_spec.data_ptr(), float(strength), out.data_ptr(), None, B, N,
-                                               ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    self._run(audio, self.bias_spec, strength, out, None, lengths_dev)

@@ -16,9 +16,8 @@ synthesises): the backward then also runs the training direction's weight-gradie
   data-gradient chain, then the d spect GEMM and the transposed upsample for ``d mel``; with ``grads`` also the packed
   weight gradients (``GradBuffers``), among them ``d W_k = - sum (W_k^-T d w) (x) w`` of every inverse 1x1 step.
 
-Both are called through their ``_ragged`` forms, which take the per-utterance frame counts of a padded batch
-(``infer_differentiable(..., frames=)``: int32 [B] on the device, kept on ``ctx`` for the backward) and are the dense calls
-when there are none.
+Both take the per-utterance frame counts of a padded batch (``infer_differentiable(..., frames=)``: int32 [B] on the
+device, kept on ``ctx`` for the backward), or none for a dense one.
 
 The binding uses ``_TrainFn``'s plumbing (waveglow_amd/train.py): ``_Weights`` from ``wg_train_prepare``, one training
 workspace per outstanding graph (``request_workspace``), the fp16 loss scale and ``model.grad_finite``
@@ -65,10 +64,9 @@ class _InferFn(torch.autograd.Function):
     ws = slot["ws"]
     audio = torch.empty((B, S), dtype=torch.float32, device=mel.device)
     ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
-    _lib.check(lib.wg_train_infer_forward_ragged(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
-                                                 float(sigma), _ptr(audio), B, T,
-                                                 _ptr(frames) if frames is not None else None, 1 if fresh else 0, _ptr(ws),
-                                                 ws.numel(), flags, C.c_void_p(stream)))
+    _lib.check(lib.wg_train_infer_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
+                                          float(sigma), _ptr(audio), B, T, _ptr(frames) if frames is not None else None,
+                                          1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
     ctx.frames = frames
     ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.guard = model, wts, ws, (B, M, T), _SlotGuard(slot)
     ctx.flags, ctx.wgrads = flags, wgrads
@@ -114,12 +112,12 @@ class _InferFn(torch.autograd.Function):
     gstruct, _keep = bufs.struct() if want_params else (None, None)
     views = None
     try:
-      _lib.check(lib.wg_train_infer_backward_ragged(eng.handle, C.byref(ctx.wts.struct),
-                                                    C.byref(gstruct) if want_params else None, _ptr(ga), C.c_float(ctx.scale),
-                                                    C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
-                                                    _ptr(g_zi) if want_zi else None, ze, ne, B, T,
-                                                    _ptr(ctx.frames) if ctx.frames is not None else None,
-                                                    _ptr(ctx.ws), ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
+      _lib.check(lib.wg_train_infer_backward(eng.handle, C.byref(ctx.wts.struct),
+                                             C.byref(gstruct) if want_params else None, _ptr(ga), C.c_float(ctx.scale),
+                                             C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
+                                             _ptr(g_zi) if want_zi else None, ze, ne, B, T,
+                                             _ptr(ctx.frames) if ctx.frames is not None else None,
+                                             _ptr(ctx.ws), ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
       if want_params:      # (no logdet term in this direction)
         views = param_grad_views(eng, ctx.wts, gstruct, ctx.shapes, stream)
     finally:

@@ -3,8 +3,9 @@
 WaveGlow is a normalising flow: the quantity it is trained on, the negative log-likelihood of audio given its mel
 (``WaveGlowLoss``, src/waveglow/train.py:31-45), is also the most direct figure of merit of a checkpoint.  The reference
 logs it as one scalar of a dense batch; here every utterance of a batch of different lengths gets its own, with a track per
-mel frame: the no-grad forward with per-utterance frame counts (``wg_forward_ragged``, src/waveglow/model.py:178-221) and
-a two-level fp64 reduction (``wg_nll``).  The definitions are stated in include/waveglow_amd.h and DESIGN.md section 7.
+mel frame: the no-grad forward with per-utterance frame counts (``wg_forward`` with ``frames``,
+src/waveglow/model.py:178-221) and a two-level fp64 reduction (``wg_nll``).  The definitions are stated in
+include/waveglow_amd.h and DESIGN.md section 7.
 
 Always without a hipGraph and without autograd: this is for evaluation.  Everything is enqueued on the current stream;
 only ``log_likelihood`` copies to the host (once).  No CPU fallback.
@@ -82,8 +83,8 @@ def _frames(frames: Frames, mel: torch.Tensor, audio: torch.Tensor) -> torch.Ten
 
 def _forward(model, mel: torch.Tensor, audio: torch.Tensor, frames: Frames):
   """The no-grad forward at fp32 outputs: ``(engine, z [B, 8, L], [log_s_k [B, h_k, L]], frames_dev or None)``.
-  Dense: the batch on ``S - S % 8`` samples as ``WaveGlow.forward`` crops it (``wg_forward``).  With counts: both inputs
-  are brought to the pitch ``min(T, S // 256)`` frames and ``wg_forward_ragged`` runs."""
+  Dense: the batch on ``S - S % 8`` samples as ``WaveGlow.forward`` crops it.  With counts: both inputs are brought
+  to the pitch ``min(T, S // 256)`` frames and ``wg_forward`` takes them as ``frames``."""
   _inputs(model, mel, audio)
   if frames is not None:
     fr = _frames(frames, mel, audio)          # refused before any launch
@@ -113,13 +114,9 @@ def _forward(model, mel: torch.Tensor, audio: torch.Tensor, frames: Frames):
   ls = (C.c_void_p * model.n_flows)(*[t.data_ptr() for t in log_s])
   stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
   with torch.cuda.device(dev):
-    if fr is None:
-      log_det = (C.c_float * model.n_flows)()
-      _lib.check(eng.lib.wg_forward(eng.handle, mel.data_ptr(), audio.data_ptr(), z.data_ptr(), ls, log_det, B, T, S, io,
-                                    ws.data_ptr(), ws.numel(), stream))
-    else:
-      _lib.check(eng.lib.wg_forward_ragged(eng.handle, mel.data_ptr(), fr.data_ptr(), audio.data_ptr(), z.data_ptr(), ls,
-                                           B, T, io, ws.data_ptr(), ws.numel(), stream))
+    log_det = (C.c_float * model.n_flows)() if fr is None else None     # required without counts only; never read here
+    _lib.check(eng.lib.wg_forward(eng.handle, mel.data_ptr(), fr.data_ptr() if fr is not None else None, audio.data_ptr(),
+                                  z.data_ptr(), ls, log_det, B, T, S, io, ws.data_ptr(), ws.numel(), stream))
   return eng, z, log_s, fr
 
 

@@ -326,7 +326,7 @@ class WaveGlow(nn.Module):
                        sigma: float = 1.0, frames: Optional[torch.Tensor] = None, graph: bool = False) -> torch.Tensor:
     """``infer`` with the three noise draws injected (z_early in descending flow order).
     ``frames`` (int32 [B], optional): mel-frame count of every utterance of a padded batch -- each utterance then gets
-    exactly its batch-of-one result (``wg_infer_ragged``); the audio behind ``256 * frames[b]`` is zero.
+    exactly its batch-of-one result (``wg_infer`` with ``frames``); the audio behind ``256 * frames[b]`` is zero.
     ``graph=True`` replays the call's ~110 kernel launches from a captured hipGraph (one graph per input shape, dtype
     and sigma; the inputs are copied into the graph's static buffers) -- for single utterances the launch gaps are a
     measurable part of the latency.  Results are bit-identical to the direct launches."""
@@ -355,9 +355,9 @@ class WaveGlow(nn.Module):
         assert int(frames.min()) >= 1 and int(frames.max()) <= T
       elif not torch.cuda.is_current_stream_capturing():
         assert int(fr.min()) >= 1 and int(fr.max()) <= T
-    _lib.check(eng.lib.wg_infer_ragged(eng.handle, spect.data_ptr(), fr.data_ptr() if fr is not None else None,
-                                       z_init.data_ptr(), ze, len(z_early), float(sigma), audio.data_ptr(), B, T, io,
-                                       ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    _lib.check(eng.lib.wg_infer(eng.handle, spect.data_ptr(), fr.data_ptr() if fr is not None else None,
+                                z_init.data_ptr(), ze, len(z_early), float(sigma), audio.data_ptr(), B, T, io,
+                                ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     return audio
 
   def _infer_graphed(self, spect, z_init, z_early, sigma, frames):
@@ -465,7 +465,7 @@ class WaveGlow(nn.Module):
     ws = eng.workspace("fwd", nbytes, (B, F_, S))
     ls = (C.c_void_p * self.n_flows)(*[t.data_ptr() for t in log_s])
     stream = torch.cuda.current_stream(spect.device).cuda_stream
-    _lib.check(eng.lib.wg_forward(eng.handle, spect.data_ptr(), audio.data_ptr(), z.data_ptr(), ls, log_det,
+    _lib.check(eng.lib.wg_forward(eng.handle, spect.data_ptr(), None, audio.data_ptr(), z.data_ptr(), ls, log_det,
                                   B, F_, S, io, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     log_det_list = [torch.tensor(log_det[k], dtype=torch.float32, device=spect.device) for k in range(self.n_flows)]
     if spect.dtype != torch.float32:

@@ -215,24 +215,16 @@ class MultiResolutionSTFTLoss(_WaveformLoss):
     out = torch.empty(3, dtype=torch.float32, device=x.device)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    if lens is None:
-      fn = self.lib.wg_stftloss_forward_saved if saved else self.lib.wg_stftloss_forward
-      _lib.check(fn(self._h, x.data_ptr(), y.data_ptr(), self.factor_sc, self.factor_mag, out.data_ptr(), B, N,
-                    ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    else:
-      fn = self.lib.wg_stftloss_forward_saved_ragged if saved else self.lib.wg_stftloss_forward_ragged
-      _lib.check(fn(self._h, x.data_ptr(), y.data_ptr(), lens.data_ptr(), self.factor_sc, self.factor_mag,
-                    out.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    _lib.check(self.lib.wg_stftloss_forward(self._h, x.data_ptr(), y.data_ptr(),
+                                            lens.data_ptr() if lens is not None else None, self.factor_sc,
+                                            self.factor_mag, out.data_ptr(), B, N, 1 if saved else 0, ws.data_ptr(),
+                                            ws.numel(), C.c_void_p(stream)))
     return out, ws
 
   def _backward(self, ws, g, lens, B, N):
     gx = torch.empty((B, N), dtype=torch.float32, device=ws.device)
     stream = torch.cuda.current_stream(ws.device).cuda_stream
-    if lens is None:
-      _lib.check(self.lib.wg_stftloss_backward(self._h, g.data_ptr(), self.factor_sc, self.factor_mag, gx.data_ptr(), B,
-                                               N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    else:
-      _lib.check(self.lib.wg_stftloss_backward_ragged(self._h, g.data_ptr(), lens.data_ptr(), self.factor_sc,
-                                                      self.factor_mag, gx.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
-                                                      C.c_void_p(stream)))
+    _lib.check(self.lib.wg_stftloss_backward(self._h, g.data_ptr(), lens.data_ptr() if lens is not None else None,
+                                             self.factor_sc, self.factor_mag, gx.data_ptr(), B, N, ws.data_ptr(),
+                                             ws.numel(), C.c_void_p(stream)))
     return gx

@@ -10,7 +10,7 @@ and the denoiser reads 3 more frames of raw audio on either side (``filter_lengt
 inside a window that carries this halo on both sides therefore sees exactly the inputs it sees in the whole utterance;
 the library's ragged entry points give every utterance of a batch the bits of its own call wherever its columns lie, and
 treat the padding behind a count as the end of the sequence.  So the windows of a step run as a ragged batch
-(``wg_infer_ragged``, ``wg_stft_denoise_ragged``) and the interiors, concatenated, ARE the whole-utterance audio -- no
+(``wg_infer``, ``wg_stft_denoise`` with counts) and the interiors, concatenated, ARE the whole-utterance audio -- no
 overlap-add, no seams.  Every chunk recomputes its halo: a step over a ``C``-frame chunk does the flow's work for
 ``C + Hl + Hr`` frames, and a chunk can only leave once ``Hr`` frames behind it have arrived (the algorithmic look-ahead).
 
@@ -413,16 +413,16 @@ class _PinnedRing:
 
 
 def _infer_windows(eng, mel, frames_dev, z_init, z_early, sigma, audio) -> None:
-  """One ``wg_infer_ragged`` sequence on the windows into ``audio`` [B, 256 w_max] (the body of ``infer_with_noise`` with
+  """One ragged ``wg_infer`` sequence on the windows into ``audio`` [B, 256 w_max] (the body of ``infer_with_noise`` with
   the output given, so that its address can stand in the step's one table)."""
   B, _, T = mel.shape
   nbytes = eng.workspace_bytes("infer", B, T)
   ws = eng.workspace("infer", nbytes, (B, T, 0))
   ze = (C.c_void_p * max(1, len(z_early)))(*[z.data_ptr() for z in z_early])
   stream = torch.cuda.current_stream(mel.device).cuda_stream
-  _lib.check(eng.lib.wg_infer_ragged(eng.handle, mel.data_ptr(), frames_dev.data_ptr(), z_init.data_ptr(), ze, len(z_early),
-                                     float(sigma), audio.data_ptr(), B, T, _io(mel.dtype), ws.data_ptr(), ws.numel(),
-                                     C.c_void_p(stream)))
+  _lib.check(eng.lib.wg_infer(eng.handle, mel.data_ptr(), frames_dev.data_ptr(), z_init.data_ptr(), ze, len(z_early),
+                              float(sigma), audio.data_ptr(), B, T, _io(mel.dtype), ws.data_ptr(), ws.numel(),
+                              C.c_void_p(stream)))
 
 
 def stream_step(synth, sessions: Sequence[StreamSession], pcm: bool = True) -> list:
@@ -431,8 +431,8 @@ def stream_step(synth, sessions: Sequence[StreamSession], pcm: bool = True) -> l
 
   1. one table (gather rows, crop rows, frame and sample counts) through a pinned buffer,
   2. one ``wg_stream_gather`` launch,
-  3. one ``wg_infer_ragged`` sequence over the windows as a ragged batch at the fixed pitch ``C + Hl + Hr``,
-  4. one ``wg_stft_denoise_ragged`` call over the sessions with a strength above 0 (one strength per step),
+  3. one ``wg_infer`` sequence over the windows as a ragged batch at the fixed pitch ``C + Hl + Hr``,
+  4. one ``wg_stft_denoise`` call with lengths over the sessions with a strength above 0 (one strength per step),
   5. one ``wg_stream_emit`` launch,
   6. one pinned copy and one stream synchronise.
 

@@ -114,7 +114,7 @@ class Synthesizer:
   def _infer_batch_device(self, mels, sigma, denoiser_strength, seed):
     """The device work of a ragged batch, enqueued without a synchronise: noise drawn per utterance exactly as ``infer``
     draws it (seed reset, then the three tensors in the reference's order and shapes, model.py:234-271), one
-    ``wg_infer_ragged`` sequence and, for a strength above 0, one ragged denoiser call.  Returns the raw fp32 audio
+    ragged ``wg_infer`` sequence and, for a strength above 0, one ragged denoiser call.  Returns the raw fp32 audio
     [B, 256 Tmax], the denoised audio (the raw tensor itself at strength 0), the frame counts, the sample counts as an
     int32 tensor on the device and three events: before the flow, behind it, behind the denoiser."""
     mels = [m.squeeze(0) if m.dim() == 3 else m for m in mels]
@@ -153,7 +153,7 @@ class Synthesizer:
     """Several mel-spectrograms ``[1 or -, n_mel, T_i]`` of different lengths in ONE ragged launch sequence (the
     reference's commented-out ``--batch-size``, inference_v2.py:64).  Every utterance gets the audio that ``infer`` on
     it alone would return with the same seed: its noise is drawn exactly as that call draws it, and the kernels treat the
-    padding behind an utterance as the end of the sequence (``wg_infer_ragged``, ``wg_stft_denoise_ragged``).  Returns
+    padding behind an utterance as the end of the sequence (``wg_infer``, ``wg_stft_denoise`` with counts).  Returns
     one InferenceResult per utterance; the durations are the batch's on the device, divided evenly."""
     timepoint = datetime.datetime.now()
     audio, den, lens, _, ev = self._infer_batch_device(mels, sigma, denoiser_strength, seed)

@@ -111,13 +111,9 @@ class _MelFn(torch.autograd.Function):
     mel = torch.empty((B, taco.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=y.device)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
     stream = torch.cuda.current_stream(y.device).cuda_stream
-    if lens is None:
-      _lib.check(lib.wg_stft_mel_forward_saved(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, y.data_ptr(),
-                                               mel.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    else:
-      _lib.check(lib.wg_stft_mel_forward_saved_ragged(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels,
-                                                      y.data_ptr(), lens.data_ptr(), mel.data_ptr(), B, N,
-                                                      ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    _lib.check(lib.wg_stft_mel_forward_saved(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, y.data_ptr(),
+                                             lens.data_ptr() if lens is not None else None, mel.data_ptr(), B, N,
+                                             ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     ctx.taco, ctx.ws, ctx.dims, ctx.lens = taco, ws, (B, N), lens
     return mel
 
@@ -128,13 +124,9 @@ class _MelFn(torch.autograd.Function):
     g = g_mel.to(torch.float32).contiguous()
     gy = torch.empty((B, N), dtype=torch.float32, device=ws.device)
     stream = torch.cuda.current_stream(ws.device).cuda_stream
-    if ctx.lens is None:
-      _lib.check(taco.lib.wg_stft_mel_backward(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, g.data_ptr(),
-                                               gy.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    else:
-      _lib.check(taco.lib.wg_stft_mel_backward_ragged(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels,
-                                                      g.data_ptr(), ctx.lens.data_ptr(), gy.data_ptr(), B, N,
-                                                      ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    _lib.check(taco.lib.wg_stft_mel_backward(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, g.data_ptr(),
+                                             ctx.lens.data_ptr() if ctx.lens is not None else None, gy.data_ptr(), B, N,
+                                             ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     return None, gy, None
 
 
@@ -178,22 +170,24 @@ class TacotronSTFT(torch.nn.Module):
     y = y.to(self.device, torch.float32).contiguous()
     return self._mel(y)
 
-  def _mel(self, y: torch.Tensor) -> torch.Tensor:
-    """wg_stft_mel on contiguous fp32 audio [B, N] on the module's device; no graph."""
+  def _mel(self, y: torch.Tensor, lens_dev=None) -> torch.Tensor:
+    """wg_stft_mel on contiguous fp32 audio [B, N] on the module's device, with the device copy of the lengths
+    (int32 [B]) of a ragged batch or None; no graph."""
     B, N = y.shape
     nbytes = self.lib.wg_stft_mel_workspace_bytes(self._h, B, N)
     if nbytes == 0:
       raise _lib.WgError(f"mel front-end: audio of {N} samples is too short (reflect padding needs > 512)")
     F_ = N // 256 + 1
-    out = torch.empty((B, self.n_mel_channels, F_), dtype=torch.float32, device=self.device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-    stream = torch.cuda.current_stream(self.device).cuda_stream
+    out = torch.empty((B, self.n_mel_channels, F_), dtype=torch.float32, device=y.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
+    stream = torch.cuda.current_stream(y.device).cuda_stream
     _lib.check(self.lib.wg_stft_mel(self._h, self.mel_basis.data_ptr(), self.n_mel_channels, y.data_ptr(),
-                                    out.data_ptr(), B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+                                    lens_dev.data_ptr() if lens_dev is not None else None, out.data_ptr(), B, N,
+                                    ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
     return out
 
   def mel_spectrogram_ragged(self, wavs):
-    """``mel_spectrogram`` of several utterances of different lengths in one upload and one ``wg_stft_mel_ragged`` call.
+    """``mel_spectrogram`` of several utterances of different lengths in one upload and one ``wg_stft_mel`` call.
 
     ``wavs``: 1-D float32 CPU tensors in [-1, 1], each longer than 512 samples.  Returns ``(mel, frames)``: ``mel``
     [B, n_mel_channels, Tmax] on the module's device, ``frames[b] = len(wavs[b]) // 256 + 1``; ``mel[b, :, :frames[b]]``
@@ -223,14 +217,8 @@ class TacotronSTFT(torch.nn.Module):
       audio[b, :lens[b]] = w
     host[4 * B * N:].view(torch.int32).copy_(torch.tensor(lens, dtype=torch.int32))
     dev = host.to(self.device)
-    y, lens_dev = dev[:4 * B * N], dev[4 * B * N:]
-    out = torch.empty((B, self.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=self.device)
-    ws = torch.empty(self.lib.wg_stft_mel_workspace_bytes(self._h, B, N), dtype=torch.uint8, device=self.device)
-    stream = torch.cuda.current_stream(self.device).cuda_stream
-    _lib.check(self.lib.wg_stft_mel_ragged(self._h, self.mel_basis.data_ptr(), self.n_mel_channels, y.data_ptr(),
-                                           lens_dev.data_ptr(), out.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
-                                           C.c_void_p(stream)))
-    return out, [n // 256 + 1 for n in lens], y.view(torch.float32).view(B, N), lens_dev.view(torch.int32)
+    y, lens_dev = dev[:4 * B * N].view(torch.float32).view(B, N), dev[4 * B * N:].view(torch.int32)
+    return self._mel(y, lens_dev), [n // 256 + 1 for n in lens], y, lens_dev
 
   def mel_spectrogram_ragged_device(self, audio: torch.Tensor, lens):
     """``mel_spectrogram_ragged`` of audio that is on the device already (synthesised audio on its way to the metrics).
@@ -253,13 +241,7 @@ class TacotronSTFT(torch.nn.Module):
       raise _lib.WgError(f"mel front-end: lengths in (512, {N}] expected (reflect padding needs > 512), got {lens}")
     audio = audio.contiguous()
     both = torch.tensor([lens, [n // 256 + 1 for n in lens]], dtype=torch.int32).to(audio.device)
-    out = torch.empty((B, self.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=audio.device)
-    ws = torch.empty(self.lib.wg_stft_mel_workspace_bytes(self._h, B, N), dtype=torch.uint8, device=audio.device)
-    stream = torch.cuda.current_stream(audio.device).cuda_stream
-    _lib.check(self.lib.wg_stft_mel_ragged(self._h, self.mel_basis.data_ptr(), self.n_mel_channels, audio.data_ptr(),
-                                           both[0].data_ptr(), out.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
-                                           C.c_void_p(stream)))
-    return out, [n // 256 + 1 for n in lens], both[1]
+    return self._mel(audio, both[0]), [n // 256 + 1 for n in lens], both[1]
 
   def mel_spectrogram_differentiable(self, y: torch.Tensor, lengths=None) -> torch.Tensor:
     """``mel_spectrogram(y)`` with an autograd graph back to ``y`` (taco_stft.py:84-104 without the detach at :99).
