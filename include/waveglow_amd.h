@@ -220,6 +220,37 @@ int wg_stft_denoise(wg_stft* h, const float* audio, const int32_t* lens, const f
                     float* audio_out, float* mag0_out, int32_t B, int32_t n_samples, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* Denoiser with an audio gradient, Denoiser.forward_differentiable (denoiser.py:51-57 under autograd: stft.py:135-198).
+ * Same arguments and n_samples rule as wg_stft_denoise (audio_out is required, there is no mag0_out), with one typed
+ * fp32 device buffer `state` of wg_stft_denoise_grad_workspace_bytes in place of the untyped workspace: it holds the
+ * spectrum that lives from the forward to its backward, and in front of it the planes either call fills for itself.
+ * wg_stft_denoise_forward_saved: audio_out bit-identical to wg_stft_denoise; keeps the raw (re, im) of the forward
+ *   transform in `state` for the backward.
+ * wg_stft_denoise_backward: g_out [B][n_samples] fp32 device = d loss / d audio_out -> audio_grad_out [B][n_samples] =
+ *   d loss / d audio, through the crop and the window-sum-square normalisation (stft.py:175-196), the transposed inverse
+ *   transform (stft.py:169-173), the spectral subtraction (denoiser.py:54-55), the conv-STFT and the reflect padding
+ *   (stft.py:141-153).  Per (bin, frame), with c = strength * bias_mag[bin]: no gradient where |X| = 0 (never NaN) and
+ *   where |X| - c < 0 (the clamp passes its bound).  phase_grad != 0: the derivative of what the forward computes,
+ *   max(|X| - c, 0) X / |X|.  phase_grad = 0: what the reference's own autograd gives, whose STFT.transform detaches the
+ *   phase (stft.py:160-161): g X = (Re(conj(X) g Y) / |X|^2) X.  bias_mag and strength are constants: pass the forward's.
+ *   bias_mag null => no subtraction.  Reads the `state` of a forward_saved call with the same B and n_samples; leaves
+ *   that call's saved state intact, so it may run more than once.
+ * With `lens` (as in wg_stft_denoise: device [B], multiples of 256 in [1024, n_samples], anything else counts as 0;
+ *   read by the kernels only; n_samples the row pitch): g_out at and behind lens[b] is not read;
+ *   audio_grad_out[b][:lens[b]] is bit for bit the backward of that utterance alone with a null lens,
+ *   audio_grad_out[b][lens[b]:] = 0.  Pass the backward the lens of its forward.  lens == NULL: every row has n_samples.
+ * One `state` of wg_stft_denoise_grad_workspace_bytes serves both; what it holds before forward_saved does not matter.
+ *   The saved spectrum [B][1056][Fs] is its tail of (bytes - B * 4096) / 2 bytes; the rest ([B][1056][Fs] for the
+ *   recombined spectrum, then d (re, im); [B][1024] edges) each call zeroes for itself, so the caller may use it between
+ *   the two calls.  Enqueue-only. */
+size_t wg_stft_denoise_grad_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples);
+int wg_stft_denoise_forward_saved(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag,
+                                  float strength, float* audio_out, int32_t B, int32_t n_samples, float* state,
+                                  size_t state_bytes, void* stream);
+int wg_stft_denoise_backward(wg_stft* h, const float* g_out, const int32_t* lens, const float* bias_mag, float strength,
+                             int32_t phase_grad, float* audio_grad_out, int32_t B, int32_t n_samples, float* state,
+                             size_t state_bytes, void* stream);
+
 /* Mel front-end, TacotronSTFT.mel_spectrogram (src/waveglow/taco_stft.py:84-104): STFT magnitudes (reflect padding,
  * stft.py:141-152) x mel filterbank -> log(clamp(., 1e-5)).  audio [B][n_samples] fp32 device (any n_samples > 512),
  * mel_basis [n_mel][513] fp32 DEVICE, mel_out [B][n_mel][n_samples/256 + 1] fp32 device.  Enqueue-only.

@@ -122,6 +122,11 @@ SIGNATURES = {
   "wg_stft_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
   "wg_stft_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                 C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_denoise_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
+  "wg_stft_denoise_forward_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                              C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+  "wg_stft_denoise_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
+                                         C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
   "wg_stft_mel_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
   "wg_stft_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                             C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -8,6 +8,9 @@
 // with the forward basis, and reflect_fold_kernel adds the reflect-padded edges back onto the audio gradient.
 // With per-utterance lengths (a non-null lens) the three take the utterance's own frames and samples: d (re, im)
 // behind its frames stays zero, the interior is stored up to its length, the edges fold about its own last sample.
+// Denoiser gradients (Denoiser.forward_differentiable): stft_kernel<true> also keeps the raw (re, im), denoise_bwd_kernel
+// turns d audio_out into d (re, im) (transposed istft + the epilogue's derivative), and the mel gradient's
+// istft_kernel<true> + reflect_fold_kernel take that back to the audio.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -32,6 +35,8 @@ __device__ __forceinline__ int ragged_len(const int* lens, int b, int pitch, int
 }
 __device__ __forceinline__ int ragged_frames(int n) { return n ? n / kHop + 1 : 0; }
 
+// kRaw = true (wg_stft_denoise_forward_saved): the same kernel also keeps (re, im) as the GEMM gave them in a.raw
+template <bool kRaw>
 __global__ void __launch_bounds__(512) stft_kernel(const StftArgs a) {
   __shared__ float seg[8960 + 40];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -87,7 +92,12 @@ __global__ void __launch_bounds__(512) stft_kernel(const StftArgs a) {
           if (a.mag0 && f == 0) a.mag0[(size_t)b * kCut + bin] = mag;
           if (a.mag) a.mag[((size_t)b * kCut + bin) * a.F + f] = mag;
           if (!a.rec) continue;
-          if (a.bias) {                                 // denoiser.py:54-55, recombined with the original phase
+          if (kRaw) {
+            float* wp = a.raw + ((size_t)b * kRows + row0 + 2 * e) * a.Fs + 3 + f;
+            wp[0] = re;
+            wp[a.Fs] = im;
+          }
+          if (a.bias) {                                // denoiser.py:54-55, recombined with the original phase
             const float md = fmaxf(mag - a.bias[bin] * a.strength, 0.0f);
             const float sc = mag > 0.0f ? md / mag : 0.0f;
             im = mag > 0.0f ? im * sc : 0.0f;
@@ -97,6 +107,106 @@ __global__ void __launch_bounds__(512) stft_kernel(const StftArgs a) {
           rp[0] = re;
           rp[a.Fs] = im;
         }
+      }
+    }
+  }
+}
+
+// Backward of istft_kernel<false> and of stft_kernel's denoiser epilogue in one GEMM of stft_kernel's shape:
+//   gfull[n] = g[n - 512] 4 / ws(n) inside the utterance (4 alone where ws <= tiny), 0 in the cropped margins: the
+//     transpose of the crop and the window-sum-square normalisation, so zero padding where the forward reflects;
+//   gY[c][f] = sum_t inv[c][t] gfull[256 f + t]: a conv-STFT of gfull with the INVERSE basis (the transposed istft);
+//   epilogue per (bin, frame) with the forward's raw (re, im), c = strength bias[bin], u = (re, im) / mag:
+//     0 where mag == 0 and where mag - c < 0 (torch's clamp passes its bound);
+//     phase_grad:  gX = ((mag - c) / mag) gY + (c / mag) (u . gY) u   (the derivative of max(mag - c, 0) X / mag)
+//     otherwise:   gX = (u . gY) u            (the phase is a constant, as stft.py:160-161 detaches it)
+// grid (ceil(F/32), B); one owner per gX cell, fixed fma order, no atomics.  gX comes zeroed: columns behind F, the
+// pad rows and the tiles behind a shorter utterance are not written.
+__global__ void __launch_bounds__(512) denoise_bwd_kernel(const DenoiseBwdArgs a) {
+  __shared__ float seg[8960 + 40];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int f0 = blockIdx.x * 32, b = blockIdx.y;
+  const float* g = a.g + (size_t)b * a.N;
+  int N = a.N, F = a.F;                                 // this utterance's samples and frames; a.N / a.F are the pitches
+  if (a.lens) {
+    N = ragged_len(a.lens, b, a.N, kFL, kHop - 1);
+    F = ragged_frames(N);
+    if (f0 >= F) return;                                // tile wholly behind the utterance: its columns stay zero
+  }
+  for (int i = tid; i < 8960; i += 512) {
+    const int n = f0 * kHop + i;                        // position in the un-cropped inverse transform
+    const int o = n - kFL / 2;
+    float v = 0.0f;
+    if (o >= 0 && o < N) {                              // g behind the utterance is never read
+      const int q = n / kHop, r = n % kHop;
+      float ws = 0.0f;                                  // window_sumsquare at n, summed as istft_kernel sums it
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int fr = q - jj;
+        if (fr >= 0 && fr < F) ws += a.win_sq[r + kHop * jj];
+      }
+      v = g[o] * (float)(kFL / kHop);
+      if (ws > 1.17549435e-38f) v /= ws;                // tiny(float32)
+    }
+    seg[seg_idx(i)] = v;
+  }
+  __syncthreads();
+  constexpr int TPWV = 5;                               // M tiles per wave (wave w: w, w+8, ...; 33 tiles)
+  f32x16 acc[TPWV];
+#pragma unroll
+  for (int t = 0; t < TPWV; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+  const int col = lane & 31, kk = lane >> 5;
+  const float* ap = a.invA + lane;
+  for (int ks = 0; ks < kFL / 2; ++ks) {
+    const float bv = seg[seg_idx(col * kHop + 2 * ks + kk)];
+#pragma unroll
+    for (int t = 0; t < TPWV; ++t) {
+      const int mt = wave + 8 * t;
+      if (mt < kMT) {
+        const float av = ap[((size_t)mt * (kFL / 2) + ks) * 64];
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  const int f = f0 + col;
+#pragma unroll
+  for (int t = 0; t < TPWV; ++t) {
+    const int mt = wave + 8 * t;
+    if (mt >= kMT) continue;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int row0 = mt * 32 + 8 * gq + 4 * kk;       // rows row0..row0+3 = (re, im) of bins row0/2, row0/2+1
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int bin = row0 / 2 + e;
+        if (bin >= kCut || f >= F) continue;
+        const float gre = acc[t][4 * gq + 2 * e], gim = acc[t][4 * gq + 2 * e + 1];
+        const size_t i = ((size_t)b * kRows + row0 + 2 * e) * a.Fs + 3 + f;
+        const float re = a.raw[i], im = a.raw[i + a.Fs];
+        const float mag = sqrtf(re * re + im * im);     // the forward's own magnitude and clamp decision
+        float c = 0.0f, d = mag;
+        if (a.bias) {
+          c = a.bias[bin] * a.strength;
+          d = mag - a.bias[bin] * a.strength;
+        }
+        float xr = 0.0f, xi = 0.0f;
+        if (mag > 0.0f && d >= 0.0f) {
+          const float ur = re / mag, ui = im / mag;
+          const float dn = ur * gre + ui * gim;
+          if (a.phase_grad) {
+            const float sc = d / mag, tc = (c / mag) * dn;
+            xr = sc * gre + tc * ur;
+            xi = sc * gim + tc * ui;
+          } else {
+            xr = dn * ur;
+            xi = dn * ui;
+          }
+        }
+        a.gX[i] = xr;
+        a.gX[i + a.Fs] = xi;
       }
     }
   }
@@ -298,7 +408,16 @@ hipError_t launch_mel(const MelArgs& a, int B, hipStream_t s) {
 }
 
 hipError_t launch_stft(const StftArgs& a, int B, hipStream_t s) {
-  hipLaunchKernelGGL(stft_kernel, dim3((a.F + 31) / 32, B), dim3(512), 0, s, a);
+  hipLaunchKernelGGL(stft_kernel<false>, dim3((a.F + 31) / 32, B), dim3(512), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_stft_saved(const StftArgs& a, int B, hipStream_t s) {
+  if (!a.rec || !a.raw) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(stft_kernel<true>, dim3((a.F + 31) / 32, B), dim3(512), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_denoise_bwd(const DenoiseBwdArgs& a, int B, hipStream_t s) {
+  hipLaunchKernelGGL(denoise_bwd_kernel, dim3((a.F + 31) / 32, B), dim3(512), 0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_istft(const IstftArgs& a, int B, hipStream_t s) {

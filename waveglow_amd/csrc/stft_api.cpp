@@ -8,6 +8,7 @@ struct wg_stft {
   int device;
   float *d_fwdA = nullptr, *d_invA = nullptr, *d_win = nullptr;
   float* d_fwdT = nullptr;   // forward basis in the inverse's polyphase pack: A operand of the transposed conv-STFT
+  float* d_invF = nullptr;   // inverse basis in the forward's pack: A operand of the transposed inverse STFT
 };
 
 extern "C" {
@@ -20,12 +21,15 @@ int wg_stft_create(const float* fwd_basis, const float* inv_basis, const float* 
   // basis row c of the library = interleaved (re_k, im_k): c = 2k -> reference row k, c = 2k+1 -> row 513 + k
   auto ref_row = [](int c) { return (c & 1) ? kCut + (c >> 1) : (c >> 1); };
   std::vector<float> fa((size_t)(kRows / 32) * (kFL / 2) * 64, 0.f), ia((size_t)8 * 4 * (kRows / 2) * 64, 0.f);
-  std::vector<float> ft(ia.size(), 0.f);
+  std::vector<float> ft(ia.size(), 0.f), iv(fa.size(), 0.f);
   for (int mt = 0; mt < kRows / 32; ++mt)
     for (int ks = 0; ks < kFL / 2; ++ks)
       for (int lane = 0; lane < 64; ++lane) {
         const int c = mt * 32 + (lane & 31), k = 2 * ks + (lane >> 5);
-        if (c < 2 * kCut) fa[((size_t)mt * (kFL / 2) + ks) * 64 + lane] = fwd_basis[(size_t)ref_row(c) * kFL + k];
+        if (c < 2 * kCut) {
+          fa[((size_t)mt * (kFL / 2) + ks) * 64 + lane] = fwd_basis[(size_t)ref_row(c) * kFL + k];
+          iv[((size_t)mt * (kFL / 2) + ks) * 64 + lane] = inv_basis[(size_t)ref_row(c) * kFL + k];
+        }
       }
   for (int w = 0; w < 8; ++w)
     for (int j = 0; j < 4; ++j)
@@ -47,10 +51,12 @@ int wg_stft_create(const float* fwd_basis, const float* inv_basis, const float* 
   HIP_TRY(hipMalloc((void**)&h->d_invA, ia.size() * 4));
   HIP_TRY(hipMalloc((void**)&h->d_win, kFL * 4));
   HIP_TRY(hipMalloc((void**)&h->d_fwdT, ft.size() * 4));
+  HIP_TRY(hipMalloc((void**)&h->d_invF, iv.size() * 4));
   HIP_TRY(hipMemcpy(h->d_fwdA, fa.data(), fa.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->d_invA, ia.data(), ia.size() * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->d_win, win_sq, kFL * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->d_fwdT, ft.data(), ft.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d_invF, iv.data(), iv.size() * 4, hipMemcpyHostToDevice));
   *out = h;
   return WG_OK;
 }
@@ -61,6 +67,7 @@ int wg_stft_destroy(wg_stft* h) {
   if (h->d_invA) (void)hipFree(h->d_invA);
   if (h->d_win) (void)hipFree(h->d_win);
   if (h->d_fwdT) (void)hipFree(h->d_fwdT);
+  if (h->d_invF) (void)hipFree(h->d_invF);
   delete h;
   return WG_OK;
 }
@@ -92,6 +99,74 @@ int wg_stft_denoise(wg_stft* h, const float* audio, const int32_t* lens, const f
     IstftArgs b{(const float*)workspace, h->d_invA, h->d_win, audio_out, n_samples, F, Fs, nullptr, lens};
     HIP_TRY(launch_istft(b, B, s));
   }
+  return WG_OK;
+}
+
+// Denoiser-gradient state buffer, in floats: [rec, then gX | edge | raw].  rec (the recombined spectrum the forward hands
+// its inverse) and gX (the backward's d (re, im)) share the first plane, each zeroed by the call that fills it; edge is
+// [B][1024]; raw, the (re, im) of the forward STFT, is the one part a backward reads and needs no zeroing: only cells of
+// an utterance's own bins and frames are ever read.
+struct DenoiseGradLayout {
+  int F, Fs;
+  size_t plane, edge, raw, total;          // float offsets; total in floats
+};
+static DenoiseGradLayout denoise_grad_layout(int B, int n_samples) {
+  DenoiseGradLayout L;
+  L.F = n_samples / kHop + 1;
+  L.Fs = frames_padded(L.F);
+  L.plane = 0;
+  L.edge = (size_t)B * kRows * L.Fs;
+  L.raw = L.edge + (size_t)B * kFL;
+  L.total = L.raw + (size_t)B * kRows * L.Fs;
+  return L;
+}
+
+size_t wg_stft_denoise_grad_workspace_bytes(const wg_stft* h, int32_t B, int32_t n_samples) {
+  if (!h || B < 1 || n_samples < kFL || n_samples % kHop) return 0;
+  return denoise_grad_layout(B, n_samples).total * 4;
+}
+
+static int denoise_grad_check(wg_stft* h, const void* in, const void* out, int32_t B, int32_t n_samples, float* state,
+                              size_t state_bytes) {
+  if (!h || !in || !out || !state) return fail(WG_ERR_INVALID, "null argument");
+  const size_t need = wg_stft_denoise_grad_workspace_bytes(h, B, n_samples);
+  if (!need) return fail(WG_ERR_INVALID, "n_samples must be a multiple of 256 and >= 1024");
+  if (state_bytes < need) return fail(WG_ERR_WORKSPACE, "denoiser gradient state buffer too small");
+  return WG_OK;
+}
+
+// lens as in wg_stft_denoise.
+int wg_stft_denoise_forward_saved(wg_stft* h, const float* audio, const int32_t* lens, const float* bias_mag,
+                                  float strength, float* audio_out, int32_t B, int32_t n_samples, float* state,
+                                  size_t state_bytes, void* stream) {
+  const int rc = denoise_grad_check(h, audio, audio_out, B, n_samples, state, state_bytes);
+  if (rc != WG_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const DenoiseGradLayout L = denoise_grad_layout(B, n_samples);
+  float* ws = state;
+  HIP_TRY(hipMemsetAsync(ws + L.plane, 0, (L.edge - L.plane) * 4, s));   // zero lead/tail columns and pad rows of rec
+  StftArgs a{audio, h->d_fwdA, bias_mag, strength, ws + L.plane, nullptr, n_samples, L.F, L.Fs, nullptr,
+             lens, kFL, kHop - 1, ws + L.raw};
+  HIP_TRY(launch_stft_saved(a, B, s));
+  IstftArgs b{ws + L.plane, h->d_invA, h->d_win, audio_out, n_samples, L.F, L.Fs, nullptr, lens};
+  HIP_TRY(launch_istft(b, B, s));
+  return WG_OK;
+}
+
+int wg_stft_denoise_backward(wg_stft* h, const float* g_out, const int32_t* lens, const float* bias_mag, float strength,
+                             int32_t phase_grad, float* audio_grad_out, int32_t B, int32_t n_samples, float* state,
+                             size_t state_bytes, void* stream) {
+  const int rc = denoise_grad_check(h, g_out, audio_grad_out, B, n_samples, state, state_bytes);
+  if (rc != WG_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const DenoiseGradLayout L = denoise_grad_layout(B, n_samples);
+  float* ws = state;
+  HIP_TRY(hipMemsetAsync(ws + L.plane, 0, (L.raw - L.plane) * 4, s));    // gX pads and uncovered edge positions are zero
+  DenoiseBwdArgs d{g_out, h->d_invF, h->d_win, bias_mag, strength, ws + L.raw, ws + L.plane, n_samples, L.F, L.Fs,
+                   phase_grad ? 1 : 0, lens};
+  HIP_TRY(launch_denoise_bwd(d, B, s));
+  IstftArgs t{ws + L.plane, h->d_fwdT, nullptr, audio_grad_out, n_samples, L.F, L.Fs, ws + L.edge, lens};
+  HIP_TRY(launch_stft_grad(t, B, s));
   return WG_OK;
 }
 

@@ -20,6 +20,7 @@ struct StftArgs {
   float* mag;              // optional [B][513][F]: all magnitudes (mel front-end); rec may then be null
   const int* lens;         // ragged batch: device [B] sample counts (N is then the row pitch, F the frames of N) or null
   int min_len, len_mask;   // ragged batch: a length < min_len, > N or with (length & len_mask) != 0 counts as 0
+  float* raw;              // stft_kernel<true> only: [B][1056][Fs] (re, im) before the denoiser epilogue, cells of rec
 };
 struct MelArgs {
   const float* mag;        // [B][513][F]
@@ -52,7 +53,24 @@ struct MelBwdArgs {
   int N;                   // ragged batch: row pitch of the audio, the upper limit of a length
 };
 
+// Backward of the denoiser's spectral part (wg_stft_denoise_backward): d audio_out -> d (re, im) of the forward STFT.
+struct DenoiseBwdArgs {
+  const float* g;          // [B][N]  d loss / d audio_out
+  const float* invA;       // inverse basis as packed A fragments [33 mtile][512 kstep][64 lanes] (the layout of fwdA)
+  const float* win_sq;     // [1024]
+  const float* bias;       // [513] or null
+  float strength;
+  const float* raw;        // [B][1056][Fs]  raw (re, im) of the forward
+  float* gX;               // [B][1056][Fs]  d (re, im); pad rows / columns zero
+  int N, F, Fs;
+  int phase_grad;          // 1: the derivative of the forward; 0: the reference's graph (phase detached, stft.py:160-161)
+  const int* lens;         // ragged batch: device [B] sample counts (g behind an utterance is unread, gX behind its
+                           // frames stays zero) or null
+};
+
 hipError_t launch_stft(const StftArgs& a, int B, hipStream_t s);
+hipError_t launch_stft_saved(const StftArgs& a, int B, hipStream_t s);
+hipError_t launch_denoise_bwd(const DenoiseBwdArgs& a, int B, hipStream_t s);
 hipError_t launch_mel(const MelArgs& a, int B, hipStream_t s);
 hipError_t launch_istft(const IstftArgs& a, int B, hipStream_t s);
 hipError_t launch_mel_bwd(const MelBwdArgs& a, int B, hipStream_t s);

@@ -6,10 +6,15 @@ to the library once.  librosa's ``pad_center`` is restated (the reference import
 post-filter is pinned against ``oracle/stft_oracle.py`` (numpy fp64 restatement) and against outputs of the reference's own
 ``STFT`` and ``Denoiser`` classes, run with functional stand-ins for the librosa names (tests/golden/stft_ref.npz,
 tests/test_gpu_stft_ref.py; ``stft_bases`` row by row in tests/test_stft_ref_cpu.py).  No torch/CPU fallback.
+
+``Denoiser.forward_differentiable`` is ``forward`` with an autograd graph back to the audio (``wg_stft_denoise_forward_saved``
+/ ``wg_stft_denoise_backward``), so that a waveform loss can be computed on the signal a listener hears.  The bias is a
+constant of that graph; ``Denoiser.refresh_bias`` recomputes it after the vocoder's weights have moved.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -35,6 +40,68 @@ def stft_bases(filter_length=1024, hop_length=256, win_length=1024, window="hann
           np.ascontiguousarray(win ** 2, dtype=np.float32))
 
 
+def _host_lengths(lengths, B: int, N: int):
+  """``lengths`` (a list, a tuple or a 1-D integer CPU tensor) as a list of B ints, each a multiple of 256 in [1024, N]:
+  the rule of ``Denoiser.run_ragged``, with WgError for everything else.  Pure host code."""
+  if isinstance(lengths, torch.Tensor):
+    if lengths.device.type != "cpu" or lengths.dim() != 1 or lengths.dtype.is_floating_point or \
+        lengths.dtype.is_complex or lengths.dtype == torch.bool:
+      raise _lib.WgError("denoiser: lengths must be a list, a tuple, a 1-D integer CPU tensor or an int32 tensor on the device")
+    lengths = lengths.tolist()
+  elif not isinstance(lengths, (list, tuple)):
+    raise _lib.WgError(f"denoiser: lengths must be a list, a tuple or a tensor, got {type(lengths).__name__}")
+  if len(lengths) != B:
+    raise _lib.WgError(f"denoiser: {len(lengths)} lengths for a batch of {B}")
+  out = []
+  for n in lengths:
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+      raise _lib.WgError(f"denoiser: length {n!r} is not an integer")
+    if n < 1024 or n % 256 or n > N:
+      raise _lib.WgError(f"denoiser: unsupported utterance length {n} (multiple of 256, >= 1024, <= {N})")
+    out.append(int(n))
+  return out
+
+
+class _DenoiseFn(torch.autograd.Function):
+  """Inputs: the Denoiser, the audio [B, N], the strength, the device copy of the lengths (int32 [B]) or None, and the
+  phase mode.  The forward keeps the library's workspace (the raw spectrum) and a private copy of the bias on ctx; the
+  backward writes its d (re, im) to another part of that workspace, so the saved state survives and a second backward
+  under retain_graph gives the same gradient."""
+
+  @staticmethod
+  def forward(ctx, den, audio, strength, lens, phase_grad):
+    audio = audio.contiguous()
+    B, N = audio.shape
+    lib = den.lib
+    nbytes = lib.wg_stft_denoise_grad_workspace_bytes(den._h, B, N)
+    if nbytes == 0:
+      raise _lib.WgError(f"denoiser: unsupported audio length {N} (multiple of 256, >= 1024)")
+    bias = den.bias_spec.detach().reshape(-1).clone()          # refresh_bias writes bias_spec in place
+    out = torch.empty_like(audio)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
+    stream = torch.cuda.current_stream(audio.device).cuda_stream
+    _lib.check(lib.wg_stft_denoise_forward_saved(den._h, audio.data_ptr(), lens.data_ptr() if lens is not None else None,
+                                                 bias.data_ptr(), strength, out.data_ptr(), B, N, ws.data_ptr(),
+                                                 ws.numel(), C.c_void_p(stream)))
+    ctx.den, ctx.ws, ctx.bias, ctx.lens = den, ws, bias, lens
+    ctx.args = (B, N, strength, 1 if phase_grad else 0)
+    return out[:, None, :]
+
+  @staticmethod
+  @torch.autograd.function.once_differentiable
+  def backward(ctx, g_out):
+    den, ws = ctx.den, ctx.ws
+    B, N, strength, phase_grad = ctx.args
+    g = g_out.to(torch.float32).reshape(B, N).contiguous()
+    gx = torch.empty((B, N), dtype=torch.float32, device=ws.device)
+    stream = torch.cuda.current_stream(ws.device).cuda_stream
+    _lib.check(den.lib.wg_stft_denoise_backward(den._h, g.data_ptr(),
+                                                ctx.lens.data_ptr() if ctx.lens is not None else None,
+                                                ctx.bias.data_ptr(), strength, phase_grad, gx.data_ptr(), B, N,
+                                                ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    return None, gx, None, None, None
+
+
 class Denoiser(torch.nn.Module):
   """Removes model bias from audio produced with waveglow (denoiser.py:14-57)."""
 
@@ -48,18 +115,35 @@ class Denoiser(torch.nn.Module):
     self._h = C.c_void_p()
     _lib.check(self.lib.wg_stft_create(fwd.ctypes.data, inv.ctypes.data, wsq.ctypes.data, hparams.filter_length,
                                        hparams.hop_length, _lib.device_index(device), C.byref(self._h)))
+    self.device = device
+    self._n_mel, self._n_bins = hparams.n_mel_channels, hparams.filter_length // 2 + 1
+    self.register_buffer("bias_spec", self._bias(waveglow, mode))      # [1, 513, 1] like bias_spec[:, :, 0][:, :, None]
+
+  def _bias(self, waveglow, mode: str):
+    """denoiser.py:38-49: |STFT| of frame 0 of what ``waveglow`` makes of an empty (or random) mel at sigma 0."""
     w = waveglow.upsample.weight
     if mode == "zeros":
-      mel = torch.zeros((1, hparams.n_mel_channels, BIAS_MEL_LENGTH), dtype=w.dtype, device=w.device)
+      mel = torch.zeros((1, self._n_mel, BIAS_MEL_LENGTH), dtype=w.dtype, device=w.device)
     elif mode == "normal":
-      mel = torch.randn((1, hparams.n_mel_channels, BIAS_MEL_LENGTH), dtype=w.dtype, device=w.device)
+      mel = torch.randn((1, self._n_mel, BIAS_MEL_LENGTH), dtype=w.dtype, device=w.device)
     else:
       raise Exception(f"Mode {mode} if not supported")
     with torch.no_grad():
       bias_audio = waveglow.infer(mel, sigma=0.0).float()              # denoiser.py:45-47 (the HIP hot path)
-      mag0 = torch.empty((1, hparams.filter_length // 2 + 1), dtype=torch.float32, device=bias_audio.device)
+      mag0 = torch.empty((1, self._n_bins), dtype=torch.float32, device=bias_audio.device)
       self._run(bias_audio, None, 0.0, None, mag0)
-    self.register_buffer("bias_spec", mag0[:, :, None])                # [1, 513, 1] like bias_spec[:, :, 0][:, :, None]
+    return mag0[:, :, None]
+
+  def refresh_bias(self, waveglow, mode: str = "zeros"):
+    """Recomputes ``bias_spec`` in place from ``waveglow``'s CURRENT weights, exactly as ``__init__`` computed it, under
+    no-grad.  The bias is measured once at construction; after the vocoder has been fine-tuned (``weight_grads=True``)
+    it describes weights that no longer exist until this is called.  ``waveglow.infer`` after a weight change pays the
+    engine's re-finalisation of the weights.  Graphs of earlier ``forward_differentiable`` calls keep the bias they were
+    built with.  Returns ``bias_spec``."""
+    new = self._bias(waveglow, mode)
+    with torch.no_grad():
+      self.bias_spec.copy_(new.to(self.bias_spec.device))
+    return self.bias_spec
 
   def __del__(self):
     try:
@@ -97,6 +181,55 @@ class Denoiser(torch.nn.Module):
     else:
       lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
       self.run_ragged(audio, lengths, torch.tensor(lengths, dtype=torch.int32).to(audio.device), strength, out)
+    return out[:, None, :]
+
+  def grad_workspace_bytes(self, B: int, N: int) -> int:
+    """Bytes of device memory a ``forward_differentiable`` of audio [B, N] keeps alive until its backward has run (the
+    library's workspace; 513 more floats hold the bias).  0 for a shape the denoiser does not take."""
+    return int(self.lib.wg_stft_denoise_grad_workspace_bytes(self._h, int(B), int(N)))
+
+  def forward_differentiable(self, audio: torch.Tensor, strength: float, lengths=None, phase_grad: bool = True):
+    """``forward(audio, strength, lengths)`` with an autograd graph back to ``audio``: [B, N] fp32 on the module's device
+    -> [B, 1, N], ``torch.equal`` to ``forward``.  Enqueued on the current stream, nothing synchronised.
+
+    ``phase_grad=True``: the backward is the derivative of what the forward computes, ``max(|X| - c, 0) X / |X|`` with
+    ``c = strength * bias_spec`` per bin.  ``phase_grad=False``: the gradient the reference's own autograd gives, whose
+    ``STFT.transform`` detaches the phase (stft.py:160-161), so only the path through ``|X|`` is followed.  Both are 0
+    where ``|X| == 0`` (the reference gives NaN there) and where ``|X| - c < 0``.
+
+    ``lengths``: sample counts of a padded batch as in ``forward`` -- a list, a tuple or a CPU integer tensor, checked
+    here and uploaded in one small copy; or an int32 tensor [B] on the device, which is trusted (a count outside the
+    limits zeroes that row's output and gradient).  ``audio.grad[b, :lengths[b]]`` has the bits of the backward of that
+    utterance alone, ``audio.grad[b, lengths[b]:]`` is 0; audio and incoming gradient behind a length are never read.
+
+    ``strength`` and ``bias_spec`` are constants of the graph (no gradient; no graph from the bias to the vocoder's
+    weights).  Without grad mode, or when ``audio`` does not require grad, this is ``forward`` and nothing is saved.  No
+    CPU fallback and no double backward; other devices, dtypes, ranks and a non-finite strength raise WgError."""
+    if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda" or \
+        _lib.device_index(audio.device) != _lib.device_index(self.device):
+      raise _lib.WgError(f"forward_differentiable: audio must be on {self.device} (no CPU fallback)")
+    if audio.dtype != torch.float32:
+      raise _lib.WgError(f"forward_differentiable takes float32 audio, got {audio.dtype}")
+    if audio.dim() != 2:
+      raise _lib.WgError(f"forward_differentiable takes audio [B, N], got shape {tuple(audio.shape)}")
+    strength = float(strength)
+    if not math.isfinite(strength):
+      raise _lib.WgError(f"forward_differentiable: strength must be finite, got {strength}")
+    B, N = audio.shape
+    if self.grad_workspace_bytes(B, N) == 0:
+      raise _lib.WgError(f"denoiser: unsupported audio length {N} (multiple of 256, >= 1024)")
+    lens = None
+    if isinstance(lengths, torch.Tensor) and lengths.device.type == "cuda":
+      if lengths.dtype != torch.int32 or lengths.shape != (B,) or \
+          _lib.device_index(lengths.device) != _lib.device_index(self.device):
+        raise _lib.WgError(f"forward_differentiable: device lengths must be int32 [{B}] on {self.device}")
+      lens = lengths.contiguous()
+    elif lengths is not None:
+      lens = torch.tensor(_host_lengths(lengths, B, N), dtype=torch.int32).to(audio.device)
+    if torch.is_grad_enabled() and audio.requires_grad:
+      return _DenoiseFn.apply(self, audio, strength, lens, bool(phase_grad))
+    out = torch.empty_like(audio, memory_format=torch.contiguous_format)
+    self._run(audio.detach(), self.bias_spec.reshape(-1).contiguous(), strength, out, None, lens)
     return out[:, None, :]
 
   def run_ragged(self, audio, lengths, lengths_dev, strength, out):
