@@ -20,7 +20,7 @@ import numpy as np
 import torch
 from scipy.signal import get_window
 
-from . import _lib
+from . import _args, _lib
 
 BIAS_MEL_LENGTH = 88   # denoiser.py:11
 
@@ -40,26 +40,14 @@ def stft_bases(filter_length=1024, hop_length=256, win_length=1024, window="hann
           np.ascontiguousarray(win ** 2, dtype=np.float32))
 
 
-def _host_lengths(lengths, B: int, N: int):
-  """``lengths`` (a list, a tuple or a 1-D integer CPU tensor) as a list of B ints, each a multiple of 256 in [1024, N]:
-  the rule of ``Denoiser.run_ragged``, with WgError for everything else.  Pure host code."""
-  if isinstance(lengths, torch.Tensor):
-    if lengths.device.type != "cpu" or lengths.dim() != 1 or lengths.dtype.is_floating_point or \
-        lengths.dtype.is_complex or lengths.dtype == torch.bool:
-      raise _lib.WgError("denoiser: lengths must be a list, a tuple, a 1-D integer CPU tensor or an int32 tensor on the device")
-    lengths = lengths.tolist()
-  elif not isinstance(lengths, (list, tuple)):
-    raise _lib.WgError(f"denoiser: lengths must be a list, a tuple or a tensor, got {type(lengths).__name__}")
-  if len(lengths) != B:
-    raise _lib.WgError(f"denoiser: {len(lengths)} lengths for a batch of {B}")
-  out = []
-  for n in lengths:
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-      raise _lib.WgError(f"denoiser: length {n!r} is not an integer")
-    if n < 1024 or n % 256 or n > N:
-      raise _lib.WgError(f"denoiser: unsupported utterance length {n} (multiple of 256, >= 1024, <= {N})")
-    out.append(int(n))
-  return out
+def stft_handle(lib, hparams, device, window="hann") -> _args.Handle:
+  """The ``wg_stft`` handle of ``stft_bases(hparams.filter_length, hparams.hop_length, hparams.win_length, window)`` on
+  ``device``, with its owner: what the denoiser and the mel front-end both run on."""
+  fwd, inv, wsq = stft_bases(hparams.filter_length, hparams.hop_length, hparams.win_length, window)
+  h = _args.Handle(lib, "wg_stft_destroy")
+  _lib.check(lib.wg_stft_create(fwd.ctypes.data, inv.ctypes.data, wsq.ctypes.data, hparams.filter_length,
+                                hparams.hop_length, _lib.device_index(device), C.byref(h.value)))
+  return h
 
 
 class _DenoiseFn(torch.autograd.Function):
@@ -72,17 +60,14 @@ class _DenoiseFn(torch.autograd.Function):
   def forward(ctx, den, audio, strength, lens, phase_grad):
     audio = audio.contiguous()
     B, N = audio.shape
-    lib = den.lib
-    nbytes = lib.wg_stft_denoise_grad_workspace_bytes(den._h, B, N)
-    if nbytes == 0:
-      raise _lib.WgError(f"denoiser: unsupported audio length {N} (multiple of 256, >= 1024)")
+    h = den._h
+    ws = _args.workspace(den.lib.wg_stft_denoise_grad_workspace_bytes(h, B, N), audio.device,
+                         f"denoiser: audio length {N} (multiple of 256, >= 1024)")
     bias = den.bias_spec.detach().reshape(-1).clone()          # refresh_bias writes bias_spec in place
     out = torch.empty_like(audio)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
-    stream = torch.cuda.current_stream(audio.device).cuda_stream
-    _lib.check(lib.wg_stft_denoise_forward_saved(den._h, audio.data_ptr(), lens.data_ptr() if lens is not None else None,
-                                                 bias.data_ptr(), strength, out.data_ptr(), B, N, ws.data_ptr(),
-                                                 ws.numel(), C.c_void_p(stream)))
+    _lib.check(den.lib.wg_stft_denoise_forward_saved(h, _args.ptr(audio), _args.ptr(lens), _args.ptr(bias), strength,
+                                                     _args.ptr(out), B, N, _args.ptr(ws), ws.numel(),
+                                                     _args.stream(audio.device)))
     ctx.den, ctx.ws, ctx.bias, ctx.lens = den, ws, bias, lens
     ctx.args = (B, N, strength, 1 if phase_grad else 0)
     return out[:, None, :]
@@ -94,11 +79,9 @@ class _DenoiseFn(torch.autograd.Function):
     B, N, strength, phase_grad = ctx.args
     g = g_out.to(torch.float32).reshape(B, N).contiguous()
     gx = torch.empty((B, N), dtype=torch.float32, device=ws.device)
-    stream = torch.cuda.current_stream(ws.device).cuda_stream
-    _lib.check(den.lib.wg_stft_denoise_backward(den._h, g.data_ptr(),
-                                                ctx.lens.data_ptr() if ctx.lens is not None else None,
-                                                ctx.bias.data_ptr(), strength, phase_grad, gx.data_ptr(), B, N,
-                                                ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    _lib.check(den.lib.wg_stft_denoise_backward(den._h, _args.ptr(g), _args.ptr(ctx.lens), _args.ptr(ctx.bias),
+                                                strength, phase_grad, _args.ptr(gx), B, N, _args.ptr(ws), ws.numel(),
+                                                _args.stream(ws.device)))
     return None, gx, None, None, None
 
 
@@ -111,10 +94,8 @@ class Denoiser(torch.nn.Module):
     if device.type != "cuda":
       raise _lib.WgError("the denoiser runs on the GPU library only")
     self.lib = _lib.load()
-    fwd, inv, wsq = stft_bases(hparams.filter_length, hparams.hop_length, hparams.win_length)
-    self._h = C.c_void_p()
-    _lib.check(self.lib.wg_stft_create(fwd.ctypes.data, inv.ctypes.data, wsq.ctypes.data, hparams.filter_length,
-                                       hparams.hop_length, _lib.device_index(device), C.byref(self._h)))
+    self._owner = stft_handle(self.lib, hparams, device)
+    self._h = self._owner.value                # what every call takes; the owner releases it
     self.device = device
     self._n_mel, self._n_bins = hparams.n_mel_channels, hparams.filter_length // 2 + 1
     self.register_buffer("bias_spec", self._bias(waveglow, mode))      # [1, 513, 1] like bias_spec[:, :, 0][:, :, None]
@@ -145,42 +126,32 @@ class Denoiser(torch.nn.Module):
       self.bias_spec.copy_(new.to(self.bias_spec.device))
     return self.bias_spec
 
-  def __del__(self):
-    try:
-      if getattr(self, "_h", None):
-        self.lib.wg_stft_destroy(self._h)
-    except Exception:
-      pass
-
   def _run(self, audio, bias, strength, out, mag0, lengths_dev=None):
     """The one wg_stft_denoise call: fp32 ``audio`` [B, N], ``lengths_dev`` int32 [B] on the device or None."""
     audio = audio.contiguous()
     B, N = audio.shape
-    nbytes = self.lib.wg_stft_workspace_bytes(self._h, B, N)
-    if nbytes == 0:
-      raise _lib.WgError(f"denoiser: unsupported audio length {N} (multiple of 256, >= 1024)")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
-    stream = torch.cuda.current_stream(audio.device).cuda_stream
-    _lib.check(self.lib.wg_stft_denoise(self._h, audio.data_ptr(),
-                                        lengths_dev.data_ptr() if lengths_dev is not None else None,
-                                        bias.data_ptr() if bias is not None else None, float(strength),
-                                        out.data_ptr() if out is not None else None,
-                                        mag0.data_ptr() if mag0 is not None else None, B, N, ws.data_ptr(),
-                                        ws.numel(), C.c_void_p(stream)))
+    ws = _args.workspace(self.lib.wg_stft_workspace_bytes(self._h, B, N), audio.device,
+                         f"denoiser: audio length {N} (multiple of 256, >= 1024)")
+    _lib.check(self.lib.wg_stft_denoise(self._h, _args.ptr(audio), _args.ptr(lengths_dev), _args.ptr(bias),
+                                        float(strength), _args.ptr(out), _args.ptr(mag0), B, N, _args.ptr(ws), ws.numel(),
+                                        _args.stream(audio.device)))
+
+  def _lens(self, lengths, audio, device, allow_device=True):
+    """The one length check of the denoiser: B multiples of 256 in [1024, N] (``_args.counts``), as int32 on ``device``."""
+    B, N = audio.shape
+    return _args.counts("denoiser: lengths", lengths, B, 1024, N, device=device, multiple_of=256,
+                        allow_device=allow_device)[0]
 
   def forward(self, audio: torch.Tensor, strength: float, lengths=None):
     """denoiser.py:51-57; returns [B, 1, N] like the reference's conv_transpose1d output.
 
-    ``lengths`` (a list or an int tensor [B] of sample counts) makes the rows of ``audio`` [B, N] utterances of
+    ``lengths`` (B sample counts, see ``forward_differentiable``) makes the rows of ``audio`` [B, N] utterances of
     different lengths, denoised in ONE call: utterance b comes out bit for bit as ``forward(audio[b:b+1, :lengths[b]])``
     gives it, with zeros behind it.  Every length is a multiple of 256 in [1024, N], as for the call without lengths."""
     audio = audio.float()
     out = torch.empty_like(audio)
-    if lengths is None:
-      self._run(audio, self.bias_spec.reshape(-1).contiguous(), strength, out, None)
-    else:
-      lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-      self.run_ragged(audio, lengths, torch.tensor(lengths, dtype=torch.int32).to(audio.device), strength, out)
+    lens = None if lengths is None else self._lens(lengths, audio, audio.device)
+    self._run(audio, self.bias_spec.reshape(-1).contiguous(), strength, out, None, lens)
     return out[:, None, :]
 
   def grad_workspace_bytes(self, B: int, N: int) -> int:
@@ -197,35 +168,24 @@ class Denoiser(torch.nn.Module):
     ``STFT.transform`` detaches the phase (stft.py:160-161), so only the path through ``|X|`` is followed.  Both are 0
     where ``|X| == 0`` (the reference gives NaN there) and where ``|X| - c < 0``.
 
-    ``lengths``: sample counts of a padded batch as in ``forward`` -- a list, a tuple or a CPU integer tensor, checked
-    here and uploaded in one small copy; or an int32 tensor [B] on the device, which is trusted (a count outside the
-    limits zeroes that row's output and gradient).  ``audio.grad[b, :lengths[b]]`` has the bits of the backward of that
-    utterance alone, ``audio.grad[b, lengths[b]:]`` is 0; audio and incoming gradient behind a length are never read.
+    ``lengths``: B integers as ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an integer dtype; a
+    float or a bool entry raises WgError), or an int32 tensor ``[B]`` on the device, which is trusted and never read on
+    the host (a count outside the limits zeroes that row's output and gradient): the sample counts of a padded batch,
+    multiples of 256 in [1024, N], uploaded in one small copy.  ``audio.grad[b, :lengths[b]]`` has the bits of the
+    backward of that utterance alone, ``audio.grad[b, lengths[b]:]`` is 0; audio and incoming gradient behind a length
+    are never read.
 
     ``strength`` and ``bias_spec`` are constants of the graph (no gradient; no graph from the bias to the vocoder's
     weights).  Without grad mode, or when ``audio`` does not require grad, this is ``forward`` and nothing is saved.  No
     CPU fallback and no double backward; other devices, dtypes, ranks and a non-finite strength raise WgError."""
-    if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda" or \
-        _lib.device_index(audio.device) != _lib.device_index(self.device):
-      raise _lib.WgError(f"forward_differentiable: audio must be on {self.device} (no CPU fallback)")
-    if audio.dtype != torch.float32:
-      raise _lib.WgError(f"forward_differentiable takes float32 audio, got {audio.dtype}")
-    if audio.dim() != 2:
-      raise _lib.WgError(f"forward_differentiable takes audio [B, N], got shape {tuple(audio.shape)}")
+    _args.tensor("forward_differentiable: audio", audio, device=self.device, ndim=2)
     strength = float(strength)
     if not math.isfinite(strength):
       raise _lib.WgError(f"forward_differentiable: strength must be finite, got {strength}")
     B, N = audio.shape
     if self.grad_workspace_bytes(B, N) == 0:
       raise _lib.WgError(f"denoiser: unsupported audio length {N} (multiple of 256, >= 1024)")
-    lens = None
-    if isinstance(lengths, torch.Tensor) and lengths.device.type == "cuda":
-      if lengths.dtype != torch.int32 or lengths.shape != (B,) or \
-          _lib.device_index(lengths.device) != _lib.device_index(self.device):
-        raise _lib.WgError(f"forward_differentiable: device lengths must be int32 [{B}] on {self.device}")
-      lens = lengths.contiguous()
-    elif lengths is not None:
-      lens = torch.tensor(_host_lengths(lengths, B, N), dtype=torch.int32).to(audio.device)
+    lens = None if lengths is None else self._lens(lengths, audio, audio.device)
     if torch.is_grad_enabled() and audio.requires_grad:
       return _DenoiseFn.apply(self, audio, strength, lens, bool(phase_grad))
     out = torch.empty_like(audio, memory_format=torch.contiguous_format)
@@ -235,11 +195,5 @@ class Denoiser(torch.nn.Module):
   def run_ragged(self, audio, lengths, lengths_dev, strength, out):
     """One wg_stft_denoise call with lengths on fp32 ``audio`` [B, N] into ``out``; ``lengths`` is checked here on the host,
     ``lengths_dev`` is the same as an int32 tensor on the device (the library never reads it on the host)."""
-    audio = audio.contiguous()
-    B, N = audio.shape
-    if len(lengths) != B:
-      raise _lib.WgError(f"denoiser: {len(lengths)} lengths for a batch of {B}")
-    for n in lengths:
-      if n < 1024 or n % 256 or n > N:
-        raise _lib.WgError(f"denoiser: unsupported utterance length {n} (multiple of 256, >= 1024, <= {N})")
+    self._lens(lengths, audio, None, allow_device=False)
     self._run(audio, self.bias_spec, strength, out, None, lengths_dev)

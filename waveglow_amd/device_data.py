@@ -19,7 +19,7 @@ from typing import Iterator, List, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .audio import convert_wav
 from .taco_stft import FLOAT32_64_MAX_WAV, FLOAT32_64_MIN_WAV, TacotronSTFT
 
@@ -174,11 +174,9 @@ class DeviceWavPool:
       raise _lib.WgError(f"gather takes contiguous int32 picks [B, 2] on {self.device}")
     B = picks_dev.shape[0]
     out = torch.empty((B, segment_length), dtype=torch.float32, device=self.device)
-    stream = torch.cuda.current_stream(self.device).cuda_stream
-    _lib.check(_lib.load().wg_data_gather(self.pool.data_ptr(), self.dtype_code, self.elems, self.offsets.data_ptr(),
-                                          self.n_utt, picks_dev.data_ptr(), out.data_ptr(),
-                                          status.data_ptr() if status is not None else None, B, segment_length,
-                                          C.c_void_p(stream)))
+    _lib.check(_lib.load().wg_data_gather(_args.ptr(self.pool), self.dtype_code, self.elems, _args.ptr(self.offsets),
+                                          self.n_utt, _args.ptr(picks_dev), _args.ptr(out), _args.ptr(status), B,
+                                          segment_length, _args.stream(self.device)))
     return out
 
 

@@ -31,8 +31,9 @@ from typing import List
 
 import torch
 
-from . import _lib
-from .train import (GradBuffers, _ddp_group, _ptr, _SlotGuard, _Weights, canonical_params, new_grad, param_grad_views,
+from . import _args, _lib
+from ._args import ptr as _ptr
+from .train import (GradBuffers, _ddp_group, _SlotGuard, _Weights, canonical_params, new_grad, param_grad_views,
                     request_workspace, set_grad_finite)
 
 
@@ -56,7 +57,7 @@ class _InferFn(torch.autograd.Function):
     lib = eng.lib
     B, M, T = mel.shape
     flow_c = model.flow_channels()
-    stream = torch.cuda.current_stream(mel.device).cuda_stream
+    stream = _args.stream(mel.device).value     # as an int: _Weights takes it so
     want_mel = ctx.needs_input_grad[_InferFn.N_META]
     wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=want_mel, want_winv=wgrads)
     S = 256 * T
@@ -65,7 +66,7 @@ class _InferFn(torch.autograd.Function):
     audio = torch.empty((B, S), dtype=torch.float32, device=mel.device)
     ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
     _lib.check(lib.wg_train_infer_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
-                                          float(sigma), _ptr(audio), B, T, _ptr(frames) if frames is not None else None,
+                                          float(sigma), _ptr(audio), B, T, _ptr(frames),
                                           1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
     ctx.frames = frames
     ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.guard = model, wts, ws, (B, M, T), _SlotGuard(slot)
@@ -106,7 +107,7 @@ class _InferFn(torch.autograd.Function):
     g_ze = [new_grad(ctx.z_shapes[1 + i], dev) if w else None for i, w in enumerate(want_ze)]
     ga = g_audio.float().contiguous() if g_audio is not None else torch.zeros((B, 256 * T), dtype=torch.float32, device=dev)
     ze = (C.c_void_p * max(1, ne))(*[(g.data_ptr() if g is not None else None) for g in g_ze])
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = _args.stream(dev).value
     hp = model._hp
     bufs = GradBuffers(hp.n_channels, hp.n_layers, model.n_flows, hp.n_mel_channels * 8, dev) if want_params else None
     gstruct, _keep = bufs.struct() if want_params else (None, None)
@@ -114,9 +115,7 @@ class _InferFn(torch.autograd.Function):
     try:
       _lib.check(lib.wg_train_infer_backward(eng.handle, C.byref(ctx.wts.struct),
                                              C.byref(gstruct) if want_params else None, _ptr(ga), C.c_float(ctx.scale),
-                                             C.c_float(ctx.sigma), _ptr(g_mel) if want_mel else None,
-                                             _ptr(g_zi) if want_zi else None, ze, ne, B, T,
-                                             _ptr(ctx.frames) if ctx.frames is not None else None,
+                                             C.c_float(ctx.sigma), _ptr(g_mel), _ptr(g_zi), ze, ne, B, T, _ptr(ctx.frames),
                                              _ptr(ctx.ws), ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
       if want_params:      # (no logdet term in this direction)
         views = param_grad_views(eng, ctx.wts, gstruct, ctx.shapes, stream)
@@ -130,34 +129,6 @@ class _InferFn(torch.autograd.Function):
     return (None,) * nm + (g_mel, g_zi, *g_ze, *grads)
 
 
-def _check_frames(frames, spect: torch.Tensor):
-  """The counts as a CPU int32 tensor [B], or None for a device tensor.  Host counts (list, tuple, CPU integer tensor) are
-  range-checked here, before any launch and before anything else about the call is looked at; a device tensor is only
-  checked for its type and shape -- its values are trusted and never read on the host."""
-  if spect.dim() != 3:
-    raise _lib.WgError(f"infer_differentiable: mel [B, n_mel, T] expected, got {tuple(spect.shape)}")
-  B, _, T = spect.shape
-  if isinstance(frames, torch.Tensor) and frames.device.type == "cuda":
-    if frames.device != spect.device or frames.dtype != torch.int32 or frames.dim() != 1 or frames.numel() != B:
-      raise _lib.WgError(f"infer_differentiable: frame counts on the device must be int32 [{B}] on {spect.device}")
-    return None
-  if isinstance(frames, torch.Tensor):
-    if frames.dtype.is_floating_point or frames.dtype == torch.bool or frames.dim() != 1:
-      raise _lib.WgError(f"infer_differentiable: a 1-d tensor of integer frame counts expected, got {frames.dtype} "
-                         f"{tuple(frames.shape)}")
-    frames = frames.tolist()
-  elif not isinstance(frames, (list, tuple)):
-    raise _lib.WgError("infer_differentiable: frames must be a list, a tuple or a tensor of integer frame counts")
-  if any(isinstance(n, float) or isinstance(n, bool) for n in frames):
-    raise _lib.WgError(f"infer_differentiable: integer frame counts expected, got {list(frames)}")
-  host = [int(n) for n in frames]
-  if len(host) != B:
-    raise _lib.WgError(f"infer_differentiable: {len(host)} frame counts for a batch of {B}")
-  if any(n < 1 or n > T for n in host):
-    raise _lib.WgError(f"infer_differentiable: frame counts in [1, {T}] expected, got {host}")
-  return torch.tensor(host, dtype=torch.int32)
-
-
 def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_early: List[torch.Tensor], sigma: float,
                          grad_scale: float = 0.0, recompute: bool = False, weight_grads: bool = False,
                          frames=None) -> torch.Tensor:
@@ -166,15 +137,18 @@ def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_ear
   Without grad mode, or when nothing requires grad, exactly ``infer_with_noise`` (nothing is saved).  ``recompute``:
   activation recomputation (``WG_TRAIN_RECOMPUTE``).  ``frames``: per-utterance mel-frame counts of a ragged batch
   (``WaveGlow.infer_differentiable``), None for a dense one."""
-  fr_host = _check_frames(frames, spect) if frames is not None else None
+  # the counts first: refused for what is wrong with them before any launch and before anything else about the call is
+  # looked at.  Host counts are checked where they are and go up only once a graph is certain; device counts are trusted
+  fr = fr_host = None
+  if frames is not None:
+    if spect.dim() != 3:
+      raise _lib.WgError(f"infer_differentiable: mel [B, n_mel, T] expected, got {tuple(spect.shape)}")
+    on_device = isinstance(frames, torch.Tensor) and frames.device.type != "cpu"
+    fr, fr_host = _args.counts("infer_differentiable: frame counts", frames, spect.shape[0], 1, spect.shape[2],
+                               device=spect.device if on_device else "cpu", allow_device=True)
   ins = [spect, z_init] + list(z_early)
   for t in ins:
-    if t.device.type != "cuda":
-      raise _lib.WgError("waveglow_amd runs on MI355X only: there is no CPU fallback")
-    if t.dtype != torch.float32:
-      raise _lib.WgError("infer_differentiable takes float32 mel and noise (the training direction's kernels)")
-  # what infer_with_noise takes (it checks host counts where they are, without a synchronise)
-  fr_plain = fr_host if fr_host is not None else frames
+    _args.tensor("infer_differentiable: mel and noise (the training direction's kernels)", t, ndim=3)
   eng = model._get_engine(spect.device, need_weights=False)
   if eng.width != eng.n_channels or eng.mel_width != eng.n_mel or int(eng.lib.wg_wn_waves(eng.n_channels)) <= 0:
     raise _lib.WgError(f"n_channels={eng.n_channels}, n_mel_channels={eng.n_mel}: infer_differentiable runs on the training "
@@ -192,21 +166,19 @@ def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_ear
                        "(enable_data_parallel covers the training direction only): unset model.ddp_group and reduce the "
                        "parameter gradients yourself")
   if not torch.is_grad_enabled():
-    return model.infer_with_noise(spect, z_init, z_early, sigma, frames=fr_plain)
+    return model.infer_with_noise(spect, z_init, z_early, sigma, frames=fr)
   trainable = any(p.requires_grad for p in model.parameters())
   if trainable and not weight_grads:
     raise _lib.WgError("infer_differentiable treats the vocoder's weights as constants and gives no weight gradients: "
                        "freeze the model first (model.requires_grad_(False)) or ask for them (weight_grads=True)")
   if not trainable and not any(t.requires_grad for t in ins):
-    return model.infer_with_noise(spect, z_init, z_early, sigma, frames=fr_plain)
+    return model.infer_with_noise(spect, z_init, z_early, sigma, frames=fr)
   _names, tensors, wn = canonical_params(model, eng)
   ins = [t.contiguous() for t in ins]
   flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
-  fr_dev = None
   if fr_host is not None:
-    fr_dev = fr_host.to(spect.device)          # one small copy, nothing synchronises
-  elif frames is not None:
+    fr = fr.to(spect.device)                   # one small copy, nothing synchronises
+  elif fr is not None:
     # trusted device counts: one outside [1, T] becomes 0, which the kernels take as an utterance that is all padding
-    fr_dev = frames.contiguous()
-    fr_dev = fr_dev.masked_fill((fr_dev < 1) | (fr_dev > spect.shape[2]), 0)
-  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, flags, n_early, bool(weight_grads), fr_dev, *ins, *tensors)
+    fr = fr.masked_fill((fr < 1) | (fr > spect.shape[2]), 0)
+  return _InferFn.apply(model, float(sigma), float(grad_scale), wn, flags, n_early, bool(weight_grads), fr, *ins, *tensors)

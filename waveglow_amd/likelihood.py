@@ -17,7 +17,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 N_ROW = 8               # fp64 values per utterance (include/waveglow_amd.h: wg_nll)
 NLL, BITS_PER_SAMPLE, SUM_Z2, SUM_LOG_S, LOG_DET, SAMPLES, Z_MEAN, Z_VAR = range(8)
@@ -47,12 +47,9 @@ def rows_to_likelihoods(rows: torch.Tensor) -> List[Likelihood]:
 
 
 def _inputs(model, mel, audio) -> None:
-  for name, t in (("mel", mel), ("audio", audio)):
-    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-      raise _lib.WgError(f"log_likelihood: {name} must be a tensor on the GPU (no CPU fallback)")
-    if t.dtype not in (torch.float32, torch.float16):
-      raise _lib.WgError(f"log_likelihood: {name} takes float32 or float16, got {t.dtype}")
-  if mel.dim() != 3 or audio.dim() != 2 or mel.shape[0] != audio.shape[0] or mel.shape[0] < 1:
+  for name, t, ndim in (("mel [B, n_mel, T]", mel, 3), ("audio [B, S]", audio, 2)):
+    _args.tensor(f"log_likelihood: {name}", t, dtypes=(torch.float32, torch.float16), ndim=ndim)
+  if mel.shape[0] != audio.shape[0] or mel.shape[0] < 1:
     raise _lib.WgError(f"log_likelihood: mel [B, n_mel, T] and audio [B, S] expected, got {tuple(mel.shape)} and "
                        f"{tuple(audio.shape)}")
   if mel.dtype != audio.dtype or mel.device != audio.device:
@@ -63,22 +60,11 @@ def _frames(frames: Frames, mel: torch.Tensor, audio: torch.Tensor) -> torch.Ten
   """int32 [B] on the device.  Host counts are range-checked here, before any launch; a device tensor is trusted (the
   kernels give an utterance with a count outside the range zeros, and read nothing outside the buffers)."""
   B, _, T = mel.shape
-  if isinstance(frames, torch.Tensor) and frames.device.type == "cuda":
-    if frames.device != mel.device or frames.dtype != torch.int32 or frames.dim() != 1 or frames.numel() != B:
-      raise _lib.WgError(f"log_likelihood: frame counts on the device must be int32 [{B}] on {mel.device}")
-    return frames.contiguous()
-  if isinstance(frames, torch.Tensor):
-    if frames.dtype.is_floating_point or frames.dtype == torch.bool:
-      raise _lib.WgError(f"log_likelihood: integer frame counts expected, got {frames.dtype}")
-    frames = frames.tolist()
-  host = [int(n) for n in frames]
-  if len(host) != B:
-    raise _lib.WgError(f"log_likelihood: {len(host)} frame counts for a batch of {B}")
-  for n in host:
-    if n < 1 or n > T or FRAME_SAMPLES * n > audio.shape[1]:
-      raise _lib.WgError(f"log_likelihood: frame counts in [1, {T}] with 256 * frames <= {audio.shape[1]} samples "
-                         f"expected, got {host}")
-  return torch.tensor(host, dtype=torch.int32).to(mel.device)
+  dev, host = _args.counts("log_likelihood: frame counts", frames, B, 1, T, device=mel.device, allow_device=True)
+  if host is not None and FRAME_SAMPLES * max(host) > audio.shape[1]:
+    raise _lib.WgError(f"log_likelihood: frame counts with {FRAME_SAMPLES} * frames <= {audio.shape[1]} samples expected, "
+                       f"got {host}")
+  return dev
 
 
 def _forward(model, mel: torch.Tensor, audio: torch.Tensor, frames: Frames):
@@ -112,11 +98,11 @@ def _forward(model, mel: torch.Tensor, audio: torch.Tensor, frames: Frames):
   log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=dev) for c in model.flow_channels()]
   ws = eng.workspace("fwd", nbytes, (B, T, S))
   ls = (C.c_void_p * model.n_flows)(*[t.data_ptr() for t in log_s])
-  stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+  stream = _args.stream(dev)
   with torch.cuda.device(dev):
     log_det = (C.c_float * model.n_flows)() if fr is None else None     # required without counts only; never read here
-    _lib.check(eng.lib.wg_forward(eng.handle, mel.data_ptr(), fr.data_ptr() if fr is not None else None, audio.data_ptr(),
-                                  z.data_ptr(), ls, log_det, B, T, S, io, ws.data_ptr(), ws.numel(), stream))
+    _lib.check(eng.lib.wg_forward(eng.handle, _args.ptr(mel), _args.ptr(fr), _args.ptr(audio), _args.ptr(z), ls, log_det,
+                                  B, T, S, io, _args.ptr(ws), ws.numel(), stream))
   return eng, z, log_s, fr
 
 
@@ -151,9 +137,8 @@ def nll_enqueue(eng, z: torch.Tensor, log_s: List[torch.Tensor], frames_dev: Opt
   ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
   ls = (C.c_void_p * len(log_s))(*[t.data_ptr() for t in log_s])
   with torch.cuda.device(dev):
-    _lib.check(eng.lib.wg_nll(eng.handle, z.data_ptr(), ls, frames_dev.data_ptr() if frames_dev is not None else None,
-                              sigma, B, L, rows.data_ptr(), track.data_ptr() if per_frame else None, ws.data_ptr(),
-                              ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    _lib.check(eng.lib.wg_nll(eng.handle, _args.ptr(z), ls, _args.ptr(frames_dev), sigma, B, L, _args.ptr(rows),
+                              _args.ptr(track), _args.ptr(ws), ws.numel(), _args.stream(dev)))
   return rows, track
 
 
@@ -172,11 +157,12 @@ def log_likelihood_enqueue(model, mel: torch.Tensor, audio: torch.Tensor, frames
 
 def log_likelihood(model, mel: torch.Tensor, audio: torch.Tensor, frames: Frames = None, sigma: Optional[float] = None,
                    per_frame: bool = False):
-  """One ``Likelihood`` per utterance (one device-to-host copy); with ``per_frame`` a pair with the track, which stays on
-  the device.  ``frames``: list, tuple or CPU integer tensor of mel-frame counts, each in ``[1, mel.shape[2]]`` with
-  ``256 * f <= audio.shape[1]`` (``WgError`` before any launch otherwise), or an int32 device tensor, which is trusted;
-  None scores the dense batch on ``S - S % 8`` samples as ``forward`` crops it.  ``sigma`` None: 1.0, the
-  ``WaveGlowLoss`` default."""
+  """One ``Likelihood`` per utterance (one device-to-host copy); with ``per_frame`` a pair with the track, which stays
+  on the device.  ``frames``: B integers as ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an
+  integer dtype; a float or a bool entry raises WgError), the mel-frame counts, each in ``[1, mel.shape[2]]`` with ``256
+  * f <= audio.shape[1]`` (``WgError`` before any launch otherwise), or an int32 tensor ``[B]`` on the device, which is
+  trusted and never read on the host; None scores the dense batch on ``S - S % 8`` samples as ``forward`` crops it.
+  ``sigma`` None: 1.0, the ``WaveGlowLoss`` default."""
   res = log_likelihood_enqueue(model, mel, audio, frames, sigma, per_frame)
   rows = rows_to_likelihoods((res[0] if per_frame else res).cpu())
   return (rows, res[1]) if per_frame else rows

@@ -24,7 +24,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .stft_loss import _WaveformLoss, check_geometry, forward_basis
 from .taco_stft import slaney_mel_filterbank
 
@@ -52,9 +52,9 @@ class MultiScaleMelLoss(_WaveformLoss):
   fp32 arrays ``[n_mels, n_fft / 2 + 1]`` instead (``sampling_rate``, ``fmin`` and ``fmax`` are then unused).  A bank row
   of zeros is legal.
 
-  ``lengths``: B host integers (list, tuple or CPU tensor), each in ``(max(n_ffts) / 2, N]`` (checked on the host,
-  WgError otherwise); they go up in one small copy per call.  ``audio.grad[b, lengths[b]:]`` is 0 and
-  ``lengths=[N] * B`` gives the bits of ``lengths=None``.
+  ``lengths``: B integers as ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an integer dtype; a
+  float or a bool entry raises WgError), each in ``(max(n_ffts) / 2, N]``; they go up in one small copy per call.
+  ``audio.grad[b, lengths[b]:]`` is 0 and ``lengths=[N] * B`` gives the bits of ``lengths=None``.
 
   ``audio``, ``target``: fp32 ``[B, N]`` on the module's device, same shape, ``N > max(n_ffts) / 2``; anything else
   raises WgError.  Only ``audio`` gets a gradient (a ``target`` that requires grad raises WgError): ``sign(0) = 0``, the
@@ -66,7 +66,7 @@ class MultiScaleMelLoss(_WaveformLoss):
   Supported: 1 to 8 scales, ``n_fft`` a multiple of 32 in [32, 2048], ``1 <= hop, win <= n_fft``,
   ``1 <= n_mels <= n_fft / 2 + 1``, ``clamp > 0`` and finite.  Everything else raises WgError at construction."""
 
-  _NAME, _DESTROY = "MultiScaleMelLoss", "wg_melloss_destroy"
+  _NAME = "MultiScaleMelLoss"
 
   def __init__(self, sampling_rate=22050, n_ffts=DAC_N_FFTS, hop_sizes=None, win_lengths=None, n_mels=DAC_N_MELS,
                fmin=0.0, fmax=None, clamp=1e-5, factor_log=1.0, factor_lin=0.0, device="cuda", mel_bases=None):
@@ -103,14 +103,16 @@ class MultiScaleMelLoss(_WaveformLoss):
     bases = [forward_basis(nf, w) for nf, _, w, _ in self.scales]
     arr = lambda v: (C.c_int32 * n)(*v)
     ptrs = lambda a: (C.c_void_p * n)(*[b.ctypes.data for b in a])
-    self._h = C.c_void_p()
+    self._owner = _args.Handle(self.lib, "wg_melloss_destroy")
+    self._h = self._owner.value                # what every call takes; the owner releases it
     _lib.check(self.lib.wg_melloss_create(n, arr(n_ffts), arr(hop_sizes), arr(win_lengths), arr(n_mels), ptrs(bases),
                                           ptrs(banks), self.clamp, _lib.device_index(device), C.byref(self._h)))
 
   def workspace_bytes(self, B: int, N: int) -> int:
     """Bytes one forward with a graph keeps until its backward (0 when N <= max(n_ffts) / 2): per scale the prediction's
     (re, im) [B, n_fft, F] and both linear mels [B, n_mels, F] (F rounded up to 64), and the cell counts."""
-    return 4 * int(self.lib.wg_melloss_spectra_elems(self._h, B, N) + self.lib.wg_melloss_mels_elems(self._h, B, N))
+    h = self._h
+    return 4 * int(self.lib.wg_melloss_spectra_elems(h, B, N) + self.lib.wg_melloss_mels_elems(h, B, N))
 
   def _need(self):
     return max(s[0] for s in self.scales) // 2
@@ -120,24 +122,22 @@ class MultiScaleMelLoss(_WaveformLoss):
     lens: int32 [B] on the device, or None."""
     x, y = x.detach().contiguous(), y.detach().contiguous()
     B, N = x.shape
-    ns, nm = self.lib.wg_melloss_spectra_elems(self._h, B, N), self.lib.wg_melloss_mels_elems(self._h, B, N)
+    h = self._h
+    ns, nm = self.lib.wg_melloss_spectra_elems(h, B, N), self.lib.wg_melloss_mels_elems(h, B, N)
     if ns == 0 or nm == 0:
       raise _lib.WgError(f"MultiScaleMelLoss: unsupported batch {B} x {N}")
     out = torch.empty(3, dtype=torch.float32, device=x.device)
     spectra = torch.empty(ns, dtype=torch.float32, device=x.device) if saved else None
     mels = torch.empty(nm, dtype=torch.float32, device=x.device) if saved else None
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _lib.check(self.lib.wg_melloss_forward(self._h, x.data_ptr(), y.data_ptr(),
-                                           lens.data_ptr() if lens is not None else None, self.factor_log,
-                                           self.factor_lin, out.data_ptr(), spectra.data_ptr() if saved else None,
-                                           mels.data_ptr() if saved else None, B, N, C.c_void_p(stream)))
+    _lib.check(self.lib.wg_melloss_forward(h, _args.ptr(x), _args.ptr(y), _args.ptr(lens), self.factor_log,
+                                           self.factor_lin, _args.ptr(out), _args.ptr(spectra), _args.ptr(mels), B, N,
+                                           _args.stream(x.device)))
     return out, (spectra, mels)
 
   def _backward(self, state, g, lens, B, N):
     spectra, mels = state
     gx = torch.empty((B, N), dtype=torch.float32, device=mels.device)
-    stream = torch.cuda.current_stream(mels.device).cuda_stream
-    _lib.check(self.lib.wg_melloss_backward(self._h, g.data_ptr(), lens.data_ptr() if lens is not None else None,
-                                            self.factor_log, self.factor_lin, spectra.data_ptr(), mels.data_ptr(),
-                                            gx.data_ptr(), B, N, C.c_void_p(stream)))
+    _lib.check(self.lib.wg_melloss_backward(self._h, _args.ptr(g), _args.ptr(lens), self.factor_log,
+                                            self.factor_lin, _args.ptr(spectra), _args.ptr(mels), _args.ptr(gx), B, N,
+                                            _args.stream(mels.device)))
     return gx

@@ -27,7 +27,8 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import ptr
 
 MAX_FRAMES = 4096       # frames per utterance (include/waveglow_amd.h: wg_metrics_*)
 MAX_FEATURES = 128      # mel channels / feature rows
@@ -45,6 +46,9 @@ STOI_FRAME_TILE = 8                              # frames per workgroup of the b
 STOI_SEGMENT_TILE = 4                            # segments per workgroup of the segment kernel
 STOI, ESTOI, STOI_FRAMES, STOI_FRAMES_KEPT, STOI_SEGMENTS = range(5)
 
+# Per-utterance frame counts and sample counts: None (all), or B integers as ``_args.counts`` takes them (a list, a
+# tuple or a 1-D CPU tensor of an integer dtype; a float or a bool entry raises WgError), or an int32 tensor ``[B]`` on
+# the device, which is trusted and never read on the host
 Frames = Union[None, Sequence[int], torch.Tensor]
 
 
@@ -81,14 +85,7 @@ class IntelligibilityMetrics:
 
 
 def _features(name: str, x, device=None) -> torch.Tensor:
-  if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-    raise _lib.WgError(f"{name}: the metrics run on the GPU library only (no CPU fallback)")
-  if device is not None and x.device != device:
-    raise _lib.WgError(f"{name}: both sides must be on one GPU, got {x.device} and {device}")
-  if x.dtype != torch.float32:
-    raise _lib.WgError(f"{name} takes float32, got {x.dtype}")
-  if x.dim() != 3:
-    raise _lib.WgError(f"{name} takes [B, C, T], got shape {tuple(x.shape)}")
+  _args.tensor(name, x, device=device, ndim=3)
   B, K, T = x.shape
   if B < 1 or not 1 <= K <= MAX_FEATURES or not 1 <= T <= MAX_FRAMES:
     raise _lib.WgError(f"{name}: B >= 1, 1 <= C <= {MAX_FEATURES} and 1 <= T <= {MAX_FRAMES} expected, "
@@ -96,26 +93,14 @@ def _features(name: str, x, device=None) -> torch.Tensor:
   return x.contiguous()
 
 
-def _frames(name: str, frames: Frames, x: torch.Tensor) -> torch.Tensor:
-  """int32 [B] on x's device.  A host list is range-checked here; a device tensor is never read on the host (the kernels
-  treat a count outside the limits as 0)."""
+def _frames(name: str, frames: Frames, x: torch.Tensor, upload: bool = True) -> torch.Tensor:
+  """int32 [B] on x's device.  Host counts are range-checked (``_args.counts``); a device tensor is never read on the host
+  (the kernels treat a count outside the limits as 0).  Without ``upload`` checked host counts stay on the host, for a
+  caller that wants both sides of a pair checked before either goes up."""
   B, _, T = x.shape
-  if frames is None:
-    frames = [T] * B
-  if isinstance(frames, torch.Tensor) and frames.device.type == "cuda":
-    if frames.device != x.device or frames.dtype != torch.int32 or frames.dim() != 1 or frames.numel() != B:
-      raise _lib.WgError(f"{name}: frame counts on the device must be int32 [{B}] on {x.device}")
-    return frames.contiguous()
-  host = [int(n) for n in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
-  if len(host) != B:
-    raise _lib.WgError(f"{name}: {len(host)} frame counts for a batch of {B}")
-  if any(n < 1 or n > min(T, MAX_FRAMES) for n in host):
-    raise _lib.WgError(f"{name}: frame counts in [1, {min(T, MAX_FRAMES)}] expected, got {host}")
-  return torch.tensor(host, dtype=torch.int32).to(x.device)
-
-
-def _stream(x: torch.Tensor):
-  return C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+  on_device = isinstance(frames, torch.Tensor) and frames.device.type != "cpu"
+  return _args.counts(name, [T] * B if frames is None else frames, B, 1, min(T, MAX_FRAMES),
+                      device=x.device if upload or on_device else "cpu", allow_device=True)[0]
 
 
 def mfcc(mel: torch.Tensor, frames: Frames = None, n_mfcc: int = 16) -> torch.Tensor:
@@ -130,8 +115,8 @@ def mfcc(mel: torch.Tensor, frames: Frames = None, n_mfcc: int = 16) -> torch.Te
   out = torch.empty((B, n_mfcc, T), dtype=torch.float32, device=mel.device)
   ws = torch.empty(lib.wg_metrics_workspace_bytes(B, n_mel, n_mfcc, T, T), dtype=torch.uint8, device=mel.device)
   with torch.cuda.device(mel.device):
-    _lib.check(lib.wg_metrics_mfcc(mel.data_ptr(), fr.data_ptr(), out.data_ptr(), B, n_mel, n_mfcc, T, ws.data_ptr(),
-                                   ws.numel(), _stream(mel)))
+    _lib.check(lib.wg_metrics_mfcc(ptr(mel), ptr(fr), ptr(out), B, n_mel, n_mfcc, T, ptr(ws),
+                                   ws.numel(), _args.stream(mel.device)))
   return out
 
 
@@ -149,8 +134,8 @@ def dtw_distance(feat_a: torch.Tensor, frames_a: Frames, feat_b: torch.Tensor,
   cost = torch.empty(B, dtype=torch.float64, device=a.device)
   length = torch.empty(B, dtype=torch.int32, device=a.device)
   with torch.cuda.device(a.device):
-    _lib.check(_lib.load().wg_metrics_dtw(a.data_ptr(), fa.data_ptr(), b.data_ptr(), fb.data_ptr(), cost.data_ptr(),
-                                          length.data_ptr(), B, K, Ta, b.shape[2], _stream(a)))
+    _lib.check(_lib.load().wg_metrics_dtw(ptr(a), ptr(fa), ptr(b), ptr(fb), ptr(cost),
+                                          ptr(length), B, K, Ta, b.shape[2], _args.stream(a.device)))
   return cost, length
 
 
@@ -171,8 +156,8 @@ def mel_metrics_enqueue(mel_a: torch.Tensor, frames_a: Frames, mel_b: torch.Tens
   rows = torch.empty((B, N_ROW), dtype=torch.float64, device=a.device)
   ws = torch.empty(lib.wg_metrics_workspace_bytes(B, n_mel, n_mfcc, Ta, Tb), dtype=torch.uint8, device=a.device)
   with torch.cuda.device(a.device):
-    _lib.check(lib.wg_metrics_mel(a.data_ptr(), fa.data_ptr(), b.data_ptr(), fb.data_ptr(), rows.data_ptr(), B, n_mel,
-                                  n_mfcc, Ta, Tb, ws.data_ptr(), ws.numel(), _stream(a)))
+    _lib.check(lib.wg_metrics_mel(ptr(a), ptr(fa), ptr(b), ptr(fb), ptr(rows), B, n_mel,
+                                  n_mfcc, Ta, Tb, ptr(ws), ws.numel(), _args.stream(a.device)))
   return rows
 
 
@@ -231,35 +216,17 @@ def pitch_frames(n_samples: int, p: _lib.WgPitchParams) -> int:
 
 
 def _audio(name: str, x, device=None) -> torch.Tensor:
-  if not isinstance(x, torch.Tensor):
-    raise _lib.WgError(f"{name} takes a tensor, got {type(x).__name__}")
-  if x.dtype != torch.float32:
-    raise _lib.WgError(f"{name} takes float32, got {x.dtype}")
-  if x.dim() != 2 or x.shape[0] < 1 or x.shape[0] > 65535 or x.shape[1] < 1 or x.shape[1] >= 2 ** 31:
+  _args.tensor(name, x, device=device, ndim=2)
+  if x.shape[0] < 1 or x.shape[0] > 65535 or x.shape[1] < 1 or x.shape[1] >= 2 ** 31:
     raise _lib.WgError(f"{name} takes [B, N] with 1 <= B <= 65535 and N >= 1, got shape {tuple(x.shape)}")
-  if x.device.type != "cuda":
-    raise _lib.WgError(f"{name}: the pitch metrics run on the GPU library only (no CPU fallback)")
-  if device is not None and x.device != device:
-    raise _lib.WgError(f"{name}: both sides must be on one GPU, got {x.device} and {device}")
   return x.contiguous()
 
 
 def _lengths(name: str, lengths: Frames, x: torch.Tensor) -> torch.Tensor:
-  """int32 [B] on x's device.  A host list is range-checked here; a device tensor is never read on the host (the kernels
-  treat a length outside [0, N] as 0 frames)."""
+  """int32 [B] on x's device.  Host counts are range-checked (``_args.counts``); a device tensor is never read on the host
+  (the kernels treat a length outside [0, N] as 0 frames)."""
   B, N = x.shape
-  if lengths is None:
-    lengths = [N] * B
-  if isinstance(lengths, torch.Tensor) and lengths.device.type == "cuda":
-    if lengths.device != x.device or lengths.dtype != torch.int32 or lengths.dim() != 1 or lengths.numel() != B:
-      raise _lib.WgError(f"{name}: lengths on the device must be int32 [{B}] on {x.device}")
-    return lengths.contiguous()
-  host = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
-  if len(host) != B:
-    raise _lib.WgError(f"{name}: {len(host)} lengths for a batch of {B}")
-  if any(n < 0 or n > N for n in host):
-    raise _lib.WgError(f"{name}: lengths in [0, {N}] expected, got {host}")
-  return torch.tensor(host, dtype=torch.int32).to(x.device)
+  return _args.counts(name, [N] * B if lengths is None else lengths, B, 0, N, device=x.device, allow_device=True)[0]
 
 
 def yin_f0(audio: torch.Tensor, lengths: Frames = None, *, sampling_rate=22050, frame_length: int = 1024,
@@ -277,28 +244,27 @@ def yin_f0(audio: torch.Tensor, lengths: Frames = None, *, sampling_rate=22050, 
   ap = torch.empty((B, F), dtype=torch.float64, device=x.device)
   frames = torch.empty(B, dtype=torch.int32, device=x.device)
   with torch.cuda.device(x.device):
-    _lib.check(_lib.load().wg_pitch_yin(x.data_ptr(), ln.data_ptr(), C.byref(p), f0.data_ptr(), ap.data_ptr(),
-                                        frames.data_ptr(), B, N, F, _stream(x)))
+    _lib.check(_lib.load().wg_pitch_yin(ptr(x), ptr(ln), C.byref(p), ptr(f0), ptr(ap),
+                                        ptr(frames), B, N, F, _args.stream(x.device)))
   return f0, ap, frames
 
 
 def pitch_compare(f0_a: torch.Tensor, frames_a: torch.Tensor, f0_b: torch.Tensor, frames_b: torch.Tensor) -> torch.Tensor:
   """Rows fp64 [B, 8] (wg_pitch_compare) of two track sets as ``yin_f0`` returns them: fp64 [B, F] and int32 [B] on one
   GPU."""
-  for name, f0, fr in (("f0_a", f0_a, frames_a), ("f0_b", f0_b, frames_b)):
-    if not isinstance(f0, torch.Tensor) or f0.device.type != "cuda" or not isinstance(fr, torch.Tensor):
-      raise _lib.WgError(f"pitch_compare: {name}: the pitch metrics run on the GPU library only (no CPU fallback)")
-    if f0.dtype != torch.float64 or f0.dim() != 2 or f0.shape[0] < 1 or f0.shape[0] > 65535 or f0.shape[1] < 1:
-      raise _lib.WgError(f"pitch_compare: {name} takes float64 [B, F], got {f0.dtype} {tuple(f0.shape)}")
-    if fr.device != f0_a.device or f0.device != f0_a.device or fr.dtype != torch.int32 or fr.dim() != 1 or \
-        fr.numel() != f0_a.shape[0] or f0.shape[0] != f0_a.shape[0]:
-      raise _lib.WgError(f"pitch_compare: {name} and its frame counts must be [B, F] and int32 [B] on {f0_a.device}")
+  fr = []
+  for name, f0, frames in (("f0_a", f0_a, frames_a), ("f0_b", f0_b, frames_b)):
+    _args.tensor(f"pitch_compare: {name}", f0, device=getattr(f0_a, "device", None), dtypes=(torch.float64,), ndim=2)
+    B, F = f0.shape
+    if not 1 <= B <= 65535 or F < 1 or B != f0_a.shape[0]:
+      raise _lib.WgError(f"pitch_compare: {name} takes [B, F] with 1 <= B <= 65535 and F >= 1, one B on both sides, got "
+                         f"{tuple(f0.shape)}")
+    fr.append(_args.counts(f"pitch_compare: frames of {name}", frames, B, 0, F, device=f0.device, allow_device=True)[0])
   a, b = f0_a.contiguous(), f0_b.contiguous()
   rows = torch.empty((a.shape[0], N_ROW), dtype=torch.float64, device=a.device)
   with torch.cuda.device(a.device):
-    _lib.check(_lib.load().wg_pitch_compare(a.data_ptr(), frames_a.contiguous().data_ptr(), b.data_ptr(),
-                                            frames_b.contiguous().data_ptr(), rows.data_ptr(), a.shape[0], a.shape[1],
-                                            b.shape[1], _stream(a)))
+    _lib.check(_lib.load().wg_pitch_compare(ptr(a), ptr(fr[0]), ptr(b), ptr(fr[1]), ptr(rows), a.shape[0], a.shape[1],
+                                            b.shape[1], _args.stream(a.device)))
   return rows
 
 
@@ -319,8 +285,8 @@ def pitch_metrics_enqueue(audio_a: torch.Tensor, lengths_a: Frames, audio_b: tor
   rows = torch.empty((B, N_ROW), dtype=torch.float64, device=a.device)
   ws = torch.empty(lib.wg_pitch_workspace_bytes(C.byref(p), B, a.shape[1], b.shape[1]), dtype=torch.uint8, device=a.device)
   with torch.cuda.device(a.device):
-    _lib.check(lib.wg_pitch_metrics(a.data_ptr(), la.data_ptr(), a.shape[1], b.data_ptr(), lb.data_ptr(), b.shape[1],
-                                    C.byref(p), rows.data_ptr(), B, ws.data_ptr(), ws.numel(), _stream(a)))
+    _lib.check(lib.wg_pitch_metrics(ptr(a), ptr(la), a.shape[1], ptr(b), ptr(lb), b.shape[1],
+                                    C.byref(p), ptr(rows), B, ptr(ws), ws.numel(), _args.stream(a.device)))
   return rows
 
 
@@ -410,8 +376,8 @@ def stoi_enqueue(x10k: torch.Tensor, lengths_x: Frames, y10k: torch.Tensor, leng
     p = _stoi_params(x.device)
     rows = torch.empty((B, N_ROW), dtype=torch.float64, device=x.device)
     ws = torch.empty(lib.wg_stoi_workspace_bytes(B, N), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.wg_stoi(x.data_ptr(), lx.data_ptr(), y.data_ptr(), ly.data_ptr(), B, N, C.byref(p), rows.data_ptr(),
-                           ws.data_ptr(), ws.numel(), _stream(x)))
+    _lib.check(lib.wg_stoi(ptr(x), ptr(lx), ptr(y), ptr(ly), B, N, C.byref(p), ptr(rows),
+                           ptr(ws), ws.numel(), _args.stream(x.device)))
   return rows
 
 
@@ -492,8 +458,8 @@ def stoi_forward_saved(x10k: torch.Tensor, lengths_x: Frames, y10k: torch.Tensor
     rows = torch.empty((B, N_ROW), dtype=torch.float64, device=x.device)
     saved = torch.empty(lib.wg_stoi_saved_bytes(B, N), dtype=torch.uint8, device=x.device)
     ws = torch.empty(lib.wg_stoi_workspace_bytes(B, N), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.wg_stoi_forward(x.data_ptr(), lx.data_ptr(), y.data_ptr(), ly.data_ptr(), B, N, C.byref(p),
-                                   rows.data_ptr(), saved.data_ptr(), saved.numel(), ws.data_ptr(), ws.numel(), _stream(x)))
+    _lib.check(lib.wg_stoi_forward(ptr(x), ptr(lx), ptr(y), ptr(ly), B, N, C.byref(p),
+                                   ptr(rows), ptr(saved), saved.numel(), ptr(ws), ws.numel(), _args.stream(x.device)))
   return rows, (y.detach(), saved)
 
 
@@ -513,8 +479,8 @@ def stoi_backward_enqueue(state, g_rows: torch.Tensor) -> torch.Tensor:
     p = _stoi_params(y.device)
     d_y = torch.empty((B, N), dtype=torch.float64, device=y.device)
     ws = torch.empty(lib.wg_stoi_backward_workspace_bytes(B, N), dtype=torch.uint8, device=y.device)
-    _lib.check(lib.wg_stoi_backward(y.data_ptr(), B, N, C.byref(p), g.data_ptr(), saved.data_ptr(), saved.numel(),
-                                    d_y.data_ptr(), ws.data_ptr(), ws.numel(), _stream(y)))
+    _lib.check(lib.wg_stoi_backward(ptr(y), B, N, C.byref(p), ptr(g), ptr(saved), saved.numel(),
+                                    ptr(d_y), ptr(ws), ws.numel(), _args.stream(y.device)))
   return d_y
 
 

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 from torch import nn
 
-from . import _lib
+from . import _args, _lib
 from .hparams import HParams
 
 
@@ -88,10 +88,10 @@ class _Engine:
       raise _lib.WgError("n_early_size=0 unsupported (even, >= 2)")
     cfg = _lib.WgConfig(self.mel_width, hp.n_flows, hp.n_group, hp.n_early_every, hp.n_early_size,
                         hp.n_layers, self.width, hp.kernel_size, 1024, 256)
-    handle = C.c_void_p()
-    _lib.check(lib.wg_create(C.byref(cfg), _lib.device_index(device), C.byref(handle)))
+    self._owner = _args.Handle(lib, "wg_destroy")
+    _lib.check(lib.wg_create(C.byref(cfg), _lib.device_index(device), C.byref(self._owner.value)))
     self.lib = lib
-    self.handle = handle
+    self.handle = self._owner.value            # what every call takes; the owner releases it
     self.device = device
     self.signature: Optional[tuple] = None
     self._ws: Dict[Tuple[str, int, int, int], torch.Tensor] = {}
@@ -99,13 +99,6 @@ class _Engine:
     self._graphs: Dict[tuple, tuple] = {}      # captured hipGraphs of wg_infer, keyed by input shape / dtype / sigma
     self._graphs_sig: Optional[tuple] = None   # weight signature the graphs were captured with
     self.cache: Dict[tuple, object] = {}       # small per-handle lookups (canonical parameter names of the training direction)
-
-  def __del__(self):
-    try:
-      if getattr(self, "handle", None):
-        self.lib.wg_destroy(self.handle)
-    except Exception:
-      pass
 
   def upload(self, tensors: Dict[str, torch.Tensor]) -> None:
     n = self.lib.wg_num_expected_tensors(self.handle)
@@ -422,9 +415,10 @@ class WaveGlow(nn.Module):
     synthesised alone: ``audio[b, :256 * frames[b]]`` has the bits of that batch-of-one call and the audio behind it is 0;
     ``spect.grad``, ``z_init.grad`` and ``z_early[i].grad`` are 0 behind the count and have the single call's bits in
     front of it (same loss scale); with ``weight_grads`` every parameter gradient is the sum of the single calls'.  Nothing
-    behind a count is read -- mel, noise and the incoming audio gradient may hold NaN there.  A list, tuple or CPU integer
-    tensor is checked before any launch (every count in ``[1, T]``, else ``WgError``) and uploaded in one small copy; an
-    int32 device tensor is trusted and never read on the host: a count outside ``[1, T]`` makes its utterance all padding
+    behind a count is read -- mel, noise and the incoming audio gradient may hold NaN there.  ``frames``: B integers as
+    ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an integer dtype; a float or a bool entry raises
+    WgError), each in ``[1, T]``, checked before any launch and uploaded in one small copy, or an int32 tensor ``[B]`` on
+    the device, which is trusted and never read on the host: a count outside ``[1, T]`` makes its utterance all padding
     (zero audio, zero gradients).  None, or ``[T] * B``: the dense result, bit for bit.  The automatic loss scale is
     that of the padded tensor.  Without grad mode, or when nothing requires grad, the call is
     ``infer_with_noise(..., frames=)``, which holds a device tensor to ``[1, T]`` with an assertion of its own."""

@@ -4,12 +4,10 @@ audio_utils.py:36-95, :132-138), bit for bit, so that one int16 copy comes back 
 No CPU fallback."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 # columns of the statistics, one row of 8 floats per utterance (include/waveglow_amd.h: wg_wav_finish)
 RAW_MIN, RAW_MAX, RAW_PEAK, DEN_MIN, DEN_MAX, DEN_PEAK, NON_FINITE = range(7)
@@ -32,9 +30,8 @@ def finish_enqueue(raw: torch.Tensor, denoised: torch.Tensor, lengths_dev: torch
   lib = _lib.load()
   out = torch.empty(2 * B * N + 4 * N_STATS * B, dtype=torch.uint8, device=raw.device)
   ws = torch.empty(lib.wg_wav_finish_workspace_bytes(B), dtype=torch.uint8, device=raw.device)
-  stream = torch.cuda.current_stream(raw.device).cuda_stream
-  _lib.check(lib.wg_wav_finish(raw.data_ptr(), denoised.data_ptr(), lengths_dev.data_ptr(), out.data_ptr(),
-                               out.data_ptr() + 2 * B * N, B, N, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+  _lib.check(lib.wg_wav_finish(_args.ptr(raw), _args.ptr(denoised), _args.ptr(lengths_dev), _args.ptr(out),
+                               out.data_ptr() + 2 * B * N, B, N, _args.ptr(ws), ws.numel(), _args.stream(raw.device)))
   return out
 
 
@@ -54,9 +51,6 @@ def finish(raw: torch.Tensor, denoised: torch.Tensor, lengths):
   """``finish_enqueue`` + one copy to the host + one synchronise.  ``lengths``: B sample counts in [1, N].
   Returns (pcm int16 [B, N] with zeros behind each utterance, stats fp32 [B, 8])."""
   B, N = raw.shape
-  lengths = [int(n) for n in lengths]
-  if len(lengths) != B or any(n < 1 or n > N for n in lengths):
-    raise _lib.WgError(f"wav finish: {B} lengths in [1, {N}] expected, got {lengths}")
-  out = finish_enqueue(raw, denoised, torch.tensor(lengths, dtype=torch.int32).to(raw.device))
+  out = finish_enqueue(raw, denoised, _args.counts("wav finish: lengths", lengths, B, 1, N, device=raw.device)[0])
   host = out.cpu()
   return finish_read(host, B, N)

@@ -21,7 +21,7 @@ from typing import Dict, List, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 MAX_RATE = 1024          # max(up, down) of the reduced ratio (csrc/wg_resample.h)
 MAX_SAMPLES = 1 << 26    # row pitch of the input
@@ -105,15 +105,10 @@ def _device_table(up: int, down: int, half: int, taps: np.ndarray, device: torch
   return t
 
 
-def _check_audio(audio, what: str):
-  if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda":
-    raise _lib.WgError(f"{what}: audio must be on the GPU (no CPU fallback)")
-  if audio.dtype not in (torch.float32, torch.int16):
-    raise _lib.WgError(f"{what} takes float32 or int16 audio, got {audio.dtype}")
-  if audio.dim() != 2 or audio.shape[0] < 1:
-    raise _lib.WgError(f"{what} takes audio [B, N], got shape {tuple(audio.shape)}")
-  if not 1 <= audio.shape[1] <= MAX_SAMPLES:
-    raise _lib.WgError(f"{what}: 1 <= N <= {MAX_SAMPLES} expected, got {audio.shape[1]}")
+def _check_audio(audio, what: str, dtypes=(torch.float32, torch.int16)):
+  _args.tensor(f"{what}: audio", audio, dtypes=dtypes, ndim=2)
+  if audio.shape[0] < 1 or not 1 <= audio.shape[1] <= MAX_SAMPLES:
+    raise _lib.WgError(f"{what}: audio [B, N] with B >= 1 and 1 <= N <= {MAX_SAMPLES} expected, got {tuple(audio.shape)}")
 
 
 def resample_enqueue(audio: torch.Tensor, lengths_dev: torch.Tensor, sr_in, sr_out, *, clip: bool = False,
@@ -125,12 +120,9 @@ def resample_enqueue(audio: torch.Tensor, lengths_dev: torch.Tensor, sr_in, sr_o
   Returns fp32 ``[B, out_len(N)]`` -- ``[B, pitch]`` for a ``pitch >= out_len(N)`` -- with row b holding
   ``out_len(lengths[b])`` samples and zeros behind them.  ``clip`` clamps the result to [-1, 1]."""
   _check_audio(audio, "resample")
-  if not isinstance(lengths_dev, torch.Tensor) or lengths_dev.dtype != torch.int32 or lengths_dev.device.type != "cuda" or \
-      _lib.device_index(lengths_dev.device) != _lib.device_index(audio.device) or lengths_dev.dim() != 1 or \
-      lengths_dev.numel() != audio.shape[0] or not lengths_dev.is_contiguous():
-    raise _lib.WgError(f"resample_enqueue takes the lengths as a contiguous int32 tensor [{audio.shape[0]}] on {audio.device}")
-  up, down, half, taps = resample_plan(sr_in, sr_out)
   B, N = audio.shape
+  lengths_dev, _ = _args.counts("resample_enqueue: lengths", lengths_dev, B, 0, N, device=audio.device, allow_device=True)
+  up, down, half, taps = resample_plan(sr_in, sr_out)
   n_out = out_len(N, up, down)
   if pitch is not None:
     if int(pitch) < n_out:
@@ -141,44 +133,30 @@ def resample_enqueue(audio: torch.Tensor, lengths_dev: torch.Tensor, sr_in, sr_o
   audio = audio.contiguous()
   table = _device_table(up, down, half, taps, audio.device)
   out = torch.empty((B, n_out), dtype=torch.float32, device=audio.device)
-  stream = torch.cuda.current_stream(audio.device).cuda_stream
-  _lib.check(_lib.load().wg_resample(audio.data_ptr(), _lib.WG_PCM_I16 if audio.dtype == torch.int16 else _lib.WG_PCM_F32,
-                                     lengths_dev.data_ptr(), out.data_ptr(), table.data_ptr(), up, down, half,
-                                     _lib.WG_RESAMPLE_CLIP if clip else 0, B, N, n_out, C.c_void_p(stream)))
+  _lib.check(_lib.load().wg_resample(_args.ptr(audio), _lib.WG_PCM_I16 if audio.dtype == torch.int16 else _lib.WG_PCM_F32,
+                                     _args.ptr(lengths_dev), _args.ptr(out), _args.ptr(table), up, down, half,
+                                     _lib.WG_RESAMPLE_CLIP if clip else 0, B, N, n_out, _args.stream(audio.device)))
   return out
 
 
 def check_lengths(lengths, B: int, N: int) -> List[int]:
-  """``lengths`` (None: all N; a list, a tuple or a CPU tensor of B integers in [0, N]) as a list."""
-  if lengths is None:
-    return [N] * B
-  if isinstance(lengths, torch.Tensor):
-    if lengths.device.type != "cpu" or lengths.dim() != 1 or lengths.dtype.is_floating_point or \
-        lengths.dtype in (torch.bool, torch.complex64, torch.complex128):
-      raise _lib.WgError("resample takes the lengths as None, a list, a tuple or a 1-D integer CPU tensor")
-    lengths = lengths.tolist()
-  elif not isinstance(lengths, (list, tuple)):
-    raise _lib.WgError("resample takes the lengths as None, a list, a tuple or a 1-D integer CPU tensor")
-  if any(isinstance(n, bool) or not isinstance(n, (int, np.integer)) for n in lengths):
-    raise _lib.WgError(f"resample: integer lengths expected, got {list(lengths)}")
-  lens = [int(n) for n in lengths]
-  if len(lens) != B or any(n < 0 or n > N for n in lens):
-    raise _lib.WgError(f"resample: {B} lengths in [0, {N}] expected, got {lens}")
-  return lens
+  """``lengths`` (None: all N; B integers in [0, N] as ``_args.counts`` takes them) as a list."""
+  return [N] * B if lengths is None else _args.counts("resample: lengths", lengths, B, 0, N, device=None)[1]
 
 
 def resample(audio: torch.Tensor, lengths, sr_in, sr_out, *, clip: bool = False):
   """``(out, out_lengths)``: ``audio`` (fp32 or int16 ``[B, N]`` on the GPU) resampled from ``sr_in`` to ``sr_out`` Hz.
 
-  ``lengths``: None (all N), a list, a tuple or a CPU tensor of B integers in [0, N].  ``out``: fp32 ``[B, out_len(N)]`` on
-  the device, row b holding ``out_lengths[b] = out_len(lengths[b])`` samples -- ``scipy.signal.resample_poly`` of the crop,
+  ``lengths``: None (all N), or B integers as ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an
+  integer dtype; a float or a bool entry raises WgError), each in [0, N].  ``out``: fp32 ``[B, out_len(N)]`` on the
+  device, row b holding ``out_lengths[b] = out_len(lengths[b])`` samples -- ``scipy.signal.resample_poly`` of the crop,
   rounded to fp32 once -- and zeros behind them; ``out_lengths`` is a list.  Enqueues on the current stream (one small
   upload for the lengths, one launch) and never synchronises.  ``sr_in == sr_out`` copies.  CPU tensors, other dtypes,
   other ranks and lengths outside the range raise WgError."""
   _check_audio(audio, "resample")
   up, down, _, _ = resample_plan(sr_in, sr_out)
-  lens = check_lengths(lengths, audio.shape[0], audio.shape[1])
-  lens_dev = torch.tensor(lens, dtype=torch.int32).to(audio.device)
+  B, N = audio.shape
+  lens_dev, lens = _args.counts("resample: lengths", [N] * B if lengths is None else lengths, B, 0, N, device=audio.device)
   return resample_enqueue(audio, lens_dev, sr_in, sr_out, clip=clip), [out_len(n, up, down) for n in lens]
 
 
@@ -211,30 +189,22 @@ def resample_backward_enqueue(d_out: torch.Tensor, lengths_dev: torch.Tensor, sr
   ``n_out >= out_len(n_in)``, the gradient with respect to its result.  ``lengths_dev`` are the lengths of the INPUT rows,
   int32 ``[B]`` on the device.  Returns fp32 ``[B, n_in]``: written below a row's length, exact zeros behind; nothing of
   ``d_out`` at or behind ``out_len(length)`` is read."""
-  if not isinstance(d_out, torch.Tensor) or d_out.device.type != "cuda":
-    raise _lib.WgError("resample backward: d_out must be on the GPU (no CPU fallback)")
-  if d_out.dtype not in (torch.float32, torch.float64):
-    raise _lib.WgError(f"resample backward takes float32 or float64 gradients, got {d_out.dtype}")
-  if d_out.dim() != 2 or d_out.shape[0] < 1:
-    raise _lib.WgError(f"resample backward takes d_out [B, n_out], got shape {tuple(d_out.shape)}")
-  if not isinstance(lengths_dev, torch.Tensor) or lengths_dev.dtype != torch.int32 or lengths_dev.device.type != "cuda" or \
-      _lib.device_index(lengths_dev.device) != _lib.device_index(d_out.device) or lengths_dev.dim() != 1 or \
-      lengths_dev.numel() != d_out.shape[0] or not lengths_dev.is_contiguous():
-    raise _lib.WgError(f"resample backward takes the lengths as a contiguous int32 tensor [{d_out.shape[0]}] on {d_out.device}")
-  up, down, half, taps = resample_plan(sr_in, sr_out)
+  _args.tensor("resample backward: d_out", d_out, dtypes=(torch.float32, torch.float64), ndim=2)
   B, n_out = d_out.shape
   n_in = int(n_in)
-  if not 1 <= n_in <= MAX_SAMPLES:
-    raise _lib.WgError(f"resample backward: 1 <= n_in <= {MAX_SAMPLES} expected, got {n_in}")
+  if B < 1 or not 1 <= n_in <= MAX_SAMPLES:
+    raise _lib.WgError(f"resample backward: B >= 1 and 1 <= n_in <= {MAX_SAMPLES} expected, got {B} and {n_in}")
+  lengths_dev, _ = _args.counts("resample backward: lengths", lengths_dev, B, 0, n_in, device=d_out.device,
+                                allow_device=True)
+  up, down, half, taps = resample_plan(sr_in, sr_out)
   if n_out < out_len(n_in, up, down) or n_out > MAX_PITCH:
     raise _lib.WgError(f"resample backward: rows of {n_out} gradients do not fit {n_in} samples at {up}/{down}")
   d_out = d_out.contiguous()
   table = _device_table_backward(up, down, half, taps, d_out.device)
   d_in = torch.empty((B, n_in), dtype=torch.float32, device=d_out.device)
-  stream = torch.cuda.current_stream(d_out.device).cuda_stream
   _lib.check(_lib.load().wg_resample_backward(
-    d_out.data_ptr(), _lib.WG_PCM_F64 if d_out.dtype == torch.float64 else _lib.WG_PCM_F32, lengths_dev.data_ptr(),
-    d_in.data_ptr(), table.data_ptr(), up, down, half, B, n_in, n_out, C.c_void_p(stream)))
+    _args.ptr(d_out), _lib.WG_PCM_F64 if d_out.dtype == torch.float64 else _lib.WG_PCM_F32, _args.ptr(lengths_dev),
+    _args.ptr(d_in), _args.ptr(table), up, down, half, B, n_in, n_out, _args.stream(d_out.device)))
   return d_in
 
 
@@ -260,14 +230,14 @@ def resample_differentiable(audio: torch.Tensor, lengths, sr_in, sr_out, *, clip
   Without grad mode, or when ``audio`` does not require grad, this is plain ``resample``.  No double backward."""
   if clip:
     raise _lib.WgError("resample_differentiable: there is no clipped variant of the differentiable path")
-  _check_audio(audio, "resample_differentiable")
-  if audio.dtype != torch.float32:
-    raise _lib.WgError(f"resample_differentiable takes float32 audio, got {audio.dtype}")
+  _check_audio(audio, "resample_differentiable", (torch.float32,))
   up, down, _, _ = resample_plan(sr_in, sr_out)
-  lens = check_lengths(lengths, audio.shape[0], audio.shape[1])
-  if not (torch.is_grad_enabled() and audio.requires_grad):
+  B, N = audio.shape
+  graph = torch.is_grad_enabled() and audio.requires_grad
+  lens_dev, lens = _args.counts("resample_differentiable: lengths", [N] * B if lengths is None else lengths, B, 0, N,
+                                device=audio.device if graph else None)
+  if not graph:
     return resample(audio, lens, sr_in, sr_out)
-  lens_dev = torch.tensor(lens, dtype=torch.int32).to(audio.device)
   with torch.cuda.device(audio.device):
     out = _ResampleFn.apply(audio, lens_dev, sr_in, sr_out)
   return out, [out_len(n, up, down) for n in lens]

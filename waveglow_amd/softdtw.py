@@ -15,7 +15,8 @@ import math
 
 import torch
 
-from . import _lib, metrics
+from . import _args, _lib, metrics
+from ._args import ptr
 
 COSTS = {"l2": _lib.WG_SDTW_L2, "sq": _lib.WG_SDTW_SQ}
 FEATURES = ("mfcc", "mel")
@@ -37,33 +38,6 @@ def _cost(cost) -> int:
   return COSTS[cost]
 
 
-def _counts(name, frames, x):
-  """The counts of one side, checked: an int32 [B] tensor on x's device as it is (trusted, never read on the host), anything
-  else as a host list with every count in [1, T].  ``_upload`` makes the device tensor once both sides have passed."""
-  B, _, T = x.shape
-  if frames is None:
-    return [T] * B
-  if isinstance(frames, torch.Tensor) and frames.device.type == "cuda":
-    if frames.device != x.device or frames.dtype != torch.int32 or frames.dim() != 1 or frames.numel() != B:
-      raise _lib.WgError(f"{name}: frame counts on the device must be int32 [{B}] on {x.device}")
-    return frames.contiguous()
-  if isinstance(frames, torch.Tensor) and (frames.dtype.is_floating_point or frames.dtype == torch.bool or frames.dim() != 1):
-    raise _lib.WgError(f"{name}: frame counts must be integers [{B}], got {frames.dtype} {tuple(frames.shape)}")
-  try:
-    host = [int(n) for n in (frames.tolist() if isinstance(frames, torch.Tensor) else frames)]
-  except (TypeError, ValueError):
-    raise _lib.WgError(f"{name}: frame counts must be None, a list, a tuple or an integer tensor")
-  if len(host) != B:
-    raise _lib.WgError(f"{name}: {len(host)} frame counts for a batch of {B}")
-  if any(n < 1 or n > min(T, metrics.MAX_FRAMES) for n in host):
-    raise _lib.WgError(f"{name}: frame counts in [1, {min(T, metrics.MAX_FRAMES)}] expected, got {host}")
-  return host
-
-
-def _upload(counts, x):
-  return counts if isinstance(counts, torch.Tensor) else torch.tensor(counts, dtype=torch.int32).to(x.device)
-
-
 def _check(feat_a, frames_a, feat_b, frames_b, gamma, cost):
   """Every refusal, before any launch: (a, fa, b, fb, gamma, cost id) with contiguous features and device counts."""
   g, c = _gamma(gamma), _cost(cost)
@@ -71,8 +45,9 @@ def _check(feat_a, frames_a, feat_b, frames_b, gamma, cost):
   b = metrics._features("soft_dtw: feat_b", feat_b, a.device)
   if a.shape[0] != b.shape[0] or a.shape[1] != b.shape[1]:
     raise _lib.WgError(f"soft_dtw: batch and feature sizes differ, {tuple(a.shape)} against {tuple(b.shape)}")
-  fa, fb = _counts("soft_dtw: frames_a", frames_a, a), _counts("soft_dtw: frames_b", frames_b, b)
-  return a, _upload(fa, a), b, _upload(fb, b), g, c
+  fa = metrics._frames("soft_dtw: frames_a", frames_a, a, upload=False)
+  fb = metrics._frames("soft_dtw: frames_b", frames_b, b, upload=False)
+  return a, fa.to(a.device), b, fb.to(b.device), g, c
 
 
 def r_bytes(B: int, Ta: int, Tb: int) -> int:
@@ -87,9 +62,8 @@ def _forward(a, fa, b, fb, gamma, cost, keep_r):
   with torch.cuda.device(a.device):
     value = torch.empty(B, dtype=torch.float64, device=a.device)
     r = torch.empty(lib.wg_softdtw_bytes(B, Ta, Tb) // 8, dtype=torch.float64, device=a.device) if keep_r else None
-    _lib.check(lib.wg_softdtw_forward(a.data_ptr(), fa.data_ptr(), b.data_ptr(), fb.data_ptr(), gamma, cost,
-                                      value.data_ptr(), r.data_ptr() if keep_r else None, B, K, Ta, Tb,
-                                      metrics._stream(a)))
+    _lib.check(lib.wg_softdtw_forward(ptr(a), ptr(fa), ptr(b), ptr(fb), gamma, cost, ptr(value), ptr(r), B, K, Ta, Tb,
+                                      _args.stream(a.device)))
   return value, r
 
 
@@ -102,10 +76,8 @@ def _backward(a, fa, b, fb, gamma, cost, r, g_value, want_e, want_a, want_b):
     e = torch.empty((B, Ta, Tb), dtype=torch.float64, device=a.device)
     g_a = torch.empty((B, K, Ta), dtype=torch.float32, device=a.device) if want_a else None
     g_b = torch.empty((B, K, Tb), dtype=torch.float32, device=a.device) if want_b else None
-    _lib.check(lib.wg_softdtw_backward(a.data_ptr(), fa.data_ptr(), b.data_ptr(), fb.data_ptr(), gamma, cost, r.data_ptr(),
-                                       g_value.data_ptr() if g_value is not None else None, e.data_ptr(),
-                                       g_a.data_ptr() if want_a else None, g_b.data_ptr() if want_b else None, B, K, Ta, Tb,
-                                       metrics._stream(a)))
+    _lib.check(lib.wg_softdtw_backward(ptr(a), ptr(fa), ptr(b), ptr(fb), gamma, cost, ptr(r), ptr(g_value), ptr(e),
+                                       ptr(g_a), ptr(g_b), B, K, Ta, Tb, _args.stream(a.device)))
   return (e if want_e else None), g_a, g_b
 
 
@@ -136,11 +108,12 @@ def soft_dtw(feat_a: torch.Tensor, frames_a, feat_b: torch.Tensor, frames_b, gam
   [B, K, Tb] (fp32 on one GPU, K <= 128, T <= 4096) with ``frames_a[b]`` / ``frames_b[b]`` frames each, and a graph to
   whichever of the two requires grad; the same tensor may stand on both sides.  ``cost``: "l2", the Euclidean frame
   distance of ``metrics.dtw_distance`` (the value tends to its cost as gamma -> 0), or "sq", its square.  Frame counts:
-  None (all), a list, a tuple or a CPU integer tensor, checked against ``[1, T]`` before any launch, or an int32 tensor on
-  the device, which is trusted: a count outside the limits there gives a NaN value and zero gradients for that utterance.
-  Nothing behind a count is read.  Gradients are computed in fp64 and rounded to fp32 once.  Without grad mode, or when
-  nothing requires grad, only the values are computed: no R is kept and nothing is saved.  Enqueue-only; bit-reproducible;
-  no double backward."""
+  None (all), or B integers as ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an integer dtype; a
+  float or a bool entry raises WgError), each in ``[1, T]`` (checked before any launch), or an int32 tensor ``[B]`` on
+  the device, which is trusted and never read on the host: a count outside the limits there gives a NaN value and zero
+  gradients for that utterance. Nothing behind a count is read.  Gradients are computed in fp64 and rounded to fp32
+  once.  Without grad mode, or when nothing requires grad, only the values are computed: no R is kept and nothing is
+  saved.  Enqueue-only; bit-reproducible; no double backward."""
   a, fa, b, fb, g, c = _check(feat_a, frames_a, feat_b, frames_b, gamma, cost)
   if torch.is_grad_enabled() and (feat_a.requires_grad or feat_b.requires_grad):
     return _SoftDtwFn.apply(feat_a, fa, feat_b, fb, g, c)
@@ -211,12 +184,8 @@ class SoftDTWLoss(torch.nn.Module):
 
   def _check(self, mel_hat, mel_ref):
     for name, t in (("mel_hat", mel_hat), ("mel_ref", mel_ref)):
-      if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or \
-          _lib.device_index(t.device) != _lib.device_index(self.device):
-        raise _lib.WgError(f"SoftDTWLoss: {name} must be on {self.device} (no CPU fallback)")
-      if t.dtype != torch.float32:
-        raise _lib.WgError(f"SoftDTWLoss takes float32 {name}, got {t.dtype}")
-      if t.dim() != 3 or t.shape[0] < 1 or t.shape[1] < 1 or not 1 <= t.shape[2] <= metrics.MAX_FRAMES:
+      _args.tensor(f"SoftDTWLoss: {name}", t, device=self.device, ndim=3)
+      if t.shape[0] < 1 or t.shape[1] < 1 or not 1 <= t.shape[2] <= metrics.MAX_FRAMES:
         raise _lib.WgError(f"SoftDTWLoss takes {name} [B, n_mel, T] with 1 <= T <= {metrics.MAX_FRAMES}, got shape "
                            f"{tuple(t.shape)}")
     if mel_hat.shape[0] != mel_ref.shape[0] or mel_hat.shape[1] != mel_ref.shape[1]:
@@ -239,10 +208,10 @@ class SoftDTWLoss(torch.nn.Module):
 
   def _run(self, mel_hat, frames_hat, mel_ref, frames_ref):
     self._check(mel_hat, mel_ref)
-    fa = _counts("SoftDTWLoss: frames_hat", frames_hat, mel_hat)
-    fb = _counts("SoftDTWLoss: frames_ref", frames_ref, mel_ref)
+    fa = metrics._frames("SoftDTWLoss: frames_hat", frames_hat, mel_hat, upload=False)
+    fb = metrics._frames("SoftDTWLoss: frames_ref", frames_ref, mel_ref, upload=False)
     with torch.cuda.device(mel_hat.device):
-      fa, fb = _upload(fa, mel_hat), _upload(fb, mel_ref)
+      fa, fb = fa.to(mel_hat.device), fb.to(mel_ref.device)
       return soft_dtw(self.feats(mel_hat), fa, self.feats(mel_ref), fb, self.gamma, self.cost), fa, fb
 
   def values(self, mel_hat: torch.Tensor, frames_hat, mel_ref: torch.Tensor, frames_ref) -> torch.Tensor:

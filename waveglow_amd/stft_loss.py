@@ -24,7 +24,7 @@ import numpy as np
 import torch
 from scipy.signal import get_window
 
-from . import _lib
+from . import _args, _lib
 
 MAX_RESOLUTIONS, MAX_FFT = 8, 2048
 
@@ -58,26 +58,8 @@ def check_geometry(fft_sizes, hop_sizes, win_lengths):
 
 def check_lengths(lengths, B: int, N: int, min_exclusive: int):
   """``lengths`` of a padded batch [B, N] as a list of B ints, each in (min_exclusive, N]; anything else raises WgError
-  naming the offending value.  ``lengths``: a list, tuple or CPU tensor of integers.  Pure host code."""
-  if isinstance(lengths, torch.Tensor):
-    if lengths.device.type != "cpu":
-      raise _lib.WgError("lengths must be host integers (a list, a tuple or a CPU tensor)")
-    if lengths.dim() != 1 or lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
-      raise _lib.WgError(f"lengths must be a 1-D integer tensor, got {lengths.dtype} of shape {tuple(lengths.shape)}")
-    lengths = lengths.tolist()
-  elif not isinstance(lengths, (list, tuple)):
-    raise _lib.WgError(f"lengths must be a list, a tuple or a CPU tensor, got {type(lengths).__name__}")
-  if len(lengths) != B:
-    raise _lib.WgError(f"{len(lengths)} lengths for a batch of {B}")
-  out = []
-  for b, n in enumerate(lengths):
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-      raise _lib.WgError(f"lengths[{b}] = {n!r} is not an integer")
-    if not min_exclusive < n <= N:
-      raise _lib.WgError(f"lengths[{b}] = {n} is outside ({min_exclusive}, {N}] (reflect padding needs > "
-                         f"{min_exclusive} samples, the batch holds {N})")
-    out.append(int(n))
-  return out
+  naming the offending value (``_args.counts``).  Pure host code."""
+  return _args.counts("lengths", lengths, B, min_exclusive + 1, N, device=None)[1]
 
 
 class _LossFn(torch.autograd.Function):
@@ -101,28 +83,15 @@ class _LossFn(torch.autograd.Function):
 
 class _WaveformLoss(torch.nn.Module):
   """What the waveform losses over conv-STFTs share: input checks, the upload of the lengths, the choice between the
-  graph and the no-graph path, and the handle's release.  A subclass sets ``_NAME`` (its name in messages) and
-  ``_DESTROY`` (the library function that frees ``self._h``), and supplies ``_need()`` (the largest ``n_fft // 2``),
+  graph and the no-graph path.  A subclass sets ``_NAME`` (its name in messages) and ``self._h`` (its library handle, with
+  the ``_args.Handle`` that owns it in ``self._owner``), and supplies ``_need()`` (the largest ``n_fft // 2``),
   ``_run(x, y, saved, lens) -> (out3, state)`` (one library call on fp32 [B, N]; ``state`` is what the backward needs,
   nothing of it allocated unless ``saved``) and ``_backward(state, g, lens, B, N) -> gx``.  ``lens``: int32 [B] on the
   device, or None."""
 
-  def __del__(self):
-    try:
-      if getattr(self, "_h", None):
-        getattr(self.lib, self._DESTROY)(self._h)
-    except Exception:
-      pass
-
   def _check(self, x, y):
     for name, t in (("audio", x), ("target", y)):
-      if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or \
-          _lib.device_index(t.device) != _lib.device_index(self.device):
-        raise _lib.WgError(f"{self._NAME}: {name} must be on {self.device} (no CPU fallback)")
-      if t.dtype != torch.float32:
-        raise _lib.WgError(f"{self._NAME} takes float32 {name}, got {t.dtype}")
-      if t.dim() != 2:
-        raise _lib.WgError(f"{self._NAME} takes {name} [B, N], got shape {tuple(t.shape)}")
+      _args.tensor(f"{self._NAME}: {name}", t, device=self.device, ndim=2)
     if x.shape != y.shape:
       raise _lib.WgError(f"audio {tuple(x.shape)} and target {tuple(y.shape)} differ in shape")
     if y.requires_grad:
@@ -130,16 +99,11 @@ class _WaveformLoss(torch.nn.Module):
     if x.shape[0] < 1 or x.shape[1] <= self._need():
       raise _lib.WgError(f"audio of {x.shape[1]} samples is too short (reflect padding needs > {self._need()})")
 
-  def _lens(self, lengths, x):
-    """The checked lengths as an int32 tensor on x's device (one small copy), or None."""
-    if lengths is None:
-      return None
-    B, N = x.shape
-    return torch.tensor(check_lengths(lengths, B, N, self._need()), dtype=torch.int32).to(x.device)
-
   def _out3(self, audio, target, lengths=None):
     self._check(audio, target)
-    lens = self._lens(lengths, audio)
+    B, N = audio.shape
+    lens = None if lengths is None else \
+        _args.counts(f"{self._NAME}: lengths", lengths, B, self._need() + 1, N, device=audio.device)[0]
     if torch.is_grad_enabled() and audio.requires_grad:
       return _LossFn.apply(self, audio, target, lens)
     return self._run(audio, target, saved=False, lens=lens)[0]
@@ -157,10 +121,11 @@ class MultiResolutionSTFTLoss(_WaveformLoss):
   """``crit(audio, target, lengths=None)`` -> 0-dim fp32 loss on the device with a graph back to ``audio``;
   ``crit.terms(audio, target, lengths=None)`` -> ``(sc, mag)``.
 
-  ``lengths``: B host integers (list, tuple or CPU tensor), the sample count of every utterance of a padded batch, each
-  in ``(max(fft_sizes) / 2, N]`` (checked on the host by ``check_lengths``, WgError otherwise); they go up in one small
-  copy per call.  The loss is then that of the crops ``audio[b, :lengths[b]]`` with their frames concatenated (see the
-  module docstring), ``audio.grad[b, lengths[b]:]`` is 0, and ``lengths=[N] * B`` gives the bits of ``lengths=None``.
+  ``lengths``: B integers as ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an integer dtype; a
+  float or a bool entry raises WgError), the sample count of every utterance of a padded batch, each in
+  ``(max(fft_sizes) / 2, N]``; they go up in one small copy per call.  The loss is then that of the crops ``audio[b,
+  :lengths[b]]`` with their frames concatenated (see the module docstring), ``audio.grad[b, lengths[b]:]`` is 0, and
+  ``lengths=[N] * B`` gives the bits of ``lengths=None``.
 
   ``audio``, ``target``: fp32 ``[B, N]`` on the module's device, same shape, ``N > max(fft_sizes) / 2``; anything else
   raises WgError.  Only ``audio`` gets a gradient (a ``target`` that requires grad raises WgError); the clamp at ``eps``
@@ -172,7 +137,7 @@ class MultiResolutionSTFTLoss(_WaveformLoss):
   (it need not divide ``n_fft``) and ``1 <= win_length <= n_fft``; ``window`` is any name ``scipy.signal.get_window``
   knows.  Everything else raises WgError at construction."""
 
-  _NAME, _DESTROY = "MultiResolutionSTFTLoss", "wg_stftloss_destroy"
+  _NAME = "MultiResolutionSTFTLoss"
 
   def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240),
                window="hann", factor_sc=1.0, factor_mag=1.0, eps=1e-7, device="cuda"):
@@ -192,7 +157,8 @@ class MultiResolutionSTFTLoss(_WaveformLoss):
     bases = [forward_basis(nf, w, window) for nf, _, w in self.resolutions]
     arr = lambda v: (C.c_int32 * n)(*v)
     ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bases])
-    self._h = C.c_void_p()
+    self._owner = _args.Handle(self.lib, "wg_stftloss_destroy")
+    self._h = self._owner.value                # what every call takes; the owner releases it
     _lib.check(self.lib.wg_stftloss_create(n, arr(fft_sizes), arr(hop_sizes), arr(win_lengths), ptrs, self.eps,
                                            _lib.device_index(device), C.byref(self._h)))
 
@@ -209,22 +175,17 @@ class MultiResolutionSTFTLoss(_WaveformLoss):
     """One library call on contiguous fp32 [B, N]: (out3, workspace).  lens: int32 [B] on the device, or None."""
     x, y = x.detach().contiguous(), y.detach().contiguous()
     B, N = x.shape
-    nbytes = self.lib.wg_stftloss_workspace_bytes(self._h, B, N, 1 if saved else 0)
-    if nbytes == 0:
-      raise _lib.WgError(f"MultiResolutionSTFTLoss: unsupported batch {B} x {N}")
+    ws = _args.workspace(self.lib.wg_stftloss_workspace_bytes(self._h, B, N, 1 if saved else 0), x.device,
+                         f"MultiResolutionSTFTLoss: batch {B} x {N}")
     out = torch.empty(3, dtype=torch.float32, device=x.device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _lib.check(self.lib.wg_stftloss_forward(self._h, x.data_ptr(), y.data_ptr(),
-                                            lens.data_ptr() if lens is not None else None, self.factor_sc,
-                                            self.factor_mag, out.data_ptr(), B, N, 1 if saved else 0, ws.data_ptr(),
-                                            ws.numel(), C.c_void_p(stream)))
+    _lib.check(self.lib.wg_stftloss_forward(self._h, _args.ptr(x), _args.ptr(y), _args.ptr(lens), self.factor_sc,
+                                            self.factor_mag, _args.ptr(out), B, N, 1 if saved else 0, _args.ptr(ws),
+                                            ws.numel(), _args.stream(x.device)))
     return out, ws
 
   def _backward(self, ws, g, lens, B, N):
     gx = torch.empty((B, N), dtype=torch.float32, device=ws.device)
-    stream = torch.cuda.current_stream(ws.device).cuda_stream
-    _lib.check(self.lib.wg_stftloss_backward(self._h, g.data_ptr(), lens.data_ptr() if lens is not None else None,
-                                             self.factor_sc, self.factor_mag, gx.data_ptr(), B, N, ws.data_ptr(),
-                                             ws.numel(), C.c_void_p(stream)))
+    _lib.check(self.lib.wg_stftloss_backward(self._h, _args.ptr(g), _args.ptr(lens), self.factor_sc,
+                                             self.factor_mag, _args.ptr(gx), B, N, _args.ptr(ws), ws.numel(),
+                                             _args.stream(ws.device)))
     return gx

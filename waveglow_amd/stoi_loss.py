@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, metrics, resample
+from . import _args, _lib, metrics, resample
 
 
 class _ScoresFn(torch.autograd.Function):
@@ -44,13 +44,15 @@ class STOILoss(torch.nn.Module):
   ``crit.scores(audio, target, lengths=None)`` -> fp64 ``[B, 2]`` (STOI, ESTOI), NaN where an utterance has no segment.
 
   ``audio`` (processed) and ``target`` (clean): fp32 ``[B, N]`` on the module's device at ``sampling_rate``, same shape.
-  Only ``audio`` gets a gradient (a ``target`` that requires grad raises WgError).  ``lengths``: None (all N), a list, a
-  tuple or a CPU integer tensor of B counts in ``[0, N]``; samples behind a length are never read and their gradient is
-  exactly 0.  The scores are the bits of ``metrics.intelligibility_metrics_enqueue(target, lengths, audio, lengths,
-  sampling_rate)``.  The loss averages over the utterances that have a segment -- the mask and the means are small tensor
-  ops on the device, nothing is read back -- and is 0 with zero gradients when none has.  CPU tensors, other dtypes or
-  ranks, a shape mismatch and a rate the resampler refuses raise WgError before any launch.  Forward and backward enqueue
-  on the current stream and never synchronise; values and gradients are bit-reproducible.  No double backward."""
+  Only ``audio`` gets a gradient (a ``target`` that requires grad raises WgError).  ``lengths``: None (all N), or B
+  integers as ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an integer dtype; a float or a bool
+  entry raises WgError), each in ``[0, N]``; samples behind a length are never read and their gradient is exactly 0.
+  The scores are the bits of ``metrics.intelligibility_metrics_enqueue(target, lengths, audio, lengths,
+  sampling_rate)``.  The loss averages over the utterances that have a segment -- the mask and the means are small
+  tensor ops on the device, nothing is read back -- and is 0 with zero gradients when none has.  CPU tensors, other
+  dtypes or ranks, a shape mismatch and a rate the resampler refuses raise WgError before any launch.  Forward and
+  backward enqueue on the current stream and never synchronise; values and gradients are bit-reproducible.  No double
+  backward."""
 
   def __init__(self, sampling_rate=22050, factor_stoi=1.0, factor_estoi=0.0, device="cuda"):
     super().__init__()
@@ -75,12 +77,8 @@ class STOILoss(torch.nn.Module):
 
   def _check(self, audio, target):
     for name, t in (("audio", audio), ("target", target)):
-      if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or \
-          _lib.device_index(t.device) != _lib.device_index(self.device):
-        raise _lib.WgError(f"STOILoss: {name} must be on {self.device} (no CPU fallback)")
-      if t.dtype != torch.float32:
-        raise _lib.WgError(f"STOILoss takes float32 {name}, got {t.dtype}")
-      if t.dim() != 2 or t.shape[0] < 1 or t.shape[0] > 65535 or t.shape[1] < 1:
+      _args.tensor(f"STOILoss: {name}", t, device=self.device, ndim=2)
+      if t.shape[0] < 1 or t.shape[0] > 65535 or t.shape[1] < 1:
         raise _lib.WgError(f"STOILoss takes {name} [B, N] with 1 <= B <= 65535 and N >= 1, got shape {tuple(t.shape)}")
     if audio.shape != target.shape:
       raise _lib.WgError(f"audio {tuple(audio.shape)} and target {tuple(target.shape)} differ in shape")
@@ -102,9 +100,9 @@ class STOILoss(torch.nn.Module):
   def scores(self, audio: torch.Tensor, target: torch.Tensor, lengths=None) -> torch.Tensor:
     """fp64 ``[B, 2]``: STOI and ESTOI of every utterance, with a graph back to ``audio`` in grad mode."""
     self._check(audio, target)
-    lens = resample.check_lengths(lengths, audio.shape[0], audio.shape[1])
+    B, N = audio.shape
     with torch.cuda.device(audio.device):
-      lens = torch.tensor(lens, dtype=torch.int32).to(audio.device)
+      lens = _args.counts("STOILoss: lengths", [N] * B if lengths is None else lengths, B, 0, N, device=audio.device)[0]
       if torch.is_grad_enabled() and audio.requires_grad:
         return _ScoresFn.apply(self, audio, target, lens)
       x10, y10, n10 = self._to_10k(audio.detach(), target, lens)

@@ -27,7 +27,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 # columns of the statistics, one row of 8 floats per chunk (include/waveglow_amd.h: wg_stream_emit)
 RAW_MIN, RAW_MAX, DEN_MIN, DEN_MAX, CLIPPED, NON_FINITE = range(6)
@@ -164,9 +164,8 @@ def gather_launch(table_ptr: int, B: int, n_mel: int, n_mel_out: int, n_rem: int
     if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != torch.device(device):
       raise _lib.WgError(f"stream gather: an output is not a contiguous {dtype} tensor {shape} on {device}")
   ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
-  stream = torch.cuda.current_stream(device).cuda_stream
-  _lib.check(_lib.load().wg_stream_gather(table_ptr, mel.data_ptr(), z_init.data_ptr(), ze, n_early, B, n_mel, n_mel_out,
-                                          n_rem, n_early_size, w_max, cpf, _io(dtype), C.c_void_p(stream)))
+  _lib.check(_lib.load().wg_stream_gather(table_ptr, _args.ptr(mel), _args.ptr(z_init), ze, n_early, B, n_mel, n_mel_out,
+                                          n_rem, n_early_size, w_max, cpf, _io(dtype), _args.stream(device)))
   return mel, z_init, list(z_early)
 
 
@@ -205,9 +204,8 @@ def emit_launch(table_ptr: int, B: int, n_max: int, device) -> torch.Tensor:
   """One ``wg_stream_emit`` launch on the current stream from a table already on the device.  Returns one uint8 device
   buffer: the int16 samples [B, n_max], then the statistics [B, 8] fp32 -- what ``emit_read`` takes apart on the host."""
   out = torch.empty(2 * B * n_max + 4 * N_STATS * B, dtype=torch.uint8, device=device)
-  stream = torch.cuda.current_stream(device).cuda_stream
-  _lib.check(_lib.load().wg_stream_emit(table_ptr, out.data_ptr(), out.data_ptr() + 2 * B * n_max, B, n_max,
-                                        C.c_void_p(stream)))
+  _lib.check(_lib.load().wg_stream_emit(table_ptr, _args.ptr(out), out.data_ptr() + 2 * B * n_max, B, n_max,
+                                        _args.stream(device)))
   return out
 
 
@@ -419,10 +417,9 @@ def _infer_windows(eng, mel, frames_dev, z_init, z_early, sigma, audio) -> None:
   nbytes = eng.workspace_bytes("infer", B, T)
   ws = eng.workspace("infer", nbytes, (B, T, 0))
   ze = (C.c_void_p * max(1, len(z_early)))(*[z.data_ptr() for z in z_early])
-  stream = torch.cuda.current_stream(mel.device).cuda_stream
-  _lib.check(eng.lib.wg_infer(eng.handle, mel.data_ptr(), frames_dev.data_ptr(), z_init.data_ptr(), ze, len(z_early),
-                              float(sigma), audio.data_ptr(), B, T, _io(mel.dtype), ws.data_ptr(), ws.numel(),
-                              C.c_void_p(stream)))
+  _lib.check(eng.lib.wg_infer(eng.handle, _args.ptr(mel), _args.ptr(frames_dev), _args.ptr(z_init), ze, len(z_early),
+                              float(sigma), _args.ptr(audio), B, T, _io(mel.dtype), _args.ptr(ws), ws.numel(),
+                              _args.stream(mel.device)))
 
 
 def stream_step(synth, sessions: Sequence[StreamSession], pcm: bool = True) -> list:

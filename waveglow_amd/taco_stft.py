@@ -19,10 +19,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .audio import convert_wav, wav_to_float32
-from .denoiser import stft_bases
-from .stft_loss import check_lengths
+from .denoiser import stft_handle
 
 FLOAT32_64_MIN_WAV, FLOAT32_64_MAX_WAV = -1.0, 1.0   # audio_utils.py
 
@@ -104,16 +103,13 @@ class _MelFn(torch.autograd.Function):
   def forward(ctx, taco, y, lens):
     y = y.contiguous()
     B, N = y.shape
-    lib = taco.lib
-    nbytes = lib.wg_stft_mel_grad_workspace_bytes(taco._h, B, N)
-    if nbytes == 0:
-      raise _lib.WgError(f"mel front-end: audio of {N} samples is too short (reflect padding needs > 512)")
+    h = taco._h
+    ws = _args.workspace(taco.lib.wg_stft_mel_grad_workspace_bytes(h, B, N), y.device,
+                         f"mel front-end: audio of {N} samples is too short (reflect padding needs > 512)")
     mel = torch.empty((B, taco.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=y.device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
-    stream = torch.cuda.current_stream(y.device).cuda_stream
-    _lib.check(lib.wg_stft_mel_forward_saved(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, y.data_ptr(),
-                                             lens.data_ptr() if lens is not None else None, mel.data_ptr(), B, N,
-                                             ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    _lib.check(taco.lib.wg_stft_mel_forward_saved(h, _args.ptr(taco.mel_basis), taco.n_mel_channels, _args.ptr(y),
+                                                  _args.ptr(lens), _args.ptr(mel), B, N, _args.ptr(ws), ws.numel(),
+                                                  _args.stream(y.device)))
     ctx.taco, ctx.ws, ctx.dims, ctx.lens = taco, ws, (B, N), lens
     return mel
 
@@ -123,10 +119,9 @@ class _MelFn(torch.autograd.Function):
     B, N = ctx.dims
     g = g_mel.to(torch.float32).contiguous()
     gy = torch.empty((B, N), dtype=torch.float32, device=ws.device)
-    stream = torch.cuda.current_stream(ws.device).cuda_stream
-    _lib.check(taco.lib.wg_stft_mel_backward(taco._h, taco.mel_basis.data_ptr(), taco.n_mel_channels, g.data_ptr(),
-                                             ctx.lens.data_ptr() if ctx.lens is not None else None, gy.data_ptr(), B, N,
-                                             ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    _lib.check(taco.lib.wg_stft_mel_backward(taco._h, _args.ptr(taco.mel_basis), taco.n_mel_channels, _args.ptr(g),
+                                             _args.ptr(ctx.lens), _args.ptr(gy), B, N, _args.ptr(ws), ws.numel(),
+                                             _args.stream(ws.device)))
     return None, gy, None
 
 
@@ -143,20 +138,11 @@ class TacotronSTFT(torch.nn.Module):
     self.sampling_rate = hparams.sampling_rate
     self.device = device
     self.lib = _lib.load()
-    fwd, inv, wsq = stft_bases(hparams.filter_length, hparams.hop_length, hparams.win_length, hparams.window)
-    self._h = C.c_void_p()
-    _lib.check(self.lib.wg_stft_create(fwd.ctypes.data, inv.ctypes.data, wsq.ctypes.data, hparams.filter_length,
-                                       hparams.hop_length, _lib.device_index(device), C.byref(self._h)))
+    self._owner = stft_handle(self.lib, hparams, device, hparams.window)
+    self._h = self._owner.value                # what every call takes; the owner releases it
     basis = slaney_mel_filterbank(hparams.sampling_rate, hparams.filter_length, hparams.n_mel_channels,
                                   hparams.mel_fmin, hparams.mel_fmax)
     self.register_buffer("mel_basis", torch.from_numpy(basis).to(device))
-
-  def __del__(self):
-    try:
-      if getattr(self, "_h", None):
-        self.lib.wg_stft_destroy(self._h)
-    except Exception:
-      pass
 
   def spectral_normalize(self, magnitudes):
     return dynamic_range_compression(magnitudes)
@@ -174,16 +160,12 @@ class TacotronSTFT(torch.nn.Module):
     """wg_stft_mel on contiguous fp32 audio [B, N] on the module's device, with the device copy of the lengths
     (int32 [B]) of a ragged batch or None; no graph."""
     B, N = y.shape
-    nbytes = self.lib.wg_stft_mel_workspace_bytes(self._h, B, N)
-    if nbytes == 0:
-      raise _lib.WgError(f"mel front-end: audio of {N} samples is too short (reflect padding needs > 512)")
-    F_ = N // 256 + 1
-    out = torch.empty((B, self.n_mel_channels, F_), dtype=torch.float32, device=y.device)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=y.device)
-    stream = torch.cuda.current_stream(y.device).cuda_stream
-    _lib.check(self.lib.wg_stft_mel(self._h, self.mel_basis.data_ptr(), self.n_mel_channels, y.data_ptr(),
-                                    lens_dev.data_ptr() if lens_dev is not None else None, out.data_ptr(), B, N,
-                                    ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    ws = _args.workspace(self.lib.wg_stft_mel_workspace_bytes(self._h, B, N), y.device,
+                         f"mel front-end: audio of {N} samples is too short (reflect padding needs > 512)")
+    out = torch.empty((B, self.n_mel_channels, N // 256 + 1), dtype=torch.float32, device=y.device)
+    _lib.check(self.lib.wg_stft_mel(self._h, _args.ptr(self.mel_basis), self.n_mel_channels, _args.ptr(y),
+                                    _args.ptr(lens_dev), _args.ptr(out), B, N, _args.ptr(ws), ws.numel(),
+                                    _args.stream(y.device)))
     return out
 
   def mel_spectrogram_ragged(self, wavs):
@@ -223,22 +205,19 @@ class TacotronSTFT(torch.nn.Module):
   def mel_spectrogram_ragged_device(self, audio: torch.Tensor, lens):
     """``mel_spectrogram_ragged`` of audio that is on the device already (synthesised audio on its way to the metrics).
 
-    ``audio``: fp32 [B, N] on the module's device, row b holding ``lens[b]`` samples; ``lens``: B host integers in
-    (512, N].  Returns ``(mel, frames, frames_dev)``: ``mel`` [B, n_mel_channels, N // 256 + 1], ``frames[b] = lens[b] //
-    256 + 1`` as a list and as an int32 tensor on the device; ``mel[b, :, :frames[b]]`` is bit for bit
-    ``mel_spectrogram(audio[b:b+1, :lens[b]])[0]`` and the columns behind it are 0.  The device copy of ``lens`` is uploaded
-    here.  No range assert and no synchronise: the caller answers for the audio lying in [-1, 1].  No graph."""
-    if not isinstance(audio, torch.Tensor) or audio.device.type != "cuda" or \
-        _lib.device_index(audio.device) != _lib.device_index(self.device):
-      raise _lib.WgError(f"mel_spectrogram_ragged_device: audio must be on {self.device} (no CPU fallback)")
-    if audio.dtype != torch.float32 or audio.dim() != 2:
-      raise _lib.WgError("mel_spectrogram_ragged_device takes float32 audio [B, N]")
+    ``audio``: fp32 [B, N] on the module's device, row b holding ``lens[b]`` samples; ``lens``: B integers as
+    ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an integer dtype; a float or a bool entry raises
+    WgError), each in (512, N].  Returns ``(mel, frames, frames_dev)``: ``mel`` [B, n_mel_channels, N // 256 + 1],
+    ``frames[b] = lens[b] // 256 + 1`` as a list and as an int32 tensor on the device; ``mel[b, :, :frames[b]]`` is bit
+    for bit ``mel_spectrogram(audio[b:b+1, :lens[b]])[0]`` and the columns behind it are 0.  The device copy of ``lens``
+    is uploaded here.  No range assert and no synchronise: the caller answers for the audio lying in [-1, 1].  No
+    graph."""
+    _args.tensor("mel_spectrogram_ragged_device: audio", audio, device=self.device, ndim=2)
     B, N = audio.shape
-    lens = [int(n) for n in lens]
-    if len(lens) != B or B < 1:
-      raise _lib.WgError(f"mel_spectrogram_ragged_device: {len(lens)} lengths for a batch of {B}")
-    if any(n <= 512 or n > N for n in lens):
-      raise _lib.WgError(f"mel front-end: lengths in (512, {N}] expected (reflect padding needs > 512), got {lens}")
+    if B < 1:
+      raise _lib.WgError("mel_spectrogram_ragged_device: empty batch")
+    # checked only (no device): the lengths go up together with the frame counts, in one tensor, below
+    lens = _args.counts("mel_spectrogram_ragged_device: lengths", lens, B, 513, N, device=None)[1]
     audio = audio.contiguous()
     both = torch.tensor([lens, [n // 256 + 1 for n in lens]], dtype=torch.int32).to(audio.device)
     return self._mel(audio, both[0]), [n // 256 + 1 for n in lens], both[1]
@@ -246,28 +225,24 @@ class TacotronSTFT(torch.nn.Module):
   def mel_spectrogram_differentiable(self, y: torch.Tensor, lengths=None) -> torch.Tensor:
     """``mel_spectrogram(y)`` with an autograd graph back to ``y`` (taco_stft.py:84-104 without the detach at :99).
 
-    ``lengths``: B host integers in (512, N] (list, tuple or CPU tensor; WgError otherwise), the sample counts of a padded
-    batch.  The result is then what ``mel_spectrogram_ragged_device(y, lengths)`` returns as ``mel``, bit for bit: row b
-    is the mel of the crop ``y[b, :lengths[b]]`` in its first ``lengths[b] // 256 + 1`` columns and 0 behind them.  Its
-    backward ignores the gradient of those zero columns, gives ``y.grad[b, :lengths[b]]`` the bits of the crop's own
-    backward (reflect padding about its own last sample) and ``y.grad[b, lengths[b]:] = 0``.
+    ``lengths``: B integers as ``_args.counts`` takes them (a list, a tuple or a 1-D CPU tensor of an integer dtype; a
+    float or a bool entry raises WgError), each in (512, N]: the sample counts of a padded batch.  The result is then
+    what ``mel_spectrogram_ragged_device(y, lengths)`` returns as ``mel``, bit for bit: row b is the mel of the crop
+    ``y[b, :lengths[b]]`` in its first ``lengths[b] // 256 + 1`` columns and 0 behind them.  Its backward ignores the
+    gradient of those zero columns, gives ``y.grad[b, :lengths[b]]`` the bits of the crop's own backward (reflect
+    padding about its own last sample) and ``y.grad[b, lengths[b]:] = 0``.
 
     ``y`` [B, N] fp32 on the module's device, any N > 512 -> [B, n_mel_channels, N // 256 + 1], bit-identical to
     ``mel_spectrogram``.  No range assert and no host synchronisation: generated audio may leave [-1, 1].  With grad
     mode on and ``y.requires_grad`` the result's graph leads to ``y``; otherwise it is the same tensor without one.
     ``mel_basis`` is a constant.  Other devices, CPU tensors and other dtypes raise WgError."""
-    if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or \
-        _lib.device_index(y.device) != _lib.device_index(self.device):
-      raise _lib.WgError(f"mel_spectrogram_differentiable: audio must be on {self.device} (no CPU fallback)")
-    if y.dtype != torch.float32:
-      raise _lib.WgError(f"mel_spectrogram_differentiable takes float32 audio, got {y.dtype}")
-    if y.dim() != 2:
-      raise _lib.WgError(f"mel_spectrogram_differentiable takes audio [B, N], got shape {tuple(y.shape)}")
+    _args.tensor("mel_spectrogram_differentiable: audio", y, device=self.device, ndim=2)
     if lengths is not None:
-      lens = check_lengths(lengths, y.shape[0], y.shape[1], 512)
-      if torch.is_grad_enabled() and y.requires_grad:
-        return _MelFn.apply(self, y, torch.tensor(lens, dtype=torch.int32).to(y.device))
-      return self.mel_spectrogram_ragged_device(y.detach(), lens)[0]
+      B, N = y.shape
+      graph = torch.is_grad_enabled() and y.requires_grad
+      lens_dev, lens = _args.counts("mel_spectrogram_differentiable: lengths", lengths, B, 513, N,
+                                    device=y.device if graph else None)
+      return _MelFn.apply(self, y, lens_dev) if graph else self.mel_spectrogram_ragged_device(y.detach(), lens)[0]
     if torch.is_grad_enabled() and y.requires_grad:
       return _MelFn.apply(self, y, None)
     return self._mel(y.detach().contiguous())

@@ -31,6 +31,7 @@ from typing import List, Tuple
 import torch
 
 from . import _lib
+from ._args import ptr as _ptr
 
 
 def pos_perm(n: int) -> torch.Tensor:
@@ -176,10 +177,6 @@ def to_fragments(mat: torch.Tensor, c2p: torch.Tensor = None) -> torch.Tensor:
   v = mat.reshape(*lead, M // 32, 32, K // 64, 2, 4, 8).index_select(len(lead) + 1, c2p)   # [.., b, r, t, h, s, j]
   n = len(lead)
   return v.permute(*range(n), n + 2, n, n + 4, n + 3, n + 1, n + 5).contiguous()            # [.., t, b, s, h, r, j]
-
-
-def _ptr(t: torch.Tensor) -> C.c_void_p:
-  return C.c_void_p(t.data_ptr())
 
 
 K_TANH_SCALE = 2.8853900817779268     # 2*log2(e): the gate evaluates tanh / sigmoid through exp2 (kernels.hip: gate_act)
