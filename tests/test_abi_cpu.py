@@ -129,3 +129,61 @@ def test_train_entry_points_validate_arguments_without_a_gpu():
                                  0, None) == -1
     assert b"null argument" in lib.wg_last_error()
   lib.wg_destroy(h)
+
+
+FLOW_CALLS = ("wg_infer", "wg_forward", "wg_train_forward", "wg_train_backward", "wg_train_infer_forward",
+              "wg_train_infer_backward", "wg_train_prepare", "wg_train_param_grads", "wg_train_workspace_bytes")
+PACKING_CHECKER = ("pos_perm", "_PERM_CACHE", "_perms", "_Perms", "_PERM_PLAN", "to_pos_order", "_dense_stack", "_shape_runs",
+                   "pack_weights", "to_fragments", "K_TANH_SCALE", "K_SIGM_SCALE", "wn_forward_fragments", "plain_fragments",
+                   "packed_grads")
+
+
+def _package_text():
+  import glob
+  files = sorted(glob.glob(os.path.join(ROOT, "waveglow_amd", "*.py")))
+  assert len(files) >= 25
+  return {os.path.basename(f): open(f).read() for f in files}
+
+
+@pytest.mark.parametrize("name", FLOW_CALLS)
+def test_every_flow_entry_point_has_one_python_call_site(name):
+  """Each call of the C ABI that the flow itself stands on is written once in the package, comments and docstrings
+  included: a second caller is a second copy of the plumbing around it (sizes, pointer arrays, stream, error check)."""
+  sites = [(f, m.start()) for f, text in _package_text().items() for m in re.finditer(rf"\b{name}\(", text)]
+  assert len(sites) == 1, sites
+
+
+def test_the_packing_checker_is_not_in_the_package():
+  """The torch restatement of the library's weight packing is test code (tests/_packing.py): none of its names is left
+  in the package, and the tests' module needs nothing from the binding."""
+  for f, text in _package_text().items():
+    for name in PACKING_CHECKER:
+      assert not re.search(rf"(?<![A-Za-z0-9_]){name}(?![A-Za-z0-9_])", text), (f, name)
+  packing = open(os.path.join(ROOT, "tests", "_packing.py")).read()
+  for name in PACKING_CHECKER[:-1]:
+    assert re.search(rf"^(def|class) {name}\b|^{name}\b", packing, flags=re.M), name
+  assert "waveglow_amd" not in re.sub(r'""".*?"""', "", packing, flags=re.S)
+
+
+def test_parameter_of_another_size_is_refused_by_name(lib):
+  """canonical_params holds every parameter to the element count the library will read and write for it
+  (wg_train_param_numel), before the dtype / device checks and before anything is launched: on a handle-only engine
+  (no GPU) a model whose flow-1 ``end`` conv has 2 output rows instead of 2 h = 8 is refused by name."""
+  import importlib
+  import torch
+  from waveglow_amd import synthetic
+  train = importlib.import_module("waveglow_amd.train")      # the package also exports a function of this name
+  from waveglow_amd.hparams import HParams
+  from waveglow_amd.model import WaveGlow, _Engine
+  hp = HParams(n_channels=64, n_layers=4, n_flows=4, n_early_every=2)
+  model = WaveGlow(hp)
+  model.load_state_dict(synthetic.to_weightnorm_form(synthetic.make_state_dict(hp, seed=3)))
+  eng = _Engine(hp, torch.device("cuda", 0))
+  with pytest.raises(_lib.WgError, match="the GPU"):          # sizes agree: the next check (CPU tensors) speaks
+    train.canonical_params(model, eng)
+  names, numels = eng.cache[("train_params", True)]
+  assert numels[names.index("WN.1.end.weight")] == 512 and numels == [dict(model.named_parameters())[n].numel() for n in names]
+  model.WN[1].end = torch.nn.Conv1d(64, 2, 1)                 # 128 elements where flow 1 (h = 4) has 8 x 64
+  with pytest.raises(_lib.WgError, match=r"WN\.1\.end\.weight.*128.*512"):
+    train.canonical_params(model, eng)
+  assert eng._train_pool == []

@@ -16,6 +16,7 @@ import torch
 from _cases import GRAD_TOL, _check, oracle_cfg_from_hp
 from _prepare import check_prepare_matches_torch_packing
 from waveglow_amd import synthetic
+from waveglow_amd._lib import WgError
 from waveglow_amd.hparams import HParams
 from waveglow_amd.model import WaveGlow, WaveGlowLoss
 
@@ -404,7 +405,7 @@ def test_custom_grad_scale_and_finite_check(monkeypatch):
 def test_prepare_matches_torch_packing(channels, wn):
   """wg_train_prepare (the library reads the module's own parameter tensors: weight norm, W_end x W_skip fold, permutations,
   gate pre-scale, fragment orders -- train_prep.hip, pack_kernel) against the same computation written as torch ops
-  (waveglow_amd/train.py: pack_weights, wn_forward_fragments, plain_fragments, to_fragments -- pinned element by element to
+  (tests/_packing.py: pack_weights, wn_forward_fragments, plain_fragments, to_fragments -- pinned element by element to
   the header's index maps in tests/test_host_cpu.py).  Dense weights (after remove_weightnorm): every tensor that is pure
   data movement is bit-identical; with weight norm (and for the fold) the fp32 summation order differs from torch's, so
   fp16 values may differ in the last place."""
@@ -445,3 +446,68 @@ def test_unfused_dgrad_launches_give_the_same_gradients(channels, monkeypatch):
   _, _, plain = _gpu_step(hp, sd, mel, wav)
   for name in fused:
     assert torch.equal(fused[name], plain[name]), name
+
+
+# ------------------------------------------------------------------ what backward() and forward() refuse
+SMALL = dict(n_channels=64, n_layers=4, n_flows=4, n_early_every=2)      # flow channels 8, 8, 6, 6
+
+
+def _small_model():
+  """(model on the GPU, mel [1, 80, 4], audio [1, 1024])."""
+  hp, sd, mel, wav = _setup(SMALL, 1, 4, 7, crop=0)
+  model = WaveGlow(hp)
+  model.load_state_dict(sd)
+  return model.to("cuda:0").train(), mel.cuda(), wav.cuda()
+
+
+def _small_grads(model, mel, wav):
+  model.zero_grad()
+  WaveGlowLoss(1.0)(model((mel, wav)), None).backward()
+  torch.cuda.synchronize()
+  assert bool(model.grad_finite)
+  return {n: p.grad.detach().clone() for n, p in model.named_parameters()}
+
+
+@pytest.fixture(scope="module")
+def untouched_twin_grads():
+  model, mel, wav = _small_model()
+  return _small_grads(model, mel, wav)
+
+
+@pytest.mark.parametrize("how", ["in_place", "new_storage"])
+def test_backward_refuses_weights_that_moved_since_the_forward(how, untouched_twin_grads):
+  """wg_train_param_grads reads the parameters again in backward(): one that was written in place since the forward (a
+  version bump; the values stay) or was given another storage (same version, another data_ptr) makes backward() raise
+  before any launch, the workspace goes back to the pool, and the next step on the same model has the bits of a model that
+  was never touched."""
+  model, mel, wav = _small_model()
+  loss = WaveGlowLoss(1.0)(model((mel, wav)), None)
+  p = model.WN[1].in_layers[0].bias
+  version, address = p._version, p.data_ptr()
+  with torch.no_grad():
+    if how == "in_place":
+      p.mul_(1.0)
+      assert p._version > version and p.data_ptr() == address
+    else:
+      p.data = p.data.clone()
+      assert p._version == version and p.data_ptr() != address
+  with pytest.raises(WgError, match="weights changed"):
+    loss.backward()
+  pool = model._engine._train_pool
+  assert len(pool) == 1 and not pool[0]["busy"]
+  grads = _small_grads(model, mel, wav)          # (zero_grad first: the logdet branch may have run before the refusal)
+  assert len(pool) == 1 and not pool[0]["busy"]
+  assert grads.keys() == untouched_twin_grads.keys()
+  for n, g in grads.items():
+    assert torch.equal(g, untouched_twin_grads[n]), n
+
+
+def test_forward_refuses_a_parameter_of_another_size_by_name():
+  """A module edited after construction: flow 1 has h = 4, so ``WN[1].end.weight`` has 8 x 64 = 512 elements and the
+  library would read and write that many through the bare pointer.  Refused by name before anything is launched or held."""
+  model, mel, wav = _small_model()
+  model._get_engine(mel.device, need_weights=False)
+  model.WN[1].end = torch.nn.Conv1d(64, 2, 1).to("cuda:0")
+  with pytest.raises(WgError, match=r"WN\.1\.end\.weight"):
+    model((mel, wav))
+  assert model._engine._train_pool == []

@@ -150,7 +150,7 @@ def test_stft_oracle_is_self_consistent():
 
 
 def test_training_weight_packing_reproduces_the_reference_forward():
-  """Host logic of the training direction (waveglow_amd/train.py: pack_weights) without the GPU: a plain-torch
+  """Host logic of the training direction (tests/_packing.py: pack_weights) without the GPU: a plain-torch
   evaluation of exactly the matrices the library receives -- (pos,pos) permutation, tap-major K, cond slice as a
   K-segment, W_end folded into the skip rows, per-phase upsample matrices -- must reproduce the oracle's forward."""
   import torch
@@ -159,7 +159,7 @@ def test_training_weight_packing_reproduces_the_reference_forward():
   from waveglow_amd import synthetic
   from waveglow_amd.hparams import HParams
   from waveglow_amd.model import WaveGlow
-  from waveglow_amd.train import _perms, pack_weights, pos_perm, to_fragments, to_pos_order
+  from _packing import _perms, pack_weights, pos_perm, to_fragments, to_pos_order
   hp = HParams(n_channels=64, n_layers=3, n_flows=4, n_early_every=2)
   sd = synthetic.to_weightnorm_form(synthetic.make_state_dict(hp, seed=2))
   model = WaveGlow(hp)
@@ -343,11 +343,11 @@ def test_wav_helpers_match_reference_fixture(tmp_path):
 
 def test_wn_kernel_fragment_orders():
   """The A-fragment orders of the WN-layer kernel as the training direction packs them on the device
-  (waveglow_amd/train.py: wn_forward_fragments, plain_fragments; include/waveglow_amd.h: wg_train_weights a1 / a1c / a2 /
+  (tests/_packing.py: wn_forward_fragments, plain_fragments; include/waveglow_amd.h: wg_train_weights a1 / a1c / a2 /
   es / wat / wbt): every element of the packed tensors against the documented index map, on matrices whose entries encode
   their own (row, column)."""
   import torch
-  from waveglow_amd.train import K_SIGM_SCALE, K_TANH_SCALE, _perms, plain_fragments, pos_perm, wn_forward_fragments
+  from _packing import K_SIGM_SCALE, K_TANH_SCALE, _perms, plain_fragments, pos_perm, wn_forward_fragments
   Cc, M8, NW, FL = 64, 128, 2, 2
   MB = Cc // (32 * NW)
   pm = _perms(Cc, M8, torch.device("cpu"))
@@ -414,9 +414,9 @@ def test_batched_log_det_w_equals_per_flow_logdet():
 
 
 def test_shape_runs_keep_flow_order():
-  """waveglow_amd/train.py: _shape_runs -- the per-flow small tensors (end, start, 1x1; model.py:165-176: c_k drops at
+  """tests/_packing.py: _shape_runs -- the per-flow small tensors (end, start, 1x1; model.py:165-176: c_k drops at
   the early outputs) are stacked per run of equal shape; concatenating the runs must give back flow order."""
-  from waveglow_amd.train import _shape_runs
+  from _packing import _shape_runs
   assert _shape_runs([8, 8, 8, 8, 6, 6, 6, 6, 4, 4, 4, 4]) == [(8, [0, 1, 2, 3]), (6, [4, 5, 6, 7]), (4, [8, 9, 10, 11])]
   assert _shape_runs([4]) == [(4, [0])]
   runs = _shape_runs([8, 6, 8, 8])                  # a shape that comes back starts a new run: order is never permuted

@@ -3,15 +3,14 @@ the oracle alone -- that the family leaves everything but the (g, v) gradients a
 family (g = ||v||, row scale s = 1) cannot: faults in how the weight-norm row scale is indexed and applied.
 
 (a), (b): invariance in both directions.  (c): each fault is planted into a torch restatement of what the library does with
-the row scale -- ``waveglow_amd.train.pack_weights`` (the packing wg_train_prepare is held to) with its weight-norm
+the row scale -- ``_packing.pack_weights`` (the packing wg_train_prepare is held to) with its weight-norm
 evaluation replaced by ``v * s[index]`` and the backward formulas of csrc/train_prep.hip: wn_grad_kernel -- and must change
 nothing on the manifold and more than 10 x GRAD_TOL off it.
 """
-import importlib
-
 import pytest
 import torch
 
+import _packing as T
 from _cases import GRAD_TOL, Case, oracle_cfg_from_hp, rms
 from _offmanifold import (FLOOR, V0, V1, check, floor_only_names, oracle_infer_grads, raw_worst, reparametrise,
                           to_on_metric)
@@ -19,8 +18,6 @@ from oracle import torch_oracle as O
 from waveglow_amd import synthetic
 from waveglow_amd.hparams import HParams
 from waveglow_amd.model import WaveGlow
-
-T = importlib.import_module("waveglow_amd.train")      # the package also exports a function of this name
 
 INVARIANT_TOL = 1e-5      # the relations between the two parametrisations, relative L2 per tensor (measured 4e-7)
 OVER = dict(n_channels=64, n_layers=3, n_flows=4, n_early_every=1, n_early_size=2)      # h_k = 4, 3, 2, 1

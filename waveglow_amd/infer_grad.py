@@ -19,22 +19,21 @@ synthesises): the backward then also runs the training direction's weight-gradie
 Both take the per-utterance frame counts of a padded batch (``infer_differentiable(..., frames=)``: int32 [B] on the
 device, kept on ``ctx`` for the backward), or none for a dense one.
 
-The binding uses ``_TrainFn``'s plumbing (waveglow_amd/train.py): ``_Weights`` from ``wg_train_prepare``, one training
-workspace per outstanding graph (``request_workspace``), the fp16 loss scale and ``model.grad_finite``
-(``set_grad_finite``), ``param_grad_views``.  Its own: the stale-weights check.  There is no fallback: CPU tensors raise.
+The node's lifecycle is ``_TrainFn``'s (waveglow_amd/train.py: ``begin_node`` / ``finish_node``): per-call weights from
+``wg_train_prepare``, one training workspace per outstanding graph, the fp16 loss scale and ``model.grad_finite``, the
+refusal of a second backward() and of weights that moved in between.  Its own: its two library calls, and in the frozen
+mode the rule that the inference engine was not re-finalised since.  There is no fallback: CPU tensors raise.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import List
 
 import torch
 
 from . import _args, _lib
 from ._args import ptr as _ptr
-from .train import (GradBuffers, _ddp_group, _SlotGuard, _Weights, canonical_params, new_grad, param_grad_views,
-                    request_workspace, set_grad_finite)
+from .train import _ddp_group, begin_node, canonical_params, finish_node, new_grad
 
 
 class _InferFn(torch.autograd.Function):
@@ -54,79 +53,44 @@ class _InferFn(torch.autograd.Function):
     # frozen: finalised with the current weights, the W^-1 of infer.  Weight-gradient mode: the weights move every step,
     # W^-1 comes with the per-call weights and the inference engine is left alone
     eng = model._get_engine(mel.device, need_weights=not wgrads)
-    lib = eng.lib
     B, M, T = mel.shape
-    flow_c = model.flow_channels()
-    stream = _args.stream(mel.device).value     # as an int: _Weights takes it so
-    want_mel = ctx.needs_input_grad[_InferFn.N_META]
-    wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=want_mel, want_winv=wgrads)
     S = 256 * T
-    slot, fresh = request_workspace(eng, B, T, S, flags)             # held until this graph's backward has run
-    ws = slot["ws"]
+    stream = _args.stream(mel.device).value     # as an int: _Weights takes it so
+    # the automatic scale assumes a loss normalised by the number of samples (|d loss / d audio| ~ 1 / N)
+    wts, ws, fresh = begin_node(ctx, "infer_differentiable", model, eng, params, wn, flags, (B, T, S), B * S, scale, stream,
+                                want_wupt=ctx.needs_input_grad[_InferFn.N_META], want_winv=wgrads)
     audio = torch.empty((B, S), dtype=torch.float32, device=mel.device)
     ze = (C.c_void_p * max(1, n_early))(*[z.data_ptr() for z in z_early])
-    _lib.check(lib.wg_train_infer_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
-                                          float(sigma), _ptr(audio), B, T, _ptr(frames),
-                                          1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
-    ctx.frames = frames
-    ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.guard = model, wts, ws, (B, M, T), _SlotGuard(slot)
-    ctx.flags, ctx.wgrads = flags, wgrads
-    ctx.sigma, ctx.n_early, ctx.n_params = float(sigma), n_early, len(params)
-    ctx.sig = model._weights_signature() if wgrads else eng.signature
+    _lib.check(eng.lib.wg_train_infer_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(z_init), ze, n_early,
+                                              float(sigma), _ptr(audio), B, T, _ptr(frames),
+                                              1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
+    ctx.frames, ctx.wgrads, ctx.sigma, ctx.n_early, ctx.n_mel = frames, wgrads, float(sigma), n_early, M
+    ctx.sig = eng.signature                     # frozen: the engine whose W^-1 the forward used must still be this one
     ctx.z_shapes = [tuple(z_init.shape)] + [tuple(z.shape) for z in z_early]
-    ctx.shapes = [t.shape for t in params]
-    # the automatic scale assumes a loss normalised by the number of samples (|d loss / d audio| ~ 1 / N)
-    ctx.scale = float(scale) if scale else float(2.0 ** round(math.log2(audio.numel())))
     return audio
 
   @staticmethod
   def backward(ctx, g_audio):
-    model = ctx.model
-    if ctx.wts is None:
-      raise _lib.WgError("the saved state of this infer_differentiable call is gone: backward() already ran for it "
-                         "(retain_graph is not supported)")
-    eng = model._engine
-    stale = eng is None or model._weights_signature() != ctx.sig or (not ctx.wgrads and eng.signature != ctx.sig)
-    if stale:
-      ctx.wts = None
-      ctx.guard.release()
-      raise _lib.WgError("the vocoder's weights changed between infer_differentiable and backward(): the saved state "
-                         "belongs to the old weights")
-    lib = eng.lib
-    B, M, T = ctx.dims
-    dev = ctx.ws.device
-    ne = ctx.n_early
-    need = ctx.needs_input_grad
-    nm = _InferFn.N_META
+    ne, nm, need = ctx.n_early, _InferFn.N_META, ctx.needs_input_grad
     want_mel, want_zi = need[nm], need[nm + 1]
-    want_ze = list(need[nm + 2:nm + 2 + ne])
-    need_p = list(need[nm + 2 + ne:])
-    want_params = ctx.wgrads and any(need_p)
-    g_mel = new_grad((B, M, T), dev) if want_mel else None
-    g_zi = new_grad(ctx.z_shapes[0], dev) if want_zi else None
-    g_ze = [new_grad(ctx.z_shapes[1 + i], dev) if w else None for i, w in enumerate(want_ze)]
-    ga = g_audio.float().contiguous() if g_audio is not None else torch.zeros((B, 256 * T), dtype=torch.float32, device=dev)
-    ze = (C.c_void_p * max(1, ne))(*[(g.data_ptr() if g is not None else None) for g in g_ze])
-    stream = _args.stream(dev).value
-    hp = model._hp
-    bufs = GradBuffers(hp.n_channels, hp.n_layers, model.n_flows, hp.n_mel_channels * 8, dev) if want_params else None
-    gstruct, _keep = bufs.struct() if want_params else (None, None)
-    views = None
-    try:
-      _lib.check(lib.wg_train_infer_backward(eng.handle, C.byref(ctx.wts.struct),
-                                             C.byref(gstruct) if want_params else None, _ptr(ga), C.c_float(ctx.scale),
-                                             C.c_float(ctx.sigma), _ptr(g_mel), _ptr(g_zi), ze, ne, B, T, _ptr(ctx.frames),
-                                             _ptr(ctx.ws), ctx.ws.numel(), ctx.flags, C.c_void_p(stream)))
-      if want_params:      # (no logdet term in this direction)
-        views = param_grad_views(eng, ctx.wts, gstruct, ctx.shapes, stream)
-    finally:
-      ctx.guard.release()
-      ctx.wts = None
-    set_grad_finite(model, [bufs.flat if want_params else None, g_mel, g_zi] + g_ze, ctx.scale)
-    if not want_params:
-      return (None,) * nm + (g_mel, g_zi, *g_ze) + (None,) * ctx.n_params
-    grads = [v if w else None for v, w in zip(views, need_p)]
-    return (None,) * nm + (g_mel, g_zi, *g_ze, *grads)
+    want_ze = need[nm + 2:nm + 2 + ne]
+    need_p = need[nm + 2 + ne:] if ctx.wgrads else (False,) * len(ctx.shapes)
+
+    def launch(eng, wts, bufs, gs_ptr, stream):      # (no logdet term in this direction)
+      B, T, S = ctx.dims
+      dev = ctx.ws.device
+      g_mel = new_grad((B, ctx.n_mel, T), dev) if want_mel else None
+      g_zi = new_grad(ctx.z_shapes[0], dev) if want_zi else None
+      g_ze = [new_grad(ctx.z_shapes[1 + i], dev) if w else None for i, w in enumerate(want_ze)]
+      ga = g_audio.float().contiguous() if g_audio is not None else torch.zeros((B, S), dtype=torch.float32, device=dev)
+      ze = (C.c_void_p * max(1, ne))(*[(g.data_ptr() if g is not None else None) for g in g_ze])
+      _lib.check(eng.lib.wg_train_infer_backward(eng.handle, C.byref(wts.struct), gs_ptr, _ptr(ga), C.c_float(ctx.scale),
+                                                 C.c_float(ctx.sigma), _ptr(g_mel), _ptr(g_zi), ze, ne, B, T,
+                                                 _ptr(ctx.frames), _ptr(ctx.ws), ctx.ws.numel(), ctx.flags,
+                                                 C.c_void_p(stream)))
+      return (g_mel, g_zi, *g_ze)
+
+    return finish_node(ctx, nm, need_p, launch, also_stale=not ctx.wgrads and ctx.eng.signature != ctx.sig)
 
 
 def infer_differentiable(model, spect: torch.Tensor, z_init: torch.Tensor, z_early: List[torch.Tensor], sigma: float,

@@ -75,7 +75,6 @@ def _forward(model, mel: torch.Tensor, audio: torch.Tensor, frames: Frames):
   if frames is not None:
     fr = _frames(frames, mel, audio)          # refused before any launch
   eng = model._get_engine(mel.device)
-  io = model._io_dtype(mel)
   if frames is None:
     S = audio.shape[1] - audio.shape[1] % model.n_group
     T = mel.shape[2]
@@ -88,21 +87,8 @@ def _forward(model, mel: torch.Tensor, audio: torch.Tensor, frames: Frames):
       raise _lib.WgError(f"log_likelihood: {audio.shape[1]} samples are less than one frame of {FRAME_SAMPLES}")
     S = FRAME_SAMPLES * T
     mel = mel[:, :, :T]
-  nbytes = eng.workspace_bytes("fwd", mel.shape[0], T, S)     # raises outside the size range, before any allocation
-  mel = eng.pad_mel_input(mel).contiguous()
-  audio = audio[:, :S].contiguous()
-  B = mel.shape[0]
-  L = S // model.n_group
-  dev = mel.device
-  z = torch.empty((B, model.n_group, L), dtype=torch.float32, device=dev)
-  log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=dev) for c in model.flow_channels()]
-  ws = eng.workspace("fwd", nbytes, (B, T, S))
-  ls = (C.c_void_p * model.n_flows)(*[t.data_ptr() for t in log_s])
-  stream = _args.stream(dev)
-  with torch.cuda.device(dev):
-    log_det = (C.c_float * model.n_flows)() if fr is None else None     # required without counts only; never read here
-    _lib.check(eng.lib.wg_forward(eng.handle, _args.ptr(mel), _args.ptr(fr), _args.ptr(audio), _args.ptr(z), ls, log_det,
-                                  B, T, S, io, _args.ptr(ws), ws.numel(), stream))
+  with torch.cuda.device(mel.device):
+    z, log_s, _ = eng.run_forward(eng.pad_mel_input(mel).contiguous(), fr, audio[:, :S].contiguous(), S)
   return eng, z, log_s, fr
 
 

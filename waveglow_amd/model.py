@@ -60,6 +60,14 @@ class WN(nn.Module):
       self.res_skip_layers.append(wn(nn.Conv1d(self.n_channels, rs, 1), name="weight"))
 
 
+def _io_dtype(t: torch.Tensor) -> int:
+  if t.dtype == torch.float32:
+    return _lib.WG_F32
+  if t.dtype == torch.float16:
+    return _lib.WG_F16
+  raise _lib.WgError(f"unsupported dtype {t.dtype} (float32 or float16)")
+
+
 class _Engine:
   """Owns one wg_handle and the packed device weights derived from a module's parameters."""
 
@@ -76,6 +84,8 @@ class _Engine:
     if not self.width or hp.n_channels < 1:
       raise _lib.WgError(f"n_channels={hp.n_channels} unsupported (1..512)")
     self.n_layers = hp.n_layers
+    self.n_group = hp.n_group
+    self.flow_c = [hp.n_group - hp.n_early_size * (k // hp.n_early_every) for k in range(hp.n_flows)]   # model.py:160-176
     # the same for the mel axis: the conditioning K-steps take multiples of 16 mel channels (<= 80); other counts run with
     # zero filter taps / conditioning columns for the extra channels and a zero-padded input
     self.n_mel = hp.n_mel_channels
@@ -187,6 +197,38 @@ class _Engine:
       self._ws[k] = ws
     return ws
 
+  def run_infer(self, mel, frames_dev, z_init, z_early, sigma, audio_out=None) -> torch.Tensor:
+    """The package's one synthesis call, on prepared tensors: checked by the caller, ``mel`` padded to ``mel_width``, all
+    contiguous; ``frames_dev`` int32 [B] on the device or None; ``audio_out`` [B, 256 T] in ``mel``'s dtype, or None for a new
+    tensor.  The size is asked first: a batch outside the range raises the library's message before anything is allocated."""
+    B, _, T = mel.shape
+    io = _io_dtype(mel)
+    nbytes = self.workspace_bytes("infer", B, T)
+    ws = self.workspace("infer", nbytes, (B, T, 0))
+    if audio_out is None:
+      audio_out = torch.empty((B, T * 256), dtype=mel.dtype, device=mel.device)
+    ze = (C.c_void_p * max(1, len(z_early)))(*[z.data_ptr() for z in z_early])
+    _lib.check(self.lib.wg_infer(self.handle, _args.ptr(mel), _args.ptr(frames_dev), _args.ptr(z_init), ze, len(z_early),
+                                 float(sigma), _args.ptr(audio_out), B, T, io, _args.ptr(ws), ws.numel(),
+                                 _args.stream(mel.device)))
+    return audio_out
+
+  def run_forward(self, mel, frames_dev, audio, S: int):
+    """The package's one no-grad forward call: ``(z [B, n_group, L], [log_s_k], log_det)`` at fp32 for prepared tensors
+    (``mel`` padded to ``mel_width``, ``audio`` [B, S] with S a multiple of n_group, contiguous, one dtype).  ``log_det``: the
+    host array of the flows' ``B L log|det W_k|``, or None with ``frames_dev``.  The size is asked first, as in ``run_infer``."""
+    B, _, T = mel.shape
+    io = _io_dtype(mel)
+    nbytes = self.workspace_bytes("fwd", B, T, S)
+    ws = self.workspace("fwd", nbytes, (B, T, S))
+    L = S // self.n_group
+    z = torch.empty((B, self.n_group, L), dtype=torch.float32, device=mel.device)
+    log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=mel.device) for c in self.flow_c]
+    ls = (C.c_void_p * len(log_s))(*[t.data_ptr() for t in log_s])
+    log_det = (C.c_float * len(log_s))() if frames_dev is None else None
+    _lib.check(self.lib.wg_forward(self.handle, _args.ptr(mel), _args.ptr(frames_dev), _args.ptr(audio), _args.ptr(z), ls,
+                                   log_det, B, T, S, io, _args.ptr(ws), ws.numel(), _args.stream(mel.device)))
+    return z, log_s, log_det
 
   def train_workspace(self, nbytes: int, key: Tuple[int, ...], flags: int = 0) -> Tuple[dict, bool]:
     """A workspace of the training direction (saved activations) that no pending backward still needs.
@@ -306,14 +348,6 @@ class WaveGlow(nn.Module):
       self._engine.signature = sig
     return self._engine
 
-  @staticmethod
-  def _io_dtype(t: torch.Tensor) -> int:
-    if t.dtype == torch.float32:
-      return _lib.WG_F32
-    if t.dtype == torch.float16:
-      return _lib.WG_F16
-    raise _lib.WgError(f"unsupported dtype {t.dtype} (float32 or float16)")
-
   # ------------------------------------------------------------------ reference API
   def infer_with_noise(self, spect: torch.Tensor, z_init: torch.Tensor, z_early: List[torch.Tensor],
                        sigma: float = 1.0, frames: Optional[torch.Tensor] = None, graph: bool = False) -> torch.Tensor:
@@ -326,8 +360,7 @@ class WaveGlow(nn.Module):
     if graph:
       return self._infer_graphed(spect, z_init, z_early, sigma, frames)
     eng = self._get_engine(spect.device)
-    io = self._io_dtype(spect)
-    nbytes = eng.workspace_bytes("infer", spect.shape[0], spect.shape[2])    # raises outside the size range, before any allocation
+    _io_dtype(spect)                                       # float32 or float16, refused first
     spect = eng.pad_mel_input(spect).contiguous()
     B, M, T = spect.shape
     L = T * 256 // self.n_group
@@ -336,10 +369,6 @@ class WaveGlow(nn.Module):
     z_early = [z.contiguous() for z in z_early]
     for z in z_early:
       assert z.shape == (B, self.n_early_size, L) and z.dtype == spect.dtype and z.device == spect.device
-    audio = torch.empty((B, T * 256), dtype=spect.dtype, device=spect.device)
-    ws = eng.workspace("infer", nbytes, (B, T, 0))
-    ze = (C.c_void_p * max(1, len(z_early)))(*[z.data_ptr() for z in z_early])
-    stream = torch.cuda.current_stream(spect.device).cuda_stream
     fr = None
     if frames is not None:
       fr = frames.to(device=spect.device, dtype=torch.int32).contiguous()
@@ -348,10 +377,7 @@ class WaveGlow(nn.Module):
         assert int(frames.min()) >= 1 and int(frames.max()) <= T
       elif not torch.cuda.is_current_stream_capturing():
         assert int(fr.min()) >= 1 and int(fr.max()) <= T
-    _lib.check(eng.lib.wg_infer(eng.handle, spect.data_ptr(), fr.data_ptr() if fr is not None else None,
-                                z_init.data_ptr(), ze, len(z_early), float(sigma), audio.data_ptr(), B, T, io,
-                                ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
-    return audio
+    return eng.run_infer(spect, fr, z_init, z_early, sigma)
 
   def _infer_graphed(self, spect, z_init, z_early, sigma, frames):
     eng = self._get_engine(spect.device)        # re-uploads weights if they changed: then the old graphs are stale
@@ -442,25 +468,15 @@ class WaveGlow(nn.Module):
       # grad_scale: loss scale of the fp16 gradient planes (0 = automatic, 2^round(log2 N) for the reference's mean loss)
       return train_forward(self, spect, audio, float(getattr(self, "grad_scale", 0.0)), bool(self.recompute_activations))
     eng = self._get_engine(spect.device)
-    io = self._io_dtype(spect)
+    _io_dtype(spect)                                       # float32 or float16, refused first
     assert audio.dtype == spect.dtype and audio.device == spect.device
-    nbytes = eng.workspace_bytes("fwd", spect.shape[0], spect.shape[2], audio.shape[1] - audio.shape[1] % self.n_group)
     spect, audio = eng.pad_mel_input(spect).contiguous(), audio.contiguous()
-    B, M, F_ = spect.shape
     S = audio.shape[1]
-    assert (F_ - 1) * 256 + 1024 >= S   # model.py:187
+    assert (spect.shape[2] - 1) * 256 + 1024 >= S   # model.py:187
     S = S - S % self.n_group            # unfold drops the remainder (model.py:191,195)
     if S != audio.shape[1]:
       audio = audio[:, :S].contiguous()
-    L = S // self.n_group
-    z = torch.empty((B, self.n_group, L), dtype=torch.float32, device=spect.device)
-    log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=spect.device) for c in self.flow_channels()]
-    log_det = (C.c_float * self.n_flows)()
-    ws = eng.workspace("fwd", nbytes, (B, F_, S))
-    ls = (C.c_void_p * self.n_flows)(*[t.data_ptr() for t in log_s])
-    stream = torch.cuda.current_stream(spect.device).cuda_stream
-    _lib.check(eng.lib.wg_forward(eng.handle, spect.data_ptr(), None, audio.data_ptr(), z.data_ptr(), ls, log_det,
-                                  B, F_, S, io, ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    z, log_s, log_det = eng.run_forward(spect, None, audio, S)
     log_det_list = [torch.tensor(log_det[k], dtype=torch.float32, device=spect.device) for k in range(self.n_flows)]
     if spect.dtype != torch.float32:
       z = z.to(spect.dtype)
@@ -504,10 +520,8 @@ class WaveGlow(nn.Module):
     if recompute is None:
       recompute = bool(self.recompute_activations)
     flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
-    n = int(eng.lib.wg_train_workspace_bytes(eng.handle, int(batch_size), int(n_frames), int(audio_len), flags))
-    if n == 0:
-      raise _lib.WgError(eng.lib.wg_last_error().decode())
-    return n
+    from .train import train_workspace_bytes
+    return train_workspace_bytes(eng, batch_size, n_frames, audio_len, flags)
 
   @staticmethod
   def remove_weightnorm(model: "WaveGlow") -> "WaveGlow":

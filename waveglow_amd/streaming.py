@@ -410,18 +410,6 @@ class _PinnedRing:
     self.events[i].record(stream)
 
 
-def _infer_windows(eng, mel, frames_dev, z_init, z_early, sigma, audio) -> None:
-  """One ragged ``wg_infer`` sequence on the windows into ``audio`` [B, 256 w_max] (the body of ``infer_with_noise`` with
-  the output given, so that its address can stand in the step's one table)."""
-  B, _, T = mel.shape
-  nbytes = eng.workspace_bytes("infer", B, T)
-  ws = eng.workspace("infer", nbytes, (B, T, 0))
-  ze = (C.c_void_p * max(1, len(z_early)))(*[z.data_ptr() for z in z_early])
-  _lib.check(eng.lib.wg_infer(eng.handle, _args.ptr(mel), _args.ptr(frames_dev), _args.ptr(z_init), ze, len(z_early),
-                              float(sigma), _args.ptr(audio), B, T, _io(mel.dtype), _args.ptr(ws), ws.numel(),
-                              _args.stream(mel.device)))
-
-
 def stream_step(synth, sessions: Sequence[StreamSession], pcm: bool = True) -> list:
   """``Synthesizer.stream_step``: every session with a ready chunk advances by one chunk, all of them in one launch
   sequence on the current stream --
@@ -489,7 +477,7 @@ def stream_step(synth, sessions: Sequence[StreamSession], pcm: bool = True) -> l
     gather_launch(base + int(offs[0]), B, s0.n_mel, eng.mel_width, s0.n_rem, s0.n_early, s0.n_early_size, w_max, cpf, dtype,
                   dev, out=bufs)
     frames_dev = table[int(offs[2]):int(offs[2]) + 4 * B].view(torch.int32)
-    _infer_windows(eng, bufs[0], frames_dev, bufs[1], bufs[2], s0.sigma, audio)
+    eng.run_infer(bufs[0], frames_dev, bufs[1], bufs[2], s0.sigma, audio)      # its address stands in the step's table
     if raw is not audio:
       raw.copy_(audio)
     if Bd:

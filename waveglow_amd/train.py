@@ -12,12 +12,12 @@ weight-normed parameters).  Everything that touches a weight, an activation or a
 * ``wg_train_param_grads``: packed gradients -> one gradient per parameter (weight-norm backward, the fold's chain rule) in
   ONE flat buffer; autograd gets views of it.
 
-This file is the binding: the autograd node (``_TrainFn``), buffer allocation, the data-parallel schedule, and the
-plumbing that ``_TrainFn`` shares with the synthesis direction's node (waveglow_amd/infer_grad.py): ``request_workspace``,
-``new_grad``, ``set_grad_finite``, ``param_grad_views``.  What is left to torch is ``logdet`` of the twelve 1x1 weights
-(model.py:63) and the optimiser.  ``pack_weights`` /
-``wn_forward_fragments`` / ``plain_fragments`` / ``to_fragments`` are the library's packing written as torch ops -- the
-checker of tests/test_gpu_train.py::test_prepare_matches_torch_packing and tests/test_host_cpu.py, not on the product path.
+This file is the binding and nothing else: the autograd node (``_TrainFn``), buffer allocation, the data-parallel
+schedule, and what ``_TrainFn`` shares with the synthesis direction's node (waveglow_amd/infer_grad.py) -- the lifecycle
+of a node between its forward and its backward (``begin_node`` / ``finish_node``: per-call weights, one pool workspace
+behind a guard, the loss scale, the refusals, packed gradients -> parameter gradients) and its parts
+(``request_workspace``, ``new_grad``, ``set_grad_finite``, ``param_grad_views``).  What is left to torch is ``logdet`` of
+the twelve 1x1 weights (model.py:63) and the optimiser.
 
 There is no fallback: CPU tensors raise.
 """
@@ -34,208 +34,27 @@ from . import _lib
 from ._args import ptr as _ptr
 
 
-def pos_perm(n: int) -> torch.Tensor:
-  """perm[P] = channel stored at position P (wg_common.h: pos_to_chan) for n channels (n % 32 == 0)."""
-  P = torch.arange(n)
-  blk, p = P // 32, P % 32
-  h, g, i = p // 16, (p // 4) % 4, p % 4
-  return blk * 32 + 8 * g + 4 * h + i
-
-
-_PERM_CACHE: dict = {}
-
-
-def _perms(Cc: int, M8: int, device) -> "_Perms":
-  """Index tensors are built (and copied to the device) once per geometry, not once per step."""
-  key = (Cc, M8, str(device))
-  if key not in _PERM_CACHE:
-    _PERM_CACHE[key] = _Perms(Cc, M8, device)
-  return _PERM_CACHE[key]
-
-
-class _Perms:
-  def __init__(self, Cc: int, M8: int, device):
-    pc = pos_perm(Cc)
-    self.c = pc.to(device)
-    self.c2 = torch.cat([pc, Cc + pc]).to(device)
-    self.m8 = pos_perm(M8).to(device)
-    self.k1 = torch.cat([pc, Cc + pc, 2 * Cc + pc, 3 * Cc + pos_perm(M8)]).to(device)
-    self.r32 = pos_perm(32).to(device)
-    for name in ("c", "c2", "m8", "k1"):
-      setattr(self, "i" + name, torch.argsort(getattr(self, name)))       # inverse permutations (gradients)
-    r = torch.arange(32)
-    self.c2p = (16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3)).to(device)   # chan_to_pos inside a 32-block
-
-
-# (tensor index in the packed tuple, dims that carry a channel-position permutation, which permutation)
-_PERM_PLAN = ((0, ((1, "c2"), (2, "k1"))), (1, ((1, "c2"),)), (2, ((1, "c"), (2, "c"))), (3, ((1, "c"),)), (4, ((2, "c"),)),
-              (5, ((1, "m8"),)), (6, ((0, "m8"),)), (7, ((2, "c"),)))
-
-
-def to_pos_order(packed, pm: "_Perms", inverse: bool = False):
-  """Natural channel order -> the kernels' position-major order (or back, for gradients).  Plain gathers, done
-  outside autograd (inside the autograd node): an indexing op under autograd costs a zero-filled full-size tensor and
-  an atomic scatter in its backward; the inverse permutation is just another gather."""
-  out = list(packed)
-  for idx, dims in _PERM_PLAN:
-    t = out[idx]
-    for dim, name in dims:
-      t = t.index_select(dim, getattr(pm, ("i" if inverse else "") + name))
-    out[idx] = t
-  return out
-
-
-def _dense_stack(mods) -> torch.Tensor:
-  """Dense weights of same-shaped conv modules, stacked [n, out, in, k].  Weight-normed modules (the training case) are
-  evaluated with ONE ``torch._weight_norm`` over their concatenated (g, v) -- what the parametrization computes per
-  module (rows are normalised independently), in one kernel each way instead of one per module."""
-  is_p = torch.nn.utils.parametrize.is_parametrized
-  if len(mods) > 1 and all(is_p(m, "weight") for m in mods):
-    g = torch.cat([m.parametrizations.weight.original0 for m in mods])
-    v = torch.cat([m.parametrizations.weight.original1 for m in mods])
-    return torch._weight_norm(v, g, 0).view(len(mods), v.shape[0] // len(mods), *v.shape[1:])
-  return torch.stack([m.weight for m in mods])
-
-
-def _shape_runs(sizes):
-  """[(size, [flow indices])] for maximal runs of consecutive flows with equal size (flow order is kept by concatenating
-  the runs)."""
-  runs = []
-  for k, r in enumerate(sizes):
-    if runs and runs[-1][0] == r:
-      runs[-1][1].append(k)
-    else:
-      runs.append((r, [k]))
-  return runs
-
-
-def pack_weights(model) -> Tuple[torch.Tensor, ...]:
-  """Differentiable packing of the module's parameters into the stacked matrices of wg_train_weights, in NATURAL
-  channel order (to_pos_order applies the kernels' permutation).
-
-  Few, LARGE autograd nodes: modules of one shape are gathered across ALL flows and go through one weight-norm
-  evaluation (``_dense_stack``), and everything per flow (W_end x W_skip fold, start, 1x1) is a batched op over the
-  flow axis -- a per-module formulation costs ~2000 tiny kernels per step (~8 ms of the round-1 step), and every
-  per-layer slice of a big tensor costs a zero-filled full-size gradient in its backward."""
-  hp = model._hp
-  Cc, nl, nf, M, M8 = hp.n_channels, hp.n_layers, model.n_flows, hp.n_mel_channels, hp.n_mel_channels * 8
-  pad = torch.nn.functional.pad
-  WN = model.WN
-  w_in = _dense_stack([WN[k].in_layers[i] for k in range(nf) for i in range(nl)])              # [FL, 2C, C, 3]
-  b_in = torch.stack([WN[k].in_layers[i].bias for k in range(nf) for i in range(nl)])          # [FL, 2C]
-  w_cond = _dense_stack([WN[k].cond_layer for k in range(nf)]).squeeze(3).reshape(nf * nl, 2 * Cc, M8)
-  b_cond = torch.stack([WN[k].cond_layer.bias for k in range(nf)]).reshape(nf * nl, 2 * Cc)
-  last_w = _dense_stack([WN[k].res_skip_layers[nl - 1] for k in range(nf)]).squeeze(3)         # [nf, C, C]: all skip rows
-  last_b = torch.stack([WN[k].res_skip_layers[nl - 1].bias for k in range(nf)])                # [nf, C]
-  if nl > 1:
-    rs_w = _dense_stack([WN[k].res_skip_layers[i] for k in range(nf) for i in range(nl - 1)]).squeeze(3)
-    rs_w = rs_w.view(nf, nl - 1, 2 * Cc, Cc)
-    rs_b = torch.stack([WN[k].res_skip_layers[i].bias for k in range(nf) for i in range(nl - 1)]).view(nf, nl - 1, 2 * Cc)
-    w2 = pad(rs_w[:, :, :Cc], (0, 0, 0, 0, 0, 1)).reshape(nf * nl, Cc, Cc)      # model.py:131-134; the last layer has no res rows
-    b2 = pad(rs_b[:, :, :Cc], (0, 0, 0, 1)).reshape(nf * nl, Cc)
-    w_skips = torch.cat([rs_w[:, :, Cc:], last_w[:, None]], 1)                  # [nf, nl, C, C]   model.py:135-136
-    b_skip_sum = rs_b[:, :, Cc:].sum(1) + last_b                                # [nf, C]
-  else:
-    w2 = torch.zeros_like(last_w)
-    b2 = torch.zeros_like(last_b)
-    w_skips, b_skip_sum = last_w[:, None], last_b
-  # Per-flow small tensors (end, start, 1x1): flows of one shape (h_k changes at the early outputs) are stacked and padded as
-  # ONE tensor per shape group -- a per-flow formulation costs ~25 tiny kernels per flow and step each way.
-  runs = _shape_runs([WN[k].end.weight.shape[0] for k in range(nf)])
-  # WN.end (not weight-normed, 2h_k rows) zero-padded to 8 rows: end(sum_i skip_i) for every flow in one batched GEMM
-  w_end8 = torch.cat([pad(torch.stack([WN[k].end.weight.squeeze(2) for k in ks]), (0, 0, 0, 8 - r)) for r, ks in runs])
-  b_end8 = torch.cat([pad(torch.stack([WN[k].end.bias for k in ks]), (0, 8 - r)) for r, ks in runs])
-  wes = torch.matmul(w_end8[:, None], w_skips).reshape(nf * nl, 8, Cc)           # [nf, nl, 8, C]
-  out_init = torch.bmm(w_end8, b_skip_sum[:, :, None]).squeeze(2) + b_end8       # [nf, 8]
-  # start conv [C, h_k] (weight norm per shape group), zero-padded to 4 columns, + bias row -> [nf, 5, C]
-  start5 = torch.cat([torch.cat([pad(_dense_stack([WN[k].start for k in ks]).squeeze(3), (0, 4 - r // 2)).transpose(1, 2),
-                                 torch.stack([WN[k].start.bias for k in ks])[:, None, :]], 1) for r, ks in runs])
-  w1x1 = torch.cat([pad(torch.stack([model.convinv[k].conv.weight.squeeze(2) for k in ks]), (0, 8 - r, 0, 8 - r))
-                    for r, ks in _shape_runs([model.convinv[k].conv.weight.shape[0] for k in range(nf)])])
-  FL = nf * nl
-  w_in = w_in.permute(0, 1, 3, 2).reshape(FL, 2 * Cc, 3 * Cc)                    # K = tap-major
-  w1 = torch.cat([w_in, w_cond], 2)                                              # [FL, 2C, 3C + M8]
-  # "* 1.0": AddBackward hands the SAME gradient tensor to both operands and cat / stack backward only slice it, so
-  # in_layers[i].bias.grad and cond_layer.bias.grad would become overlapping views of one buffer (AccumulateGrad
-  # installs them without a copy) and the next in-place accumulation would count a gradient twice
-  b1 = b_in + b_cond * 1.0
-  up = model.upsample.weight                                                     # [M_in, M_out, 1024]
-  wup = up.view(M, M, 4, 32, 8).permute(3, 1, 4, 2, 0).reshape(32, M8, 4, M)     # [p][(o,g)][j][i]
-  wup = torch.nn.functional.pad(wup, (0, 128 - M)).reshape(32, M8, 512)
-  bup = model.upsample.bias.repeat_interleave(8)
-  return (w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous(), wes.contiguous(), wup.contiguous(),
-          bup.contiguous(), start5.contiguous(), out_init.contiguous(), w1x1.contiguous())
-
-
-def to_fragments(mat: torch.Tensor, c2p: torch.Tensor = None) -> torch.Tensor:
-  """[..., M, K] (pos,pos) fp16 -> MFMA-fragment order [..., K/64, M/32, 4, 64, 8] (wg_train.h: PGemmArgs::A):
-  lane (r, h), element j of sub-step s of block b, K-step t = mat[32b + chan_to_pos(r)][64t + 32h + 8s + j]."""
-  *lead, M, K = mat.shape
-  if c2p is None:
-    r = torch.arange(32)
-    c2p = (16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3)).to(mat.device)
-  v = mat.reshape(*lead, M // 32, 32, K // 64, 2, 4, 8).index_select(len(lead) + 1, c2p)   # [.., b, r, t, h, s, j]
-  n = len(lead)
-  return v.permute(*range(n), n + 2, n, n + 4, n + 3, n + 1, n + 5).contiguous()            # [.., t, b, s, h, r, j]
-
-
-K_TANH_SCALE = 2.8853900817779268     # 2*log2(e): the gate evaluates tanh / sigmoid through exp2 (kernels.hip: gate_act)
-K_SIGM_SCALE = -1.4426950408889634    # -log2(e)
-
-
-def wn_forward_fragments(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, wes: torch.Tensor, pm: "_Perms", NW: int):
-  """Natural-order stacked matrices -> the forward kernel's operands (include/waveglow_amd.h: wg_train_weights a1, a1c,
-  b1, a2, es): rows stay in natural channel order, K goes to position order, the gate pre-scale is folded into the
-  GEMM-1 rows and bias, and everything is laid out in the WN-layer kernel's MFMA A-fragment order.
-  w1 [FL, 2C, 3C + M8], b1 [FL, 2C], w2 [FL, C, C], wes [FL, 8, C] (fp32)."""
-  FL, C2, K1 = w1.shape
-  Cc = C2 // 2
-  MB = Cc // (32 * NW)
-  nK = K1 // 64
-  scale = torch.cat([torch.full((Cc,), K_TANH_SCALE), torch.full((Cc,), K_SIGM_SCALE)]).to(w1)
-  wk = (w1.index_select(2, pm.k1) * scale[None, :, None]).half()                   # K in position order, rows natural
-  # rows (gate, w, mb, r), K (ks, u1, k2, hh, j)  ->  [ks, u1, w, (gate, mb) = mt, k2, (hh, r) = lane, j]
-  a = wk.reshape(FL, 2, NW, MB, 32, nK, 2, 2, 2, 8).permute(0, 5, 6, 2, 1, 3, 7, 8, 4, 9).contiguous()
-  a = a.reshape(FL, nK, 2 * NW * 2 * MB * 2 * 64 * 8)
-  n_tap = 3 * Cc // 64
-  a1 = a[:, :n_tap].contiguous()
-  a1c = a[:, n_tap:].contiguous()
-  b1s = (b1 * scale[None, :]).float().contiguous()
-  w2k = w2.index_select(2, pm.c).half()                                            # [FL, C rows natural, C pos]
-  a2 = w2k.reshape(FL, NW, MB, 32, Cc // 16, 2, 8).permute(0, 1, 2, 4, 5, 3, 6).contiguous()   # [FL, w, mb, k16, hh, r, j]
-  wek = wes.index_select(2, pm.c)
-  hi = wek.half()
-  lo = (wek - hi.float()).half()
-  rows16 = torch.cat([hi, lo], 1)                                                  # [FL, 16, C pos]
-  es = rows16.reshape(FL, 16, Cc // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous()  # [FL, s, l4, row, j]: lane = 16 l4 + row
-  return a1, a1c, b1s, a2, es
-
-
-def plain_fragments(mat: torch.Tensor, NW: int) -> torch.Tensor:
-  """[FL, M, K] fp16 (rows natural, K already in the order of the planes it multiplies) -> the WN-layer kernel's A-fragment
-  order for plain row blocks [FL, K/64, 2, NW, MB, 2, 64, 8] (include/waveglow_amd.h: wat, wbt)."""
-  FL, M, K = mat.shape
-  MB = M // (32 * NW)
-  v = mat.reshape(FL, NW, MB, 32, K // 64, 2, 2, 2, 8)                      # rows (w, mb, r), K (ks, u1, k2, hh, j)
-  return v.permute(0, 4, 5, 1, 2, 6, 7, 3, 8).contiguous()                  # [FL, ks, u1, w, mb, k2, hh, r, j]
-
-
 def canonical_params(model, eng):
-  """(tensors in the library's canonical order, weight_normed flag) for wg_train_prepare / wg_train_param_grads: the
-  module's own parameter tensors, looked up by state_dict key (include/waveglow_amd.h: wg_train_param_name)."""
+  """(names, tensors in the library's canonical order, weight_normed flag) for wg_train_prepare / wg_train_param_grads: the
+  module's own parameter tensors, looked up by state_dict key (include/waveglow_amd.h: wg_train_param_name), each held to
+  the element count the library will read and write through its bare pointer (wg_train_param_numel) before anything else."""
   wn = torch.nn.utils.parametrize.is_parametrized(model.WN[0].start, "weight")
-  key = ("train_param_names", wn)
-  names = eng.cache.get(key)
-  if names is None:
+  key = ("train_params", wn)
+  if key not in eng.cache:
     n = eng.lib.wg_train_param_count(eng.handle, int(wn))
-    names = [eng.lib.wg_train_param_name(eng.handle, int(wn), i).decode() for i in range(n)]
-    eng.cache[key] = names
+    eng.cache[key] = ([eng.lib.wg_train_param_name(eng.handle, int(wn), i).decode() for i in range(n)],
+                      [int(eng.lib.wg_train_param_numel(eng.handle, int(wn), i)) for i in range(n)])
+  names, numels = eng.cache[key]
   byname = dict(model.named_parameters())
   try:
     tensors = [byname[n] for n in names]
   except KeyError as e:
     raise _lib.WgError(f"parameter {e} missing: the training direction needs every WN module in the same form "
                        "(all weight-normed, or all dense after remove_weightnorm)")
+  for n, t, numel in zip(names, tensors, numels):
+    if t.numel() != numel:
+      raise _lib.WgError(f"parameter {n}: {t.numel()} elements of shape {tuple(t.shape)}, the library reads and writes "
+                         f"{numel} for this model")
   for n, t in zip(names, tensors):
     if t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda":
       raise _lib.WgError(f"parameter {n}: the training direction takes contiguous float32 parameters on the GPU")
@@ -246,8 +65,9 @@ class _Weights:
   """Device buffers + the ctypes struct handed to the library (kept alive between forward and backward).  Everything in
   them -- fp16 fragment tensors and the small fp32 vectors -- is filled by the library itself from the module's own
   parameter tensors (``wg_train_prepare``: weight norm, the W_end x W_skip fold, permutations, gate pre-scale, fragment
-  orders).  ``pack_weights`` / ``wn_forward_fragments`` / ``plain_fragments`` / ``to_fragments`` above are the same
-  computation written as torch ops: the tests hold the library to them."""
+  orders); tests/_packing.py is the same computation written as torch ops, and the tests hold the library to it.
+  ``tensors`` (the detached parameters) stay here, so their storage lives as long as the node that holds this object, and
+  ``sig`` is their ``(_version, data_ptr())`` when the library read them: ``moved`` tells whether that still holds."""
 
   def __init__(self, model, tensors, wn: bool, flow_c: List[int], eng, stream, want_wupt: bool = False,
                want_winv: bool = False):
@@ -289,10 +109,18 @@ class _Weights:
                                       _ptr(self.wupt) if want_wupt else None,
                                       C.cast(self._arrs[4], C.c_void_p) if want_winv else None)
     self.wn = int(wn)
-    self.params = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+    ptrs = [t.data_ptr() for t in tensors]
+    self.params = (C.c_void_p * len(tensors))(*ptrs)
+    self.tensors = tensors
+    self.sig = [(t._version, p) for t, p in zip(tensors, ptrs)]
     self.aux = torch.empty(eng.lib.wg_train_prepare_bytes(eng.handle), dtype=torch.uint8, device=dev)
     _lib.check(eng.lib.wg_train_prepare(eng.handle, self.params, self.wn, C.byref(self.struct), _ptr(self.aux),
                                         self.aux.numel(), C.c_void_p(stream)))
+
+  def moved(self, live) -> bool:
+    """Whether one of ``live`` -- the parameters ``tensors`` were detached from (a detached tensor shares its parameter's
+    version counter, not a storage the parameter is given later) -- was written in place or moved since the library read it."""
+    return [(t._version, t.data_ptr()) for t in live] != self.sig
 
 
 class _SlotGuard:
@@ -337,13 +165,19 @@ def enable_data_parallel(model, group=None, force: bool = False) -> bool:
   return True
 
 
-def request_workspace(eng, B: int, n_frames: int, audio_len: int, flags: int) -> Tuple[dict, bool]:
-  """(slot, fresh) of ``_Engine.train_workspace`` for one forward of either direction: the saved state of its graph, of the
-  library's own size for the geometry and the wg_train ``flags``.  The caller hands the slot to a ``_SlotGuard``."""
-  nbytes = eng.lib.wg_train_workspace_bytes(eng.handle, B, n_frames, audio_len, flags)
+def train_workspace_bytes(eng, B: int, n_frames: int, audio_len: int, flags: int) -> int:
+  """The library's size of the saved state of one forward of either direction, for the geometry and the wg_train ``flags``;
+  its message as a WgError for a geometry it does not take."""
+  nbytes = int(eng.lib.wg_train_workspace_bytes(eng.handle, int(B), int(n_frames), int(audio_len), int(flags)))
   if nbytes == 0:
     raise _lib.WgError(eng.lib.wg_last_error().decode())
-  return eng.train_workspace(nbytes, (B, n_frames, audio_len), flags)
+  return nbytes
+
+
+def request_workspace(eng, B: int, n_frames: int, audio_len: int, flags: int) -> Tuple[dict, bool]:
+  """(slot, fresh) of ``_Engine.train_workspace`` for one forward of either direction: the saved state of its graph, of
+  ``train_workspace_bytes``.  The caller hands the slot to a ``_SlotGuard``."""
+  return eng.train_workspace(train_workspace_bytes(eng, B, n_frames, audio_len, flags), (B, n_frames, audio_len), flags)
 
 
 def new_grad(shape, device) -> torch.Tensor:
@@ -425,13 +259,6 @@ class GradBuffers:
                           C.cast(keep[2], C.c_void_p), self.rec, self.flow_stride)
     return g, keep
 
-  def packed_grads(self) -> list:
-    """Gradients in the shapes of pack_weights' outputs.  The library already writes them in natural channel order
-    (wg_train_grads); the per-layer views are strided, so merging the (flow, layer) axes makes them dense."""
-    merge = lambda t: t.reshape(t.shape[0] * t.shape[1], *t.shape[2:])
-    return [merge(self.dw1), merge(self.db1), merge(self.dw2), merge(self.db2), merge(self.dwes), self.dwup, self.dbup,
-            self.dstart.contiguous(), self.dout_init.contiguous(), self.dw1x1.contiguous()]
-
 
 def flow_backward_schedule(n_flows: int, run_flow, bufs, group=None) -> None:
   """The data-parallel backward schedule, independent of what computes the gradients (so that the CPU tests drive it
@@ -458,89 +285,115 @@ def flow_backward_schedule(n_flows: int, run_flow, bufs, group=None) -> None:
     bufs.flat.mul_(1.0 / world)
 
 
+def begin_node(ctx, what: str, model, eng, params, wn, flags: int, dims, n_out: int, scale: float, stream,
+               want_wupt: bool, want_winv: bool = False):
+  """Forward side of the lifecycle the two autograd nodes share (``what`` names the call in their refusals): the per-call
+  weights from ``wg_train_prepare``, one pool workspace for ``dims = (B, n_frames, audio_len)`` behind a guard that returns
+  it when the graph goes away (also when the node's forward call raises), and on ``ctx`` what the backward side needs: flags,
+  parameters, shapes, the loss scale (``scale``, or 2^round(log2 ``n_out``)).  Returns ``(weights, workspace, fresh)``."""
+  wts = _Weights(model, [p.detach() for p in params], wn, model.flow_channels(), eng, stream, want_wupt=want_wupt,
+                 want_winv=want_winv)
+  slot, fresh = request_workspace(eng, *dims, flags)                         # held until this graph's backward has run
+  ctx.what, ctx.model, ctx.eng, ctx.wts, ctx.ws, ctx.guard = what, model, eng, wts, slot["ws"], _SlotGuard(slot)
+  ctx.dims, ctx.flags, ctx.params, ctx.shapes = dims, flags, params, [t.shape for t in params]
+  ctx.scale = float(scale) if scale else float(2.0 ** round(math.log2(n_out)))
+  return wts, slot["ws"], fresh
+
+
+def finish_node(ctx, n_meta: int, need_p, launch, also_stale: bool = False):
+  """Backward side.  Refused before any launch: a second backward() of one graph, and weights that moved since the forward
+  (written in place, another storage, another engine; ``also_stale``: the node's own reason) -- the saved state belongs to
+  the old weights, and ``wg_train_param_grads`` would read the new ones.  ``launch(eng, wts, bufs, grads_ptr, stream)``
+  issues the node's own calls (``bufs``: a ``GradBuffers`` when ``need_p`` asks for a parameter gradient, else None) and
+  returns its data gradients in input order; raised or not, the workspace goes back to the pool and the saved state goes.
+  Returns backward()'s tuple: ``n_meta`` Nones, the data gradients, one gradient (or None) per parameter."""
+  model, wts, eng = ctx.model, ctx.wts, ctx.eng
+  if wts is None:
+    raise _lib.WgError(f"the saved state of this {ctx.what} call is gone: backward() already ran for it "
+                       "(retain_graph is not supported)")
+  if also_stale or model._engine is not eng or wts.moved(ctx.params):
+    ctx.wts = None
+    ctx.guard.release()
+    raise _lib.WgError(f"the weights changed between {ctx.what} and backward(): the saved state belongs to the old weights")
+  hp, dev = model._hp, ctx.ws.device
+  stream = torch.cuda.current_stream(dev).cuda_stream
+  want_params = any(need_p)
+  bufs = GradBuffers(hp.n_channels, hp.n_layers, model.n_flows, hp.n_mel_channels * 8, dev) if want_params else None
+  gstruct, _keep = bufs.struct() if want_params else (None, None)
+  views = [None] * len(ctx.shapes)
+  try:
+    data_grads = launch(eng, wts, bufs, C.byref(gstruct) if want_params else None, stream)
+    if want_params:
+      views = param_grad_views(eng, wts, gstruct, ctx.shapes, stream)
+  finally:
+    ctx.guard.release()
+    ctx.wts = None
+  set_grad_finite(model, [bufs.flat if want_params else None, *data_grads], ctx.scale)
+  return (None,) * n_meta + (*data_grads, *[v if w else None for v, w in zip(views, need_p)])
+
+
 class _TrainFn(torch.autograd.Function):
-  """Inputs: mel, audio, the loss scale, the weight-norm flag, the wg_train flags (``WG_TRAIN_RECOMPUTE``: activation
-  recomputation; the backward runs with the flags of its own forward) and the module's parameters in the library's
-  canonical order (``canonical_params``); outputs (z, log_s...).  backward() returns what ``ctx.needs_input_grad`` asks for: d mel / d audio (written by the library
-  into tensors of their own), and one gradient per parameter, each a view of ONE flat buffer the library fills --
-  or, when no parameter needs one (a frozen model used as a loss), no parameter gradient at all: the library then runs
-  the data-gradient chain alone (include/waveglow_amd.h: wg_train_backward)."""
+  """Inputs: model, the loss scale, the weight-norm flag, the wg_train flags (``WG_TRAIN_RECOMPUTE``: activation
+  recomputation; the backward runs with the flags of its own forward), mel, audio and the module's parameters in the
+  library's canonical order (``canonical_params``); outputs (z, log_s...).  backward() returns what
+  ``ctx.needs_input_grad`` asks for: d mel / d audio (written by the library into tensors of their own), and one gradient
+  per parameter, each a view of ONE flat buffer the library fills -- or, when no parameter needs one (a frozen model used
+  as a loss), no parameter gradient at all: the library then runs the data-gradient chain alone
+  (include/waveglow_amd.h: wg_train_backward)."""
+
+  N_META = 4      # model, scale, wn, flags
 
   @staticmethod
-  def forward(ctx, model, mel, audio, scale, wn, flags, *params):
+  def forward(ctx, model, scale, wn, flags, mel, audio, *params):
     eng = model._get_engine(mel.device, need_weights=False)
-    lib = eng.lib
     B, M, F_ = mel.shape
     S = audio.shape[1]
     L = S // model.n_group
-    flow_c = model.flow_channels()
-    if int(lib.wg_wn_waves(model._hp.n_channels)) <= 0:
+    if int(eng.lib.wg_wn_waves(model._hp.n_channels)) <= 0:
       raise _lib.WgError(f"n_channels={model._hp.n_channels} unsupported (64, 128, 256, 512)")
     stream = torch.cuda.current_stream(mel.device).cuda_stream
-    wts = _Weights(model, [p.detach() for p in params], wn, flow_c, eng, stream, want_wupt=ctx.needs_input_grad[1])
+    wts, ws, fresh = begin_node(ctx, "forward", model, eng, params, wn, flags, (B, F_, S), B * model.n_group * L, scale,
+                                stream, want_wupt=ctx.needs_input_grad[_TrainFn.N_META])
     z = torch.empty((B, model.n_group, L), dtype=torch.float32, device=mel.device)
-    log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=mel.device) for c in flow_c]
-    slot, fresh = request_workspace(eng, B, F_, S, flags)                    # held until this graph's backward has run
-    ws = slot["ws"]
+    log_s = [torch.empty((B, c // 2, L), dtype=torch.float32, device=mel.device) for c in model.flow_channels()]
     ls = (C.c_void_p * len(log_s))(*[t.data_ptr() for t in log_s])
-    _lib.check(lib.wg_train_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(audio), _ptr(z), ls, B, F_, S,
-                                    1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
-    ctx.model, ctx.wts, ctx.ws, ctx.dims, ctx.audio, ctx.guard = model, wts, ws, (B, F_, S), audio, _SlotGuard(slot)
-    ctx.flags = flags
-    ctx.scale = float(scale) if scale else float(2.0 ** round(math.log2(z.numel())))
-    ctx.shapes = [t.shape for t in params]
+    _lib.check(eng.lib.wg_train_forward(eng.handle, C.byref(wts.struct), _ptr(mel), _ptr(audio), _ptr(z), ls, B, F_, S,
+                                        1 if fresh else 0, _ptr(ws), ws.numel(), flags, C.c_void_p(stream)))
+    ctx.audio = audio
     return (z, *log_s)
 
   @staticmethod
   def backward(ctx, g_z, *g_log_s):
-    model, wts = ctx.model, ctx.wts
-    eng = model._engine
-    lib = eng.lib
-    if ctx.wts is None:
-      raise _lib.WgError("the saved activations of this forward pass are gone: backward() already ran for it "
-                         "(retain_graph is not supported by the training direction)")
-    B, F_, S = ctx.dims
-    dev = ctx.audio.device
-    nf = model.n_flows
-    hp = model._hp
-    want_mel, want_audio = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-    want_params = any(ctx.needs_input_grad[6:])
-    g_mel = new_grad((B, hp.n_mel_channels, F_), dev) if want_mel else None
-    g_audio = new_grad((B, S), dev) if want_audio else None
-    bufs = GradBuffers(hp.n_channels, hp.n_layers, nf, hp.n_mel_channels * 8, dev) if want_params else None
-    gstruct, _keep = bufs.struct() if want_params else (None, None)
-    gs_ptr = C.byref(gstruct) if want_params else None
-    gm_ptr = _ptr(g_mel) if want_mel else None
-    ga_ptr = _ptr(g_audio) if want_audio else None
-    gz = g_z.float().contiguous() if g_z is not None else None
-    gls = [g.float().contiguous() if g is not None else None for g in g_log_s]
-    gl_arr = (C.c_void_p * nf)(*[(g.data_ptr() if g is not None else None) for g in gls])
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    gz_ptr = _ptr(gz) if gz is not None else None
-    # input gradients stay local (as under torch DDP); only parameter gradients are averaged over the ranks
-    group = _ddp_group(model) if want_params else None
-    if group is None:
-      _lib.check(lib.wg_train_backward(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
-                                       _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(), nf - 1, 0,
-                                       ctx.flags, C.c_void_p(stream)))
-    else:
-      # Data parallel: the backward pass is cut at flow boundaries and every flow's gradients -- ONE contiguous region
-      # of the flat buffer -- are all-reduced right behind it (flow_backward_schedule).  What follows (weight-norm
-      # backward, the fold's chain rule: wg_train_param_grads) is linear in these gradients, so averaging here equals
-      # averaging the parameter gradients (the logdet term of the 1x1 weights is identical on every rank).
-      def run_flow(k):
-        _lib.check(lib.wg_train_backward(eng.handle, C.byref(wts.struct), gs_ptr, gz_ptr, gl_arr, C.c_float(ctx.scale),
-                                         _ptr(ctx.audio), gm_ptr, ga_ptr, B, F_, S, _ptr(ctx.ws), ctx.ws.numel(), k, k,
-                                         ctx.flags, C.c_void_p(stream)))
-      flow_backward_schedule(nf, run_flow, bufs, group)
-    ctx.guard.release()
-    try:
-      set_grad_finite(model, (bufs.flat if want_params else None, g_mel, g_audio), ctx.scale)
-    finally:
-      ctx.wts = None
-    if not want_params:
-      return (None, g_mel, g_audio, None, None, None, *([None] * len(ctx.shapes)))
-    return (None, g_mel, g_audio, None, None, None, *param_grad_views(eng, wts, gstruct, ctx.shapes, stream))
+    nm = _TrainFn.N_META
+    want_mel, want_audio = ctx.needs_input_grad[nm], ctx.needs_input_grad[nm + 1]
+
+    def launch(eng, wts, bufs, gs_ptr, stream):
+      model = ctx.model
+      B, F_, S = ctx.dims
+      dev, nf = ctx.audio.device, model.n_flows
+      g_mel = new_grad((B, model._hp.n_mel_channels, F_), dev) if want_mel else None
+      g_audio = new_grad((B, S), dev) if want_audio else None
+      gz = g_z.float().contiguous() if g_z is not None else None
+      gls = [g.float().contiguous() if g is not None else None for g in g_log_s]
+      gl_arr = (C.c_void_p * nf)(*[(g.data_ptr() if g is not None else None) for g in gls])
+
+      def run_flows(hi, lo):
+        _lib.check(eng.lib.wg_train_backward(eng.handle, C.byref(wts.struct), gs_ptr, _ptr(gz), gl_arr,
+                                             C.c_float(ctx.scale), _ptr(ctx.audio), _ptr(g_mel), _ptr(g_audio), B, F_, S,
+                                             _ptr(ctx.ws), ctx.ws.numel(), hi, lo, ctx.flags, C.c_void_p(stream)))
+      # input gradients stay local (as under torch DDP); only parameter gradients are averaged over the ranks
+      group = _ddp_group(model) if bufs is not None else None
+      if group is None:
+        run_flows(nf - 1, 0)
+      else:
+        # Data parallel: the backward pass is cut at flow boundaries and every flow's gradients -- ONE contiguous region
+        # of the flat buffer -- are all-reduced right behind it (flow_backward_schedule).  What follows (weight-norm
+        # backward, the fold's chain rule: wg_train_param_grads) is linear in these gradients, so averaging here equals
+        # averaging the parameter gradients (the logdet term of the 1x1 weights is identical on every rank).
+        flow_backward_schedule(nf, lambda k: run_flows(k, k), bufs, group)
+      return g_mel, g_audio
+
+    return finish_node(ctx, nm, ctx.needs_input_grad[nm + 2:], launch)
 
 
 def nonfinite_message(scale: float) -> str:
@@ -571,7 +424,7 @@ def train_forward(model, mel: torch.Tensor, audio: torch.Tensor, grad_scale: flo
                        "zero-pad the others)")
   _names, tensors, wn = canonical_params(model, eng)
   flags = _lib.WG_TRAIN_RECOMPUTE if recompute else 0
-  out = _TrainFn.apply(model, mel, audio, grad_scale, wn, flags, *tensors)
+  out = _TrainFn.apply(model, grad_scale, wn, flags, mel, audio, *tensors)
   z, log_s = out[0], list(out[1:])
   L = S // model.n_group
   return z, log_s, _log_det_w(model, B * L)
