@@ -561,6 +561,41 @@ int wg_softdtw_backward(const float* feat_a, const int32_t* frames_a, const floa
                         double gamma, int32_t cost, const double* r, const double* g_value, double* e_out, float* g_a,
                         float* g_b, int32_t B, int32_t K, int32_t tmax_a, int32_t tmax_b, void* stream);
 
+/* ---- Soft-DTW inside a Sakoe-Chiba band -------------------------------------------------------------------------------
+ * The calls above with the warping restricted to a band around the diagonal, an integer `band` = w in [1, 511] (anything
+ * else is WG_ERR_INVALID; w = 0 would disconnect pairs of unequal lengths).  With n = Ta - 1, m = Tb - 1 and
+ * W = w max(n, m), cell (i,j) is inside the band iff |i m - j n| <= W, in integer arithmetic (it fits int32 within the
+ * limits): |i - j| <= w for Ta = Tb, otherwise the band around the line from (0,0) to (n,m).  A cell outside the band
+ * counts as +infinity, exactly as a cell outside the matrix; everything else in the recursions for R and E, the gradient
+ * formulas, the frame-count rule and the arithmetic is the text above, with the terms of cells outside the band left out
+ * of the gradient sums (the order of the remaining terms is unchanged, so it depends on the counts and w alone).
+ * (0,0) and (n,m) are inside the band, every in-band cell has an in-band predecessor and all but (n,m) an in-band
+ * successor.  On the anti-diagonal d = i + j the in-band rows are the interval lo(d) .. hi(d),
+ *     lo(d) = max(0, d - m, ceil((d n - W) / (n + m))),   hi(d) = min(n, d, floor((d n + W) / (n + m)))      (n + m > 0),
+ *   of at most 2 w + 1 rows; lo and hi advance by 0 or 1 per diagonal.  With w >= min(n, m) the band is the whole matrix
+ *   and every output has the bits of the dense call.
+ * wg_softdtw_banded_bytes: B (tmax_a + tmax_b - 1) S 8 with S = min(2 band + 1, tmax_a); 0 outside the limits.
+ * r_out / r: diagonal-major, S slots per diagonal:
+ *     R(i,j) of pair b at r[(b (tmax_a + tmax_b - 1) + (i + j)) S + (i - lo_b(i + j))]   for (i,j) inside the band,
+ *   lo_b from the pair's own counts; the other elements are neither written nor read.
+ * wg_softdtw_banded_backward: e_out null, or fp64 [B][tmax_a][tmax_b] written whole: E inside the band, exact zeros
+ *   elsewhere.  With gradients wanted the call takes a temporary of wg_softdtw_banded_bytes for E in the layout of r from
+ *   the stream-ordered allocator; e_out is filled only when given.
+ * Launches: forward one (one workgroup of P threads per pair, P the smallest power of two >= 2 w + 2, at least 64);
+ *   backward a memset of e_out if given, one wavefront launch and one launch per gradient. */
+size_t wg_softdtw_banded_bytes(int32_t B, int32_t tmax_a, int32_t tmax_b, int32_t band);
+int wg_softdtw_banded_forward(const float* feat_a, const int32_t* frames_a, const float* feat_b, const int32_t* frames_b,
+                              double gamma, int32_t cost, double* value_out, double* r_out, int32_t B, int32_t K,
+                              int32_t tmax_a, int32_t tmax_b, int32_t band, void* stream);
+int wg_softdtw_banded_backward(const float* feat_a, const int32_t* frames_a, const float* feat_b, const int32_t* frames_b,
+                               double gamma, int32_t cost, const double* r, const double* g_value, double* e_out,
+                               float* g_a, float* g_b, int32_t B, int32_t K, int32_t tmax_a, int32_t tmax_b, int32_t band,
+                               void* stream);
+/* The soft-DTW divergence (Blondel, Mensch and Vert, "Differentiable divergences between time series", AISTATS 2021) is
+ * D_b = v_ab - 0.5 (v_aa + v_bb) in fp64, in exactly that form, each v the value of that pair under the same gamma, cost
+ * and band; NaN where any of the three is.  It is composed by the caller (waveglow_amd/softdtw.py: soft_dtw_divergence)
+ * from one forward and one backward call over 3 B pairs. */
+
 /* ---- Resampling by a rational ratio: wav data of any sampling rate in, any rate out, no handle ------------------------
  * The reference has no counterpart.  The definition is scipy.signal.resample_poly(x, up, down) with its defaults
  * (window ('kaiser', 5.0), padtype 'constant') in closed form.  With up / down reduced, M = max(up, down), half = 10 M and

@@ -9,10 +9,18 @@ shapes: 16 pairs of 864 / 865 frames and a ragged batch of 16 pairs with 200 .. 
   dtw       for scale: ``metrics.dtw_distance`` (wg_metrics_dtw), the exact warping of the same pairs
   infer     for scale: ``infer_differentiable(..., weight_grads=True)`` forward + backward at 32 x 63 frames, 256 channels
 
+With ``--band W`` and / or ``--divergence`` further legs run beside these, with the same alternation and repetitions:
+
+  b-values, b-saved, b-backward   the three soft-DTW legs inside a Sakoe-Chiba band of half-width W (wg_softdtw_banded_*)
+  div, b-div                      ``soft_dtw_divergence`` forward + backward, dense and (with ``--band``) banded
+
+and the report gives the bytes every form keeps between forward and backward.
+
 The legs alternate in one process, repetition by repetition, after warm-ups of all of them; each line gives the median and
 the 10th and 90th percentile in ms (host clock around the call and a device synchronise).
 
-  python tools/bench_softdtw.py [--reps 10] [--warmup 3] [--gamma 1.0] [--out profiles/softdtw_ab.txt]
+  python tools/bench_softdtw.py [--reps 10] [--warmup 3] [--gamma 1.0] [--band W] [--divergence] [--skip-scale]
+                                [--out profiles/softdtw_ab.txt]
 """
 import argparse
 import os
@@ -41,7 +49,7 @@ def timed(fn, dev):
 
 def line(name, ms):
   a = np.asarray(ms)
-  return f"  {name:9s} {np.median(a):9.3f} [{np.percentile(a, 10):.3f} - {np.percentile(a, 90):.3f}]  n = {a.size}"
+  return f"  {name:10s} {np.median(a):9.3f} [{np.percentile(a, 10):.3f} - {np.percentile(a, 90):.3f}]  n = {a.size}"
 
 
 def torch_soft_dtw(fa, na, fb, nb, gamma):
@@ -89,6 +97,9 @@ def main():
   ap.add_argument("--features", type=int, default=16)
   ap.add_argument("--infer-batch", type=int, default=32)
   ap.add_argument("--infer-frames", type=int, default=63)
+  ap.add_argument("--band", type=int, default=0, help="also time the banded legs at this half-width")
+  ap.add_argument("--divergence", action="store_true", help="also time soft_dtw_divergence forward + backward")
+  ap.add_argument("--skip-scale", action="store_true", help="leave out the torch, dtw and infer legs")
   ap.add_argument("--out", default=None, help="also write the report to this file")
   a = ap.parse_args()
   dev = torch.device("cuda:0")
@@ -115,6 +126,7 @@ def main():
     na = torch.tensor(counts_a, dtype=torch.int32, device=dev)
     nb = torch.tensor(counts_b, dtype=torch.int32, device=dev)
     state = {}
+    fb_leaf = fa.detach().requires_grad_(True)        # the banded legs' own leaf: fa.grad stays the dense gradient
 
     def leg_values():
       with torch.no_grad():
@@ -136,20 +148,63 @@ def main():
     def leg_dtw():
       state["dtw"] = metrics.dtw_distance(fa.detach(), na, fb, nb)[0]
 
-    legs = {"values": leg_values, "saved": leg_saved, "backward": leg_backward, "torch": leg_torch, "dtw": leg_dtw,
-            "infer": leg_infer}
+    def leg_band_values():
+      with torch.no_grad():
+        state["band_values"] = softdtw.soft_dtw(fa, na, fb, nb, gamma, band=a.band)
+
+    def leg_band_saved():
+      state["band_graph"] = softdtw.soft_dtw(fb_leaf, na, fb, nb, gamma, band=a.band)
+
+    def leg_band_backward():
+      fb_leaf.grad = None
+      state["band_graph"].sum().backward()
+
+    def leg_div(band):
+      def run():
+        x = fa.detach().requires_grad_(True)
+        v = softdtw.soft_dtw_divergence(x, na, fb, nb, gamma, band=band)
+        v.sum().backward()
+        state["div", band] = v.detach()
+      return run
+
+    legs = {"values": leg_values, "saved": leg_saved, "backward": leg_backward}
+    if not a.skip_scale:
+      legs.update({"torch": leg_torch, "dtw": leg_dtw, "infer": leg_infer})
+    if a.band:
+      legs.update({"b-values": leg_band_values, "b-saved": leg_band_saved, "b-backward": leg_band_backward})
+    if a.divergence:
+      legs["div"] = leg_div(None)
+      if a.band:
+        legs["b-div"] = leg_div(a.band)
     times = {k: [] for k in legs}
     for it in range(a.warmup + a.reps):
       ms = {k: timed(fn, dev)[0] for k, fn in legs.items()}
       if it >= a.warmup:
         for k, v in ms.items():
           times[k].append(v)
-    v, tv = state["values"], state["torch_values"]
-    g, tg = fa.grad.double(), state["torch_grad"].double()
     med = {k: float(np.median(t)) for k, t in times.items()}
     report.append(f"{name} (cells {sum(x * y for x, y in zip(counts_a, counts_b))}, R buffer "
                   f"{softdtw.r_bytes(B, T, T + 1) / 2 ** 20:.0f} MiB)")
     report += [line(k, t) for k, t in times.items()]
+    plain = med["saved"] + med["backward"]
+    if a.band:
+      banded = med["b-saved"] + med["b-backward"]
+      report.append(f"  band {a.band}: R buffer {softdtw.r_bytes(B, T, T + 1, a.band) / 2 ** 20:.1f} MiB; forward + backward "
+                    f"{banded:.3f} ms against {plain:.3f} ms dense; banded - dense values in "
+                    f"[{float((state['band_values'] - state['values']).min()):.3f}, "
+                    f"{float((state['band_values'] - state['values']).max()):.3f}]")
+    if a.divergence:
+      for k, band in (("div", None), ("b-div", a.band or None)):
+        if k in med:
+          ref = med["b-saved"] + med["b-backward"] if band else plain
+          report.append(f"  divergence{f' band {band}' if band else ''}: R buffer "
+                        f"{softdtw.r_bytes(3 * B, T + 1, T + 1, band) / 2 ** 20:.1f} MiB; forward + backward {med[k]:.3f} ms = "
+                        f"{med[k] / ref:.2f}x the plain loss; D in [{float(state['div', band].min()):.3f}, "
+                        f"{float(state['div', band].max()):.3f}]")
+    if a.skip_scale:
+      continue
+    v, tv = state["values"], state["torch_values"]
+    g, tg = fa.grad.double(), state["torch_grad"].double()
     report.append(f"  forward + backward {med['saved'] + med['backward']:.3f} ms = {med['torch'] / (med['saved'] + med['backward']):.1f}x "
                   f"faster than the torch leg, {100 * (med['saved'] + med['backward']) / med['infer']:.1f} % of the infer leg; "
                   f"values against torch: max relative difference {float(((v - tv).abs() / tv.abs()).max()):.2e}, gradient "

@@ -27,7 +27,7 @@ def __getattr__(name):
   if name == "STOILoss":
     from .stoi_loss import STOILoss
     return STOILoss
-  if name in ("SoftDTWLoss", "soft_dtw", "soft_dtw_alignment"):
+  if name in ("SoftDTWLoss", "soft_dtw", "soft_dtw_alignment", "soft_dtw_divergence"):
     from . import softdtw
     return getattr(softdtw, name)
   if name in ("mel_metrics", "MelMetrics", "pitch_metrics", "PitchMetrics", "yin_f0", "intelligibility_metrics",

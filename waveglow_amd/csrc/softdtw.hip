@@ -381,4 +381,333 @@ hipError_t launch_sdtw_grads(const float* fa, const int* frames_a, const float* 
   return hipGetLastError();
 }
 
+// ===================================================================================================== Sakoe-Chiba band
+// The same recursions with the cells outside the band |i m - j n| <= W counting as +infinity (include/waveglow_amd.h:
+// wg_softdtw_banded_*).  On an anti-diagonal the band is the row interval lo(d) .. hi(d) of at most 2 w + 1 rows, and both
+// ends advance by 0 or 1 per diagonal, so the wavefront needs no more threads than the band is wide.
+struct SdtwBand {
+  int n, m, W, nm;                                 // Ta - 1, Tb - 1, w max(n, m), max(n + m, 1)
+};
+
+__device__ __forceinline__ SdtwBand sdtw_band(int Ta, int Tb, int w) {
+  SdtwBand g;
+  g.n = Ta - 1, g.m = Tb - 1;
+  g.W = w * (g.n > g.m ? g.n : g.m);
+  g.nm = g.n + g.m > 0 ? g.n + g.m : 1;
+  return g;
+}
+
+__device__ __forceinline__ int sdtw_floordiv(int a, int b) {                   // b > 0
+  const int q = a / b;
+  return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+__device__ __forceinline__ int sdtw_ceildiv(int a, int b) { return -sdtw_floordiv(-a, b); }
+__device__ __forceinline__ int sdtw_max(int a, int b) { return a > b ? a : b; }
+__device__ __forceinline__ int sdtw_min(int a, int b) { return a < b ? a : b; }
+
+// first and last in-band row of the anti-diagonal d, 0 <= d <= n + m
+__device__ __forceinline__ int sdtw_band_lo(const SdtwBand& g, int d) {
+  return sdtw_max(sdtw_max(0, d - g.m), sdtw_ceildiv(d * g.n - g.W, g.nm));
+}
+__device__ __forceinline__ int sdtw_band_hi(const SdtwBand& g, int d) {
+  return sdtw_min(sdtw_min(g.n, d), sdtw_floordiv(d * g.n + g.W, g.nm));
+}
+// E or R of the in-band cell (i, j) in the band layout of wg_softdtw.h, relative to the pair's first element
+__device__ __forceinline__ size_t sdtw_band_at(const SdtwBand& g, int S, int i, int j) {
+  return (size_t)(i + j) * S + (i - sdtw_band_lo(g, i + j));
+}
+
+// Forward.  One workgroup of P threads per pair, P a power of two > 2 w + 1: on every diagonal thread t serves the one row
+// i = t (mod P) of the interval, if there is one.  A row that enters the band needs its upper neighbour's cells of the two
+// diagonals before, which another thread computed while this one served another row or none, so nothing is carried in
+// registers: the last three diagonals live in LDS, slot i mod P holding R(i, d - i) and +infinity where the interval has
+// no such row.  Every thread writes its slot on every step, so a buffer describes its whole diagonal; row i - 1 of the
+// diagonals d - 1 and d - 2 is the only row those intervals can hold in slot (i - 1) mod P, because the intervals of three
+// consecutive diagonals span at most 2 w + 3 <= P + 1 rows and row i - 1 +- P lies outside them.  Three buffers, so the
+// buffer written on step d + 1 was last read before the barrier of step d: one barrier per step.  The cell itself is the
+// dense kernel's expression.
+template <bool SQ>
+__global__ void __launch_bounds__(1024) sdtw_band_forward_kernel(const float* fa, const int* frames_a, const float* fb,
+                                                                 const int* frames_b, double gamma, double inv_gamma,
+                                                                 double* value, double* rbuf, int K, int tmax_a,
+                                                                 int tmax_b, int w, int S) {
+  __shared__ double s_c[3][1024];
+  const int tid = threadIdx.x, b = blockIdx.x, mask = (int)blockDim.x - 1;
+  const int Ta = sdtw_frames(frames_a, b, tmax_a), Tb = sdtw_frames(frames_b, b, tmax_b);
+  if (Ta == 0 || Tb == 0) {                                                    // the whole block leaves: no barrier follows
+    if (tid == 0) value[b] = NAN;
+    return;
+  }
+  const SdtwBand g = sdtw_band(Ta, Tb, w);
+  const float* A = fa + (size_t)b * K * tmax_a;
+  const float* Bm = fb + (size_t)b * K * tmax_b;
+  double* Rb = rbuf ? rbuf + (size_t)b * (size_t)(tmax_a + tmax_b - 1) * S : nullptr;
+  const int nd = Ta + Tb - 1;
+  int lo = 0, hi = 0;                                                          // the interval of diagonal 0
+  double dcur = tid == 0 ? sdtw_dist<SQ>(A, Bm, K, tmax_a, tmax_b, 0, 0) : 0.0;
+  int cur = 0, prev1 = 2, prev2 = 1;                                           // buffers of the diagonals d, d-1, d-2
+  for (int d = 0; d < nd; ++d) {
+    int lo_n = 0, hi_n = -1;                                                   // the interval of d + 1; empty behind the end
+    if (d + 1 < nd) lo_n = sdtw_band_lo(g, d + 1), hi_n = sdtw_band_hi(g, d + 1);
+    const int i_n = lo_n + ((tid - lo_n) & mask);
+    const double dnext = i_n <= hi_n ? sdtw_dist<SQ>(A, Bm, K, tmax_a, tmax_b, i_n, d + 1 - i_n) : 0.0;
+    const int i = lo + ((tid - lo) & mask);
+    double c = INFINITY;
+    if (i <= hi) {
+      const double up = (i > 0 && d > 0) ? s_c[prev1][(i - 1) & mask] : INFINITY;      // (i-1, j)
+      const double lf = d > 0 ? s_c[prev1][tid] : INFINITY;                            // (i, j-1)
+      const double dg = (i > 0 && d > 1) ? s_c[prev2][(i - 1) & mask] : INFINITY;      // (i-1, j-1)
+      c = dcur + sdtw_softmin(up, lf, dg, gamma, inv_gamma);
+      if (d == 0) c = dcur;
+      if (Rb) Rb[(size_t)d * S + (i - lo)] = c;
+      if (d == nd - 1) value[b] = c;               // cell (Ta-1, Tb-1) is the last diagonal
+    }
+    s_c[cur][tid] = c;
+    __syncthreads();
+    const int t = prev2;
+    prev2 = prev1, prev1 = cur, cur = t;
+    dcur = dnext, lo = lo_n, hi = hi_n;
+  }
+}
+
+// Backward: the mirror image, descending diagonals, E and Q = R - d of the last three diagonals in LDS with zeros where
+// the interval has no row.  A successor outside the band or the matrix is left out by predicate, as in the dense kernel.
+// E goes to the band layout (e_band, for the gradient kernels) and to the dense e_out (zeroed by the launcher), each if
+// it is given.  R and the distances of the next diagonal are fetched before the barrier.
+template <bool SQ>
+__global__ void __launch_bounds__(1024) sdtw_band_backward_kernel(const float* fa, const int* frames_a, const float* fb,
+                                                                  const int* frames_b, double inv_gamma,
+                                                                  const double* rbuf, double* e_band, double* e_out, int K,
+                                                                  int tmax_a, int tmax_b, int w, int S) {
+  __shared__ double s_e[3][1024], s_q[3][1024];
+  const int tid = threadIdx.x, b = blockIdx.x, mask = (int)blockDim.x - 1;
+  const int Ta = sdtw_frames(frames_a, b, tmax_a), Tb = sdtw_frames(frames_b, b, tmax_b);
+  if (Ta == 0 || Tb == 0) return;                                              // the whole block leaves; e_out stays zero
+  const SdtwBand g = sdtw_band(Ta, Tb, w);
+  const float* A = fa + (size_t)b * K * tmax_a;
+  const float* Bm = fb + (size_t)b * K * tmax_b;
+  const size_t pair = (size_t)b * (size_t)(tmax_a + tmax_b - 1) * S;
+  const double* Rb = rbuf + pair;
+  double* Eb = e_band ? e_band + pair : nullptr;
+  double* Eo = e_out ? e_out + (size_t)b * tmax_a * tmax_b : nullptr;
+  const int nd = Ta + Tb - 1;
+  int lo = sdtw_band_lo(g, nd - 1), hi = sdtw_band_hi(g, nd - 1);
+  int lo1 = 0, hi1 = -1, lo2 = 0, hi2 = -1;                                    // the intervals of d + 1 and d + 2
+  double rcur = 0.0, qcur = 0.0;
+  {
+    const int i = lo + ((tid - lo) & mask);
+    if (i <= hi) {
+      rcur = Rb[(size_t)(nd - 1) * S + (i - lo)];
+      qcur = rcur - sdtw_dist<SQ>(A, Bm, K, tmax_a, tmax_b, i, nd - 1 - i);
+    }
+  }
+  int cur = 0, next1 = 2, next2 = 1;                                           // buffers of the diagonals d, d+1, d+2
+  for (int d = nd - 1; d >= 0; --d) {
+    int lo_p = 0, hi_p = -1;                                                   // the interval of d - 1
+    if (d > 0) lo_p = sdtw_band_lo(g, d - 1), hi_p = sdtw_band_hi(g, d - 1);
+    const int i_p = lo_p + ((tid - lo_p) & mask);
+    double rnext = 0.0, qnext = 0.0;
+    if (i_p <= hi_p) {
+      rnext = Rb[(size_t)(d - 1) * S + (i_p - lo_p)];
+      qnext = rnext - sdtw_dist<SQ>(A, Bm, K, tmax_a, tmax_b, i_p, d - 1 - i_p);
+    }
+    const int i = lo + ((tid - lo) & mask), j = d - i;
+    double e = 0.0, q = 0.0;
+    if (i <= hi) {
+      const bool below = i + 1 >= lo1 && i + 1 <= hi1;                         // (i+1, j) in the band
+      const bool right = i >= lo1 && i <= hi1;                                 // (i, j+1)
+      const bool diag = i + 1 >= lo2 && i + 1 <= hi2;                          // (i+1, j+1)
+      const int sn = (i + 1) & mask;
+      const double rc = rcur;
+      if (below) e += s_e[next1][sn] * exp((s_q[next1][sn] - rc) * inv_gamma);
+      if (right) e += s_e[next1][tid] * exp((s_q[next1][tid] - rc) * inv_gamma);
+      if (diag) e += s_e[next2][sn] * exp((s_q[next2][sn] - rc) * inv_gamma);
+      if (d == nd - 1) e = 1.0;                    // cell (Ta-1, Tb-1)
+      if (Eb) Eb[(size_t)d * S + (i - lo)] = e;
+      if (Eo) Eo[(size_t)i * tmax_b + j] = e;
+      q = qcur;
+    }
+    s_e[cur][tid] = e;
+    s_q[cur][tid] = q;
+    __syncthreads();
+    const int t = next2;
+    next2 = next1, next1 = cur, cur = t;
+    lo2 = lo1, hi2 = hi1, lo1 = lo, hi1 = hi, lo = lo_p, hi = hi_p;
+    rcur = rnext, qcur = qnext;
+  }
+}
+
+// g_a and g_b from the band-layout E: the dense kernels' sums with the cells outside the band left out, so a lane starts
+// at its first column (row) inside the band and stops behind the last; the order of what remains is unchanged.
+template <bool SQ>
+__global__ void __launch_bounds__(256) sdtw_band_grad_a_kernel(const float* fa, const int* frames_a, const float* fb,
+                                                               const int* frames_b, const double* e_band,
+                                                               const double* g_value, float* g_a, int K, int tmax_a,
+                                                               int tmax_b, int w, int S) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.x;
+  const int i = blockIdx.y * 4 + wave;
+  if (i >= tmax_a) return;
+  const int Ta = sdtw_frames(frames_a, b, tmax_a), Tb = sdtw_frames(frames_b, b, tmax_b);
+  float* out = g_a + (size_t)b * K * tmax_a + i;
+  if (Ta == 0 || Tb == 0 || i >= Ta) {
+    for (int k = lane; k < K; k += 64) out[(size_t)k * tmax_a] = 0.0f;
+    return;
+  }
+  const SdtwBand g = sdtw_band(Ta, Tb, w);
+  const float* A = fa + (size_t)b * K * tmax_a + i;
+  const float* Bm = fb + (size_t)b * K * tmax_b;
+  const double* E = e_band + (size_t)b * (size_t)(tmax_a + tmax_b - 1) * S;
+  const double gv = g_value[b];
+  int jlo = 0, jhi = g.m;                                                      // the columns of row i inside the band
+  if (g.n > 0) jlo = sdtw_max(0, sdtw_ceildiv(i * g.m - g.W, g.n)), jhi = sdtw_min(g.m, sdtw_floordiv(i * g.m + g.W, g.n));
+  const int j0 = jlo > lane ? lane + ((jlo - lane + 63) >> 6 << 6) : lane;
+  for (int kc = 0; kc < K; kc += kSdtwKc) {
+    double acc[kSdtwKc];
+#pragma unroll
+    for (int c = 0; c < kSdtwKc; ++c) acc[c] = 0.0;
+    for (int j = j0; j <= jhi; j += 64) {
+      double s = 0.0;
+      for (int k = 0; k < K; ++k) {
+        const double d = (double)A[(size_t)k * tmax_a] - (double)Bm[(size_t)k * tmax_b + j];
+        s += d * d;
+      }
+      const double wt = sdtw_weight<SQ>(E[sdtw_band_at(g, S, i, j)], s);
+#pragma unroll
+      for (int c = 0; c < kSdtwKc; ++c)
+        if (kc + c < K)
+          acc[c] = fma(wt, (double)A[(size_t)(kc + c) * tmax_a] - (double)Bm[(size_t)(kc + c) * tmax_b + j], acc[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < kSdtwKc; ++c) {
+      const double v = sdtw_wave_sum(acc[c]);
+      if (lane == 0 && kc + c < K) out[(size_t)(kc + c) * tmax_a] = (float)(gv * v);
+    }
+  }
+}
+
+template <bool SQ>
+__global__ void __launch_bounds__(64 * kSdtwGbWaves) sdtw_band_grad_b_kernel(const float* fa, const int* frames_a,
+                                                                             const float* fb, const int* frames_b,
+                                                                             const double* e_band, const double* g_value,
+                                                                             float* g_b, int K, int tmax_a, int tmax_b,
+                                                                             int w, int S) {
+  __shared__ double s_part[kSdtwGbWaves][kSdtwKc / 2][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.x;
+  const int j = blockIdx.y * 64 + lane;
+  const bool live = j < tmax_b;                    // a column of the buffer
+  const int Ta = sdtw_frames(frames_a, b, tmax_a), Tb = sdtw_frames(frames_b, b, tmax_b);
+  float* out = g_b + (size_t)b * K * tmax_b + j;
+  if (Ta == 0 || Tb == 0 || (int)blockIdx.y * 64 >= Tb) {                      // the whole block leaves: no barrier follows
+    if (live)
+      for (int k = wave; k < K; k += kSdtwGbWaves) out[(size_t)k * tmax_b] = 0.0f;
+    return;
+  }
+  const SdtwBand g = sdtw_band(Ta, Tb, w);
+  const bool inside = j < Tb;
+  const int jc = inside ? j : 0;                   // a lane behind Tb works on column 0 and writes zeros
+  const float* A = fa + (size_t)b * K * tmax_a;
+  const float* Bm = fb + (size_t)b * K * tmax_b + jc;
+  const double* E = e_band + (size_t)b * (size_t)(tmax_a + tmax_b - 1) * S;
+  const double gv = g_value[b];
+  int ilo = 0, ihi = g.n;                                                      // the rows of column jc inside the band
+  if (g.m > 0) ilo = sdtw_max(0, sdtw_ceildiv(jc * g.n - g.W, g.m)), ihi = sdtw_min(g.n, sdtw_floordiv(jc * g.n + g.W, g.m));
+  const int i0 = ilo > wave ? wave + ((ilo - wave + kSdtwGbWaves - 1) / kSdtwGbWaves * kSdtwGbWaves) : wave;
+  for (int kc = 0; kc < K; kc += kSdtwKc) {
+    double acc[kSdtwKc];
+#pragma unroll
+    for (int c = 0; c < kSdtwKc; ++c) acc[c] = 0.0;
+    for (int i = i0; i <= ihi; i += kSdtwGbWaves) {
+      double s = 0.0;
+      for (int k = 0; k < K; ++k) {
+        const double d = (double)A[(size_t)k * tmax_a + i] - (double)Bm[(size_t)k * tmax_b];
+        s += d * d;
+      }
+      const double wt = sdtw_weight<SQ>(E[sdtw_band_at(g, S, i, jc)], s);
+#pragma unroll
+      for (int c = 0; c < kSdtwKc; ++c)
+        if (kc + c < K)
+          acc[c] = fma(wt, (double)Bm[(size_t)(kc + c) * tmax_b] - (double)A[(size_t)(kc + c) * tmax_a + i], acc[c]);
+    }
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {         // eight accumulators at a time: wave w joins accumulator w
+#pragma unroll
+      for (int c = 0; c < kSdtwKc / 2; ++c) s_part[wave][c][lane] = acc[half * (kSdtwKc / 2) + c];
+      __syncthreads();
+      const double v = ((s_part[0][wave][lane] + s_part[1][wave][lane]) + (s_part[2][wave][lane] + s_part[3][wave][lane])) +
+                       ((s_part[4][wave][lane] + s_part[5][wave][lane]) + (s_part[6][wave][lane] + s_part[7][wave][lane]));
+      const int k = kc + half * (kSdtwKc / 2) + wave;
+      if (live && k < K) out[(size_t)k * tmax_b] = inside ? (float)(gv * v) : 0.0f;
+      __syncthreads();
+    }
+  }
+}
+
+namespace {
+inline int sdtw_band_threads(int band) {           // the smallest power of two >= 2 band + 2, at least a wave
+  int p = 64;
+  while (p < 2 * band + 2) p *= 2;
+  return p;
+}
+}  // namespace
+
+hipError_t launch_sdtw_band_forward(const float* fa, const int* frames_a, const float* fb, const int* frames_b,
+                                    double gamma, int cost, double* value, double* r, int B, int K, int tmax_a, int tmax_b,
+                                    int band, hipStream_t s) {
+  const int threads = sdtw_band_threads(band), S = sdtw_band_rows(tmax_a, band);
+  const double inv_gamma = 1.0 / gamma;
+  if (cost == kSdtwCostSq)
+    hipLaunchKernelGGL(sdtw_band_forward_kernel<true>, dim3(B), dim3(threads), 0, s, fa, frames_a, fb, frames_b, gamma,
+                       inv_gamma, value, r, K, tmax_a, tmax_b, band, S);
+  else
+    hipLaunchKernelGGL(sdtw_band_forward_kernel<false>, dim3(B), dim3(threads), 0, s, fa, frames_a, fb, frames_b, gamma,
+                       inv_gamma, value, r, K, tmax_a, tmax_b, band, S);
+  return hipGetLastError();
+}
+
+hipError_t launch_sdtw_band_backward(const float* fa, const int* frames_a, const float* fb, const int* frames_b,
+                                     double gamma, int cost, const double* r, double* e_band, double* e, int B, int K,
+                                     int tmax_a, int tmax_b, int band, hipStream_t s) {
+  const int threads = sdtw_band_threads(band), S = sdtw_band_rows(tmax_a, band);
+  const double inv_gamma = 1.0 / gamma;
+  if (e) {
+    const hipError_t err = hipMemsetAsync(e, 0, (size_t)B * tmax_a * tmax_b * sizeof(double), s);
+    if (err != hipSuccess) return err;
+  }
+  if (cost == kSdtwCostSq)
+    hipLaunchKernelGGL(sdtw_band_backward_kernel<true>, dim3(B), dim3(threads), 0, s, fa, frames_a, fb, frames_b, inv_gamma,
+                       r, e_band, e, K, tmax_a, tmax_b, band, S);
+  else
+    hipLaunchKernelGGL(sdtw_band_backward_kernel<false>, dim3(B), dim3(threads), 0, s, fa, frames_a, fb, frames_b,
+                       inv_gamma, r, e_band, e, K, tmax_a, tmax_b, band, S);
+  return hipGetLastError();
+}
+
+hipError_t launch_sdtw_band_grads(const float* fa, const int* frames_a, const float* fb, const int* frames_b, int cost,
+                                  const double* e_band, const double* g_value, float* g_a, float* g_b, int B, int K,
+                                  int tmax_a, int tmax_b, int band, hipStream_t s) {
+  const bool sq = cost == kSdtwCostSq;
+  const int S = sdtw_band_rows(tmax_a, band);
+  if (g_a) {
+    const dim3 grid(B, (tmax_a + 3) / 4);
+    if (sq)
+      hipLaunchKernelGGL(sdtw_band_grad_a_kernel<true>, grid, dim3(256), 0, s, fa, frames_a, fb, frames_b, e_band, g_value,
+                         g_a, K, tmax_a, tmax_b, band, S);
+    else
+      hipLaunchKernelGGL(sdtw_band_grad_a_kernel<false>, grid, dim3(256), 0, s, fa, frames_a, fb, frames_b, e_band, g_value,
+                         g_a, K, tmax_a, tmax_b, band, S);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+  }
+  if (g_b) {
+    const dim3 grid(B, (tmax_b + 63) / 64);
+    if (sq)
+      hipLaunchKernelGGL(sdtw_band_grad_b_kernel<true>, grid, dim3(64 * kSdtwGbWaves), 0, s, fa, frames_a, fb, frames_b,
+                         e_band, g_value, g_b, K, tmax_a, tmax_b, band, S);
+    else
+      hipLaunchKernelGGL(sdtw_band_grad_b_kernel<false>, grid, dim3(64 * kSdtwGbWaves), 0, s, fa, frames_a, fb, frames_b,
+                         e_band, g_value, g_b, K, tmax_a, tmax_b, band, S);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace wg

@@ -9,6 +9,7 @@ using namespace wg;
 namespace {
 
 bool frames_ok(int t) { return t >= 1 && t <= kSdtwMaxFrames; }
+bool band_ok(int w) { return w >= 1 && w <= kSdtwMaxBand; }
 
 // The checks the two calls share; 0 when the arguments are accepted.
 int check_common(const char* who, int B, int K, int tmax_a, int tmax_b, double gamma, int cost) {
@@ -54,6 +55,48 @@ int wg_softdtw_backward(const float* feat_a, const int32_t* frames_a, const floa
     err = launch_sdtw_grads(feat_a, frames_a, feat_b, frames_b, cost, e, g_value, g_a, g_b, B, K, tmax_a, tmax_b, s);
   if (!e_out) {
     const hipError_t ferr = hipFreeAsync(e, s);
+    if (err == hipSuccess) err = ferr;
+  }
+  HIP_TRY(err);
+  return WG_OK;
+}
+
+size_t wg_softdtw_banded_bytes(int32_t B, int32_t tmax_a, int32_t tmax_b, int32_t band) {
+  if (B < 1 || !frames_ok(tmax_a) || !frames_ok(tmax_b) || !band_ok(band)) return 0;
+  return sdtw_band_elems(B, tmax_a, tmax_b, band) * sizeof(double);
+}
+
+int wg_softdtw_banded_forward(const float* feat_a, const int32_t* frames_a, const float* feat_b, const int32_t* frames_b,
+                              double gamma, int32_t cost, double* value_out, double* r_out, int32_t B, int32_t K,
+                              int32_t tmax_a, int32_t tmax_b, int32_t band, void* stream) {
+  if (!feat_a || !frames_a || !feat_b || !frames_b || !value_out) return fail(WG_ERR_INVALID, "null argument");
+  if (int rc = check_common("softdtw banded forward", B, K, tmax_a, tmax_b, gamma, cost)) return rc;
+  if (!band_ok(band)) return fail(WG_ERR_INVALID, "softdtw banded forward: band %d outside [1, %d]", band, kSdtwMaxBand);
+  HIP_TRY(launch_sdtw_band_forward(feat_a, frames_a, feat_b, frames_b, gamma, cost, value_out, r_out, B, K, tmax_a,
+                                   tmax_b, band, (hipStream_t)stream));
+  return WG_OK;
+}
+
+int wg_softdtw_banded_backward(const float* feat_a, const int32_t* frames_a, const float* feat_b, const int32_t* frames_b,
+                               double gamma, int32_t cost, const double* r, const double* g_value, double* e_out,
+                               float* g_a, float* g_b, int32_t B, int32_t K, int32_t tmax_a, int32_t tmax_b, int32_t band,
+                               void* stream) {
+  if (!feat_a || !frames_a || !feat_b || !frames_b || !r) return fail(WG_ERR_INVALID, "null argument");
+  if ((g_a || g_b) && !g_value) return fail(WG_ERR_INVALID, "null argument: gradients need g_value");
+  if (int rc = check_common("softdtw banded backward", B, K, tmax_a, tmax_b, gamma, cost)) return rc;
+  if (!band_ok(band)) return fail(WG_ERR_INVALID, "softdtw banded backward: band %d outside [1, %d]", band, kSdtwMaxBand);
+  if (!e_out && !g_a && !g_b) return WG_OK;                                  // nothing asked for
+  hipStream_t s = (hipStream_t)stream;
+  double* e_band = nullptr;                                                  // the gradients read E in the band layout
+  if (g_a || g_b)
+    HIP_TRY(hipMallocAsync((void**)&e_band, sdtw_band_elems(B, tmax_a, tmax_b, band) * sizeof(double), s));
+  hipError_t err = launch_sdtw_band_backward(feat_a, frames_a, feat_b, frames_b, gamma, cost, r, e_band, e_out, B, K,
+                                             tmax_a, tmax_b, band, s);
+  if (err == hipSuccess && e_band)
+    err = launch_sdtw_band_grads(feat_a, frames_a, feat_b, frames_b, cost, e_band, g_value, g_a, g_b, B, K, tmax_a,
+                                 tmax_b, band, s);
+  if (e_band) {
+    const hipError_t ferr = hipFreeAsync(e_band, s);
     if (err == hipSuccess) err = ferr;
   }
   HIP_TRY(err);
